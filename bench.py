@@ -10,17 +10,21 @@ Default workload = BASELINE.json configs[2] ("c2"), the largest single-GPU confi
 alphabet of 64 symbols = 8 GiB of text per GPU (8-byte entries), 1 000 000 patterns of length 6..16 with occurrence
 offsets (weak scaling: the corpus grows with N).
 
+A plain run sets up, warms up, times --steps steps, writes the last step's results if --dump-outputs DIR is given (the arrays
+the caller of the timed path receives, float64 .npy; long ones as a fixed, seeded sample of their positions) and prints its
+lines.  Everything else it can measure or check (the legs below marked --full) runs only with --full.
+
 Rank 0 prints TWO stdout lines.  The LAST one is the contract's line and is bounded (< 6 KB, scalar values only):
   "roofline"     — the dominant kernel of the timed region, timed live with HIP events on the library's stream
-  "cpu_baseline" — the CPU restatement of the reference (oracle/, kind "port") timed on this host on a bounded,
+  "cpu_baseline" — (--full) the CPU restatement of the reference (oracle/, kind "port") timed on this host on a bounded,
                    doc-aligned slice of the SAME corpus (rank 0, N = 1 only)
-  "configs"      — a digest of the other single-GPU configurations of BASELINE.json: c1 (1 GiB ASCII, 100 k patterns; with the
+  "configs"      — (--full) a digest of the other single-GPU configurations of BASELINE.json: c1 (1 GiB ASCII, 100 k patterns; with the
                    literal bit-exact check of the whole array against the CPU oracle: "c1_sa_bit_exact"), c0, utf8_4g
                    (north_star target: 4 GiB UTF-8, reference-compatible order), c4shard (16 GiB UTF-8 = one GPU's share of
                    C4, 10 M patterns, $correlation ranking); at N = 4 / 8 the per-GPU shapes of C3 / C4 run on every rank
 The line BEFORE it ({"bench_detail": ...}, also written to bench_detail.json beside this file) carries everything else:
-per-kernel times, build statistics, query rooflines, PCIe-inclusive legs, cold start, lone-keyword latency, the
-whole-corpus CPU baseline of C1.
+per-kernel times, build statistics, query rooflines and, with --full, PCIe-inclusive legs, cold start, lone-keyword latency,
+the whole-corpus CPU baseline of C1.
 """
 import argparse
 import json
@@ -750,6 +754,31 @@ def emit(out):
     print(line, flush=True)
 
 
+DUMP_SAMPLE = 1 << 19   # positions kept of a longer output array (5 arrays x 2 files x 4 MiB at most: 40 MiB in all)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(torch, out_dir, r, hx, device):
+    """--dump-outputs: the arrays the last timed step handed its caller (cdb_query_batch[_offsets]_device: row_ptr, ids, counts
+    [, hit_ptr, offsets]) as float64 .npy files (every value is an integer below 2^53: exact).  An array of more than
+    DUMP_SAMPLE entries is written at DUMP_SAMPLE positions drawn with a fixed seed from its length, and <name>_index.npy holds
+    those positions, so that two builds of the project can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"row_ptr": (r.d_row_ptr, int(r.npat) + 1), "ids": (r.d_ids, int(r.nrows)), "counts": (r.d_counts, int(r.nrows))}
+    if hx is not None:
+        arrays.update({"hit_ptr": (hx.d_hit_ptr, int(r.nrows) + 1), "offsets": (hx.d_offsets, int(r.nhits))})
+    for name, (ptr, n) in arrays.items():
+        vals = np.empty(0, dtype=np.int64)
+        if n:
+            t = torch.as_tensor(_DevArr(ptr, n, "<i8"), device=device)
+            if n > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+                np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+                t = t[torch.from_numpy(idx).to(device)]
+            vals = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), vals.astype(np.float64))
+
+
 def midsize_bit_exact(torch, capi, W, nbytes=256 << 20):
     """Literal oracle parity on the bucket-wise (>= 2^32-style) build path at a size with real tiles — the siblings of
     `c1_sa_bit_exact` (the same check runs as tests/test_gpu_midsize_oracle.py with more option sets): 256 MiB of
@@ -961,6 +990,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the timed steps: cold start, order-proof leg, verify, short-pattern tail, "
+                         "PCIe-inclusive legs, the \"configs\" block, the 256 MiB oracle-parity check and the CPU baseline (the "
+                         "--configs and --no-* options below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's query results (rank 0) as DIR/<name>.npy (float64)")
     ap.add_argument("--configs", default="auto",
                     help="comma-separated extra configurations for the \"configs\" block (auto: c2,utf8_4g,c4shard at N = 1 on "
                          "the default workload, c3 at N = 4, c4 at N = 8 — the fixed 32 / 128 GiB corpora split across the ranks; none: skip)")
@@ -1008,7 +1043,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: the line would report the wrong GPU count")
 
     cold = None
-    if world == 1 and args.workload == "c2" and args.configs == "auto" and not args.no_cold_start:
+    if args.full and world == 1 and args.workload == "c2" and args.configs == "auto" and not args.no_cold_start:
         # server.cpp:44: the start-up build of a fresh process — measured FIRST, while this process has not touched the GPU
         # (VRAM a process released just before is scrubbed by the driver on re-allocation: the recycled case the configs
         # blocks measure)
@@ -1113,6 +1148,7 @@ def main():
     merger = shard.ShardMerger(capi, g, dist, rank, world, coll_device, device, mode=args.merge) if (world > 1 or args.force_merge) else None
 
     merged_rows = [None]   # row_ptr[-1] of the last step's merged CSR (N > 1)
+    last_hits = [None]     # occurrence offsets of the last step's query (workloads with offsets)
     call_wall = []         # (build call, query call) wall ms per step, as the caller sees them
 
     def step():
@@ -1124,7 +1160,7 @@ def main():
         trace(f"query (build {g.stat('build_ms'):.1f} ms, group_fallbacks {g.stat('group_fallbacks'):.0f})")
         tb = g.stat("build_ms")
         if cfg.get("offsets"):
-            r, _ = g.query_batch_offsets_device(d_blob.data_ptr(), d_offs.data_ptr(), npat, nbytes)
+            r, last_hits[0] = g.query_batch_offsets_device(d_blob.data_ptr(), d_offs.data_ptr(), npat, nbytes)
         else:
             r = g.query_batch_device(d_blob.data_ptr(), d_offs.data_ptr(), npat, nbytes)
         tq = g.stat("query_ms")
@@ -1190,6 +1226,8 @@ def main():
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         rows_per_rank = [int(x.item()) for x in allr]
+    if args.dump_outputs and rank == 0:   # (before any other query on this handle: the device arrays live until the next one)
+        dump_outputs(torch, args.dump_outputs, r, last_hits[0], device)
 
     prof = g.profile()
     steps = args.steps
@@ -1256,10 +1294,10 @@ def main():
     if merger is not None:
         merger.close()
 
-    # ---- everything below is outside the timed region; whatever fails there is reported, the headline stands
+    # ---- everything below is outside the timed region and runs with --full only; whatever fails there is reported, the headline stands
     c0 = None
     cpu_slice = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             if args.no_proof_leg:
                 raise RuntimeError("skipped (--no-proof-leg)")
@@ -1294,7 +1332,7 @@ def main():
             take = min(n, CPU_SLICE_BYTES) // cfg["doclen"] * cfg["doclen"]
             cpu_slice = text[:take].cpu().numpy()
     extras = None
-    if rank == 0 and world == 1 and small:   # the headline IS C1 (--workload c1): its extras run on the timed index
+    if args.full and rank == 0 and world == 1 and small:   # the headline IS C1 (--workload c1): its extras run on the timed index
         extras = C1Extras(torch, capi, W, args)
         try:
             extras.before_close(g, text, doc_start, ids, d_blob, d_offs, nbytes, npat, n, out)
@@ -1303,7 +1341,7 @@ def main():
     g.close()
     if extras is not None:
         extras.after_close(out, ndocs, cfg.get("doclen", 1024))
-    if rank == 0 and world == 1 and not small and not args.no_pcie and cfg["kind"] != "utf8":
+    if args.full and rank == 0 and world == 1 and not small and not args.no_pcie and cfg["kind"] != "utf8":
         # SURVEY §8(d) defines t_build INCLUDING the H2D of the text: the same corpus from host memory through
         # cdb_build_view (the caller's buffer, chunked pinned staging inside the timed call) — beside `value`, never in it
         try:
@@ -1327,7 +1365,7 @@ def main():
     del text, d_blob, d_offs
     torch.cuda.empty_cache()
     capi.load_library().cdb_release_cached_memory()
-    extra = args.configs
+    extra = args.configs if args.full else "none"
     if extra == "auto":
         extra = ("c1,c0,utf8_4g,c4shard" if world == 1 and args.workload == "c2" else
                  "c3" if world == 4 else "c4" if world == 8 else "none")  # C3 / C4 as BASELINE.json words them
@@ -1373,7 +1411,7 @@ def main():
         dist.barrier()
     if rank == 0:
         out["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline and not args.no_midsize_check and args.configs == "auto":
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.no_midsize_check and args.configs == "auto":
             try:
                 out["midsize_bit_exact"] = midsize_bit_exact(torch, capi, W)
                 for k, v in out["midsize_bit_exact"].items():
@@ -1381,7 +1419,7 @@ def main():
                         out[k] = v
             except Exception as e:  # noqa: BLE001
                 out["midsize_bit_exact"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 c0 = c0_sweep(W)
                 # the headline's CPU leg: a bounded slice of the SAME corpus (C2: the first 256 MiB of the 8 GiB, doc-aligned)

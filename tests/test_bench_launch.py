@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,6 +54,30 @@ def test_gpus_2_self_launches_two_ranks_on_one_gpu():
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["steps"] == 2 and len(line["rows_per_rank"]) == 2 and line["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_results(tmp_path):
+    """Without --full the run is the timed steps alone (no CPU baseline, no configs block); --dump-outputs writes the query
+    results of the last step as float64 arrays, the same ones in two runs with the same arguments."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "mid", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["metric"] == "sa_build_GiB_per_s"
+        assert line["cpu_baseline"] is None and line["configs"] == {} and "c1_sa_bit_exact" not in line
+        arrs = {f.name[:-4]: np.load(f) for f in sorted(d.glob("*.npy"))}
+        assert set(arrs) == {"row_ptr", "ids", "counts"}, sorted(arrs)
+        assert all(a.dtype == np.float64 for a in arrs.values()) and sum(f.stat().st_size for f in d.glob("*")) <= 64 << 20
+        rp = arrs["row_ptr"]
+        assert len(rp) == line["config"]["patterns"] + 1 and rp[0] == 0 and np.all(np.diff(rp) >= 0)
+        assert rp[-1] == line["query_rows_per_batch"] == len(arrs["ids"]) == len(arrs["counts"])
+        assert arrs["counts"].sum() == line["query_hits_per_batch"] and np.all(arrs["counts"] >= 1)
+        dumps.append(arrs)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
 
 
 def _canned_detail():
@@ -128,7 +153,7 @@ def test_gpus_8_dress_rehearsal_on_one_gpu():
     block and the bounded final line are the ones the driver's `--gpus 8` run will execute."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--share-gpu",
-                        "--workload", "c4mini", "--steps", "2", "--warmup", "1", "--configs", "c4mini", "--no-cpu-baseline"],
+                        "--workload", "c4mini", "--steps", "2", "--warmup", "1", "--full", "--configs", "c4mini", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=420)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

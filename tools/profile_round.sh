@@ -15,7 +15,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  ( time python bench.py ) > $OUT/bench_stdout.txt 2> $OUT/bench.err   # two lines: {"bench_detail": ...}, then the bounded contract line
+  ( time python bench.py --full ) > $OUT/bench_stdout.txt 2> $OUT/bench.err   # two lines: {"bench_detail": ...}, then the bounded contract line
   cp bench_detail.json $OUT/bench_detail.json 2>/dev/null
   tail -n 1 $OUT/bench_stdout.txt | wc -c
   tail -n 1 $OUT/bench_stdout.txt | cut -c1-600
