@@ -28,6 +28,8 @@ EXPORTS = [
     "cdb_shards_transport", "cdb_shards_build_views", "cdb_shards_query_batch_offsets", "cdb_shards_query_and", "cdb_shards_add_raw_dir", "cdb_shards_save", "cdb_shards_load",
     "cdb_comm_unique_id", "cdb_comm_create", "cdb_comm_create_group", "cdb_comm_destroy", "cdb_comm_last_error", "cdb_comm_merge", "cdb_comm_merge_counts",
     "cdb_comm_world", "cdb_comm_transport", "cdb_reserve", "cdb_reserve_wait",
+    "cdb_column_create", "cdb_column_destroy", "cdb_column_last_error", "cdb_column_add_bulk", "cdb_column_build", "cdb_column_query",
+    "cdb_column_query_any", "cdb_query_and_columns", "cdb_column_get_stat", "cdb_debug_column_set_option", "cdb_debug_column_profile_dump",
 ]
 
 
@@ -58,6 +60,10 @@ class CdbShardSlice(C.Structure):
 class CdbKeyQuery(C.Structure):
     _fields_ = [("index", C.c_void_p), ("blob", C.c_void_p), ("offsets", C.c_void_p), ("nkw", C.c_uint64),
                 ("ids", C.c_void_p), ("counts", C.c_void_p), ("nrows", C.c_size_t)]
+
+
+class CdbColumnKey(C.Structure):
+    _fields_ = [("column", C.c_void_p), ("blob", C.c_void_p), ("offsets", C.c_void_p), ("nranges", C.c_uint64)]
 
 
 class CdbDeviceHits(C.Structure):
@@ -197,6 +203,20 @@ def load_library():
     lib.cdb_shards_add_raw_dir.argtypes = [vp, cp, cp, C.POINTER(u64), C.POINTER(u64)]
     lib.cdb_shards_save.argtypes = [vp, cp]
     lib.cdb_shards_load.argtypes = [vp, cp]
+    lib.cdb_column_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
+    lib.cdb_column_destroy.argtypes = [vp]
+    lib.cdb_column_destroy.restype = None
+    lib.cdb_column_last_error.argtypes = [vp]
+    lib.cdb_column_last_error.restype = cp
+    lib.cdb_column_add_bulk.argtypes = [vp, vp, vp, u64]
+    lib.cdb_column_build.argtypes = [vp]
+    lib.cdb_column_query.argtypes = [vp, cp, C.c_size_t, C.POINTER(C.POINTER(i64)), C.POINTER(C.c_size_t)]
+    lib.cdb_column_query_any.argtypes = [vp, vp, vp, u64, C.POINTER(C.POINTER(i64)), C.POINTER(C.c_size_t)]
+    lib.cdb_query_and_columns.argtypes = [C.POINTER(CdbKeyQuery), C.c_int, C.POINTER(CdbColumnKey), C.c_int, C.c_int, i64, i64, u64,
+                                          C.POINTER(C.POINTER(i64)), C.POINTER(C.POINTER(i64)), C.POINTER(C.c_size_t)]
+    lib.cdb_column_get_stat.argtypes = [vp, cp, C.POINTER(C.c_double)]
+    lib.cdb_debug_column_set_option.argtypes = [vp, cp, i64]
+    lib.cdb_debug_column_profile_dump.argtypes = [vp, C.c_char_p, C.c_size_t]
     _LIB = lib
     return lib
 
@@ -627,6 +647,98 @@ class GpuShards:
         self._check(self._lib.cdb_shards_load(self._h, os.fsencode(path)))
 
 
+class GpuColumn:
+    """bool_index / integer_index / double_index on the GPU (cdb_column_*).  kind: 0 / "bool", 1 / "int64", 2 / "double" (the
+    reference's `number` tags).  add_bulk() rows become visible at the next build(); query(range) returns [(id, 0), ...] in the
+    reference's order ((value, id), bool: insertion order); query_any(ranges) the union's ids ascending (numpy int64)."""
+
+    KINDS = {"bool": 0, "int64": 1, "double": 2}
+    DTYPES = {0: np.uint8, 1: np.int64, 2: np.float64}
+
+    def __init__(self, kind, device=-1):
+        self._lib = load_library()
+        self.kind = self.KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+        if self.kind not in (0, 1, 2):
+            raise ValueError(f"GpuColumn: unknown kind {kind!r}")
+        h = C.c_void_p()
+        rc = self._lib.cdb_column_create(C.byref(h), device, self.kind)
+        if rc != 0:
+            raise RuntimeError(f"cdb_column_create failed (code {rc}): no usable gfx950 device — there is no CPU fallback")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.cdb_column_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(self._lib.cdb_column_last_error(self._h).decode(errors="replace"))
+
+    def add_bulk(self, ids, values):
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        vals = np.asarray(values)
+        vals = np.ascontiguousarray(vals != 0 if self.kind == 0 else vals, dtype=self.DTYPES[self.kind])
+        if len(ids) != len(vals):
+            raise ValueError("add_bulk: ids and values differ in length")
+        self._check(self._lib.cdb_column_add_bulk(self._h, _ptr(ids), _ptr(vals), len(ids)))
+
+    def build(self):
+        self._check(self._lib.cdb_column_build(self._h))
+
+    def query_ids(self, range_):
+        """query() as a numpy array of ids (same order)."""
+        r = range_.encode() if isinstance(range_, str) else bytes(range_)
+        ids, n = C.POINTER(C.c_int64)(), C.c_size_t(0)
+        self._check(self._lib.cdb_column_query(self._h, r, len(r), C.byref(ids), C.byref(n)))
+        try:
+            return np.ctypeslib.as_array(ids, shape=(n.value,)).copy() if n.value else np.empty(0, dtype=np.int64)
+        finally:
+            self._lib.cdb_free(ids)
+
+    def query(self, range_):
+        return [(int(i), 0) for i in self.query_ids(range_)]
+
+    @staticmethod
+    def _pack(ranges):
+        enc = [r.encode() if isinstance(r, str) else bytes(r) for r in ranges]
+        blob = np.frombuffer(b"".join(enc), dtype=np.uint8)
+        offs = np.zeros(len(enc) + 1, dtype=np.uint64)
+        np.cumsum([len(x) for x in enc], out=offs[1:])
+        return blob, offs
+
+    def query_any(self, ranges):
+        blob, offs = self._pack(ranges)
+        ids, n = C.POINTER(C.c_int64)(), C.c_size_t(0)
+        self._check(self._lib.cdb_column_query_any(self._h, _ptr(blob) if len(blob) else None, _ptr(offs), len(ranges),
+                                                   C.byref(ids), C.byref(n)))
+        try:
+            return np.ctypeslib.as_array(ids, shape=(n.value,)).copy() if n.value else np.empty(0, dtype=np.int64)
+        finally:
+            self._lib.cdb_free(ids)
+
+    def stat(self, name):
+        v = C.c_double(0)
+        if self._lib.cdb_column_get_stat(self._h, name.encode(), C.byref(v)) != 0:
+            raise KeyError(name)
+        return v.value
+
+    def set_option(self, name, value):
+        """Test / measurement hook (cdb_debug_column_set_option): "profile", "debug_query_path"."""
+        self._check(self._lib.cdb_debug_column_set_option(self._h, name.encode(), int(value)))
+
+    def profile(self):
+        buf = C.create_string_buffer(1 << 16)
+        self._lib.cdb_debug_column_profile_dump(self._h, buf, len(buf))
+        out = {}
+        for line in buf.value.decode().splitlines():
+            name, ms, launches, nbytes = line.split()
+            out[name] = {"ms": float(ms), "launches": int(launches), "bytes": int(nbytes)}
+        return out
+
+
 class ShardComm:
     """cdb_comm: one rank of a one-process-per-GPU group; merge() is collective."""
 
@@ -700,10 +812,62 @@ def memory_reset_peak():
     load_library().cdb_memory_reset_peak()
 
 
+def _query_and_columns(keys, ranked, lo, hi, limit):
+    """cdb_query_and_columns: the keys of query_and() with (GpuColumn, [ranges]) among them."""
+    lib = load_library()
+    plain = [(ix, data) for ix, data in keys if not isinstance(ix, GpuColumn)]
+    colk = [(ix, data) for ix, data in keys if isinstance(ix, GpuColumn)]
+    arr = (CdbKeyQuery * max(len(plain), 1))()
+    carr = (CdbColumnKey * len(colk))()
+    keep = []
+    lead = None
+    for k, (ix, data) in enumerate(plain):
+        if isinstance(ix, GpuStringIndex):
+            lead = lead or ix
+            blob = np.frombuffer(b"".join(data), dtype=np.uint8)
+            offs = np.zeros(len(data) + 1, dtype=np.uint64)
+            np.cumsum([len(x) for x in data], out=offs[1:])
+            keep += [blob, offs]
+            arr[k].index = ix._h
+            arr[k].blob = blob.ctypes.data if len(blob) else None
+            arr[k].offsets = offs.ctypes.data
+            arr[k].nkw = len(data)
+        elif ix is None:
+            ri = np.ascontiguousarray([r[0] for r in data], dtype=np.int64)
+            rc = np.ascontiguousarray([r[1] for r in data], dtype=np.int64)
+            keep += [ri, rc]
+            arr[k].ids = ri.ctypes.data if len(ri) else None
+            arr[k].counts = rc.ctypes.data if len(rc) else None
+            arr[k].nrows = len(ri)
+        else:
+            raise TypeError(f"query_and: column keys combine with GpuStringIndex keys and host rows only, not {type(ix).__name__}")
+    for j, (col, ranges) in enumerate(colk):
+        ranges = [ranges] if isinstance(ranges, (str, bytes)) else list(ranges)
+        blob, offs = GpuColumn._pack(ranges)
+        keep += [blob, offs]
+        carr[j].column = col._h
+        carr[j].blob = blob.ctypes.data if len(blob) else None
+        carr[j].offsets = offs.ctypes.data
+        carr[j].nranges = len(ranges)
+    ids, cnt, n = C.POINTER(C.c_int64)(), C.POINTER(C.c_int64)(), C.c_size_t(0)
+    rc_ = lib.cdb_query_and_columns(arr if plain else None, len(plain), carr, len(colk), 1 if ranked else 0, int(lo), int(hi), int(limit),
+                                    C.byref(ids), C.byref(cnt), C.byref(n))
+    if rc_ != 0:
+        if lead is not None:
+            raise RuntimeError(lib.cdb_last_error(lead._h).decode(errors="replace"))
+        raise RuntimeError(lib.cdb_column_last_error(colk[0][0]._h).decode(errors="replace"))
+    out = [(ids[i], cnt[i]) for i in range(n.value)]
+    lib.cdb_free(ids)
+    lib.cdb_free(cnt)
+    return out
+
+
 def query_and(keys, ranked=False, lo=1, hi=(1 << 62), limit=0):
-    """AND across keys on the device (cdb_query_and / cdb_shards_query_and).  keys: (GpuStringIndex or GpuShards,
-    [keywords]) for a string column or (None, [(id, count), ...]) for rows resolved elsewhere (ascending id).  Returns
-    [(id, summed count), ...]."""
+    """AND across keys on the device (cdb_query_and / cdb_shards_query_and / cdb_query_and_columns).  keys: (GpuStringIndex or
+    GpuShards, [keywords]) for a string column, (GpuColumn, [ranges]) for a numeric / bool column or (None, [(id, count), ...])
+    for rows resolved elsewhere (ascending id).  Returns [(id, summed count), ...]."""
+    if any(isinstance(ix, GpuColumn) for ix, _ in keys):
+        return _query_and_columns(keys, ranked, lo, hi, limit)
     lib = load_library()
     sharded = any(isinstance(ix, GpuShards) for ix, _ in keys)
     arr = (CdbKeyQuery * len(keys))()

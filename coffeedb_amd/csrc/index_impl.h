@@ -386,6 +386,9 @@ struct DeviceRows {
     uint64_t n;
 };
 DeviceCsr and_merge_on_device(Index& ix, const std::vector<DeviceRows>& lists, bool ranked, int64_t lo, int64_t hi, uint64_t limit);
+// rows (ids ascending) in ix.q_ids / q_counts -> filtered to lo <= count < hi and ranked in place (the tail of and_merge_on_device;
+// columns.hip runs its probe filters between the merge and this step)
+DeviceCsr rank_rows_on_device(Index& ix, DeviceCsr r, int64_t lo, int64_t hi, uint64_t limit);
 
 
 template <> inline SaOf<uint32_t>::ptr Index::sa_view<uint32_t>() const { return d_sa.as<uint32_t>(); }

@@ -1865,7 +1865,7 @@ __global__ __launch_bounds__(256) void q_ranked_out_kernel(const uint64_t* __res
 }
 
 // rows (ids ascending) in ix.q_ids / q_counts -> filtered to lo <= count < hi and ranked, in place
-static DeviceCsr rank_rows_on_device(Index& ix, DeviceCsr r, int64_t lo, int64_t hi, uint64_t limit) {
+DeviceCsr rank_rows_on_device(Index& ix, DeviceCsr r, int64_t lo, int64_t hi, uint64_t limit) {
     hipStream_t s = ix.stream;
     if (r.nrows == 0) {
         ix.prof.resolve();

@@ -18,14 +18,60 @@ using cdb_shim::parse_range;
 index::result_type index::query(const std::string&) const { throw std::logic_error("Unimplemented method index::query"); }
 void index::build() { throw std::logic_error("Unimplemented method index::build"); }
 
+// ---- GPU columns (COFFEEDB_GPU_NUMERIC=1)
+namespace {
+bool gpu_numeric() {
+    const char* e = std::getenv("COFFEEDB_GPU_NUMERIC");
+    return e && *e == '1';
+}
+cdb_column* make_column(int kind) {
+    if (!gpu_numeric()) return nullptr;
+    cdb_column* c = nullptr;
+    if (cdb_column_create(&c, -1, kind) != CDB_OK || !c) throw std::runtime_error("GPU column: no usable MI355X (gfx950) device");
+    return c;
+}
+[[noreturn]] void rethrow_column(const cdb_column* c, int rc) {
+    if (rc == CDB_E_INVALID) throw std::runtime_error(cdb_column_last_error(c));  // the reference's own wording
+    throw std::runtime_error(std::string("GPU column: ") + cdb_column_last_error(c));
+}
+index::result_type column_query(cdb_column* c, const std::string& range) {
+    int64_t* ids = nullptr;
+    size_t rows = 0;
+    const int rc = cdb_column_query(c, range.data(), range.size(), &ids, &rows);
+    if (rc != CDB_OK) rethrow_column(c, rc);
+    index::result_type out;
+    out.reserve(rows);
+    for (size_t r = 0; r < rows; ++r) out.emplace_back(ids[r], 0);
+    cdb_free(ids);
+    return out;
+}
+}  // namespace
+
 // ---- numeric indexes: sorted (value, id) pairs, half-open lower_bound window (index.cpp:63-74, 129-173)
 template <typename T, int8_t Tag>
+numeric_index<T, Tag>::numeric_index() : col(make_column(Tag)) {}
+template <typename T, int8_t Tag>
+numeric_index<T, Tag>::~numeric_index() {
+    cdb_column_destroy(col);
+}
+template <typename T, int8_t Tag>
 void numeric_index<T, Tag>::build() {
+    if (col) {
+        // the rows belong to the column once add_bulk has taken them: a failing build must not hand them over a second time
+        const int rc = cdb_column_add_bulk(col, staged_ids.data(), staged_vals.data(), staged_ids.size());
+        if (rc != CDB_OK) rethrow_column(col, rc);
+        staged_ids.clear();
+        staged_vals.clear();
+        const int rb = cdb_column_build(col);
+        if (rb != CDB_OK) rethrow_column(col, rb);
+        return;
+    }
     std::sort(rows.begin(), rows.end());
     rows.shrink_to_fit();
 }
 template <typename T, int8_t Tag>
 index::result_type numeric_index<T, Tag>::query(const std::string& range) const {
+    if (col) return column_query(col, range);
     const auto [lo, hi] = parse_range<T>(range);
     const auto first = std::lower_bound(rows.begin(), rows.end(), lo);
     const auto last = std::lower_bound(rows.begin(), rows.end(), hi);
@@ -37,12 +83,32 @@ index::result_type numeric_index<T, Tag>::query(const std::string& range) const 
 template class numeric_index<int64_t, 1>;
 template class numeric_index<double, 2>;
 
-void bool_index::add(int64_t id, bool value) { data[value ? 1 : 0].push_back(id); }
+bool_index::bool_index() : col(make_column(number)) {}
+bool_index::~bool_index() { cdb_column_destroy(col); }
+void bool_index::add(int64_t id, bool value) {
+    if (col) {
+        staged_ids.push_back(id);
+        staged_vals.push_back(value ? 1 : 0);
+        return;
+    }
+    data[value ? 1 : 0].push_back(id);
+}
 void bool_index::build() {
+    if (col) {
+        // the rows belong to the column once add_bulk has taken them: a failing build must not hand them over a second time
+        const int rc = cdb_column_add_bulk(col, staged_ids.data(), staged_vals.data(), staged_ids.size());
+        if (rc != CDB_OK) rethrow_column(col, rc);
+        staged_ids.clear();
+        staged_vals.clear();
+        const int rb = cdb_column_build(col);
+        if (rb != CDB_OK) rethrow_column(col, rb);
+        return;
+    }
     data[0].shrink_to_fit();
     data[1].shrink_to_fit();
 }
 index::result_type bool_index::query(const std::string& range) const {
+    if (col) return column_query(col, range);
     int which = -1;
     if (range == "false") which = 0;
     if (range == "true") which = 1;

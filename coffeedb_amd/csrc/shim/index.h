@@ -20,6 +20,7 @@
 
 struct cdb_index;   // opaque GPU index (include/coffeedb_gpu.h)
 struct cdb_shards;  // ... spread over several GPUs (COFFEEDB_GPUS)
+struct cdb_column;  // opaque GPU numeric / bool column (COFFEEDB_GPU_NUMERIC=1)
 
 class index {
 public:
@@ -34,16 +35,26 @@ public:
     virtual ~index() = default;
 };
 
+// With COFFEEDB_GPU_NUMERIC=1 (read when the index is made) bool / integer / double indexes live on the GPU as a cdb_column:
+// add() stages the rows, build() hands them over and sorts on the device, query() returns the same lists, and column() is what
+// cdb_query_and_columns takes to join the key with the others on the device.  Unset (the default): the CPU code below, and
+// column() is nullptr.
 class bool_index : public index {
 public:
     using value_type = bool;
     static constexpr int8_t number = 0;
+    bool_index();
+    ~bool_index() override;
     void add(int64_t id, bool value);
     void build() override;
     result_type query(const std::string& range) const override;
+    cdb_column* column() const { return col; }
 
 private:
     std::array<std::vector<int64_t>, 2> data;
+    cdb_column* col = nullptr;
+    std::vector<int64_t> staged_ids;  // (GPU column: rows since the last build)
+    std::vector<uint8_t> staged_vals;
 };
 
 // integer and double columns share one implementation: (value, id) pairs sorted at build(), answered with
@@ -53,12 +64,27 @@ class numeric_index : public index {
 public:
     using value_type = T;
     static constexpr int8_t number = Tag;
-    void add(int64_t id, T value) { rows.emplace_back(value, id); }
+    numeric_index();
+    ~numeric_index() override;
+    void add(int64_t id, T value) {
+        if (col) {
+            staged_ids.push_back(id);
+            staged_vals.push_back(value);
+        } else {
+            rows.emplace_back(value, id);
+        }
+    }
     void build() override;
     result_type query(const std::string& range) const override;
+    cdb_column* column() const { return col; }
 
 protected:
     std::vector<std::pair<T, int64_t>> rows;
+
+private:
+    cdb_column* col = nullptr;
+    std::vector<int64_t> staged_ids;
+    std::vector<T> staged_vals;
 };
 class integer_index : public numeric_index<int64_t, 1> {};
 class double_index : public numeric_index<double, 2> {};

@@ -184,6 +184,50 @@ typedef struct cdb_key_query {
 int cdb_query_and(const cdb_key_query* keys, int nkeys, int ranked, int64_t corr_lo, int64_t corr_hi, uint64_t limit, int64_t** ids,
                   int64_t** counts, size_t* nrows);
 
+/* ---- numeric and bool columns (columns.hip) ------------------------------------------------------
+ * A column replaces bool_index / integer_index / double_index (src/index.h:23-52, index.cpp:63-74, 129-173) on the
+ * device.  kind = the reference's `number` tag: 0 bool, 1 int64, 2 double.  Like cdb_create, cdb_column_create fails
+ * with CDB_E_DEVICE when no gfx950 GPU is usable: there is no CPU path.  Object ids must be unique within a column
+ * (database.cpp guarantees it); cdb_column_build refuses a duplicate with CDB_E_INVALID.  At most 2^32 - 1 rows. */
+typedef struct cdb_column cdb_column;
+int cdb_column_create(cdb_column** out, int device, int kind);
+void cdb_column_destroy(cdb_column* c);
+const char* cdb_column_last_error(const cdb_column* c);
+/* values: int64_t[n] (kind 1), double[n] (kind 2) or uint8_t[n] (kind 0, nonzero = true).  May be called repeatedly;
+ * rows become visible at the next cdb_column_build, which indexes every row added so far.  NaN is refused. */
+int cdb_column_add_bulk(cdb_column* c, const int64_t* ids, const void* values, uint64_t n);
+int cdb_column_build(cdb_column* c);
+/* numeric_query / bool_index::query for one range: int64 and double rows in (value, id) order, bool rows in insertion
+ * order; the reference's range grammar and messages ("Invalid range: ...", "Invalid value: ...", "Invalid query: \"...\"").
+ * Release ids with cdb_free. */
+int cdb_column_query(cdb_column* c, const char* range, size_t len, int64_t** ids, size_t* nrows);
+/* OR over the ranges blob[offsets[j] .. offsets[j+1]) of one numeric / bool key (interface.cpp:78-113): the union of their
+ * rows, ascending object id, each id once.  Release ids with cdb_free. */
+int cdb_column_query_any(cdb_column* c, const char* blob, const uint64_t* offsets, uint64_t nranges, int64_t** ids, size_t* nrows);
+/* AND across string keys / host row lists (keys, as in cdb_query_and) and column keys, all on one GPU: the result equals
+ * cdb_query_and given the same keys plus each column's cdb_column_query_any rows as (id, 0) host rows, ranked or not.
+ * nkeys may be 0 (keys = NULL) and ncols may be 0.  Errors are reported on the first string key's handle, or, without
+ * one, on the first column (cdb_column_last_error). */
+typedef struct cdb_column_key {
+    cdb_column* column;
+    const char* blob;        /* its ranges: blob[offsets[j] .. offsets[j+1]) */
+    const uint64_t* offsets;
+    uint64_t nranges;
+} cdb_column_key;
+int cdb_query_and_columns(const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols, int ranked, int64_t corr_lo,
+                          int64_t corr_hi, uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows);
+/* "rows", "staged_rows", "build_ms", "id_sort_skipped", "sparse_queries", "dense_queries", "probe_filters",
+ * "materialised_keys", "last_k" (rows inside the last query's windows), "last_union_ms" (the last query_any's or
+ * materialised key's union on the device, result download excluded) */
+int cdb_column_get_stat(const cdb_column* c, const char* name, double* value);
+/* Test and measurement hooks of the columns — NOT part of the stable ABI (like the other cdb_debug_* entry points they may change
+ * or go without notice; the library chooses every path itself, a caller never needs them):
+ * cdb_debug_column_set_option: "profile" (0/1: time the column's kernels with HIP events, read by cdb_debug_column_profile_dump as
+ * "name ms launches bytes" lines) and "debug_query_path" (0 = automatic, 1 = always sparse, 2 = always dense: the tests of both
+ * union paths and the crossover measurement of tools/bench_columns.py). */
+int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value);
+int cdb_debug_column_profile_dump(cdb_column* c, char* buf, size_t cap);
+
 /* Highlight spans — replaces the per-document re-scan of ac_automaton::render (database.cpp:58-76) that
  * select() runs for every returned object (database.cpp:394-441): for the keyword list of ONE string
  * key, every matching document's merged highlight spans [begin, end] (byte offsets, end inclusive), with

@@ -1,0 +1,391 @@
+"""Numeric and bool columns on the GPU (cdb_column_*, capi.GpuColumn) against a pure-Python restatement of the reference:
+numeric_query (index.cpp:63-74) = two std::lower_bound calls over sorted std::pair<T, int64_t>, here bisect over sorted
+(value, id) tuples; bool_index::query = the ids of one value in insertion order; the per-key OR of interface.cpp:78-113 = the
+sorted union; the AND = cdb_query_and fed with the model's rows."""
+import bisect
+import re
+import struct
+
+import numpy as np
+import pytest
+
+from coffeedb_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
+DBL_MIN = struct.unpack("<d", struct.pack("<Q", 0x0010000000000000))[0]  # numeric_limits<double>::min()
+DBL_MAX = 1.7976931348623157e308
+
+
+# ---- the model ---------------------------------------------------------------------------------------------------------
+def _value(text, kind):
+    t = text.lower()
+    if t == "-inf":
+        return I64_MIN if kind == 1 else DBL_MIN
+    if t == "inf":
+        return I64_MAX if kind == 1 else DBL_MAX
+    if kind == 1:
+        if re.fullmatch(r"-?[0-9]+", t) and I64_MIN <= int(t) <= I64_MAX:
+            return int(t)
+    elif re.fullmatch(r"-?([0-9]+(\.[0-9]*)?|\.[0-9]+)(e[-+]?[0-9]+)?", t):
+        return float(t)
+    elif re.fullmatch(r"-?(inf|infinity|nan)", t):  # what std::from_chars also takes ("inf" / "-inf" themselves are caught above)
+        return float(t)
+    raise ValueError("Invalid value: " + t)
+
+
+def parse_range(rng, kind):
+    """range_parse.h / utility.h:49-86: ((lo, tag), (hi, tag))."""
+    fail = ValueError("Invalid range: " + rng)
+    i, n = 0, len(rng)
+    while i < n and rng[i].isspace():
+        i += 1
+    if i >= n or rng[i] not in "[(":
+        raise fail
+    open_low = rng[i] == "("
+    i += 1
+    while i < n and rng[i].isspace():
+        i += 1
+    end = n
+    while end > i and rng[end - 1].isspace():
+        end -= 1
+    if end <= i or rng[end - 1] not in "])":
+        raise fail
+    closed_high = rng[end - 1] == "]"
+    body_end = end - 1
+    comma = rng.rfind(",", 0, body_end)
+    if comma < i:
+        raise fail
+    lo = rng[i:comma]
+    j = comma + 1
+    while j < body_end and rng[j].isspace():
+        j += 1
+    hi = rng[j:body_end]
+    if not lo or not hi:
+        raise fail
+    L, R = _value(lo, kind), _value(hi, kind)
+    return (L, I64_MAX if open_low else 0), (R, I64_MAX if closed_high else 0)
+
+
+class Model:
+    def __init__(self, kind):
+        self.kind = kind
+        self.rows = []  # (value, id) in insertion order
+
+    def add(self, ids, values):
+        self.rows += [(v, int(i)) for i, v in zip(ids, values)]
+
+    def query(self, rng):
+        if self.kind == 0:
+            if rng not in ("true", "false"):
+                raise ValueError(f'Invalid query: "{rng}"')
+            want = rng == "true"
+            return [i for v, i in self.rows if bool(v) == want]
+        srt = sorted((v + 0.0 if self.kind == 2 else v, i) for v, i in self.rows)  # (-0.0 and 0.0 tie, as in std::sort)
+        lo, hi = parse_range(rng, self.kind)
+        a, b = bisect.bisect_left(srt, lo), bisect.bisect_left(srt, hi)
+        return [i for _, i in srt[a:b]] if a < b else []
+
+    def query_any(self, ranges):
+        if not ranges:
+            raise ValueError("The constraint list cannot be empty")
+        out = set()
+        for r in ranges:
+            out.update(self.query(r))
+        return sorted(out)
+
+
+def _err(fn, *a):
+    try:
+        fn(*a)
+    except (RuntimeError, ValueError) as e:
+        return str(e)
+    return None
+
+
+def _check(col, model, ranges):
+    for r in ranges:
+        e_model = _err(model.query, r)
+        if e_model is not None:
+            assert _err(col.query, r) == e_model, r
+        else:
+            assert col.query(r) == [(i, 0) for i in model.query(r)], r
+
+
+# ---- int64 ------------------------------------------------------------------------------------------------------------------
+def _int_column(rng, n=6000):
+    vals = rng.integers(-50, 50, n).astype(np.int64)
+    vals[:4] = [I64_MIN, I64_MAX, I64_MIN, I64_MAX]
+    ids = rng.choice(np.arange(-10 * n, 10 * n), n, replace=False).astype(np.int64)  # negative and non-monotone
+    ids[0] = I64_MAX
+    ids[1] = I64_MIN
+    return ids, vals
+
+
+def test_int64_parity_with_the_reference_model():
+    rng = np.random.default_rng(11)
+    ids, vals = _int_column(rng)
+    col = capi.GpuColumn("int64", device=0)
+    col.add_bulk(ids[:2500], vals[:2500])  # add_bulk may be called repeatedly before build
+    col.add_bulk(ids[2500:], vals[2500:])
+    col.build()
+    assert col.stat("rows") == len(ids) and col.stat("id_sort_skipped") == 0
+    m = Model(1)
+    m.add(ids, vals)
+    ranges = []
+    for a, b in [(-10, 10), (0, 0), (5, -5), (-50, 49), (3, 4), (-1, 1)]:
+        for lb in "[(":
+            for rb in "])":
+                ranges.append(f"{lb}{a},{b}{rb}")
+    ranges += ["[-inf,inf]", "(-inf,inf)", "[-inf,0]", "(0,inf]", "[inf,inf]", "[-inf,-inf]", "(-inf,-inf]",
+               " [ -3, 7 ] ", "( 2,\t9)", "[ -9223372036854775808,9223372036854775807]", "[9223372036854775807,inf]",
+               "[-INF,Inf]",
+               # errors, verbatim
+               "[100 ,200]", "100..200", "[1.5,2]", "[1,2,3]", "[,5]", "[5,]", "[1,2", "1,2]", "", "[]", "[1,2 ]",
+               "[99999999999999999999,1]", "[+1,2]", "[a,b]"]
+    _check(col, m, ranges)
+    assert _err(col.query, "[1.5,2]") == "Invalid value: 1.5"
+    assert _err(col.query, "100..200") == "Invalid range: 100..200"
+    assert _err(col.query, "[100 ,200]") == "Invalid value: 100 "
+    assert _err(col.query, "[1,2,3]") == "Invalid value: 1,2"  # the regex is greedy: the lower value runs to the last comma
+    col.close()
+
+
+def test_negative_id_on_a_closed_lower_bound_is_excluded():
+    # lower_bound((v, 0)) skips (v, id < 0): the reference drops those rows, and so does the column
+    col = capi.GpuColumn(1, device=0)
+    col.add_bulk([-5, 3, -1, 8], [7, 7, 6, 7])
+    col.build()
+    assert col.query("[7,7]") == [(3, 0), (8, 0)]
+    assert col.query("(6,7]") == [(-5, 0), (3, 0), (8, 0)]
+    assert col.query("[6,7)") == [(-5, 0)]  # (6, -1) < (6, 0) is left out; (7, -5) < (7, 0) is inside the open end
+    col.close()
+
+
+# ---- double -----------------------------------------------------------------------------------------------------------------
+def test_double_parity_zeros_infinities_subnormals():
+    rng = np.random.default_rng(5)
+    n = 5000
+    vals = rng.choice([-2.5, -1.0, -0.0, 0.0, 0.5, 1.7724, 2.0, 3.25], n)
+    special = [np.inf, -np.inf, 5e-324, -5e-324, 1e-310, DBL_MIN, -DBL_MIN, DBL_MAX, -DBL_MAX]
+    vals[:len(special)] = special
+    ids = rng.permutation(np.arange(-n // 2, n - n // 2)).astype(np.int64)
+    col = capi.GpuColumn("double", device=0)
+    col.add_bulk(ids, vals)
+    col.build()
+    m = Model(2)
+    m.add(ids, vals.tolist())
+    ranges = ["[-inf,0]", "[-inf,inf]", "[0,0]", "[-0.0,0]", "(-0,0]", "[0,-0)", "[-1,1]", "(-1,1)", "[1.5,2.0]", "[1.5,2.0)",
+              "[-inf,1e-300]", "[0,1e-300]", "(-1e-300,0]", "[inf,inf]", "[-2.5,-2.5]", "(-2.5,3.25]", "[1e308,inf]",
+              "[-1.7976931348623157e308,-1]", "[.5,1]", "[2.,3]", "[1e0,2E0]", "[-inf,-inf]",
+              # from_chars' own spellings: a NaN bound is unordered with every value — C++20 pair order makes it never less
+              # (Python's tuple order agrees), so lower_bound stops at the front; "infinity" is a true infinity, unlike "inf"
+              "[0,nan]", "[nan,1]", "(nan,1)", "[-nan,nan]", "[nan,nan]", "[-1,NaN)", "[0,Infinity]", "[-Infinity,-1]",
+              "(-INFINITY,infinity]",
+              "[nope,1]", "[1;2]", "[1.0 ,2]"]
+    _check(col, m, ranges)
+    # the [-inf,0] quirk: -inf is the smallest POSITIVE double, so every value <= 0 lies below the window
+    got = {i for i, _ in col.query("[-inf,0]")}
+    assert got == set() or all(v > 0 for v, i in m.rows if i in got)
+    # NaN is refused at add_bulk
+    with pytest.raises(RuntimeError, match="NaN"):
+        col.add_bulk([10 ** 9], [float("nan")])
+    col.close()
+
+
+# ---- bool -------------------------------------------------------------------------------------------------------------------
+def test_bool_insertion_order_and_messages():
+    rng = np.random.default_rng(3)
+    n = 3000
+    ids = rng.permutation(np.arange(n) * 7 - 9000).astype(np.int64)
+    vals = rng.integers(0, 2, n).astype(np.uint8)
+    col = capi.GpuColumn("bool", device=0)
+    col.add_bulk(ids, vals)
+    col.build()
+    m = Model(0)
+    m.add(ids, vals)
+    _check(col, m, ["true", "false", "maybe", "True", ""])
+    assert _err(col.query, "maybe") == 'Invalid query: "maybe"'
+    # more rows, rebuilt: insertion order continues behind the first build's rows
+    ids2 = np.arange(10 ** 6, 10 ** 6 + 500, dtype=np.int64)[::-1].copy()
+    vals2 = rng.integers(0, 2, 500).astype(np.uint8)
+    col.add_bulk(ids2, vals2)
+    col.build()
+    m.add(ids2, vals2)
+    _check(col, m, ["true", "false"])
+    assert sorted(col.query_any(["true", "false"]).tolist()) == sorted(ids.tolist() + ids2.tolist())
+    col.close()
+
+
+# ---- query_any: both materialising paths ---------------------------------------------------------------------------------
+def test_query_any_sparse_and_dense_paths():
+    rng = np.random.default_rng(21)
+    n = 1 << 22
+    ids = (np.arange(n, dtype=np.int64) * 3 + 1000)  # ascending: the id sort is skipped
+    vals = rng.integers(0, 1000, n).astype(np.int64)
+    col = capi.GpuColumn("int64", device=0)
+    col.add_bulk(ids, vals)
+    col.build()
+    assert col.stat("id_sort_skipped") == 1
+
+    def expect(ranges):
+        mask = np.zeros(n, dtype=bool)
+        for r in ranges:
+            (lo, _), (hi, _) = parse_range(r, 1)  # all ids are positive: the tags only decide the brackets here
+            if r.strip()[0] == "[":
+                mlo = vals >= lo
+            else:
+                mlo = vals > lo
+            mhi = vals <= hi if r.strip()[-1] == "]" else vals < hi
+            mask |= mlo & mhi
+        return ids[mask]
+
+    s0, d0 = col.stat("sparse_queries"), col.stat("dense_queries")
+    narrow = ["[10,14]", "[12,19)", "(500,505]"]  # ~1.5 %, overlapping
+    assert np.array_equal(col.query_any(narrow), expect(narrow))
+    assert col.stat("sparse_queries") == s0 + 1
+    broad = ["[0,499]", "[250,700)", "[990,inf]"]  # ~71 %, overlapping
+    assert np.array_equal(col.query_any(broad), expect(broad))
+    assert col.stat("dense_queries") == d0 + 1
+    assert col.query_any(["[5,1]"]).size == 0
+    # both paths agree wherever they are forced
+    for path in (1, 2):
+        col.set_option("debug_query_path", path)
+        for rs in (narrow, broad, ["[3,3]"]):
+            assert np.array_equal(col.query_any(rs), expect(rs))
+    col.set_option("debug_query_path", 0)
+    with pytest.raises(RuntimeError, match="The constraint list cannot be empty"):
+        col.query_any([])
+    col.close()
+
+
+def test_query_any_unsorted_ids_overlapping_ranges():
+    rng = np.random.default_rng(8)
+    n = 200000
+    ids = rng.permutation(np.arange(-n, n, 2)).astype(np.int64)
+    vals = rng.normal(0, 10, n)
+    col = capi.GpuColumn("double", device=0)
+    col.add_bulk(ids, vals)
+    col.build()
+    m = Model(2)
+    m.add(ids, vals.tolist())
+    for ranges in (["[-1,1]", "[0,2)", "(-0.5,0.5]"], ["[-inf,inf]"], ["[-30,-20]", "[20,30]", "[25,inf]"], ["[3,1]"]):
+        assert col.query_any(ranges).tolist() == m.query_any(ranges), ranges
+    col.close()
+
+
+# ---- AND --------------------------------------------------------------------------------------------------------------------
+def _corpus(ids, rng):
+    words = [b"alpha", b"beta", b"gamma", b"delta", b"omega", b"zeta"]
+    docs = []
+    for k in range(len(ids)):
+        w = rng.choice(len(words), rng.integers(1, 5))
+        docs.append(b" ".join(words[j] for j in w) + (b" rare" if k % 97 == 0 else b""))
+    blob = b"".join(docs)
+    ds = np.zeros(len(docs) + 1, dtype=np.uint64)
+    np.cumsum([len(d) for d in docs], out=ds[1:])
+    return np.frombuffer(blob, dtype=np.uint8), ds
+
+
+def test_and_with_columns_equals_and_with_model_rows():
+    rng = np.random.default_rng(4)
+    n = 20000
+    ids = rng.permutation(np.arange(n, dtype=np.int64) * 5 - 30000)
+    ages = rng.integers(0, 100, n).astype(np.int64)
+    active = rng.integers(0, 2, n).astype(np.uint8)
+    blob, ds = _corpus(ids, rng)
+    g = capi.GpuStringIndex(device=0)
+    g.add_bulk(ids, blob, ds)
+    g.build()
+    age = capi.GpuColumn("int64", device=0)
+    age.add_bulk(ids, ages)
+    age.build()
+    act = capi.GpuColumn("bool", device=0)
+    act.add_bulk(ids, active)
+    act.build()
+    ma, mb = Model(1), Model(0)
+    ma.add(ids, ages)
+    mb.add(ids, active)
+
+    def rows(model, ranges):
+        return [(i, 0) for i in model.query_any(ranges)]
+
+    cases = [
+        ([b"alpha", b"beta"], ["[10,20]", "[30,40]"], ["true"]),
+        ([b"rare"], ["[0,89]"], ["false"]),            # selective string key, broad numeric range: probe path
+        ([b"gamma"], ["[5,5]"], ["true", "false"]),
+        ([b"delta"], ["[50,40]"], ["true"]),           # empty window
+    ]
+    p0 = age.stat("probe_filters")
+    for kws, ar, br in cases:
+        for ranked, lo, hi, limit in ((False, 1, 1 << 62, 0), (True, 1, 1 << 62, 0), (True, 2, 4, 0), (True, 1, 1 << 62, 7)):
+            want = capi.query_and([(g, kws), (None, rows(ma, ar)), (None, rows(mb, br))], ranked=ranked, lo=lo, hi=hi, limit=limit)
+            got = capi.query_and([(g, kws), (age, ar), (act, br)], ranked=ranked, lo=lo, hi=hi, limit=limit)
+            assert got == want, (kws, ar, br, ranked, lo, hi, limit)
+    assert age.stat("probe_filters") > p0
+    assert age.stat("materialised_keys") > 0
+
+    # columns only: the smaller key is materialised, the broader one probes it
+    p0 = act.stat("probe_filters")
+    got = capi.query_and([(age, ["[10,12]"]), (act, ["true"])])
+    assert got == [(i, 0) for i in sorted(set(ma.query_any(["[10,12]"])) & set(mb.query_any(["true"])))]
+    assert act.stat("probe_filters") == p0 + 1
+    assert capi.query_and([(age, ["[1,98]"])]) == rows(ma, ["[1,98]"])
+    # host rows beside column keys, no string key
+    host = rows(ma, ["[0,30]"])[::3]
+    assert capi.query_and([(None, host), (act, ["false"])]) == \
+        [(i, 0) for i in sorted({i for i, _ in host} & set(mb.query_any(["false"])))]
+    # errors of a column key surface verbatim through the string key's handle / the first column
+    with pytest.raises(RuntimeError, match=re.escape("Invalid range: 1..2")):
+        capi.query_and([(g, [b"alpha"]), (age, ["1..2"])])
+    with pytest.raises(RuntimeError, match=re.escape('Invalid query: "yes"')):
+        capi.query_and([(act, ["yes"])])
+    with pytest.raises(RuntimeError, match="The constraint list cannot be empty"):
+        capi.query_and([(age, [])])
+    for c in (age, act):
+        c.close()
+    g.close()
+
+
+# ---- rebuild and duplicates -------------------------------------------------------------------------------------------------
+def test_rebuild_after_more_rows_and_duplicate_ids():
+    col = capi.GpuColumn("int64", device=0)
+    col.add_bulk([1, 2, 3], [30, 10, 20])
+    col.build()
+    assert col.query("[-inf,inf]") == [(2, 0), (3, 0), (1, 0)]
+    col.add_bulk([-4, 5], [20, 5])
+    assert col.stat("staged_rows") == 2
+    col.build()
+    assert col.query("[-inf,inf]") == [(5, 0), (2, 0), (-4, 0), (3, 0), (1, 0)]
+    assert col.stat("rows") == 5
+    col.add_bulk([3], [99])
+    with pytest.raises(RuntimeError, match="duplicate object id 3"):
+        col.build()
+    assert col.query("[-inf,inf]") == [(5, 0), (2, 0), (-4, 0), (3, 0), (1, 0)]  # the published column is untouched
+    col.close()
+    empty = capi.GpuColumn("double", device=0)
+    empty.build()
+    assert empty.query("[-inf,inf]") == [] and empty.query_any(["[0,1]"]).size == 0
+    empty.close()
+
+
+# ---- full size --------------------------------------------------------------------------------------------------------------
+def test_full_size_int64_column():
+    n = 10 ** 8
+    rng = np.random.default_rng(2026)
+    ids = np.arange(n, dtype=np.int64) + 1_700_000_000_000
+    vals = rng.integers(0, 10 ** 6, n, dtype=np.int64)
+    col = capi.GpuColumn("int64", device=0)
+    col.add_bulk(ids, vals)
+    col.build()
+    assert col.stat("rows") == n
+    order = np.lexsort((ids, vals))
+    sv = vals[order]
+    for lo, hi in ((0, 9_999), (0, 499_999)):  # 1 % and 50 %
+        got = col.query_any([f"[{lo},{hi}]"])
+        assert np.array_equal(got, ids[(vals >= lo) & (vals <= hi)])
+        a, b = np.searchsorted(sv, lo, "left"), np.searchsorted(sv, hi, "right")
+        assert np.array_equal(col.query_ids(f"[{lo},{hi}]"), ids[order[a:b]])
+    assert col.stat("sparse_queries") + col.stat("dense_queries") == 2
+    col.close()
