@@ -169,7 +169,8 @@ struct Index {
     DevBuf d_sa_hi;                   // packed: bits 32..39 of every entry (size bytes)
     bool sa_packed = false;           // 5-byte storage of 8-byte entries (Sa40 above)
     bool gen_prebased = true;         // option: generated passes take their tile bases from counted per-tile digits (no look-back, two
-                                      // 8 Ki-key workgroups per CU; radix_sort.h: TextGen::tile_base)
+                                      // 8 Ki-key workgroups per CU; radix_sort.h: TextGen::tile_base).  Bucket-wise builds only: the
+                                      // MSD-first sort below 2^32 always counts its top digits per tile
     TileBaseWorkspace tbw;
     bool key_cost_model = true;       // option: bucket-wise builds weigh one key symbol fewer (a pass saved) against the refinement it costs
     bool pack_sa = true;              // option: builds with 8-byte entries below 2^40 store them packed

@@ -184,71 +184,11 @@ __global__ __launch_bounds__(256) void sa_sample_high_kernel(const uint8_t* __re
     if (__builtin_amdgcn_ballot_w64(hi) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
 }
 
-// MSD-first initial sort, pair form (radix_sort.h: TextGen::msd_pair): how often every pair of symbol CODES (c0, c1) starts
-// a suffix, as the number c0 * base + c1 — c1 = 0 where the document ends behind c0.  The sweep ignores document ends (and
-// counts nothing for the last byte of the text); sa_docend_pair_kernel moves the last position of every document from the
-// pair it was counted under to (c0, 0).  cnt[base^2], wrapping 64-bit adds.
-__global__ __launch_bounds__(1024) void sa_paircode_kernel(const uint8_t* __restrict__ text, uint64_t n, const uint16_t* __restrict__ symmap,
-                                                           uint32_t kbase, unsigned long long* __restrict__ cnt) {
-    extern __shared__ uint32_t s_pair[];  // [kbase * kbase]
-    __shared__ uint16_t s_map[256];
-    const uint32_t np = kbase * kbase;
-    for (uint32_t i = threadIdx.x; i < np; i += 1024) s_pair[i] = 0;
-    if (threadIdx.x < 256) s_map[threadIdx.x] = symmap[threadIdx.x];
-    __syncthreads();
-    const uint64_t words = n / 16;
-    const uint4* t4 = reinterpret_cast<const uint4*>(text);
-    const uint64_t stride = (uint64_t)gridDim.x * 1024;
-    for (uint64_t w = (uint64_t)blockIdx.x * 1024 + threadIdx.x; w < words; w += stride) {
-        const uint4 v = t4[w];
-        const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-        const bool has_next = w * 16 + 16 < n;
-        const uint32_t nxt = has_next ? (uint32_t)s_map[text[w * 16 + 16]] : 0u;
-        uint32_t c[17];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            c[4 * q] = s_map[x[q] & 0xFF];
-            c[4 * q + 1] = s_map[(x[q] >> 8) & 0xFF];
-            c[4 * q + 2] = s_map[(x[q] >> 16) & 0xFF];
-            c[4 * q + 3] = s_map[x[q] >> 24];
-        }
-        c[16] = nxt;
-#pragma unroll
-        for (int q = 0; q < 15; ++q) atomicAdd(&s_pair[__umul24(c[q], kbase) + c[q + 1]], 1u);
-        if (has_next) atomicAdd(&s_pair[__umul24(c[15], kbase) + c[16]], 1u);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 15)) {
-        const uint64_t p = words * 16 + threadIdx.x;
-        if (p + 1 < n) atomicAdd(&s_pair[__umul24((uint32_t)s_map[text[p]], kbase) + (uint32_t)s_map[text[p + 1]]], 1u);
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < np; i += 1024)
-        if (s_pair[i]) atomicAdd(&cnt[i], (unsigned long long)s_pair[i]);
-}
-__global__ __launch_bounds__(256) void sa_docend_pair_kernel(const uint8_t* __restrict__ text, const uint64_t* __restrict__ doc_start,
-                                                             uint64_t ndocs, uint64_t n, const uint16_t* __restrict__ symmap, uint32_t kbase,
-                                                             unsigned long long* __restrict__ cnt) {
-    __shared__ uint32_t s_end[257];  // documents by the code of their last symbol (few hot counters: not straight to memory)
-    for (int i = threadIdx.x; i < 257; i += 256) s_end[i] = 0;
-    __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t d = (uint64_t)blockIdx.x * 256 + threadIdx.x; d < ndocs; d += stride) {
-        const uint64_t b0 = doc_start[d], e = doc_start[d + 1];
-        if (e == b0) continue;
-        const uint32_t c0 = symmap[text[e - 1]];
-        atomicAdd(&s_end[c0], 1u);
-        if (e < n) atomicAdd(&cnt[c0 * kbase + (uint32_t)symmap[text[e]]], ~0ull);  // (- 1)
-    }
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < kbase; c += 256)
-        if (s_end[c]) atomicAdd(&cnt[c * kbase], (unsigned long long)s_end[c]);
-}
-
 // Look-back-free generated pass of the MSD-first sort (radix_sort.h: TextGen::tile_base): per tile of RS_GEN8_TILE positions, how many
 // suffixes carry each TOP digit — the digit is floor((c0 B + c1) / span) of the first two symbol codes, (a R) >> s in the pass's own
 // arithmetic (rs_pair_setup).  One workgroup per tile, wave-private LDS counters (the digit has ~200 values: shared counters would
 // serialise), the pair of the last position of every document counted with the byte BEHIND the document and moved to (c0, end) by
-// sa_tile_docend_fix_kernel.  The column sums of the table are the top-digit histogram (it replaces the pair count).
+// sa_tile_docend_fix_kernel.  The column sums of the table are the top-digit histogram.
 constexpr uint32_t TPC_TILES_PER_WAVE = 8;  // tiles a wavefront counts one after the other (a workgroup: 4 x 8 tiles)
 __global__ __launch_bounds__(256) void sa_tile_paircount_kernel(const uint8_t* __restrict__ text, uint64_t n, const uint16_t* __restrict__ symmap,
                                                                 uint32_t kbase, uint32_t pair_r, uint32_t pair_s, uint32_t tiles,
@@ -1933,163 +1873,149 @@ double now_ms() {
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-// I = type of suffix-array slot numbers, R = type of ranks / extended text positions: u32 while
-// n + D < 2^32, u64 beyond.  `big` additionally selects the bucket-wise initial sort that keeps the
-// working set inside HBM for multi-GiB corpora with 8-byte entries.
-template <typename V, typename I, typename R>
-void build_typed(Index& ix, bool big) {
-    hipStream_t s = ix.stream;
-    const uint64_t n = ix.size, D = ix.ndocs;
-    BuildStats& st = ix.bstats;
-    st = BuildStats{};
-    {
-        // the previous suffix array and kept keys go back to the block cache first: a rebuild of the same
-        // corpus shape then finds every buffer it needs there instead of asking the driver for fresh memory
-        const double tf = now_ms();
-        ix.release_sa();
-        ix.drop_keys();
-        ix.d_pivots.release();
-        ix.pivot_levels = 0;
-        st.free_ms += now_ms() - tf;
-    }
-    if (n == 0) {
-        ix.d_sa.alloc(16);
-        ix.sa_sorted = true;
-        ix.pivot_levels = 0;
-        ix.drop_keys();
-        return;
-    }
-    if (sizeof(R) == 4 && n + D + 2 >= (1ull << 32)) throw Error("internal: 32-bit ranks selected for a corpus >= 2^32");
-    const uint8_t* text = ix.d_text;
-    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
-
-    // ---- 1. alphabet -> order-preserving dense codes
+// ---- 1. alphabet -> order-preserving dense codes
+struct Alphabet {
     DevBuf d_counts, d_symmap;
-    d_counts.alloc(256 * sizeof(uint64_t));
-    d_symmap.alloc(256 * sizeof(uint16_t));
-    CDB_HIP(hipMemsetAsync(d_counts.p, 0, 256 * sizeof(uint64_t), s));
     // bucket-wise builds with look-back-free generated passes count the bytes per 8 Ki-position tile (the rows become the tile
     // bases of the records / partition pass, radix_sort.h: TextGen::tile_base); their column sums are the histogram
     DevBuf d_tbc;
-    const uint32_t tiles8 = (uint32_t)ceil_div(n, (uint64_t)RS_GEN8_TILE);
-    const bool tile_bytes = big && sizeof(V) == 8 && ix.gen_prebased && ix.segmented_sort && rs_atomic_rank_ok(s);
-    const unsigned long long* d_count_src = d_counts.as<unsigned long long>();
+    uint32_t tiles8 = 0;
+    bool tile_bytes = false;
     DevBuf d_pair_hi;      // per byte value: positions whose next byte is >= 0x80 (counted beside the bytes, PAIR form)
     bool pair_hi_counted = false;
-    if (tile_bytes) {
-        d_tbc.alloc((size_t)tiles8 * 256 * sizeof(uint32_t));
+    uint64_t h_counts[256];
+    uint16_t h_map[256];
+    int sigma = 0, symbits = 1;
+    bool high_bytes = false;
+};
+
+template <typename V>
+void count_alphabet(Index& ix, bool big, Alphabet& al) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size;
+    const uint8_t* text = ix.d_text;
+    al.d_counts.alloc(256 * sizeof(uint64_t));
+    al.d_symmap.alloc(256 * sizeof(uint16_t));
+    CDB_HIP(hipMemsetAsync(al.d_counts.p, 0, 256 * sizeof(uint64_t), s));
+    const uint32_t tiles8 = al.tiles8 = (uint32_t)ceil_div(n, (uint64_t)RS_GEN8_TILE);
+    al.tile_bytes = big && sizeof(V) == 8 && ix.gen_prebased && ix.segmented_sort && rs_atomic_rank_ok(s);
+    const unsigned long long* d_count_src = al.d_counts.as<unsigned long long>();
+    if (al.tile_bytes) {
+        al.d_tbc.alloc((size_t)tiles8 * 256 * sizeof(uint32_t));
         if (ix.reference_compat && ix.fold_root && ix.fold_depth1 && ix.fuse_pairclass) {
             // the reference-order build will want the next-byte classes if the text holds bytes >= 0x80: ask its first MiB
-            d_pair_hi.alloc(257 * sizeof(unsigned long long));
-            CDB_HIP(hipMemsetAsync(d_pair_hi.p, 0, 257 * sizeof(unsigned long long), s));
-            hipLaunchKernelGGL(sa_sample_high_kernel, dim3(64), dim3(256), 0, s, text, std::min<uint64_t>(n, 1u << 20), reinterpret_cast<uint32_t*>(d_pair_hi.as<unsigned long long>() + 256));
+            al.d_pair_hi.alloc(257 * sizeof(unsigned long long));
+            CDB_HIP(hipMemsetAsync(al.d_pair_hi.p, 0, 257 * sizeof(unsigned long long), s));
+            hipLaunchKernelGGL(sa_sample_high_kernel, dim3(64), dim3(256), 0, s, text, std::min<uint64_t>(n, 1u << 20), reinterpret_cast<uint32_t*>(al.d_pair_hi.as<unsigned long long>() + 256));
             uint32_t any = 0;
-            CDB_HIP(hipMemcpyAsync(&any, d_pair_hi.as<unsigned long long>() + 256, sizeof(any), hipMemcpyDeviceToHost, s));
+            CDB_HIP(hipMemcpyAsync(&any, al.d_pair_hi.as<unsigned long long>() + 256, sizeof(any), hipMemcpyDeviceToHost, s));
             CDB_HIP(hipStreamSynchronize(s));
-            pair_hi_counted = any != 0;
+            al.pair_hi_counted = any != 0;
         }
         int t = ix.prof.begin(s);
-        if (pair_hi_counted)
+        if (al.pair_hi_counted)
             hipLaunchKernelGGL(sa_tile_bytecount_kernel<true>, dim3((unsigned)ceil_div((uint64_t)tiles8, (uint64_t)(4 * TBC_TILES_PER_WAVE))), dim3(256), 0, s, text, n,
-                               tiles8, d_tbc.as<uint32_t>(), d_pair_hi.as<unsigned long long>());
+                               tiles8, al.d_tbc.as<uint32_t>(), al.d_pair_hi.as<unsigned long long>());
         else
         hipLaunchKernelGGL(sa_tile_bytecount_kernel<false>, dim3((unsigned)ceil_div((uint64_t)tiles8, (uint64_t)(4 * TBC_TILES_PER_WAVE))), dim3(256), 0, s, text, n,
-                           tiles8, d_tbc.as<uint32_t>(), (unsigned long long*)nullptr);
-        d_count_src = rs_tile_totals(s, ix.tbw, d_tbc.as<uint32_t>(), tiles8, nullptr);
+                           tiles8, al.d_tbc.as<uint32_t>(), (unsigned long long*)nullptr);
+        d_count_src = rs_tile_totals(s, ix.tbw, al.d_tbc.as<uint32_t>(), tiles8, nullptr);
         ix.prof.end(t, "sa_tile_bytecount", n + (uint64_t)tiles8 * 2048, s);
     } else {
         const int grid = (int)std::min<uint64_t>(ceil_div(n, 256 * 16 * 4), 256 * 8);
         int t = ix.prof.begin(s);
         hipLaunchKernelGGL(sa_bytecount_kernel, dim3(std::max(grid, 1)), dim3(256), 0, s, text, n,
-                           d_counts.as<unsigned long long>());
+                           al.d_counts.as<unsigned long long>());
         ix.prof.end(t, "sa_bytecount", n, s);
     }
-    uint64_t h_counts[256];
-    CDB_HIP(hipMemcpyAsync(h_counts, d_count_src, sizeof(h_counts), hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipMemcpyAsync(al.h_counts, d_count_src, sizeof(al.h_counts), hipMemcpyDeviceToHost, s));
     CDB_HIP(hipStreamSynchronize(s));
-    uint16_t h_map[256];
-    int sigma = 0;
-    bool high_bytes = false;
     for (int b = 0; b < 256; ++b) {
-        h_map[b] = h_counts[b] ? (uint16_t)(++sigma) : (uint16_t)0;
-        if (b >= 128 && h_counts[b]) high_bytes = true;
+        al.h_map[b] = al.h_counts[b] ? (uint16_t)(++al.sigma) : (uint16_t)0;
+        if (b >= 128 && al.h_counts[b]) al.high_bytes = true;
     }
-    const int symbits = std::max(1, bit_width64((uint64_t)sigma));
-    CDB_HIP(hipMemcpyAsync(d_symmap.p, h_map, sizeof(h_map), hipMemcpyHostToDevice, s));
+    al.symbits = std::max(1, bit_width64((uint64_t)al.sigma));
+    CDB_HIP(hipMemcpyAsync(al.d_symmap.p, al.h_map, sizeof(al.h_map), hipMemcpyHostToDevice, s));
+}
 
-    // Speculative pair count of the MSD-first sort (pair form) on a SECOND stream, beside the key-width sample below: both only
-    // need the symbol codes, the sample is a chain of small latency-bound kernels (0.7 ms) and the count a 0.4 ms sweep.
-    // Whether the sort takes the pair form is known only after the sample (6-symbol keys); if not, the counts are dropped.
-    DevBuf d_pc_spec, d_tc;  // d_tc: per-tile top-digit counts of the look-back-free generated pass (option gen_prebased)
-    bool pc_spec = false, tc_spec = false;
-    const unsigned long long* d_tc_totals = nullptr;
+// per-tile top-digit counts of the MSD-first sort's look-back-free generated pass (option gen_prebased)
+struct TopCounts {
+    DevBuf d_tc;
+    const unsigned long long* totals = nullptr;  // their column sums: the top-digit histogram
+    bool counted = false;
     struct AuxJoin {  // (declared after the buffer: an exception on the way still waits for the second stream before the
         hipStream_t a = nullptr;  //  buffer goes back to the pool)
         ~AuxJoin() { if (a) (void)hipStreamSynchronize(a); }
     } aux_join;
-    if (!big && sizeof(V) == 4 && n >= (1ull << 24) && ix.overlap_paircount && ix.msd_first && ix.msd_pair && ix.narrow_keys &&
-        ix.fuse_keygen && ix.flags_in_last_pass && ix.initial_passes == 0 && ix.digit_bits == 0 && ix.key_coding != 1 && sigma + 1 <= 128 &&
-        (ix.sort_variant == 0 || ix.sort_variant == 31 || ix.sort_variant == 33) && rs_variant_has_gen(ix.sort_variant) && rs_atomic_rank_ok(s)) {
-        if (!ix.aux_stream) CDB_HIP(hipStreamCreateWithFlags(&ix.aux_stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : ix.aux_ev)
-            if (!e) CDB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        const uint32_t pb = (uint32_t)sigma + 1u, np = pb * pb;
-        // look-back-free generated pass (radix_sort.h: TextGen::tile_base): count the top digit per 8 Ki-position tile instead of
-        // the pairs of the whole text — same sweep, and the column sums are the top-digit histogram
-        struct { uint32_t pair_span = 0, pair_r = 0, pair_s = 0; } pcs;
-        uint32_t span_spec = 0;
-        if (ix.gen_prebased) {
-            const uint64_t P4 = (uint64_t)pb * pb * pb * pb;
-            span_spec = (uint32_t)std::min<uint64_t>((1ull << 32) / P4, (uint64_t)np);
-            if (span_spec == 0 || ceil_div((uint64_t)np, (uint64_t)span_spec) > 256 || !rs_pair_setup(pcs, pb, span_spec)) span_spec = 0;
-        }
-        if (span_spec) {
-            const uint32_t tiles8 = (uint32_t)ceil_div(n, (uint64_t)RS_GEN8_TILE);
-            d_tc.alloc((size_t)tiles8 * 256 * sizeof(uint32_t));
-            CDB_HIP(hipEventRecord(ix.aux_ev[0], s));
-            CDB_HIP(hipStreamWaitEvent(ix.aux_stream, ix.aux_ev[0], 0));
-            aux_join.a = ix.aux_stream;
-            int t = ix.prof.begin(ix.aux_stream);
-            hipLaunchKernelGGL(sa_tile_paircount_kernel, dim3((unsigned)ceil_div((uint64_t)tiles8, (uint64_t)(4 * TPC_TILES_PER_WAVE))), dim3(256), 0, ix.aux_stream,
-                               text, n, (const uint16_t*)d_symmap.as<uint16_t>(), pb, pcs.pair_r, pcs.pair_s, tiles8, d_tc.as<uint32_t>());
-            hipLaunchKernelGGL(sa_tile_docend_fix_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(D, 256), 1024))), dim3(256), 0,
-                               ix.aux_stream, text, doc_start, D, n, (const uint16_t*)d_symmap.as<uint16_t>(), pb, pcs.pair_r, pcs.pair_s, d_tc.as<uint32_t>());
-            d_tc_totals = rs_tile_totals(ix.aux_stream, ix.tbw, d_tc.as<uint32_t>(), tiles8, nullptr);
-            ix.prof.end(t, "sa_tile_paircount", n + D * 18 + (uint64_t)tiles8 * 2048, ix.aux_stream);
-            CDB_HIP(hipEventRecord(ix.aux_ev[1], ix.aux_stream));
-            pc_spec = tc_spec = true;
-        } else {
-        d_pc_spec.alloc((size_t)np * sizeof(uint64_t));
-        CDB_HIP(hipMemsetAsync(d_pc_spec.p, 0, (size_t)np * sizeof(uint64_t), s));
-        CDB_HIP(hipEventRecord(ix.aux_ev[0], s));
-        CDB_HIP(hipStreamWaitEvent(ix.aux_stream, ix.aux_ev[0], 0));
-        aux_join.a = ix.aux_stream;
-        int t = ix.prof.begin(ix.aux_stream);
-        // (one workgroup per CU: the sample's kernels find room beside it)
-        hipLaunchKernelGGL(sa_paircode_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 1024 * 16 * 4), 256))), dim3(1024),
-                           np * sizeof(uint32_t), ix.aux_stream, text, n, (const uint16_t*)d_symmap.as<uint16_t>(), pb, d_pc_spec.as<unsigned long long>());
-        hipLaunchKernelGGL(sa_docend_pair_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(D, 256), 1024))), dim3(256), 0,
-                           ix.aux_stream, text, doc_start, D, n, (const uint16_t*)d_symmap.as<uint16_t>(), pb, d_pc_spec.as<unsigned long long>());
-        ix.prof.end(t, "sa_paircode", n + D * 18, ix.aux_stream);
-        CDB_HIP(hipEventRecord(ix.aux_ev[1], ix.aux_stream));
-        pc_spec = true;
-        }
-    }
+};
 
-    // Key width of the initial sort.  Every suffix left unresolved costs a refinement round (compaction,
-    // gathers, a further sort, inverse-array traffic for doubling) that is an order of magnitude more
-    // expensive per element than one more radix pass, so the key takes as many symbols as it needs for
-    // the expected unresolved share to drop below ~1/64.  The share is estimated from the text itself:
-    // S pseudo-random suffixes are keyed with the maximal width and sorted, and the number of adjacent
-    // sample pairs agreeing on their first k symbols gives the pair-collision probability c_k, hence
-    // ~ n * c_k of all suffixes share their k-prefix with another one.  (An order-0 symbol model is far
-    // too optimistic for correlated text such as multi-byte UTF-8.)  Small corpora use the order-0 model.
-    int nsym;
-    double est_k0 = 0;        // the sample's measured pair-collision probability at est_k0n symbols (>= 50 colliding pairs: meaningful)
+// Speculative pair count of the MSD-first sort (pair form) on a SECOND stream, beside the key-width sample: both only
+// need the symbol codes, the sample is a chain of small latency-bound kernels (0.7 ms) and the count a 0.4 ms sweep.
+// Whether the sort takes the pair form is known only after the sample (6-symbol keys); if not, the counts are dropped.
+template <typename V>
+void count_top_digits_aside(Index& ix, bool big, const Alphabet& al, TopCounts& tc) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, D = ix.ndocs;
+    const int sigma = al.sigma;
+    if (!(!big && sizeof(V) == 4 && n >= (1ull << 24) && ix.overlap_paircount && ix.msd_first && ix.msd_pair && ix.narrow_keys &&
+          ix.fuse_keygen && ix.flags_in_last_pass && ix.initial_passes == 0 && ix.digit_bits == 0 && ix.key_coding != 1 && sigma + 1 <= 128 &&
+          (ix.sort_variant == 0 || ix.sort_variant == 31 || ix.sort_variant == 33) && rs_variant_has_gen(ix.sort_variant) && rs_atomic_rank_ok(s)))
+        return;
+    if (!ix.aux_stream) CDB_HIP(hipStreamCreateWithFlags(&ix.aux_stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : ix.aux_ev)
+        if (!e) CDB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const uint32_t pb = (uint32_t)sigma + 1u, np = pb * pb;
+    // look-back-free generated pass (radix_sort.h: TextGen::tile_base): count the top digit per 8 Ki-position tile — the column
+    // sums are the top-digit histogram
+    struct { uint32_t pair_span = 0, pair_r = 0, pair_s = 0; } pcs;
+    const uint64_t P4 = (uint64_t)pb * pb * pb * pb;
+    const uint32_t span_spec = (uint32_t)std::min<uint64_t>((1ull << 32) / P4, (uint64_t)np);
+    if (span_spec == 0 || ceil_div((uint64_t)np, (uint64_t)span_spec) > 256 || !rs_pair_setup(pcs, pb, span_spec)) return;
+    const uint32_t tiles8 = (uint32_t)ceil_div(n, (uint64_t)RS_GEN8_TILE);
+    tc.d_tc.alloc((size_t)tiles8 * 256 * sizeof(uint32_t));
+    CDB_HIP(hipEventRecord(ix.aux_ev[0], s));
+    CDB_HIP(hipStreamWaitEvent(ix.aux_stream, ix.aux_ev[0], 0));
+    tc.aux_join.a = ix.aux_stream;
+    int t = ix.prof.begin(ix.aux_stream);
+    hipLaunchKernelGGL(sa_tile_paircount_kernel, dim3((unsigned)ceil_div((uint64_t)tiles8, (uint64_t)(4 * TPC_TILES_PER_WAVE))), dim3(256), 0, ix.aux_stream,
+                       ix.d_text, n, (const uint16_t*)al.d_symmap.as<uint16_t>(), pb, pcs.pair_r, pcs.pair_s, tiles8, tc.d_tc.as<uint32_t>());
+    hipLaunchKernelGGL(sa_tile_docend_fix_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(D, 256), 1024))), dim3(256), 0,
+                       ix.aux_stream, ix.d_text, ix.d_doc_start.as<uint64_t>(), D, n, (const uint16_t*)al.d_symmap.as<uint16_t>(), pb, pcs.pair_r,
+                       pcs.pair_s, tc.d_tc.as<uint32_t>());
+    tc.totals = rs_tile_totals(ix.aux_stream, ix.tbw, tc.d_tc.as<uint32_t>(), tiles8, nullptr);
+    ix.prof.end(t, "sa_tile_paircount", n + D * 18 + (uint64_t)tiles8 * 2048, ix.aux_stream);
+    CDB_HIP(hipEventRecord(ix.aux_ev[1], ix.aux_stream));
+    tc.counted = true;
+}
+
+// Key width of the initial sort.  Every suffix left unresolved costs a refinement round (compaction,
+// gathers, a further sort, inverse-array traffic for doubling) that is an order of magnitude more
+// expensive per element than one more radix pass, so the key takes as many symbols as it needs for
+// the expected unresolved share to drop below ~1/64.  The share is estimated from the text itself:
+// S pseudo-random suffixes are keyed with the maximal width and sorted, and the number of adjacent
+// sample pairs agreeing on their first k symbols gives the pair-collision probability c_k, hence
+// ~ n * c_k of all suffixes share their k-prefix with another one.  (An order-0 symbol model is far
+// too optimistic for correlated text such as multi-byte UTF-8.)  Small corpora use the order-0 model.
+struct KeyPlan {
+    int nsym = 0, dbits = 8, key_bits = 0;
+    uint32_t kbase = 0;
+    uint64_t kmagic = 0;
+    bool dense = false;
+    double est_k0 = 0;  // the sample's measured pair-collision probability at est_k0n symbols (>= 50 colliding pairs: meaningful)
     int est_k0n = 0;
-    uint64_t refine_depth0 = 0;  // symbols every key of the initial sort covers for certain (0: nsym; variable-length keys: fewer)
-    DevBuf d_vl_bytelen;         // variable-length keys: text byte -> code-word length (the refinement recovers every group's exact depth)
-    uint32_t vl_kb1 = 0;
+};
+
+template <typename V>
+KeyPlan plan_keys(Index& ix, bool big, const Alphabet& al) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, D = ix.ndocs;
+    BuildStats& st = ix.bstats;
+    const uint8_t* text = ix.d_text;
+    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
+    const int sigma = al.sigma, symbits = al.symbits;
+    int nsym;
+    double est_k0 = 0;
+    int est_k0n = 0;
     const int kmax = std::min(64 / symbits, 16);
     if (ix.initial_passes > 0) {
         const int passes = std::min(ix.initial_passes, 8);
@@ -2102,7 +2028,7 @@ void build_typed(Index& ix, bool big) {
         d_eq.alloc(32 * 8);
         CDB_HIP(hipMemsetAsync(d_eq.p, 0, 32 * 8, s));
         hipLaunchKernelGGL(sa_sample_keys_kernel, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s, text, doc_start, D, n,
-                           (const uint16_t*)d_symmap.as<uint16_t>(), symbits, kmax, S, sk0.as<uint64_t>());
+                           (const uint16_t*)al.d_symmap.as<uint16_t>(), symbits, kmax, S, sk0.as<uint64_t>());
         const int ssel = radix_sort<uint64_t, NoVal>(s, ix.rws, ix.prof, sk0.as<uint64_t>(), sk1.as<uint64_t>(), (NoVal*)nullptr,
                                                      (NoVal*)nullptr, S, 0, kmax * symbits, nullptr);
         hipLaunchKernelGGL(sa_sample_count_kernel, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, s,
@@ -2150,7 +2076,7 @@ void build_typed(Index& ix, bool big) {
     } else {
         double pc = 0;
         for (int b = 0; b < 256; ++b) {
-            const double p = (double)h_counts[b] / (double)n;
+            const double p = (double)al.h_counts[b] / (double)n;
             pc += p * p;
         }
         const double need = pc < 0.999 ? std::log(64.0 * (double)n) / -std::log(pc) : 1e9;
@@ -2221,22 +2147,37 @@ void build_typed(Index& ix, bool big) {
     st.key_symbols = nsym;
     st.symbol_bits = symbits;
     st.alphabet = sigma;
+    return KeyPlan{nsym, dbits, key_bits, kbase, kmagic, dense, est_k0, est_k0n};
+}
 
-    // ---- 2 + 3. keys + entries, initial sort
-    DevBuf sorted_keys, sa_buf, flags;
-    DevBuf sa_hi_buf;         // packed output (index_impl.h: Sa40): bits 32..39 of every entry; sa_buf then holds the low words
-    bool packed_out = false;
-    struct Depth1Fold {
-        uint64_t nend = 0, nlow = 0, nhigh = 0;
-        bool fold = false, done = false;  // done: the segmented sort really wrote the bucket with its blocks swapped
-    };
-    std::vector<Depth1Fold> depth1;          // ... per bucket: how its suffixes split by the class of their second symbol
-    std::vector<CompatBucket> folded_roots;  // bucket-wise build in the reference's root order: the first-symbol buckets
-    SortStats ss;
-    const bool fused = big || (ix.fuse_keygen && (dense || dbits == symbits) && nsym <= HC_MAXSYM &&
-                               rs_variant_has_gen(ix.sort_variant));
-    st.fused_keygen = fused ? 1 : 0;
+// ---- 2 + 3. keys + entries, initial sort
+// the digit histograms of the fused key generation, and the top-digit histogram of the MSD-first sort
+struct DigitHist {
+    bool fused = false, use_msd = false;
     std::vector<uint64_t> h_hist;  // [nsym][256] digit histograms of the LSD passes (fused path)
+    std::vector<uint64_t> h_top;
+    // pair form: 6-symbol keys whose top digit is a function of the first two symbols (TextGen::msd_pair); otherwise the
+    // top digit is key >> 32, counted by the key sweep
+    unsigned long long msd_m = 1ull << 32;
+    uint32_t msd_span = 0;
+    struct { uint32_t pair_span = 0, pair_r = 0, pair_s = 0; } pair_consts;
+};
+
+template <typename V>
+DigitHist digit_histograms(Index& ix, bool big, const Alphabet& al, const KeyPlan& kp, TopCounts& tc) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, D = ix.ndocs;
+    BuildStats& st = ix.bstats;
+    const uint8_t* text = ix.d_text;
+    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
+    const int sigma = al.sigma, nsym = kp.nsym, dbits = kp.dbits, key_bits = kp.key_bits;
+    const uint32_t kbase = kp.kbase;
+    const bool dense = kp.dense;
+    DigitHist dh;
+    const bool fused = dh.fused = big || (ix.fuse_keygen && (dense || dbits == al.symbits) && nsym <= HC_MAXSYM &&
+                                          rs_variant_has_gen(ix.sort_variant));
+    st.fused_keygen = fused ? 1 : 0;
+    std::vector<uint64_t>& h_hist = dh.h_hist;
     // digit histograms of the dense keys, counted in one sweep over the text
     auto key_histograms = [&](int npass, uint32_t digit_mask) {
         DevBuf d_kh;
@@ -2247,14 +2188,14 @@ void build_typed(Index& ix, bool big) {
         const bool by3 = ix.keyhist3 && nsym % 3 == 0 && nsym >= 6 && nsym <= 15;
 #define CDB_KH3(PARTS)                                                                                              \
     hipLaunchKernelGGL((sa_keyhist3_kernel<PARTS>), dim3(std::max(grid, 1)), dim3(256), 0, s, text, doc_start, D, n, \
-                       (const uint16_t*)d_symmap.as<uint16_t>(), kbase, npass, ix.text_padded, d_kh.as<unsigned long long>(), digit_mask)
+                       (const uint16_t*)al.d_symmap.as<uint16_t>(), kbase, npass, ix.text_padded, d_kh.as<unsigned long long>(), digit_mask)
         if (by3 && nsym == 6) CDB_KH3(2);
         else if (by3 && nsym == 9) CDB_KH3(3);
         else if (by3 && nsym == 12) CDB_KH3(4);
         else if (by3 && nsym == 15) CDB_KH3(5);
         else
             hipLaunchKernelGGL(sa_keyhist_kernel, dim3(std::max(grid, 1)), dim3(256), 0, s, text, doc_start, D, n,
-                               (const uint16_t*)d_symmap.as<uint16_t>(), kbase, nsym, npass, ix.text_padded,
+                               (const uint16_t*)al.d_symmap.as<uint16_t>(), kbase, nsym, npass, ix.text_padded,
                                d_kh.as<unsigned long long>(), digit_mask);
 #undef CDB_KH3
         ix.prof.end(t, "sa_keyhist", n, s);
@@ -2264,80 +2205,48 @@ void build_typed(Index& ix, bool big) {
     };
     // MSD-first form of the split sort (radix_sort.h: radix_sort_msd): dense keys of 33..40 bits, 16 Ki-key tiles with the
     // one-atomic ranking, flags written by the last pass.  Only the TOP digit's histogram comes from the text sweep.
-    const bool use_msd = fused && dense && !big && sizeof(V) == 4 && ix.narrow_keys && ix.msd_first && ix.flags_in_last_pass &&
-                         dbits == 8 && key_bits > 32 && key_bits <= 40 && rs_atomic_rank_ok(s) &&
-                         ((ix.sort_variant == 0 && n >= (1ull << 23)) || ix.sort_variant == 31 || ix.sort_variant == 33);
+    const bool use_msd = dh.use_msd = fused && dense && !big && sizeof(V) == 4 && ix.narrow_keys && ix.msd_first && ix.flags_in_last_pass &&
+                                      dbits == 8 && key_bits > 32 && key_bits <= 40 && rs_atomic_rank_ok(s) &&
+                                      ((ix.sort_variant == 0 && n >= (1ull << 23)) || ix.sort_variant == 31 || ix.sort_variant == 33);
     st.msd_first = use_msd ? 1 : 0;
-    // pair form: 6-symbol keys whose top digit is a function of the first two symbols (TextGen::msd_pair); otherwise the
-    // top digit is key >> 32, counted by the key sweep
-    unsigned long long msd_m = 1ull << 32;
-    uint32_t msd_span = 0;
-    struct { uint32_t pair_span = 0, pair_r = 0, pair_s = 0; } pair_consts;
-    std::vector<uint64_t> h_top;
+    uint32_t& msd_span = dh.msd_span;
     if (use_msd && ix.msd_pair && nsym == 6 && kbase <= 128) {
         const uint64_t P4 = (uint64_t)kbase * kbase * kbase * kbase;  // (< 2^28)
         msd_span = (uint32_t)std::min<uint64_t>((1ull << 32) / P4, (uint64_t)kbase * kbase);
         if (ceil_div((uint64_t)kbase * kbase, (uint64_t)msd_span) > 256) msd_span = 0;
-        if (msd_span && !rs_pair_setup(pair_consts, kbase, msd_span)) msd_span = 0;  // (24-bit arithmetic of the pair generator)
+        if (msd_span && !rs_pair_setup(dh.pair_consts, kbase, msd_span)) msd_span = 0;  // (24-bit arithmetic of the pair generator)
     }
-    if (pc_spec) {  // the second stream joins the first (whether or not its counts are used)
+    if (tc.counted) {  // the second stream joins the first (whether or not its counts are used)
         CDB_HIP(hipStreamWaitEvent(s, ix.aux_ev[1], 0));
-        aux_join.a = nullptr;
+        tc.aux_join.a = nullptr;
     }
-    if (msd_span && tc_spec) {  // the column sums of the per-tile counts ARE the top-digit histogram
-        msd_m = (unsigned long long)msd_span * kbase * kbase * kbase * kbase;
-        h_top.assign(256, 0);
-        CDB_HIP(hipMemcpyAsync(h_top.data(), d_tc_totals, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (msd_span && tc.counted) {  // the column sums of the per-tile counts ARE the top-digit histogram
+        dh.msd_m = (unsigned long long)msd_span * kbase * kbase * kbase * kbase;
+        dh.h_top.assign(256, 0);
+        CDB_HIP(hipMemcpyAsync(dh.h_top.data(), tc.totals, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         CDB_HIP(hipStreamSynchronize(s));
         st.msd_first = 2;
-    } else if (msd_span && pc_spec) {
-        msd_m = (unsigned long long)msd_span * kbase * kbase * kbase * kbase;
-        const uint32_t np = kbase * kbase;
-        std::vector<uint64_t> pc(np);
-        CDB_HIP(hipMemcpyAsync(pc.data(), d_pc_spec.p, (size_t)np * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        CDB_HIP(hipStreamSynchronize(s));
-        h_top.assign(256, 0);
-        for (uint32_t a = 0; a < np; ++a) h_top[a / msd_span] += pc[a];
-        st.msd_first = 2;
-    } else if (msd_span && ix.gen_prebased) {  // (no speculative count on the second stream: the same kernels on this one)
-        msd_m = (unsigned long long)msd_span * kbase * kbase * kbase * kbase;
+    } else if (msd_span) {  // (no speculative count on the second stream: the same kernels on this one)
+        dh.msd_m = (unsigned long long)msd_span * kbase * kbase * kbase * kbase;
         const uint32_t tiles8 = (uint32_t)ceil_div(n, (uint64_t)RS_GEN8_TILE);
-        d_tc.alloc((size_t)tiles8 * 256 * sizeof(uint32_t));
+        tc.d_tc.alloc((size_t)tiles8 * 256 * sizeof(uint32_t));
         int t = ix.prof.begin(s);
         hipLaunchKernelGGL(sa_tile_paircount_kernel, dim3((unsigned)ceil_div((uint64_t)tiles8, (uint64_t)(4 * TPC_TILES_PER_WAVE))), dim3(256), 0, s, text, n,
-                           (const uint16_t*)d_symmap.as<uint16_t>(), kbase, pair_consts.pair_r, pair_consts.pair_s, tiles8, d_tc.as<uint32_t>());
+                           (const uint16_t*)al.d_symmap.as<uint16_t>(), kbase, dh.pair_consts.pair_r, dh.pair_consts.pair_s, tiles8, tc.d_tc.as<uint32_t>());
         hipLaunchKernelGGL(sa_tile_docend_fix_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(D, 256), 1024))), dim3(256), 0, s,
-                           text, doc_start, D, n, (const uint16_t*)d_symmap.as<uint16_t>(), kbase, pair_consts.pair_r, pair_consts.pair_s,
-                           d_tc.as<uint32_t>());
-        d_tc_totals = rs_tile_totals(s, ix.tbw, d_tc.as<uint32_t>(), tiles8, nullptr);
+                           text, doc_start, D, n, (const uint16_t*)al.d_symmap.as<uint16_t>(), kbase, dh.pair_consts.pair_r, dh.pair_consts.pair_s,
+                           tc.d_tc.as<uint32_t>());
+        tc.totals = rs_tile_totals(s, ix.tbw, tc.d_tc.as<uint32_t>(), tiles8, nullptr);
         ix.prof.end(t, "sa_tile_paircount", n + D * 18 + (uint64_t)tiles8 * 2048, s);
-        h_top.assign(256, 0);
-        CDB_HIP(hipMemcpyAsync(h_top.data(), d_tc_totals, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        dh.h_top.assign(256, 0);
+        CDB_HIP(hipMemcpyAsync(dh.h_top.data(), tc.totals, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         CDB_HIP(hipStreamSynchronize(s));
-        tc_spec = true;
-        st.msd_first = 2;
-    } else if (msd_span) {
-        msd_m = (unsigned long long)msd_span * kbase * kbase * kbase * kbase;
-        const uint32_t np = kbase * kbase;
-        DevBuf d_pc;
-        d_pc.alloc((size_t)np * sizeof(uint64_t));
-        CDB_HIP(hipMemsetAsync(d_pc.p, 0, (size_t)np * sizeof(uint64_t), s));
-        int t = ix.prof.begin(s);
-        hipLaunchKernelGGL(sa_paircode_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 1024 * 16 * 4), 512))), dim3(1024),
-                           np * sizeof(uint32_t), s, text, n, (const uint16_t*)d_symmap.as<uint16_t>(), kbase, d_pc.as<unsigned long long>());
-        hipLaunchKernelGGL(sa_docend_pair_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(D, 256), 1024))), dim3(256), 0, s,
-                           text, doc_start, D, n, (const uint16_t*)d_symmap.as<uint16_t>(), kbase, d_pc.as<unsigned long long>());
-        ix.prof.end(t, "sa_paircode", n + D * 18, s);
-        std::vector<uint64_t> pc(np);
-        CDB_HIP(hipMemcpyAsync(pc.data(), d_pc.p, (size_t)np * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        CDB_HIP(hipStreamSynchronize(s));
-        h_top.assign(256, 0);
-        for (uint32_t a = 0; a < np; ++a) h_top[a / msd_span] += pc[a];
+        tc.counted = true;
         st.msd_first = 2;
     } else if (fused && dense) {
         const int npass = (int)ceil_div(key_bits, 8);
         key_histograms(npass, use_msd ? 1u << (npass - 1) : 0xFFFFFFFFu);
-        if (use_msd) h_top.assign(h_hist.begin() + (size_t)(npass - 1) * 256, h_hist.begin() + (size_t)npass * 256);
+        if (use_msd) dh.h_top.assign(h_hist.begin() + (size_t)(npass - 1) * 256, h_hist.begin() + (size_t)npass * 256);
     } else if (fused && !big) {
         // per-pass digit histograms from the byte counts + document-head corrections (no key is read)
         DevBuf d_corr;
@@ -2348,7 +2257,7 @@ void build_typed(Index& ix, bool big) {
             const int grid = (int)std::min<uint64_t>(ceil_div(D, 256), 256 * 4);
             int t = ix.prof.begin(s);
             hipLaunchKernelGGL(sa_headcorr_kernel, dim3(std::max(grid, 1)), dim3(256), 0, s, text, doc_start, D,
-                               (const uint16_t*)d_symmap.as<uint16_t>(), nsym, d_corr.as<unsigned long long>(),
+                               (const uint16_t*)al.d_symmap.as<uint16_t>(), nsym, d_corr.as<unsigned long long>(),
                                d_corr.as<unsigned long long>() + (size_t)HC_MAXSYM * 257);
             ix.prof.end(t, "sa_headcorr", D * (16 + (uint64_t)nsym), s);
         }
@@ -2359,7 +2268,7 @@ void build_typed(Index& ix, bool big) {
         const uint64_t* lencnt = h_corr.data() + (size_t)HC_MAXSYM * 257;
         uint64_t code_count[257] = {0};
         for (int b = 0; b < 256; ++b)
-            if (h_map[b]) code_count[h_map[b]] = h_counts[b];
+            if (al.h_map[b]) code_count[al.h_map[b]] = al.h_counts[b];
         h_hist.assign((size_t)nsym * 256, 0);
         for (int p = 0; p < nsym; ++p) {
             const int k = nsym - 1 - p;  // LSD: pass 0 sorts on the last symbol of the key
@@ -2377,24 +2286,60 @@ void build_typed(Index& ix, bool big) {
             }
         }
     }
-    TextGen gen{text, doc_start, d_symmap.as<uint16_t>(), D, (int)ix.bits, kbase, nsym, 0, ix.text_padded};
+    return dh;
+}
+
+struct Depth1Fold {
+    uint64_t nend = 0, nlow = 0, nhigh = 0;
+    bool fold = false, done = false;  // done: the segmented sort really wrote the bucket with its blocks swapped
+};
+
+// what the initial sort hands to the refinement and the finish
+struct InitialSort {
+    DevBuf sa_buf, flags;
+    DevBuf sa_hi_buf;         // packed output (index_impl.h: Sa40): bits 32..39 of every entry; sa_buf then holds the low words
+    bool packed_out = false;
+    bool flags_by_sort = false;    // the sort's last pass wrote the group flags and the tile sums of the first compaction
+    bool tile_sums_ready = false;  // the raw tile sums of the first compaction are in scan_partials already
+    DevBuf sorted_keys, sorted_k32, sorted_low;
+    int low_bits = 0, low_bytes = 0;
+    std::vector<Depth1Fold> depth1;          // ... per bucket: how its suffixes split by the class of their second symbol
+    std::vector<CompatBucket> folded_roots;  // bucket-wise build in the reference's root order: the first-symbol buckets
+    uint64_t refine_depth0 = 0;  // symbols every key of the initial sort covers for certain (0: nsym; variable-length keys: fewer)
+    DevBuf d_vl_bytelen;         // variable-length keys: text byte -> code-word length (the refinement recovers every group's exact depth)
+    uint32_t vl_kb1 = 0;
+};
+
+// builds below 2^32: one radix sort of every suffix's key, then the group flags
+template <typename V>
+InitialSort initial_sort_direct(Index& ix, const Alphabet& al, const KeyPlan& kp, const DigitHist& dh, TopCounts& tc, SortStats& ss) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, D = ix.ndocs;
+    BuildStats& st = ix.bstats;
+    const uint8_t* text = ix.d_text;
+    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
+    const int nsym = kp.nsym, dbits = kp.dbits, key_bits = kp.key_bits;
+    const uint32_t kbase = kp.kbase;
+    const uint64_t kmagic = kp.kmagic;
+    const bool fused = dh.fused, use_msd = dh.use_msd;
+    const uint32_t msd_span = dh.msd_span;
+    InitialSort out;
+    TextGen gen{text, doc_start, al.d_symmap.as<uint16_t>(), D, (int)ix.bits, kbase, nsym, 0, ix.text_padded};
     double ta = now_ms();
-    flags.alloc(n);
+    out.flags.alloc(n);
     // Layout of the sort records.  WIDE: (u64 key, entry).  When the generated first pass can drop the digit it
     // sorts on (it travels as one byte per element) and the rest of the key fits 32 bits, the other passes
     // move 9 instead of 12 bytes per suffix (SPLIT); keys of <= 32 bits need no extra byte at all (NARROW).
     enum { WIDE, NARROW, SPLIT, SPLIT2 } layout = WIDE;
-    if (fused && !big && sizeof(V) == 4 && ix.narrow_keys) {
+    if (fused && sizeof(V) == 4 && ix.narrow_keys) {
         if (key_bits <= 32) layout = NARROW;
         else if (key_bits - dbits <= 32) layout = SPLIT;
         else if (key_bits - 2 * dbits <= 32) layout = SPLIT2;  // two low digits in a u16: 10 bytes per suffix
     }
     st.key_layout = (int)layout;
-    DevBuf sorted_k32, sorted_low;
-    bool flags_by_sort = false;  // the sort's last pass wrote the group flags and the tile sums of the first compaction
-    const int low_bits = layout == SPLIT ? dbits : (layout == SPLIT2 ? 2 * dbits : 0);
-    const int low_bytes = layout == SPLIT ? 1 : (layout == SPLIT2 ? 2 : 0);
-    if (!big && layout != WIDE) {
+    const int low_bits = out.low_bits = layout == SPLIT ? dbits : (layout == SPLIT2 ? 2 * dbits : 0);
+    const int low_bytes = out.low_bytes = layout == SPLIT ? 1 : (layout == SPLIT2 ? 2 : 0);
+    if (layout != WIDE) {
         if constexpr (sizeof(V) == 4) {
             DevBuf k32[2], vals[2], low[2];
             k32[0].alloc(n * sizeof(uint32_t));
@@ -2408,7 +2353,7 @@ void build_typed(Index& ix, bool big) {
             st.alloc_ms += now_ms() - ta;
             if (getenv("CDB_DEBUG_BUFS"))
                 std::fprintf(stderr, "[bufs] k32 %p %p vals %p %p low %p %p flags %p\n", k32[0].p, k32[1].p, vals[0].p, vals[1].p, low[0].p,
-                             low[1].p, flags.p);
+                             low[1].p, out.flags.p);
             int sel = 0;
             // The last pass writes the group flags itself (radix_sort.h: SegFinalKeepArgs) where its kernel configuration
             // can (16 Ki tiles, one-atomic ranking): the flag kernel — 5-6 B read per suffix — is then not needed, and the
@@ -2422,7 +2367,7 @@ void build_typed(Index& ix, bool big) {
                 ix.scan_partials.ensure(scan_partials_slots(nbt) * sizeof(U2));
                 CDB_HIP(hipMemsetAsync(ix.scan_partials.p, 0, nbt * sizeof(U2), s));
                 edges.alloc((ceil_div(n, (uint64_t)RS_SEG_TILE) + 256) * 256 * sizeof(SegEdge));  // (MSD-first: one ragged tile per bucket)
-                keep.flags = flags.as<uint8_t>();
+                keep.flags = out.flags.as<uint8_t>();
                 keep.edges = edges.as<SegEdge>();
                 keep.low_bits = low_bits;
                 keep.kbase = kbase;
@@ -2434,48 +2379,48 @@ void build_typed(Index& ix, bool big) {
                 // the final pass writes the kept keys in the split layout (u32 = key >> 8, low byte), entries and flags
                 if (msd_span) {
                     gen.msd_pair = true;
-                    gen.pair_span = pair_consts.pair_span;
-                    gen.pair_r = pair_consts.pair_r;
-                    gen.pair_s = pair_consts.pair_s;
+                    gen.pair_span = dh.pair_consts.pair_span;
+                    gen.pair_r = dh.pair_consts.pair_r;
+                    gen.pair_s = dh.pair_consts.pair_s;
                 } else {
                     gen.msd_shift = 32;
                 }
-                const bool prebased = tc_spec && msd_span != 0;  // (the counts were made with this span: same rule, same alphabet)
+                const bool prebased = tc.counted && msd_span != 0;  // (the counts were made with this span: same rule, same alphabet)
                 radix_sort_msd(s, ix.rws, ix.msd_ws, ix.prof, k32[0].as<uint32_t>(), k32[1].as<uint32_t>(), vals[0].as<uint32_t>(),
-                               vals[1].as<uint32_t>(), low[1].as<uint8_t>(), n, h_top.data(), gen, msd_m, keep, &ss,
-                               prebased ? (const uint32_t*)d_tc.as<uint32_t>() : nullptr, prebased ? &ix.tbw : nullptr, ix.sweep_records);
+                               vals[1].as<uint32_t>(), low[1].as<uint8_t>(), n, dh.h_top.data(), gen, dh.msd_m, keep, &ss,
+                               prebased ? (const uint32_t*)tc.d_tc.as<uint32_t>() : nullptr, prebased ? &ix.tbw : nullptr, ix.sweep_records);
                 st.gen_prebased = prebased ? 1 : 0;
                 st.sweep_records = prebased && ix.sweep_records && gen.msd_pair ? 1 : 0;
-                d_tc.release();
+                tc.d_tc.release();
                 ix.tbw.base.release();
                 sel = 1;
-                sorted_low = std::move(low[1]);
-                flags_by_sort = ix.rws.keep_applied;
+                out.sorted_low = std::move(low[1]);
+                out.flags_by_sort = ix.rws.keep_applied;
             } else if (layout == SPLIT) {
                 gen.low_bits = low_bits;
                 sel = radix_sort_split<V, uint8_t>(s, ix.rws, ix.prof, k32[0].as<uint32_t>(), k32[1].as<uint32_t>(),
                                                    vals[0].as<V>(), vals[1].as<V>(), low[0].as<uint8_t>(), low[1].as<uint8_t>(), n,
-                                                   key_bits - low_bits, &ss, ix.sort_variant, dbits, h_hist.data(), &gen, 0, nullptr, -1,
+                                                   key_bits - low_bits, &ss, ix.sort_variant, dbits, dh.h_hist.data(), &gen, 0, nullptr, -1,
                                                    want_keep ? &keep : nullptr);
-                sorted_low = std::move(low[sel]);
-                flags_by_sort = ix.rws.keep_applied;
+                out.sorted_low = std::move(low[sel]);
+                out.flags_by_sort = ix.rws.keep_applied;
             } else if (layout == SPLIT2) {
                 gen.low_bits = low_bits;
                 sel = radix_sort_split<V, uint16_t>(s, ix.rws, ix.prof, k32[0].as<uint32_t>(), k32[1].as<uint32_t>(),
                                                     vals[0].as<V>(), vals[1].as<V>(), low[0].as<uint16_t>(), low[1].as<uint16_t>(),
-                                                    n, key_bits - low_bits, &ss, ix.sort_variant, dbits, h_hist.data(), &gen, 0, nullptr, -1,
+                                                    n, key_bits - low_bits, &ss, ix.sort_variant, dbits, dh.h_hist.data(), &gen, 0, nullptr, -1,
                                                     want_keep ? &keep : nullptr);
-                sorted_low = std::move(low[sel]);
-                flags_by_sort = ix.rws.keep_applied;
+                out.sorted_low = std::move(low[sel]);
+                out.flags_by_sort = ix.rws.keep_applied;
             } else {
                 sel = radix_sort<uint32_t, V>(s, ix.rws, ix.prof, k32[0].as<uint32_t>(), k32[1].as<uint32_t>(), vals[0].as<V>(),
-                                              vals[1].as<V>(), n, 0, key_bits, &ss, ix.sort_variant, dbits, h_hist.data(), &gen);
+                                              vals[1].as<V>(), n, 0, key_bits, &ss, ix.sort_variant, dbits, dh.h_hist.data(), &gen);
             }
             CDB_HIP(hipStreamSynchronize(s));
-            sorted_k32 = std::move(k32[sel]);
-            sa_buf = std::move(vals[sel]);
+            out.sorted_k32 = std::move(k32[sel]);
+            out.sa_buf = std::move(vals[sel]);
         }
-    } else if (!big) {
+    } else {
         DevBuf keys[2], vals[2];
         keys[0].alloc(n * sizeof(uint64_t));
         keys[1].alloc(n * sizeof(uint64_t));
@@ -2485,927 +2430,1069 @@ void build_typed(Index& ix, bool big) {
         int sel;
         if (fused) {
             sel = radix_sort<uint64_t, V>(s, ix.rws, ix.prof, keys[0].as<uint64_t>(), keys[1].as<uint64_t>(), vals[0].as<V>(),
-                                          vals[1].as<V>(), n, 0, key_bits, &ss, ix.sort_variant, dbits, h_hist.data(), &gen);
+                                          vals[1].as<V>(), n, 0, key_bits, &ss, ix.sort_variant, dbits, dh.h_hist.data(), &gen);
         } else {
             int t = ix.prof.begin(s);
             hipLaunchKernelGGL((sa_keygen_kernel<V>), dim3((unsigned)ceil_div(n, KG_TILE)), dim3(256), 0, s, text,
-                               doc_start, D, n, (int)ix.bits, d_symmap.as<uint16_t>(), kbase, nsym, ix.text_padded,
+                               doc_start, D, n, (int)ix.bits, al.d_symmap.as<uint16_t>(), kbase, nsym, ix.text_padded,
                                keys[0].as<uint64_t>(), vals[0].as<V>());
             ix.prof.end(t, "sa_keygen", n * (1 + sizeof(uint64_t) + sizeof(V)), s);
             sel = radix_sort<uint64_t, V>(s, ix.rws, ix.prof, keys[0].as<uint64_t>(), keys[1].as<uint64_t>(), vals[0].as<V>(),
                                           vals[1].as<V>(), n, 0, key_bits, &ss, ix.sort_variant, dbits);
         }
         CDB_HIP(hipStreamSynchronize(s));
-        sorted_keys = std::move(keys[sel]);
-        sa_buf = std::move(vals[sel]);
-    } else {
-        // Streamed bucket-wise sort (a double-buffered LSD sort of (u64 key, u64 entry) pairs would need 32 n
-        // bytes — 256 GiB at n = 2^33): ONE generated pass partitions the ENTRIES by first symbol — its keys exist only
-        // inside the tile — and every bucket then gathers its keys from the text (its entries are still in
-        // text order, so the gather walks the text front to back), LSD-sorts (key, entry) on the remaining
-        // symbols and writes its group flags.  Peak = 8 n (entries) + 24 x the largest bucket.
-        DevBuf E, KT[2], ET;  // (E: allocated below, once it is known whether the entries are partitioned at all)
-        const int top_shift = (nsym - 1) * symbits;
-        // Every position starts a suffix, and a suffix is never empty: the first symbol is never "end of document", so
-        // the partition digit is code - 1 (0 .. alphabet - 1: 8 bits even for all 256 byte values, where the codes
-        // 1 .. 256 themselves need 9) and its histogram is simply the byte histogram.
-        // Bucket order = ascending code, or — reference_compat order on text with bytes >= 0x80 — the reference's child
-        // order of the ROOT radix node (index.h:66-73: bytes 0x80..0xFF in front of 0x00..0x7F): the first-symbol buckets
-        // then sit where apply_reference_order's root rotation (three reversals of the whole array) would put them.
-        const bool root_folded = ix.reference_compat && high_bytes && ix.fold_root && n > std::max<uint64_t>(4096, n / 256);
-        std::vector<int> border;  // symbol codes in bucket order
-        if (root_folded) {
-            for (int b = 128; b < 256; ++b)
-                if (h_map[b]) border.push_back(h_map[b]);
-            for (int b = 0; b < 128; ++b)
-                if (h_map[b]) border.push_back(h_map[b]);
-        } else {
-            for (int c = 1; c <= sigma; ++c) border.push_back(c);
-        }
-        std::vector<uint64_t> first_by_code(258, 0), first_digit(256, 0);
-        uint16_t h_map_first[256];
-        uint8_t h_slotmap[260] = {0};  // symbol code -> bucket slot (the fused records pass)
-        {
-            int slot_of_code[258] = {0};
-            for (int k = 0; k < sigma; ++k) slot_of_code[border[k]] = k;
-            for (int c = 1; c <= sigma; ++c) h_slotmap[c] = (uint8_t)slot_of_code[c];
-            for (int b = 0; b < 256; ++b) {
-                h_map_first[b] = h_map[b] ? (uint16_t)slot_of_code[h_map[b]] : (uint16_t)0;
-                if (h_map[b]) {
-                    first_by_code[h_map[b]] = h_counts[b];
-                    first_digit[slot_of_code[h_map[b]]] = h_counts[b];
-                }
-            }
-        }
-        const uint64_t* h_first = first_by_code.data();  // (indexed by symbol code 1 .. alphabet)
-        DevBuf d_symmap_first;
-        d_symmap_first.alloc(256 * sizeof(uint16_t));
-        CDB_HIP(hipMemcpyAsync(d_symmap_first.p, h_map_first, sizeof(h_map_first), hipMemcpyHostToDevice, s));
-        // (look-back-free generated passes: which byte's per-tile counts feed bucket slot d; 0xFFFF = no such slot)
-        DevBuf d_src_col;
-        uint16_t h_src_col[256];
-        for (int d = 0; d < 256; ++d) h_src_col[d] = 0xFFFFu;
-        for (int b = 0; b < 256; ++b)
-            if (h_map[b]) h_src_col[h_map_first[b]] = (uint16_t)b;
-        if (tile_bytes) {
-            d_src_col.alloc(sizeof(h_src_col));
-            CDB_HIP(hipMemcpyAsync(d_src_col.p, h_src_col, sizeof(h_src_col), hipMemcpyHostToDevice, s));
-        }
-        CDB_HIP(hipStreamSynchronize(s));  // (h_map_first is a stack array)
-        uint64_t maxb = 0;
-        for (int c = 1; c <= sigma; ++c) maxb = std::max(maxb, h_first[c]);
-        // Bucket records.  Inside a bucket the first symbol is constant, so the sort key is the remaining
-        // nsym - 1 symbols — as a dense base-(alphabet + 1) number, split like the records of the single-sort
-        // path when it fits 32 bits + one or two low digits: (u32, entry, u8 / u16) instead of (u64, entry).
-        const uint32_t bbase = (uint32_t)sigma + 1u;
-        int bbits = 0;  // bits of bbase^(nsym-1) - 1; 999 beyond 56 bits
-        {
-            unsigned __int128 v = 1;
-            for (int i = 0; i + 1 < nsym && bbits != 999; ++i) {
-                v *= bbase;
-                if (v > ((unsigned __int128)1 << 56)) bbits = 999;
-            }
-            if (bbits != 999) bbits = bit_width64((uint64_t)(v - 1));
-        }
-        // ---- variable-length keys (vl_code.h): the first B - 1 bits of the suffix's alphabetic code stream + a "continues" bit instead
-        // of the dense number, when the model of key_cost_model says they are cheaper — skewed text, where equal prefixes are made of
-        // frequent symbols with short code words (8 GiB of Zipf-64 text: 40 key bits = 5 passes over 10-byte records instead of 54 bits
-        // = 7 passes over 12-byte records).  Needs the sweep form (the key of a position is a window into the tile's bit stream).
-        VlCode vlc;
-        int vl_bits = 0;
-        DevBuf d_vl_sym, d_vl_dec;
-        if (sizeof(V) == 8 && ix.vl_keys != 0 && !ix.vl_off_once && tile_bytes && ix.sweep_records && ix.segmented_sort && ix.pack_entries &&
-            ix.narrow_keys && (int)ix.bits + ix.off_bits <= 40 && sigma >= 2 && sigma <= 127 && nsym > 1 && rs_atomic_rank_ok(s) &&
-            (ix.vl_keys != 2 || (ix.initial_passes == 0 && ix.key_symbols == 0))) {
-            uint64_t cnts[257] = {0};
-            cnts[0] = D;
-            for (int c = 1; c <= sigma; ++c) cnts[c] = h_first[c];
-            if (vl_build(cnts, sigma, vlc)) {
-                auto rec_bytes = [](int b) { return 8.0 + (b <= 32 ? 1.0 : (b <= 40 ? 2.0 : 4.0)); };
-                const double refine_bytes = 2000.0;  // (what a text-extension round costs per unresolved suffix: key_cost_model above)
-                // the sample measured the dense key's unresolved share; the order-0 model q^k says what it "should" be — their ratio
-                // carries the text's correlation over to the estimate for the code stream: share(B) = ratio n q 2^(-rate (B - 1))
-                // (measured where the sample SEES collisions — the longest prefix with >= 50 colliding sample pairs; at the key width
-                //  that was chosen it sees none by construction, and "none" is no measurement: a first version divided 0 by the model
-                //  and took 32-bit code-stream keys for 16 GiB of printable ASCII, 12 % unresolved)
-                const double ratio = est_k0n > 0 ? std::min(1e3, std::max(0.2, est_k0 / std::max(std::pow(vlc.q, (double)est_k0n), 1e-300))) : 1.0;
-                const double u_fixed = std::min(1.0, ratio * (double)n * std::pow(vlc.q, (double)nsym));
-                const double cost_fixed = bbits != 999 ? std::ceil(bbits / 8.0) * 2.0 * rec_bytes(bbits) + u_fixed * refine_bytes : 1e9;
-                auto share = [&](int B) { return std::min(1.0, ratio * (double)n * vlc.q * std::pow(2.0, -vlc.rate * (double)(B - 1))); };
-                int best_b = 0;
-                double best = 1e18;
-                // (with these keys the text-extension rounds start every group at the depth its key really covered, so the open
-                //  suffixes are settled in one or two rounds: ~1000 B each — 8 GiB of Zipf text, B = 40: 46 ms for 206 M of them)
-                const double refine_bytes_vl = 1000.0;
-                for (int B : {32, 40, 48, 56}) {
-                    const double u = share(B);
-                    if (u > 1.0 / 24.0) continue;  // (text extension wants few open suffixes; the estimate errs on the high side)
-                    const double c = (double)(B / 8) * 2.0 * rec_bytes(B) + u * refine_bytes_vl + 6.0;  // (+ 6: the tile's bit offsets)
-                    if (c < best) {
-                        best = c;
-                        best_b = B;
-                    }
-                }
-                if (ix.vl_keys >= 16) best_b = std::min(56, (ix.vl_keys + 7) / 8 * 8);
-                else if (ix.vl_keys == 1 && !best_b) best_b = 56;
-                // (automatic mode also wants a code that really is shorter than the dense number's log2(alphabet + 1) bits per symbol:
-                //  on a flat alphabet the code stream can only lose)
-                const bool shorter = vlc.avg_len <= 0.93 * std::log2((double)sigma + 1.0);
-                if (best_b && (ix.vl_keys != 2 || (shorter && best < 0.93 * cost_fixed))) {
-                    vl_bits = best_b;
-                    bbits = vl_bits;
-                    std::vector<uint16_t> sym(256, 0), dec(128, (uint16_t)(0xFFu | ((unsigned)vlc.end_len << 8)));
-                    for (int c = 0; c <= sigma; ++c) {
-                        sym[c] = (uint16_t)(vlc.bits[c] | ((unsigned)vlc.len[c] << 8));
-                        if (c == 0) continue;
-                        const int l = vlc.len[c];
-                        for (unsigned x = 0; x < (1u << (VL_MAX_LEN - l)); ++x)
-                            dec[((unsigned)vlc.bits[c] << (VL_MAX_LEN - l)) | x] = (uint16_t)(h_slotmap[c] | ((unsigned)l << 8));
-                    }
-                    d_vl_sym.alloc(256 * sizeof(uint16_t));
-                    d_vl_dec.alloc(128 * sizeof(uint16_t));
-                    CDB_HIP(hipMemcpyAsync(d_vl_sym.p, sym.data(), 256 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-                    CDB_HIP(hipMemcpyAsync(d_vl_dec.p, dec.data(), 128 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-                    CDB_HIP(hipStreamSynchronize(s));  // (sym, dec)
-                    st.vl_key_bits = vl_bits;
-                    st.vl_avg_len = vlc.avg_len;
-                    st.vl_rate = vlc.rate;
-                    st.vl_est_unresolved = share(vl_bits);
-                    st.fixed_est_unresolved = u_fixed;
-                    // every key covers at least this many whole symbols behind the bucket symbol: where the refinement starts
-                    refine_depth0 = 1 + (uint64_t)((vl_bits - 1) / vlc.max_len);
-                    // (the text-extension rounds start every group at the depth its key really covered: code-word length per text byte)
-                    std::vector<uint8_t> blen(256, 0);
-                    for (int b = 0; b < 256; ++b) blen[b] = h_map[b] ? vlc.len[h_map[b]] : (uint8_t)0;
-                    d_vl_bytelen.alloc(256);
-                    CDB_HIP(hipMemcpyAsync(d_vl_bytelen.p, blen.data(), 256, hipMemcpyHostToDevice, s));
-                    CDB_HIP(hipStreamSynchronize(s));  // (blen)
-                    vl_kb1 = (uint32_t)(vl_bits - 1);
-                }
-            }
-        }
-        // ---- leftover key bits (sweep form): the dense number of nsym - 1 symbols is sorted in whole 8-bit passes; when its range
-        // leaves a factor part_m >= 2 of room, the NEXT symbol quantised to part_m levels rides along below it — order-preserving
-        // (monotone in the symbol), no extra pass or byte, fewer unresolved suffixes (16 GiB of UTF-8: 206^5 = 2^38.4 in 40 bits ->
-        // part_m = 2).  "The key ends inside the document" = key mod (base * part_m) == 0.  Like the variable-length keys it exists
-        // in the sweep kernels only; should the build fall back to another records form it is redone without.
-        TextGen part_gen{};
-        uint32_t part_m = 1;
-        if (!vl_bits && sizeof(V) == 8 && ix.partial_symbol && !ix.vl_off_once && tile_bytes && ix.sweep_records && ix.segmented_sort &&
-            ix.pack_entries && ix.narrow_keys && (int)ix.bits + ix.off_bits <= 40 && sigma <= 254 && nsym > 1 && nsym - 1 <= 10 &&
-            bbits != 999 && bbits <= 56 && rs_atomic_rank_ok(s) && rs_sweep_records_ok(bbase, nsym) && true) {
-            const int pbits = 8 * (int)ceil_div(bbits, 8);
-            unsigned __int128 range = 1;
-            for (int i = 0; i + 1 < nsym; ++i) range *= bbase;
-            const uint64_t room = (uint64_t)((((unsigned __int128)1) << pbits) / range);
-            const uint32_t m = (uint32_t)std::min<uint64_t>(room, bbase - 1);
-            if (m >= 2 && rs_part_setup(part_gen, bbase, m)) {
-                part_m = m;
-                bbits = bit_width64((uint64_t)(range * m - 1));
-                st.partial_levels = (int)m;
-            }
-        }
-        // (wider keys, up to 56 bits: dense u64 keys without low digits — still fewer passes than bit-aligned
-        //  symbols, the grouped gather and no separate histogram pass)
-        // packed entries (sa_bucket_records_packed_kernel): 8-byte entries below 2^40 travel as u32 + one byte on top of the
-        // low digits; up to three low digits then keep every key of <= 56 bits in (u32, u32, u8 / u16 / u32) records
-        const bool packed = sizeof(V) == 8 && ix.pack_entries && (int)ix.bits + ix.off_bits <= 40 && ix.narrow_keys && nsym > 1 &&
-                            bbits <= 56;
-        const int blow = bbits <= 32 ? 0 : (bbits <= 40 ? 8 : (bbits <= 48 ? 16 : (bbits <= 56 ? (packed ? 24 : 0) : -1)));
-        const bool bwide = !packed && bbits > 48 && bbits <= 56;
-        // (a one-symbol key leaves nothing behind the bucket symbol: its "ends inside the key" test would look at an
-        //  empty remainder, so that corner keeps the plain (u64 key, entry) records)
-        const bool brecords = ix.narrow_keys && blow >= 0 && nsym > 1;  // (codes up to 256 are u16 in the record kernel)
-        // FUSED form: when the records of ALL buckets fit the memory at once (one bucket group), the generated pass writes the
-        // records itself (radix_sort.h: radix_gen_records) — the entries are never partitioned on their own, no gather walks
-        // the text bucket by bucket (4 GiB of UTF-8: 22 ms partition + 32 ms gather -> one 28 ms pass + a 6 ms histogram
-        // sweep of the records), and the finished entries land in the record buffer the last pass does not read.
-        bool fuse_rec = false;
-        // (the tile stages symbol CODES as bytes: alphabets of all 256 byte values — codes up to 256 — keep the gather)
-        if (brecords && packed && sigma <= 255 && ix.segmented_sort && ix.fuse_records && sizeof(V) == 8 && rs_atomic_rank_ok(s) &&
-            (ix.bucket_group_limit == 0 || ix.bucket_group_limit >= n)) {
-            size_t fre = 0, tot = 0;
-            CDB_HIP(hipMemGetInfo(&fre, &tot));
-            const double avail = (double)fre + (double)DevPool::get().cached_bytes();
-            const int recb0 = 4 + (blow == 0 ? 1 : (blow == 8 ? 2 : 4)) + 4;
-            // (no separate entry array: the last pass writes the finished entries over the record buffer it does not read)
-            fuse_rec = avail * 0.85 / (2.0 * recb0 + 1.0 + (sa_packable(ix) ? 1.0 : 0.0)) >= (double)n;
-        }
-        // packed output (index_impl.h: Sa40): the last pass writes u32 low words over the KEY half it does not read and the high
-        // bytes into their own array — 5 instead of 8 bytes written per suffix, and the index keeps 5 n bytes instead of 8 n
-        const bool want_pack = sizeof(V) == 8 && sa_packable(ix);
-        // (allocate the record buffers NOW: if the device cannot provide them after all — fragmentation, other handles —
-        //  nothing has happened yet and the build takes partition + gather instead of failing)
-        DevBuf fr_kv[2], fr_e[2], fr_w[2];
-        if (fuse_rec) {
-            const size_t auxb0 = blow == 0 ? 1 : (blow == 8 ? 2 : 4);
-            try {
-                for (int q = 0; q < 2; ++q) {
-                    if (want_pack) {  // key and entry halves as blocks of their own: the key half of the dead buffer BECOMES the array
-                        fr_kv[q].alloc(n * sizeof(uint32_t));
-                        fr_e[q].alloc(n * sizeof(uint32_t));
-                    } else {
-                        fr_kv[q].alloc(n * 2 * sizeof(uint32_t));
-                    }
-                    fr_w[q].alloc(n * auxb0);
-                }
-                if (want_pack) sa_hi_buf.alloc(n);
-            } catch (const std::exception&) {
-                for (int q = 0; q < 2; ++q) {
-                    fr_kv[q].release();
-                    fr_e[q].release();
-                    fr_w[q].release();
-                }
-                sa_hi_buf.release();
-                (void)hipGetLastError();
-                fuse_rec = false;
-            }
-        }
-        packed_out = fuse_rec && want_pack;
-        // SWEEP form (records_sweep.h): the records do not fit at once, but with counted tile bases a sweep over the text can write
-        // the records of any bucket group in place — the entries are not partitioned and no gather re-reads them and the text
-        bool sweep_rec = !fuse_rec && tile_bytes && ix.sweep_records && brecords && packed && sigma <= 255 && ix.segmented_sort &&
-                         sizeof(V) == 8 && rs_atomic_rank_ok(s) && (vl_bits || rs_sweep_records_ok(bbase, nsym));
-        // (the fused form writes its records with the same kernel where it applies: one sweep that keeps every bucket — it beats the
-        //  generated pass of radix_gen_records, which carries whole records through the LDS: 4 GiB UTF-8 18.8 against 21.4 ms)
-        const bool sweep_fused = fuse_rec && tile_bytes && ix.sweep_records && (vl_bits || rs_sweep_records_ok(bbase, nsym));
-        // (variable-length keys exist in the sweep kernels only: build_suffix_array redoes the build with dense keys)
-        const char* vl_retry = "variable-length keys: the sweep form does not apply (retry with dense keys)";
-        if ((vl_bits || part_m > 1) && !sweep_rec && !sweep_fused) throw RetryWithDenseKeys(vl_retry);
-        // partition + gather with packed output: the partitioned entries ARE stored packed from the start (E = low words,
-        // sa_hi_buf = bits 32..39): the gather reads them through Sa40, the last pass of every group writes the finished
-        // entries back in that form — 16 GiB of text: 80 instead of 128 GiB of suffix array, during the build and after it
-        const bool pack_E = !fuse_rec && want_pack && packed && ix.segmented_sort && rs_atomic_rank_ok(s);
-        if (pack_E) {
-            E.alloc(n * sizeof(uint32_t));
-            sa_hi_buf.alloc(n);
-        } else if (!fuse_rec) {
-            E.alloc(n * sizeof(V));
-        }
-        st.alloc_ms += now_ms() - ta;
-        st.fused_records = fuse_rec ? 1 : 0;
-        DevBuf d_slotmap;
-        if (fuse_rec || sweep_rec) {
-            d_slotmap.alloc(260);
-            CDB_HIP(hipMemcpyAsync(d_slotmap.p, h_slotmap, 260, hipMemcpyHostToDevice, s));
-            CDB_HIP(hipStreamSynchronize(s));  // (h_slotmap is a stack array)
-        }
-        auto partition_entries = [&]() {
-            gen.first_only = true;
-            gen.symmap = d_symmap_first.as<uint16_t>();
-            const int fbits = std::max(1, bit_width64((uint64_t)sigma - 1));
-            if (pack_E) gen.vout_hi = sa_hi_buf.as<uint8_t>();
-            (void)radix_sort<uint64_t, V>(s, ix.rws, ix.prof, (uint64_t*)nullptr, (uint64_t*)nullptr, (V*)nullptr, E.as<V>(), n, 0, fbits,
-                                          &ss, ix.sort_variant, fbits, first_digit.data(), &gen);
-            radix_check_error(s, ix.rws);  // (the gathers below read the text through these entries)
-        };
-        if (!fuse_rec && !sweep_rec) {
-            // partition + gather reads no per-tile byte counts: they (1 KiB per 8 Ki positions: 2 GiB at 16 GiB of text) and the
-            // tile-base workspace go back to the pool BEFORE the record memory of the groups is sized
-            d_tbc.release();
-            ix.tbw.partial.release();
-            ix.tbw.blockbase.release();
-            ix.tbw.base.release();
-            partition_entries();
-        }
-        if (root_folded) {
-            uint64_t at = 0;
-            for (int k = 0; k < sigma; ++k) {
-                folded_roots.push_back(CompatBucket{(unsigned long long)at, (unsigned long long)(at + h_first[border[k]])});
-                at += h_first[border[k]];
-            }
-            st.root_folded = 1;
-            bool lo_class = false;
-            for (int b = 0; b < 128; ++b) lo_class |= h_map[b] != 0;
-            if (lo_class) st.compat_rotations += 1;  // (what the root rotation would have counted: both classes present)
-            // one level down: first-symbol buckets that are radix nodes of the reference (more than chuck suffixes) and
-            // hold children on both sides of 0x80 — their blocks are swapped by the segmented sort's last pass
-            if (ix.fold_depth1) {
-                DevBuf d_cls;
-                d_cls.alloc((512 + 768) * sizeof(uint64_t));
-                CDB_HIP(hipMemsetAsync(d_cls.p, 0, (512 + 768) * sizeof(uint64_t), s));
-                int t = ix.prof.begin(s);
-                if (!pair_hi_counted)  // (counted beside the bytes otherwise: sa_tile_bytecount_kernel<true>)
-                hipLaunchKernelGGL(sa_pairclass_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 256 * 16 * 4), 2048))),
-                                   dim3(256), 0, s, text, n, d_cls.as<unsigned long long>());
-                hipLaunchKernelGGL(sa_docend_class_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(D, 256), 1024))),
-                                   dim3(256), 0, s, text, doc_start, D, n, d_cls.as<unsigned long long>() + 512);
-                ix.prof.end(t, "sa_pairclass", n + D * 18, s);
-                std::vector<uint64_t> cls(512 + 768);
-                CDB_HIP(hipMemcpyAsync(cls.data(), d_cls.p, cls.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                uint64_t h_pair_hi[256];
-                if (pair_hi_counted) CDB_HIP(hipMemcpyAsync(h_pair_hi, d_pair_hi.p, sizeof(h_pair_hi), hipMemcpyDeviceToHost, s));
-                CDB_HIP(hipStreamSynchronize(s));
-                if (pair_hi_counted) {
-                    for (int b = 0; b < 256; ++b) {
-                        cls[2 * b + 1] = h_pair_hi[b];
-                        cls[2 * b] = h_counts[b] - h_pair_hi[b];
-                    }
-                    st.pairclass_fused = 1;
-                }
-                const uint64_t chuck1 = std::max<uint64_t>(4096, n / 256);
-                depth1.assign((size_t)sigma, Depth1Fold{});
-                for (int b = 0; b < 256; ++b) {
-                    if (!h_map[b]) continue;
-                    const uint64_t* pr = &cls[2 * b];
-                    const uint64_t* co = &cls[512 + 3 * b];
-                    Depth1Fold f;
-                    f.nend = co[2];
-                    f.nlow = pr[0] - co[0];
-                    f.nhigh = pr[1] - co[1];
-                    f.fold = h_counts[b] > chuck1 && f.nlow && f.nhigh && f.nend + f.nlow + f.nhigh == h_counts[b];
-                    int slot = 0;
-                    while (border[slot] != (int)h_map[b]) ++slot;
-                    depth1[slot] = f;
-                }
-            }
-        }
-        st.bucket_low_digits = brecords && blow > 0 ? blow / 8 : 0;
-        st.key_layout = brecords ? (packed ? 5 : (bwide ? 4 : (blow == 0 ? 1 : (blow == 8 ? 2 : 3)))) : 0;
-        if (brecords) {
-            // "the key ends inside the document" = key mod base == 0 (dense number) / its lowest bit clear (variable-length keys)
-            const uint32_t fbase = vl_bits ? 2u : bbase * part_m;
-            const uint64_t bmagic = (fbase & (fbase - 1u)) ? (uint64_t)(~0ull / fbase) + 1ull : 0ull;
-            const int bpass = (int)ceil_div(bbits, 8);
-            const int lowb = blow / 8;
-            const int keyb = bwide ? 8 : 4;  // bytes of the key part of a record
-            // non-empty buckets and their entry ranges
-            const uint32_t nb = (uint32_t)sigma;  // (every code stands for a byte that occurs)
-            std::vector<uint64_t> bstart(nb + 1, 0);  // entry ranges of the buckets, in bucket order
-            for (uint32_t b = 0; b < nb; ++b) bstart[b + 1] = bstart[b] + h_first[border[b]];
-            // where every bucket crosses the text chunks: 2 MiB, so that the chunk all concurrent work items read
-            // fits every XCD's 4 MB L2
-            const uint64_t chunk = 2ull << 20;  // (measured at 8 GiB: 1 MiB 61 ms, 2 MiB 60, 4 MiB 62, 16 MiB 88, 32 MiB 97)
-            const uint32_t nch = (uint32_t)ceil_div(n, chunk);
-            DevBuf d_bstart, d_bounds;
-            d_bstart.alloc((nb + 1) * 8);
-            d_bounds.alloc(fuse_rec ? 8 : (size_t)nb * (nch + 1) * 8);
-            CDB_HIP(hipMemcpyAsync(d_bstart.p, bstart.data(), (nb + 1) * 8, hipMemcpyHostToDevice, s));
-            auto bucket_bounds = [&]() {
-            if (pack_E)
-            hipLaunchKernelGGL((sa_bucket_bounds_kernel<Packed40>), dim3((unsigned)ceil_div((uint64_t)nb * (nch + 1), 256)), dim3(256), 0, s,
-                               Sa40{E.as<uint32_t>(), sa_hi_buf.as<uint8_t>()}, (const unsigned long long*)d_bstart.as<unsigned long long>(), nb,
-                               nch, chunk, doc_start, (int)ix.bits, ix.mask, d_bounds.as<unsigned long long>());
-            else if (!fuse_rec)
-            hipLaunchKernelGGL((sa_bucket_bounds_kernel<V>), dim3((unsigned)ceil_div((uint64_t)nb * (nch + 1), 256)), dim3(256), 0, s,
-                               (const V*)E.as<V>(), (const unsigned long long*)d_bstart.as<unsigned long long>(), nb, nch, chunk,
-                               doc_start, (int)ix.bits, ix.mask, d_bounds.as<unsigned long long>());
-            };
-            if (!sweep_rec) bucket_bounds();
-            // sweep form: array-wide tile bases of every bucket slot (4 GiB of them for 16 GiB of text: allocated BEFORE the record
-            // memory is sized; the counts they were made from go back to the pool), the document of every tile's first position
-            DevBuf sweep_doc, d_codeslot;
-            const unsigned long long* sweep_base = nullptr;
-            if (sweep_rec || sweep_fused) {
-                std::vector<uint16_t> codeslot(256, 0);  // byte -> symbol code | bucket slot << 8 (one lookup per text byte)
-                for (int b = 0; b < 256; ++b) codeslot[b] = (uint16_t)(h_map[b] | ((uint32_t)h_slotmap[h_map[b]] << 8));
-                d_codeslot.alloc(256 * sizeof(uint16_t));
-                CDB_HIP(hipMemcpyAsync(d_codeslot.p, codeslot.data(), 256 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-                std::vector<uint64_t> slot_start(256, n);
-                for (uint32_t b = 0; b < nb; ++b) slot_start[b] = bstart[b];
-                DevBuf d_slot_start;
-                d_slot_start.alloc(256 * sizeof(uint64_t));
-                CDB_HIP(hipMemcpyAsync(d_slot_start.p, slot_start.data(), 256 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-                int t = ix.prof.begin(s);
-                sweep_base = rs_tile_bases(s, ix.tbw, d_tbc.as<uint32_t>(), tiles8, d_src_col.as<uint16_t>(),
-                                           (const unsigned long long*)d_slot_start.as<unsigned long long>());
-                sweep_doc.alloc(((size_t)tiles8 + 1) * sizeof(uint64_t));
-                hipLaunchKernelGGL(rs_tiledoc_kernel, dim3((unsigned)ceil_div((uint64_t)tiles8 + 1, 256)), dim3(256), 0, s, doc_start, D, n,
-                                   (uint64_t)RS_SWEEP_TILE, (uint64_t)tiles8, sweep_doc.as<uint64_t>());
-                ix.prof.end(t, "rs_tile_bases", (uint64_t)tiles8 * 256 * (4 + 8), s);
-                CDB_HIP(hipStreamSynchronize(s));  // (slot_start, d_slot_start, codeslot)
-                d_tbc.release();
-                ix.tbw.partial.release();
-                ix.tbw.blockbase.release();
-            }
-            // groups of consecutive buckets whose records (4 + lowb bytes per suffix) fit the memory left
-            size_t fre = 0, tot = 0;
-            CDB_HIP(hipMemGetInfo(&fre, &tot));
-            const double avail = (double)fre + (double)DevPool::get().cached_bytes();
-            const int auxb = packed ? (lowb == 0 ? 1 : (lowb == 1 ? 2 : 4)) : lowb;  // bytes of the auxiliary array per suffix
-            const int recb = keyb + auxb + (packed ? 4 : 0);                         // record bytes per suffix of a group
-            // ---- segmented form (round 3): ONE launch per radix pass sorts every bucket of a group (radix_sort.h:
-            // radix_sort_segmented), the last pass writes entries + group flags itself, the gather is planned on the
-            // device and XCD-aware, and nothing in the group loop waits for the host.  Needs two record buffers per
-            // group (the passes ping-pong over the whole group) and a bucket is never split across groups.
-            uint64_t seg_cap = 0;
-            if (packed && ix.segmented_sort && sizeof(V) == 8 && rs_atomic_rank_ok(s)) {
-                const double per = 2.0 * recb + 1.0;  // + edge records (32 B per tile and digit)
-                uint64_t cap = (uint64_t)std::max(0.0, avail * 0.85 / per);
-                if (cap >= maxb) {
-                    if (ix.bucket_group_limit) cap = std::max<uint64_t>(std::min<uint64_t>(cap, ix.bucket_group_limit), maxb);
-                    seg_cap = std::min<uint64_t>(cap, n);
-                }
-                if (fuse_rec) seg_cap = n;  // (decided with the same bound before the entries were NOT partitioned)
-            }
-            if (!fuse_rec && ix.debug_no_segcap) seg_cap = 0;  // (test hook: "a bucket does not fit the record memory")
-            if (fuse_rec && !seg_cap) throw Error("bucket-wise build: fused records without the segmented sort (internal)");
-            if ((vl_bits || part_m > 1) && !seg_cap) throw RetryWithDenseKeys(vl_retry);
-            if (sweep_rec && !seg_cap) {  // (a bucket larger than the record memory: partition + gather, bucket by bucket)
-                sweep_rec = false;
-                sweep_doc.release();
-                ix.tbw.base.release();
-                partition_entries();
-                bucket_bounds();
-            }
-            if (pack_E && !seg_cap) {
-                // (a bucket larger than the record memory: the per-bucket forms below work on plain 8-byte entries)
-                if constexpr (sizeof(V) == 8) {
-                    DevBuf wide;
-                    wide.alloc(n * sizeof(uint64_t));
-                    Index tmp_view;  // (sa_expand wants an Index: borrow the two arrays for one call)
-                    tmp_view.stream = s;
-                    tmp_view.d_sa = std::move(E);
-                    tmp_view.d_sa_hi = std::move(sa_hi_buf);
-                    tmp_view.sa_packed = true;
-                    sa_expand(tmp_view, 0, n, wide.as<uint64_t>());
-                    CDB_HIP(hipStreamSynchronize(s));
-                    tmp_view.stream = nullptr;
-                    E = std::move(wide);
-                }
-            }
-            const bool pack_seg = pack_E && seg_cap;
-            auto run_segmented = [&](auto wtag) {
-                using W = decltype(wtag);
-                if constexpr (sizeof(V) == 8) {
-                    struct Group {
-                        uint32_t b0, b1, tiles, cells;
-                        uint64_t gstart, elems;
-                        GatherPlan plan;
-                    };
-                    std::vector<Group> groups;
-                    std::vector<SegInfo> h_segs(nb);
-                    uint32_t max_tiles = 0, max_gb = 0, max_cells = 0;
-                    uint64_t max_items = 0;
-                    for (uint32_t b0 = 0; b0 < nb;) {
-                        uint32_t b1 = b0 + 1;
-                        while (b1 < nb && bstart[b1 + 1] - bstart[b0] <= seg_cap) ++b1;
-                        Group g;
-                        g.b0 = b0;
-                        g.b1 = b1;
-                        g.gstart = bstart[b0];
-                        g.elems = bstart[b1] - bstart[b0];
-                        uint32_t tiles = 0;
-                        for (uint32_t b = b0; b < b1; ++b) {
-                            h_segs[b] = SegInfo{(unsigned long long)(bstart[b] - g.gstart), (unsigned long long)(bstart[b + 1] - g.gstart), tiles, 0u, 0ull, 0ull};
-                            if (!depth1.empty() && depth1[b].fold) {  // [end][low][high] is written as [end][high][low]
-                                h_segs[b].rot_a = depth1[b].nend;
-                                h_segs[b].rot_b = depth1[b].nend + depth1[b].nlow;
-                                depth1[b].done = true;
-                                st.compat_rotations += 1;
-                            }
-                            tiles += (uint32_t)ceil_div(bstart[b + 1] - bstart[b], (uint64_t)RS_SEG_TILE);
-                        }
-                        g.tiles = tiles;
-                        const uint32_t gb = b1 - b0;
-                        g.plan.cell_base[0] = 0;
-                        for (uint32_t x = 0; x < 8; ++x) g.plan.cell_base[x + 1] = g.plan.cell_base[x] + (x < nch ? (nch - x + 7) / 8 : 0u) * gb;
-                        g.cells = g.plan.cell_base[8];
-                        max_tiles = std::max(max_tiles, tiles);
-                        max_gb = std::max(max_gb, gb);
-                        max_cells = std::max(max_cells, g.cells);
-                        max_items = std::max<uint64_t>(max_items, g.elems / BR_ITEM + g.cells + 8);
-                        groups.push_back(g);
-                        b0 = b1;
-                    }
-                    uint64_t max_elems = 0;
-                    for (const Group& g : groups) max_elems = std::max(max_elems, g.elems);
-                    DevBuf kb[2], eb[2], wb[2], edges, d_starts, d_segs, tile_seg, cell_off, lists, d_items2, d_bh2;
-                    uint32_t *kbp[2], *ebp[2];
-                    // fused form: key and entry halves of a record buffer are ONE block, so that the last pass can write the
-                    // finished 8-byte entries over the buffer it does not read (the passes ping-pong: pass p reads buffer p & 1)
-                    // — that block then IS the suffix array, and no separate 8 n bytes are ever allocated
-                    const int dead = bpass & 1;
-                    for (int q = 0; q < 2; ++q) {
-                        if (fuse_rec) {
-                            kb[q] = std::move(fr_kv[q]);  // (allocated when the fused form was chosen: max_elems = n)
-                            kbp[q] = kb[q].as<uint32_t>();
-                            if (packed_out) {
-                                eb[q] = std::move(fr_e[q]);
-                                ebp[q] = eb[q].as<uint32_t>();
-                            } else {
-                                ebp[q] = kbp[q] + max_elems;
-                            }
-                            wb[q] = std::move(fr_w[q]);
-                            continue;
-                        } else {
-                            kb[q].alloc(max_elems * sizeof(uint32_t));
-                            eb[q].alloc(max_elems * sizeof(uint32_t));
-                            kbp[q] = kb[q].as<uint32_t>();
-                            ebp[q] = eb[q].as<uint32_t>();
-                        }
-                        wb[q].alloc(max_elems * sizeof(W));
-                    }
-                    edges.alloc((size_t)max_tiles * 256 * sizeof(SegEdge));
-                    d_starts.alloc((size_t)max_gb * 8 * 256 * sizeof(uint64_t));
-                    d_bh2.alloc((size_t)max_gb * 8 * 256 * sizeof(uint64_t));
-                    d_segs.alloc((size_t)nb * sizeof(SegInfo));
-                    tile_seg.alloc((size_t)max_tiles * sizeof(uint32_t));
-                    cell_off.alloc((size_t)max_cells * sizeof(uint32_t));
-                    lists.alloc(groups.size() * 16 * sizeof(uint32_t));  // per group: 8 list lengths, 8 tickets
-                    d_items2.alloc((size_t)max_items * sizeof(BucketItem));
-                    st.alloc_ms += now_ms() - ta;
-                    CDB_HIP(hipMemcpyAsync(d_segs.p, h_segs.data(), (size_t)nb * sizeof(SegInfo), hipMemcpyHostToDevice, s));
-                    CDB_HIP(hipMemsetAsync(lists.p, 0, groups.size() * 16 * sizeof(uint32_t), s));
-                    const unsigned long long* bnd = d_bounds.as<unsigned long long>();
-                    for (size_t gi = 0; gi < groups.size(); ++gi) {
-                        const Group& g = groups[gi];
-                        const uint32_t gb = g.b1 - g.b0;
-                        uint32_t* list_len = lists.as<uint32_t>() + gi * 16;
-                        uint32_t* tickets = list_len + 8;
-                        if (fuse_rec && !sweep_fused) {
-                            {
-                                hipLaunchKernelGGL(rs_seg_tilemap_kernel, dim3((unsigned)ceil_div(g.tiles, 256)), dim3(256), 0, s,
-                                                   (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, tile_seg.as<uint32_t>());
-                                TextGen rg{text, doc_start, d_symmap.as<uint16_t>(), D, (int)ix.bits, bbase, nsym, 0, ix.text_padded};
-                                rg.slotmap = d_slotmap.as<uint8_t>();
-                                rg.rec_low_bits = blow;
-                                radix_gen_records<W>(s, ix.rws, ix.prof, kbp[0], ebp[0], wb[0].as<W>(), n,
-                                                     first_digit.data(), rg, (const uint32_t*)tile_seg.as<uint32_t>(),
-                                                     (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, lowb, bpass,
-                                                     d_bh2.as<unsigned long long>(), &ss,
-                                                     tile_bytes ? (const uint32_t*)d_tbc.as<uint32_t>() : nullptr,
-                                                     tile_bytes ? (const uint16_t*)d_src_col.as<uint16_t>() : nullptr, tile_bytes ? &ix.tbw : nullptr);
-                                st.gen_prebased = tile_bytes ? 1 : 0;
-                            }
-                        } else if (sweep_rec || sweep_fused) {
-                            hipLaunchKernelGGL(rs_seg_tilemap_kernel, dim3((unsigned)ceil_div(g.tiles, 256)), dim3(256), 0, s,
-                                               (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, tile_seg.as<uint32_t>());
-                            TextGen rg{text, doc_start, d_symmap.as<uint16_t>(), D, (int)ix.bits, bbase, nsym, 0, ix.text_padded};
-                            rg.slotmap = d_slotmap.as<uint8_t>();
-                            rg.rec_low_bits = blow;
-                            rg.part_m = part_m;
-                            rg.part_r = part_gen.part_r;
-                            rg.part_s = part_gen.part_s;
-                            rg.tile_doc = sweep_doc.as<uint64_t>();
-                            rg.tile_base = sweep_base;
-                            if (vl_bits) {
-                                VlTables vt;
-                                vt.sym = d_vl_sym.as<uint16_t>();
-                                vt.dec = d_vl_dec.as<uint16_t>();
-                                vt.key_bits = vl_bits;
-                                vt.end_len = vlc.end_len;
-                                radix_sweep_records_vl<W>(s, ix.prof, kbp[0], ebp[0], wb[0].as<W>(), n, rg, (const uint16_t*)d_codeslot.as<uint16_t>(), vt,
-                                                          g.b0, g.b1, g.gstart, g.elems, (const uint32_t*)tile_seg.as<uint32_t>(),
-                                                          (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, lowb, bpass,
-                                                          d_bh2.as<unsigned long long>(), &ss);
-                            } else
-                            radix_sweep_records<W>(s, ix.prof, kbp[0], ebp[0], wb[0].as<W>(), n, rg, (const uint16_t*)d_codeslot.as<uint16_t>(), g.b0, g.b1,
-                                                   g.gstart, g.elems,
-                                                   (const uint32_t*)tile_seg.as<uint32_t>(), (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb,
-                                                   g.tiles, lowb, bpass, d_bh2.as<unsigned long long>(), &ss);
-                            st.sweep_records = 1;
-                            st.gen_prebased = 1;
-                        } else {
-                        CDB_HIP(hipMemsetAsync(d_bh2.p, 0, (size_t)gb * 8 * 256 * sizeof(uint64_t), s));
-                        int t = ix.prof.begin(s);
-                        hipLaunchKernelGGL(sa_gather_plan_kernel, dim3(8), dim3(1024), 0, s, bnd, nch, g.b0, gb, g.plan, cell_off.as<uint32_t>(),
-                                           list_len);
-                        hipLaunchKernelGGL(sa_gather_emit_kernel, dim3((unsigned)ceil_div(g.cells, 256)), dim3(256), 0, s, bnd, nch, g.b0, gb,
-                                           g.plan, (const uint32_t*)cell_off.as<uint32_t>(), (const uint32_t*)list_len,
-                                           d_items2.as<BucketItem>());
-                        ix.prof.end(t, "sa_gather_plan", (uint64_t)g.cells * 24 + (g.elems / BR_ITEM) * sizeof(BucketItem), s);
-                        t = ix.prof.begin(s);
-                        constexpr unsigned gather_wgs = 256u * 8u;
-                        if (pack_seg)
-                        hipLaunchKernelGGL((sa_bucket_records_lists_kernel<W, Packed40>), dim3(gather_wgs), dim3(256), 0, s,
-                                           Sa40{E.as<uint32_t>(), sa_hi_buf.as<uint8_t>()},
-                                           (const BucketItem*)d_items2.as<BucketItem>(), (const uint32_t*)list_len, tickets, text, n, doc_start,
-                                           (const uint16_t*)d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, bbase, blow, bpass, g.gstart,
-                                           g.b0, kbp[0], wb[0].as<W>(), ebp[0], d_bh2.as<unsigned long long>());
-                        else
-                        hipLaunchKernelGGL((sa_bucket_records_lists_kernel<W>), dim3(gather_wgs), dim3(256), 0, s, (const uint64_t*)E.as<uint64_t>(),
-                                           (const BucketItem*)d_items2.as<BucketItem>(), (const uint32_t*)list_len, tickets, text, n, doc_start,
-                                           (const uint16_t*)d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, bbase, blow, bpass, g.gstart,
-                                           g.b0, kbp[0], wb[0].as<W>(), ebp[0], d_bh2.as<unsigned long long>());
-                        ix.prof.end(t, "sa_bucket_records", g.elems * ((uint64_t)nsym + recb + sizeof(V)), s);
-                        st.gather_items += g.elems / BR_ITEM;
-                        hipLaunchKernelGGL(rs_seg_tilemap_kernel, dim3((unsigned)ceil_div(g.tiles, 256)), dim3(256), 0, s,
-                                           (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, tile_seg.as<uint32_t>());
-                        }
-                        SegFinalArgs fin;
-                        if (pack_seg) {
-                            fin.elo = E.as<uint32_t>() + g.gstart;
-                            fin.ehi = sa_hi_buf.as<uint8_t>() + g.gstart;
-                        } else if (packed_out) {
-                            fin.elo = kbp[dead] + g.gstart;
-                            fin.ehi = sa_hi_buf.as<uint8_t>() + g.gstart;
-                        } else {
-                            fin.eout = (fuse_rec ? kb[dead].as<uint64_t>() : E.as<uint64_t>()) + g.gstart;
-                        }
-                        fin.flags = flags.as<uint8_t>() + g.gstart;
-                        fin.edges = edges.as<SegEdge>();
-                        fin.hi_shift = blow;
-                        fin.low_bits = blow;
-                        fin.kbase = fbase;
-                        fin.kmagic = bmagic;
-                        radix_sort_segmented<W>(s, ix.rws, ix.prof, kbp[0], kbp[1], ebp[0], ebp[1], wb[0].as<W>(), wb[1].as<W>(), g.elems,
-                                                (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), (const uint32_t*)tile_seg.as<uint32_t>(), gb,
-                                                g.tiles, (const unsigned long long*)d_bh2.as<unsigned long long>(),
-                                                d_starts.as<unsigned long long>(), bbits - blow, lowb, fin, &ss);
-                        st.bucket_groups++;
-                    }
-                    CDB_HIP(hipStreamSynchronize(s));  // (h_segs and the group scratch go out of scope)
-                    if (sweep_rec || sweep_fused) ix.tbw.base.release();
-                    if (fuse_rec) E = std::move(kb[dead]);
-                    if (pack_seg) packed_out = true;
-                    st.segmented = 1;
-                }
-            };
-            if (seg_cap) {
-                if (lowb == 0) run_segmented(uint8_t{});
-                else if (lowb == 1) run_segmented(uint16_t{});
-                else run_segmented(uint32_t{});
-            } else {
-            std::vector<uint64_t> bounds((size_t)nb * (nch + 1));
-            CDB_HIP(hipMemcpyAsync(bounds.data(), d_bounds.p, bounds.size() * 8, hipMemcpyDeviceToHost, s));
-            CDB_HIP(hipStreamSynchronize(s));
-            // (the third entry buffer is a luxury: without it an odd number of passes costs a copy back)
-            const bool third = !packed && avail > (double)maxb * (2.0 * (keyb + lowb) + 2 * sizeof(V)) * 1.15;
-            const double scratch = packed ? (double)maxb * recb
-                                          : (double)maxb * (keyb + lowb + (third ? 2 : 1) * sizeof(V)) +
-                                                (third ? (double)(n / 32) * (sizeof(I) + 16 + 2 * sizeof(V) + 1) : 0.0);
-            uint64_t gcap = (uint64_t)std::max(0.0, (avail - scratch) * 0.85 / recb);
-            if (ix.bucket_group_limit) gcap = std::min<uint64_t>(gcap, ix.bucket_group_limit);
-            gcap = std::max<uint64_t>(std::min<uint64_t>(gcap, n), maxb);
-            DevBuf k32g, lowg, k32t, lowt, ET, EX, elog, elot, d_bh, d_items;
-            k32g.alloc(gcap * keyb);
-            if (auxb) lowg.alloc(gcap * auxb);
-            k32t.alloc(maxb * keyb);
-            if (auxb) lowt.alloc(maxb * auxb);
-            if (packed) {
-                elog.alloc(gcap * sizeof(uint32_t));
-                elot.alloc(maxb * sizeof(uint32_t));
-            } else {
-                ET.alloc(maxb * sizeof(V));
-                if (third) EX.alloc(maxb * sizeof(V));  // third entry buffer: an odd number of passes still ends in place (radix_sort.h)
-            }
-            std::vector<uint64_t> bh;
-            std::vector<BucketItem> items;
-            auto run_group = [&](auto wtag, auto ktag, uint32_t b0, uint32_t b1) {  // buckets [b0, b1)
-                using W = decltype(wtag);
-                using K = decltype(ktag);
-                constexpr bool HAS_W = !std::is_same<W, NoVal>::value;
-                using FW = typename std::conditional<HAS_W, W, uint8_t>::type;
-                const uint64_t gstart = bstart[b0];
-                const uint32_t gb = b1 - b0;
-                d_bh.ensure((size_t)gb * 8 * 256 * sizeof(uint64_t));
-                CDB_HIP(hipMemsetAsync(d_bh.p, 0, (size_t)gb * 8 * 256 * sizeof(uint64_t), s));
-                items.clear();
-                for (uint32_t x = 0; x < nch; ++x)      // text chunk major: the group's buckets share the cached text
-                    for (uint32_t b = b0; b < b1; ++b) {
-                        const uint64_t lo = bounds[(size_t)b * (nch + 1) + x], hi = bounds[(size_t)b * (nch + 1) + x + 1];
-                        for (uint64_t o = lo; o < hi; o += BR_ITEM)
-                            items.push_back(BucketItem{(unsigned long long)o, (uint32_t)std::min<uint64_t>(BR_ITEM, hi - o), b});
-                    }
-                st.gather_items += items.size();
-                if (!items.empty()) {
-                    d_items.ensure(items.size() * sizeof(BucketItem));
-                    CDB_HIP(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(BucketItem), hipMemcpyHostToDevice, s));
-                    int t = ix.prof.begin(s);
-                    hipLaunchKernelGGL((sa_bucket_records_kernel<V, W, K>), dim3((unsigned)items.size()), dim3(256), 0, s,
-                                       (const V*)E.as<V>(), (const BucketItem*)d_items.as<BucketItem>(), text, n, doc_start,
-                                       (const uint16_t*)d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, bbase, blow, bpass,
-                                       gstart, b0, k32g.as<K>(), lowg.as<W>(), d_bh.as<unsigned long long>());
-                    ix.prof.end(t, "sa_bucket_records", (bstart[b1] - gstart) * ((uint64_t)nsym + keyb + lowb + sizeof(V)), s);
-                }
-                // (the per-bucket digit histograms stay on the device: the sorts below are queued without a single host
-                //  round trip; this one synchronisation per GROUP only protects `items`, rebuilt for the next group)
-                CDB_HIP(hipStreamSynchronize(s));
-                for (uint32_t b = b0; b < b1; ++b) {
-                    const uint64_t start = bstart[b], cnt = bstart[b + 1] - start;
-                    V* eb = E.as<V>() + start;
-                    K* kb = k32g.as<K>() + (start - gstart);
-                    FW* lb = HAS_W ? lowg.as<FW>() + (start - gstart) : (FW*)nullptr;
-                    int r = 0;
-                    if (bpass > 0 && cnt > 1) {
-                        const unsigned long long* hb = d_bh.as<unsigned long long>() + (size_t)(b - b0) * 8 * 256;
-                        ix.rws.value_spare = EX.p;  // (null without the third buffer)
-                        if constexpr (HAS_W)
-                            r = radix_sort_split<V, W>(s, ix.rws, ix.prof, kb, k32t.as<uint32_t>(), eb, ET.as<V>(), lb, lowt.as<W>(), cnt,
-                                                       bbits - blow, &ss, ix.sort_variant, 8, (const uint64_t*)nullptr,
-                                                       (const TextGen*)nullptr, 0, hb);
-                        else
-                            r = radix_sort<K, V>(s, ix.rws, ix.prof, kb, k32t.as<K>(), eb, ET.as<V>(), cnt, 0, bbits, &ss,
-                                                 ix.sort_variant, 8, (const uint64_t*)nullptr, (const TextGen*)nullptr, hb);
-                        if (ix.rws.value_result == 1) CDB_HIP(hipMemcpyAsync(eb, ET.p, cnt * sizeof(V), hipMemcpyDeviceToDevice, s));
-                    }
-                    if constexpr (sizeof(K) == 8)
-                        hipLaunchKernelGGL(sa_initflags_kernel, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
-                                           (const uint64_t*)(r ? k32t.as<uint64_t>() : (uint64_t*)kb), cnt, bbase, bmagic,
-                                           flags.as<uint8_t>() + start, (start & 3) == 0);
-                    else
-                        hipLaunchKernelGGL(sa_initflags32_kernel<FW>, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
-                                           (const uint32_t*)(r ? k32t.as<uint32_t>() : (uint32_t*)kb),
-                                           HAS_W ? (const FW*)(r ? lowt.as<FW>() : lb) : (const FW*)nullptr, blow, cnt, bbase, bmagic,
-                                           flags.as<uint8_t>() + start, (start & 3) == 0);
-                }
-            };
-            auto run_group_packed = [&](auto wtag, uint32_t b0, uint32_t b1) {  // buckets [b0, b1), packed entries
-                using W = decltype(wtag);
-                if constexpr (sizeof(V) == 8) {
-                    const uint64_t gstart = bstart[b0];
-                    const uint32_t gb = b1 - b0;
-                    d_bh.ensure((size_t)gb * 8 * 256 * sizeof(uint64_t));
-                    CDB_HIP(hipMemsetAsync(d_bh.p, 0, (size_t)gb * 8 * 256 * sizeof(uint64_t), s));
-                    items.clear();
-                    for (uint32_t x = 0; x < nch; ++x)      // text chunk major: the group's buckets share the cached text
-                        for (uint32_t b = b0; b < b1; ++b) {
-                            const uint64_t lo = bounds[(size_t)b * (nch + 1) + x], hi = bounds[(size_t)b * (nch + 1) + x + 1];
-                            for (uint64_t o = lo; o < hi; o += BR_ITEM)
-                                items.push_back(BucketItem{(unsigned long long)o, (uint32_t)std::min<uint64_t>(BR_ITEM, hi - o), b});
-                        }
-                    st.gather_items += items.size();
-                    if (!items.empty()) {
-                        d_items.ensure(items.size() * sizeof(BucketItem));
-                        CDB_HIP(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(BucketItem), hipMemcpyHostToDevice, s));
-                        int t = ix.prof.begin(s);
-                        hipLaunchKernelGGL((sa_bucket_records_packed_kernel<W>), dim3((unsigned)items.size()), dim3(256), 0, s,
-                                           (const uint64_t*)E.as<uint64_t>(), (const BucketItem*)d_items.as<BucketItem>(), text, n,
-                                           doc_start, (const uint16_t*)d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, bbase,
-                                           blow, bpass, gstart, b0, k32g.as<uint32_t>(), lowg.as<W>(), elog.as<uint32_t>(),
-                                           d_bh.as<unsigned long long>());
-                        ix.prof.end(t, "sa_bucket_records", (bstart[b1] - gstart) * ((uint64_t)nsym + recb + sizeof(V)), s);
-                    }
-                    CDB_HIP(hipStreamSynchronize(s));  // (protects `items`, rebuilt for the next group)
-                    for (uint32_t b = b0; b < b1; ++b) {
-                        const uint64_t start = bstart[b], cnt = bstart[b + 1] - start;
-                        uint32_t* kb = k32g.as<uint32_t>() + (start - gstart);
-                        uint32_t* vb = elog.as<uint32_t>() + (start - gstart);
-                        W* lb = lowg.as<W>() + (start - gstart);
-                        int r = 0, vr = 0;
-                        if (bpass > 0 && cnt > 1) {
-                            const unsigned long long* hb = d_bh.as<unsigned long long>() + (size_t)(b - b0) * 8 * 256;
-                            ix.rws.value_spare = nullptr;
-                            r = radix_sort_split<uint32_t, W>(s, ix.rws, ix.prof, kb, k32t.as<uint32_t>(), vb, elot.as<uint32_t>(), lb,
-                                                              lowt.as<W>(), cnt, bbits - blow, &ss, ix.sort_variant, 8,
-                                                              (const uint64_t*)nullptr, (const TextGen*)nullptr, 0, hb, lowb);
-                            vr = ix.rws.value_result;
-                        }
-                        const W* ls = r ? lowt.as<W>() : lb;
-                        int t = ix.prof.begin(s);
-                        hipLaunchKernelGGL(sa_assemble_entries_kernel<W>, dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, s,
-                                           (const uint32_t*)(vr ? elot.as<uint32_t>() : vb), ls, blow, cnt, E.as<uint64_t>() + start);
-                        ix.prof.end(t, "sa_assemble_entries", cnt * (4 + sizeof(W) + 8), s);
-                        hipLaunchKernelGGL(sa_initflags32_kernel<W>, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
-                                           (const uint32_t*)(r ? k32t.as<uint32_t>() : kb), lowb ? ls : (const W*)nullptr, blow, cnt,
-                                           bbase, bmagic, flags.as<uint8_t>() + start, (start & 3) == 0);
-                    }
-                }
-            };
-            for (uint32_t b0 = 0; b0 < nb;) {
-                uint32_t b1 = b0 + 1;
-                while (b1 < nb && bstart[b1 + 1] - bstart[b0] <= gcap) ++b1;
-                if (packed && lowb == 0) run_group_packed(uint8_t{}, b0, b1);
-                else if (packed && lowb == 1) run_group_packed(uint16_t{}, b0, b1);
-                else if (packed) run_group_packed(uint32_t{}, b0, b1);
-                else if (bwide) run_group(NoVal{}, uint64_t{}, b0, b1);
-                else if (blow == 0) run_group(NoVal{}, uint32_t{}, b0, b1);
-                else if (blow == 8) run_group(uint8_t{}, uint32_t{}, b0, b1);
-                else run_group(uint16_t{}, uint32_t{}, b0, b1);
-                st.bucket_groups++;
-                b0 = b1;
-            }
-            }  // (per-bucket launches)
-        } else {
-        KT[0].alloc(maxb * sizeof(uint64_t));
-        if (nsym > 1 && maxb > 1) {
-            KT[1].alloc(maxb * sizeof(uint64_t));
-            ET.alloc(maxb * sizeof(V));
-        }
-        uint64_t start = 0;
-        for (int k = 0; k < sigma; ++k) {
-            const uint64_t cnt = h_first[border[k]];
-            if (!cnt) continue;
-            V* eb = E.as<V>() + start;
-            int t = ix.prof.begin(s);
-            hipLaunchKernelGGL((sa_bucket_keys_kernel<V>), dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, s, (const V*)eb, cnt,
-                               text, n, doc_start, (const uint16_t*)d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, symbits,
-                               KT[0].as<uint64_t>());
-            ix.prof.end(t, "sa_bucket_keys", cnt * ((uint64_t)nsym + 8 + sizeof(V)), s);
-            int r = 0;
-            if (nsym > 1 && cnt > 1) {
-                r = radix_sort<uint64_t, V>(s, ix.rws, ix.prof, KT[0].as<uint64_t>(), KT[1].as<uint64_t>(), eb, ET.as<V>(), cnt, 0,
-                                            top_shift, &ss, ix.sort_variant, dbits);
-                if (r == 1) CDB_HIP(hipMemcpyAsync(eb, ET.p, cnt * sizeof(V), hipMemcpyDeviceToDevice, s));
-            }
-            hipLaunchKernelGGL(sa_initflags_kernel, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
-                               (const uint64_t*)KT[r].as<uint64_t>(), cnt, kbase, kmagic, flags.as<uint8_t>() + start,
-                               (start & 3) == 0);
-            start += cnt;
-        }
-        }
-        CDB_HIP(hipStreamSynchronize(s));
-        st.bucketed = 1;
-        sa_buf = std::move(E);
+        out.sorted_keys = std::move(keys[sel]);
+        out.sa_buf = std::move(vals[sel]);
     }
-    bool tile_sums_ready = flags_by_sort;  // the raw tile sums of the first compaction are in scan_partials already
-    st.flags_in_last_pass = flags_by_sort ? 1 : 0;
-    if (!big && !flags_by_sort) {  // (the bucket-wise sort writes the flags itself)
+    out.tile_sums_ready = out.flags_by_sort;
+    st.flags_in_last_pass = out.flags_by_sort ? 1 : 0;
+    if (!out.flags_by_sort) {
         int t = ix.prof.begin(s);
         if (layout == WIDE)
             hipLaunchKernelGGL(sa_initflags_kernel, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, s,
-                               (const uint64_t*)sorted_keys.as<uint64_t>(), n, kbase, kmagic, flags.as<uint8_t>(), true);
+                               (const uint64_t*)out.sorted_keys.as<uint64_t>(), n, kbase, kmagic, out.flags.as<uint8_t>(), true);
         else {
             // (the flag kernel leaves the per-tile counts of unresolved entries for the first compaction: no second sweep
             //  over the flags for them)
             const uint64_t nbt = ceil_div(n, (uint64_t)SC_TILE);
             ix.scan_partials.ensure(scan_partials_slots(nbt) * sizeof(U2));
             CDB_HIP(hipMemsetAsync(ix.scan_partials.p, 0, nbt * sizeof(U2), s));
-            tile_sums_ready = true;
+            out.tile_sums_ready = true;
             if (layout == SPLIT2)
                 hipLaunchKernelGGL(sa_initflags32_kernel<uint16_t>, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, s,
-                                   (const uint32_t*)sorted_k32.as<uint32_t>(), (const uint16_t*)sorted_low.as<uint16_t>(), low_bits,
-                                   n, kbase, kmagic, flags.as<uint8_t>(), true, ix.scan_partials.as<U2>());
+                                   (const uint32_t*)out.sorted_k32.as<uint32_t>(), (const uint16_t*)out.sorted_low.as<uint16_t>(), low_bits,
+                                   n, kbase, kmagic, out.flags.as<uint8_t>(), true, ix.scan_partials.as<U2>());
             else
                 hipLaunchKernelGGL(sa_initflags32_kernel<uint8_t>, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, s,
-                                   (const uint32_t*)sorted_k32.as<uint32_t>(),
-                                   layout == SPLIT ? (const uint8_t*)sorted_low.as<uint8_t>() : (const uint8_t*)nullptr, low_bits,
-                                   n, kbase, kmagic, flags.as<uint8_t>(), true, ix.scan_partials.as<U2>());
+                                   (const uint32_t*)out.sorted_k32.as<uint32_t>(),
+                                   layout == SPLIT ? (const uint8_t*)out.sorted_low.as<uint8_t>() : (const uint8_t*)nullptr, low_bits,
+                                   n, kbase, kmagic, out.flags.as<uint8_t>(), true, ix.scan_partials.as<U2>());
         }
         ix.prof.end(t, "sa_initflags", n * (layout == WIDE ? 9 : 5 + low_bytes), s);
     }
-    // (a starved pass of the initial sort left garbage entries: the refinement below would index the text with them —
-    //  the error surfaces HERE, before anything dereferences an entry; build_suffix_array redoes the build in plain order)
-    radix_check_error(s, ix.rws);
-    ta = now_ms();
-    // The sorted keys stay valid for the finished array: refinement only permutes entries inside groups
-    // of equal keys.  They let a search probe decide on ONE load (query.hip) — kept when affordable.
-    ix.drop_keys();
-    if (ix.keep_keys && !big && n * 8 <= (16ull << 30)) {
-        ix.d_keys = std::move(sorted_keys);
-        ix.d_keys32 = std::move(sorted_k32);
-        ix.d_keylow = std::move(sorted_low);
-        ix.key_low_bits = low_bits;
-        ix.key_low_bytes = low_bytes;
-        ix.key_nsym = nsym;
-        ix.key_base = kbase;
-    } else {
-        sorted_keys.release();
-        sorted_k32.release();
-        sorted_low.release();
-    }
-    st.free_ms += now_ms() - ta;
+    return out;
+}
 
-    // ---- 4. refinement rounds
-    // slot order of the array as the bucket-wise build laid it out -> plain unsigned order (ranks of prefix doubling)
-    DevBuf d_order;
-    SlotOrder order;
-    if (!folded_roots.empty()) {
-        struct Blk { unsigned long long a, len; int code, cls; };  // cls: 0 = end of document, 1 = bytes < 0x80, 2 = bytes >= 0x80
-        std::vector<Blk> blks;
-        std::vector<int> code_of_root;  // first-symbol code of every root bucket, in array order
-        {
-            for (int b = 128; b < 256; ++b) if (h_map[b]) code_of_root.push_back(h_map[b]);
-            for (int b = 0; b < 128; ++b) if (h_map[b]) code_of_root.push_back(h_map[b]);
-        }
-        for (size_t b = 0; b < folded_roots.size(); ++b) {
-            const CompatBucket r = folded_roots[b];
-            if (!depth1.empty() && depth1[b].done) {  // written as [end][high][low]
-                blks.push_back(Blk{r.lo, depth1[b].nend, code_of_root[b], 0});
-                blks.push_back(Blk{r.lo + depth1[b].nend, depth1[b].nhigh, code_of_root[b], 2});
-                blks.push_back(Blk{r.lo + depth1[b].nend + depth1[b].nhigh, depth1[b].nlow, code_of_root[b], 1});
-            } else {
-                blks.push_back(Blk{r.lo, r.hi - r.lo, code_of_root[b], 0});
+// ---- bucket-wise build: the first-symbol buckets
+// Every position starts a suffix, and a suffix is never empty: the first symbol is never "end of document", so
+// the partition digit is code - 1 (0 .. alphabet - 1: 8 bits even for all 256 byte values, where the codes
+// 1 .. 256 themselves need 9) and its histogram is simply the byte histogram.
+// Bucket order = ascending code, or — reference_compat order on text with bytes >= 0x80 — the reference's child
+// order of the ROOT radix node (index.h:66-73: bytes 0x80..0xFF in front of 0x00..0x7F): the first-symbol buckets
+// then sit where apply_reference_order's root rotation (three reversals of the whole array) would put them.
+struct Buckets {
+    bool root_folded = false;
+    std::vector<int> border;  // symbol codes in bucket order
+    std::vector<uint64_t> first_by_code, first_digit;  // (first_by_code: indexed by symbol code 1 .. alphabet)
+    uint8_t h_slotmap[260] = {0};  // symbol code -> bucket slot (the fused records pass)
+    DevBuf d_symmap_first;
+    DevBuf d_src_col;  // (look-back-free generated passes: which byte's per-tile counts feed bucket slot d; 0xFFFF = no such slot)
+    uint64_t maxb = 0;
+};
+
+void make_buckets(Index& ix, const Alphabet& al, Buckets& bk) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size;
+    const int sigma = al.sigma;
+    const uint16_t* h_map = al.h_map;
+    bk.root_folded = ix.reference_compat && al.high_bytes && ix.fold_root && n > std::max<uint64_t>(4096, n / 256);
+    std::vector<int>& border = bk.border;
+    if (bk.root_folded) {
+        for (int b = 128; b < 256; ++b)
+            if (h_map[b]) border.push_back(h_map[b]);
+        for (int b = 0; b < 128; ++b)
+            if (h_map[b]) border.push_back(h_map[b]);
+    } else {
+        for (int c = 1; c <= sigma; ++c) border.push_back(c);
+    }
+    bk.first_by_code.assign(258, 0);
+    bk.first_digit.assign(256, 0);
+    uint16_t h_map_first[256];
+    {
+        int slot_of_code[258] = {0};
+        for (int k = 0; k < sigma; ++k) slot_of_code[border[k]] = k;
+        for (int c = 1; c <= sigma; ++c) bk.h_slotmap[c] = (uint8_t)slot_of_code[c];
+        for (int b = 0; b < 256; ++b) {
+            h_map_first[b] = h_map[b] ? (uint16_t)slot_of_code[h_map[b]] : (uint16_t)0;
+            if (h_map[b]) {
+                bk.first_by_code[h_map[b]] = al.h_counts[b];
+                bk.first_digit[slot_of_code[h_map[b]]] = al.h_counts[b];
             }
         }
-        // unsigned order: by first-symbol code, inside a bucket [end][low][high]
-        std::vector<size_t> by_u(blks.size());
-        for (size_t i = 0; i < by_u.size(); ++i) by_u[i] = i;
-        std::sort(by_u.begin(), by_u.end(), [&](size_t x, size_t y) {
-            return blks[x].code != blks[y].code ? blks[x].code < blks[y].code : blks[x].cls < blks[y].cls;
-        });
-        std::vector<unsigned long long> tab(2 * blks.size());
-        unsigned long long at = 0;
-        for (size_t i : by_u) {
-            tab[blks.size() + i] = at;
-            at += blks[i].len;
-        }
-        for (size_t i = 0; i < blks.size(); ++i) tab[i] = blks[i].a;
-        d_order.alloc(tab.size() * sizeof(unsigned long long));
-        CDB_HIP(hipMemcpyAsync(d_order.p, tab.data(), tab.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-        CDB_HIP(hipStreamSynchronize(s));
-        order.a_start = d_order.as<unsigned long long>();
-        order.u_start = d_order.as<unsigned long long>() + blks.size();
-        order.nseg = (uint32_t)blks.size();
     }
+    bk.d_symmap_first.alloc(256 * sizeof(uint16_t));
+    CDB_HIP(hipMemcpyAsync(bk.d_symmap_first.p, h_map_first, sizeof(h_map_first), hipMemcpyHostToDevice, s));
+    uint16_t h_src_col[256];
+    for (int d = 0; d < 256; ++d) h_src_col[d] = 0xFFFFu;
+    for (int b = 0; b < 256; ++b)
+        if (h_map[b]) h_src_col[h_map_first[b]] = (uint16_t)b;
+    if (al.tile_bytes) {
+        bk.d_src_col.alloc(sizeof(h_src_col));
+        CDB_HIP(hipMemcpyAsync(bk.d_src_col.p, h_src_col, sizeof(h_src_col), hipMemcpyHostToDevice, s));
+    }
+    CDB_HIP(hipStreamSynchronize(s));  // (h_map_first is a stack array)
+    for (int c = 1; c <= sigma; ++c) bk.maxb = std::max(bk.maxb, bk.first_by_code[c]);
+}
+
+// Bucket records.  Inside a bucket the first symbol is constant, so the sort key is the remaining
+// nsym - 1 symbols — as a dense base-(alphabet + 1) number, split like the records of the single-sort
+// path when it fits 32 bits + one or two low digits: (u32, entry, u8 / u16) instead of (u64, entry).
+// The form is decided before any record is written.
+struct RecordForm {
+    uint32_t bbase = 0;
+    int bbits = 0;  // bits of bbase^(nsym-1) - 1; 999 beyond 56 bits
+    VlCode vlc;
+    int vl_bits = 0;
+    DevBuf d_vl_sym, d_vl_dec;
+    TextGen part_gen{};
+    uint32_t part_m = 1;
+    bool packed = false, bwide = false, brecords = false;
+    int blow = 0;
+    bool fuse_rec = false, want_pack = false, sweep_rec = false, sweep_fused = false, pack_E = false;
+    DevBuf fr_kv[2], fr_e[2], fr_w[2];  // fused form: the record buffers, allocated when it was chosen
+};
+
+// (variable-length keys exist in the sweep kernels only: build_suffix_array redoes the build with dense keys)
+constexpr const char* kVlRetry = "variable-length keys: the sweep form does not apply (retry with dense keys)";
+
+template <typename V>
+void choose_record_form(Index& ix, const Alphabet& al, const KeyPlan& kp, const Buckets& bk, RecordForm& rf, InitialSort& out) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, D = ix.ndocs;
+    BuildStats& st = ix.bstats;
+    const int sigma = al.sigma, nsym = kp.nsym;
+    const bool tile_bytes = al.tile_bytes;
+    const uint64_t* h_first = bk.first_by_code.data();
+    const uint32_t bbase = rf.bbase = (uint32_t)sigma + 1u;
+    int& bbits = rf.bbits;
+    {
+        unsigned __int128 v = 1;
+        for (int i = 0; i + 1 < nsym && bbits != 999; ++i) {
+            v *= bbase;
+            if (v > ((unsigned __int128)1 << 56)) bbits = 999;
+        }
+        if (bbits != 999) bbits = bit_width64((uint64_t)(v - 1));
+    }
+    // ---- variable-length keys (vl_code.h): the first B - 1 bits of the suffix's alphabetic code stream + a "continues" bit instead
+    // of the dense number, when the model of key_cost_model says they are cheaper — skewed text, where equal prefixes are made of
+    // frequent symbols with short code words (8 GiB of Zipf-64 text: 40 key bits = 5 passes over 10-byte records instead of 54 bits
+    // = 7 passes over 12-byte records).  Needs the sweep form (the key of a position is a window into the tile's bit stream).
+    VlCode& vlc = rf.vlc;
+    int& vl_bits = rf.vl_bits;
+    if (sizeof(V) == 8 && ix.vl_keys != 0 && !ix.vl_off_once && tile_bytes && ix.sweep_records && ix.segmented_sort && ix.pack_entries &&
+        ix.narrow_keys && (int)ix.bits + ix.off_bits <= 40 && sigma >= 2 && sigma <= 127 && nsym > 1 && rs_atomic_rank_ok(s) &&
+        (ix.vl_keys != 2 || (ix.initial_passes == 0 && ix.key_symbols == 0))) {
+        uint64_t cnts[257] = {0};
+        cnts[0] = D;
+        for (int c = 1; c <= sigma; ++c) cnts[c] = h_first[c];
+        if (vl_build(cnts, sigma, vlc)) {
+            auto rec_bytes = [](int b) { return 8.0 + (b <= 32 ? 1.0 : (b <= 40 ? 2.0 : 4.0)); };
+            const double refine_bytes = 2000.0;  // (what a text-extension round costs per unresolved suffix: key_cost_model above)
+            // the sample measured the dense key's unresolved share; the order-0 model q^k says what it "should" be — their ratio
+            // carries the text's correlation over to the estimate for the code stream: share(B) = ratio n q 2^(-rate (B - 1))
+            // (measured where the sample SEES collisions — the longest prefix with >= 50 colliding sample pairs; at the key width
+            //  that was chosen it sees none by construction, and "none" is no measurement: a first version divided 0 by the model
+            //  and took 32-bit code-stream keys for 16 GiB of printable ASCII, 12 % unresolved)
+            const double ratio = kp.est_k0n > 0 ? std::min(1e3, std::max(0.2, kp.est_k0 / std::max(std::pow(vlc.q, (double)kp.est_k0n), 1e-300))) : 1.0;
+            const double u_fixed = std::min(1.0, ratio * (double)n * std::pow(vlc.q, (double)nsym));
+            const double cost_fixed = bbits != 999 ? std::ceil(bbits / 8.0) * 2.0 * rec_bytes(bbits) + u_fixed * refine_bytes : 1e9;
+            auto share = [&](int B) { return std::min(1.0, ratio * (double)n * vlc.q * std::pow(2.0, -vlc.rate * (double)(B - 1))); };
+            int best_b = 0;
+            double best = 1e18;
+            // (with these keys the text-extension rounds start every group at the depth its key really covered, so the open
+            //  suffixes are settled in one or two rounds: ~1000 B each — 8 GiB of Zipf text, B = 40: 46 ms for 206 M of them)
+            const double refine_bytes_vl = 1000.0;
+            for (int B : {32, 40, 48, 56}) {
+                const double u = share(B);
+                if (u > 1.0 / 24.0) continue;  // (text extension wants few open suffixes; the estimate errs on the high side)
+                const double c = (double)(B / 8) * 2.0 * rec_bytes(B) + u * refine_bytes_vl + 6.0;  // (+ 6: the tile's bit offsets)
+                if (c < best) {
+                    best = c;
+                    best_b = B;
+                }
+            }
+            if (ix.vl_keys >= 16) best_b = std::min(56, (ix.vl_keys + 7) / 8 * 8);
+            else if (ix.vl_keys == 1 && !best_b) best_b = 56;
+            // (automatic mode also wants a code that really is shorter than the dense number's log2(alphabet + 1) bits per symbol:
+            //  on a flat alphabet the code stream can only lose)
+            const bool shorter = vlc.avg_len <= 0.93 * std::log2((double)sigma + 1.0);
+            if (best_b && (ix.vl_keys != 2 || (shorter && best < 0.93 * cost_fixed))) {
+                vl_bits = best_b;
+                bbits = vl_bits;
+                std::vector<uint16_t> sym(256, 0), dec(128, (uint16_t)(0xFFu | ((unsigned)vlc.end_len << 8)));
+                for (int c = 0; c <= sigma; ++c) {
+                    sym[c] = (uint16_t)(vlc.bits[c] | ((unsigned)vlc.len[c] << 8));
+                    if (c == 0) continue;
+                    const int l = vlc.len[c];
+                    for (unsigned x = 0; x < (1u << (VL_MAX_LEN - l)); ++x)
+                        dec[((unsigned)vlc.bits[c] << (VL_MAX_LEN - l)) | x] = (uint16_t)(bk.h_slotmap[c] | ((unsigned)l << 8));
+                }
+                rf.d_vl_sym.alloc(256 * sizeof(uint16_t));
+                rf.d_vl_dec.alloc(128 * sizeof(uint16_t));
+                CDB_HIP(hipMemcpyAsync(rf.d_vl_sym.p, sym.data(), 256 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+                CDB_HIP(hipMemcpyAsync(rf.d_vl_dec.p, dec.data(), 128 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+                CDB_HIP(hipStreamSynchronize(s));  // (sym, dec)
+                st.vl_key_bits = vl_bits;
+                st.vl_avg_len = vlc.avg_len;
+                st.vl_rate = vlc.rate;
+                st.vl_est_unresolved = share(vl_bits);
+                st.fixed_est_unresolved = u_fixed;
+                // every key covers at least this many whole symbols behind the bucket symbol: where the refinement starts
+                out.refine_depth0 = 1 + (uint64_t)((vl_bits - 1) / vlc.max_len);
+                // (the text-extension rounds start every group at the depth its key really covered: code-word length per text byte)
+                std::vector<uint8_t> blen(256, 0);
+                for (int b = 0; b < 256; ++b) blen[b] = al.h_map[b] ? vlc.len[al.h_map[b]] : (uint8_t)0;
+                out.d_vl_bytelen.alloc(256);
+                CDB_HIP(hipMemcpyAsync(out.d_vl_bytelen.p, blen.data(), 256, hipMemcpyHostToDevice, s));
+                CDB_HIP(hipStreamSynchronize(s));  // (blen)
+                out.vl_kb1 = (uint32_t)(vl_bits - 1);
+            }
+        }
+    }
+    // ---- leftover key bits (sweep form): the dense number of nsym - 1 symbols is sorted in whole 8-bit passes; when its range
+    // leaves a factor part_m >= 2 of room, the NEXT symbol quantised to part_m levels rides along below it — order-preserving
+    // (monotone in the symbol), no extra pass or byte, fewer unresolved suffixes (16 GiB of UTF-8: 206^5 = 2^38.4 in 40 bits ->
+    // part_m = 2).  "The key ends inside the document" = key mod (base * part_m) == 0.  Like the variable-length keys it exists
+    // in the sweep kernels only; should the build fall back to another records form it is redone without.
+    if (!vl_bits && sizeof(V) == 8 && ix.partial_symbol && !ix.vl_off_once && tile_bytes && ix.sweep_records && ix.segmented_sort &&
+        ix.pack_entries && ix.narrow_keys && (int)ix.bits + ix.off_bits <= 40 && sigma <= 254 && nsym > 1 && nsym - 1 <= 10 &&
+        bbits != 999 && bbits <= 56 && rs_atomic_rank_ok(s) && rs_sweep_records_ok(bbase, nsym)) {
+        const int pbits = 8 * (int)ceil_div(bbits, 8);
+        unsigned __int128 range = 1;
+        for (int i = 0; i + 1 < nsym; ++i) range *= bbase;
+        const uint64_t room = (uint64_t)((((unsigned __int128)1) << pbits) / range);
+        const uint32_t m = (uint32_t)std::min<uint64_t>(room, bbase - 1);
+        if (m >= 2 && rs_part_setup(rf.part_gen, bbase, m)) {
+            rf.part_m = m;
+            bbits = bit_width64((uint64_t)(range * m - 1));
+            st.partial_levels = (int)m;
+        }
+    }
+    // (wider keys, up to 56 bits: dense u64 keys without low digits — still fewer passes than bit-aligned
+    //  symbols, the grouped gather and no separate histogram pass)
+    // packed entries (sa_bucket_records_packed_kernel): 8-byte entries below 2^40 travel as u32 + one byte on top of the
+    // low digits; up to three low digits then keep every key of <= 56 bits in (u32, u32, u8 / u16 / u32) records
+    const bool packed = rf.packed = sizeof(V) == 8 && ix.pack_entries && (int)ix.bits + ix.off_bits <= 40 && ix.narrow_keys && nsym > 1 &&
+                                    bbits <= 56;
+    const int blow = rf.blow = bbits <= 32 ? 0 : (bbits <= 40 ? 8 : (bbits <= 48 ? 16 : (bbits <= 56 ? (packed ? 24 : 0) : -1)));
+    rf.bwide = !packed && bbits > 48 && bbits <= 56;
+    // (a one-symbol key leaves nothing behind the bucket symbol: its "ends inside the key" test would look at an
+    //  empty remainder, so that corner keeps the plain (u64 key, entry) records)
+    const bool brecords = rf.brecords = ix.narrow_keys && blow >= 0 && nsym > 1;  // (codes up to 256 are u16 in the record kernel)
+    // FUSED form: when the records of ALL buckets fit the memory at once (one bucket group), the generated pass writes the
+    // records itself (radix_sort.h: radix_gen_records) — the entries are never partitioned on their own, no gather walks
+    // the text bucket by bucket (4 GiB of UTF-8: 22 ms partition + 32 ms gather -> one 28 ms pass + a 6 ms histogram
+    // sweep of the records), and the finished entries land in the record buffer the last pass does not read.
+    bool& fuse_rec = rf.fuse_rec;
+    // (the tile stages symbol CODES as bytes: alphabets of all 256 byte values — codes up to 256 — keep the gather)
+    if (brecords && packed && sigma <= 255 && ix.segmented_sort && ix.fuse_records && sizeof(V) == 8 && rs_atomic_rank_ok(s) &&
+        (ix.bucket_group_limit == 0 || ix.bucket_group_limit >= n)) {
+        size_t fre = 0, tot = 0;
+        CDB_HIP(hipMemGetInfo(&fre, &tot));
+        const double avail = (double)fre + (double)DevPool::get().cached_bytes();
+        const int recb0 = 4 + (blow == 0 ? 1 : (blow == 8 ? 2 : 4)) + 4;
+        // (no separate entry array: the last pass writes the finished entries over the record buffer it does not read)
+        fuse_rec = avail * 0.85 / (2.0 * recb0 + 1.0 + (sa_packable(ix) ? 1.0 : 0.0)) >= (double)n;
+    }
+    // packed output (index_impl.h: Sa40): the last pass writes u32 low words over the KEY half it does not read and the high
+    // bytes into their own array — 5 instead of 8 bytes written per suffix, and the index keeps 5 n bytes instead of 8 n
+    const bool want_pack = rf.want_pack = sizeof(V) == 8 && sa_packable(ix);
+    // (allocate the record buffers NOW: if the device cannot provide them after all — fragmentation, other handles —
+    //  nothing has happened yet and the build takes partition + gather instead of failing)
+    if (fuse_rec) {
+        const size_t auxb0 = blow == 0 ? 1 : (blow == 8 ? 2 : 4);
+        try {
+            for (int q = 0; q < 2; ++q) {
+                if (want_pack) {  // key and entry halves as blocks of their own: the key half of the dead buffer BECOMES the array
+                    rf.fr_kv[q].alloc(n * sizeof(uint32_t));
+                    rf.fr_e[q].alloc(n * sizeof(uint32_t));
+                } else {
+                    rf.fr_kv[q].alloc(n * 2 * sizeof(uint32_t));
+                }
+                rf.fr_w[q].alloc(n * auxb0);
+            }
+            if (want_pack) out.sa_hi_buf.alloc(n);
+        } catch (const std::exception&) {
+            for (int q = 0; q < 2; ++q) {
+                rf.fr_kv[q].release();
+                rf.fr_e[q].release();
+                rf.fr_w[q].release();
+            }
+            out.sa_hi_buf.release();
+            (void)hipGetLastError();
+            fuse_rec = false;
+        }
+    }
+    out.packed_out = fuse_rec && want_pack;
+    // SWEEP form (records_sweep.h): the records do not fit at once, but with counted tile bases a sweep over the text can write
+    // the records of any bucket group in place — the entries are not partitioned and no gather re-reads them and the text
+    rf.sweep_rec = !fuse_rec && tile_bytes && ix.sweep_records && brecords && packed && sigma <= 255 && ix.segmented_sort &&
+                   sizeof(V) == 8 && rs_atomic_rank_ok(s) && (vl_bits || rs_sweep_records_ok(bbase, nsym));
+    // (the fused form writes its records with the same kernel where it applies: one sweep that keeps every bucket — it beats the
+    //  generated pass of radix_gen_records, which carries whole records through the LDS: 4 GiB UTF-8 18.8 against 21.4 ms)
+    rf.sweep_fused = fuse_rec && tile_bytes && ix.sweep_records && (vl_bits || rs_sweep_records_ok(bbase, nsym));
+    if ((vl_bits || rf.part_m > 1) && !rf.sweep_rec && !rf.sweep_fused) throw RetryWithDenseKeys(kVlRetry);
+    // partition + gather with packed output: the partitioned entries ARE stored packed from the start (E = low words,
+    // sa_hi_buf = bits 32..39): the gather reads them through Sa40, the last pass of every group writes the finished
+    // entries back in that form — 16 GiB of text: 80 instead of 128 GiB of suffix array, during the build and after it
+    rf.pack_E = !fuse_rec && want_pack && packed && ix.segmented_sort && rs_atomic_rank_ok(s);
+}
+
+// bucket-wise build in the reference's root order: the first-symbol buckets, and one level down the buckets whose suffixes
+// the segmented sort's last pass writes with their two byte blocks swapped
+void fold_root_buckets(Index& ix, const Alphabet& al, const Buckets& bk, InitialSort& out) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, D = ix.ndocs;
+    BuildStats& st = ix.bstats;
+    const uint8_t* text = ix.d_text;
+    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
+    const int sigma = al.sigma;
+    const uint16_t* h_map = al.h_map;
+    const uint64_t* h_first = bk.first_by_code.data();
+    uint64_t at = 0;
+    for (int k = 0; k < sigma; ++k) {
+        out.folded_roots.push_back(CompatBucket{(unsigned long long)at, (unsigned long long)(at + h_first[bk.border[k]])});
+        at += h_first[bk.border[k]];
+    }
+    st.root_folded = 1;
+    bool lo_class = false;
+    for (int b = 0; b < 128; ++b) lo_class |= h_map[b] != 0;
+    if (lo_class) st.compat_rotations += 1;  // (what the root rotation would have counted: both classes present)
+    // one level down: first-symbol buckets that are radix nodes of the reference (more than chuck suffixes) and
+    // hold children on both sides of 0x80 — their blocks are swapped by the segmented sort's last pass
+    if (!ix.fold_depth1) return;
+    DevBuf d_cls;
+    d_cls.alloc((512 + 768) * sizeof(uint64_t));
+    CDB_HIP(hipMemsetAsync(d_cls.p, 0, (512 + 768) * sizeof(uint64_t), s));
+    int t = ix.prof.begin(s);
+    if (!al.pair_hi_counted)  // (counted beside the bytes otherwise: sa_tile_bytecount_kernel<true>)
+    hipLaunchKernelGGL(sa_pairclass_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 256 * 16 * 4), 2048))),
+                       dim3(256), 0, s, text, n, d_cls.as<unsigned long long>());
+    hipLaunchKernelGGL(sa_docend_class_kernel, dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(D, 256), 1024))),
+                       dim3(256), 0, s, text, doc_start, D, n, d_cls.as<unsigned long long>() + 512);
+    ix.prof.end(t, "sa_pairclass", n + D * 18, s);
+    std::vector<uint64_t> cls(512 + 768);
+    CDB_HIP(hipMemcpyAsync(cls.data(), d_cls.p, cls.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    uint64_t h_pair_hi[256];
+    if (al.pair_hi_counted) CDB_HIP(hipMemcpyAsync(h_pair_hi, al.d_pair_hi.p, sizeof(h_pair_hi), hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipStreamSynchronize(s));
+    if (al.pair_hi_counted) {
+        for (int b = 0; b < 256; ++b) {
+            cls[2 * b + 1] = h_pair_hi[b];
+            cls[2 * b] = al.h_counts[b] - h_pair_hi[b];
+        }
+        st.pairclass_fused = 1;
+    }
+    const uint64_t chuck1 = std::max<uint64_t>(4096, n / 256);
+    out.depth1.assign((size_t)sigma, Depth1Fold{});
+    for (int b = 0; b < 256; ++b) {
+        if (!h_map[b]) continue;
+        const uint64_t* pr = &cls[2 * b];
+        const uint64_t* co = &cls[512 + 3 * b];
+        Depth1Fold f;
+        f.nend = co[2];
+        f.nlow = pr[0] - co[0];
+        f.nhigh = pr[1] - co[1];
+        f.fold = al.h_counts[b] > chuck1 && f.nlow && f.nhigh && f.nend + f.nlow + f.nhigh == al.h_counts[b];
+        int slot = 0;
+        while (bk.border[slot] != (int)h_map[b]) ++slot;
+        out.depth1[slot] = f;
+    }
+}
+
+// bucket-wise record forms: the buckets' entry ranges, where they cross the text chunks and the record geometry — what
+// the segmented group loop and the per-bucket loop read
+struct BucketRecords {
+    // "the key ends inside the document" = key mod base == 0 (dense number) / its lowest bit clear (variable-length keys)
+    uint32_t fbase = 0;
+    uint64_t bmagic = 0;
+    int bpass = 0, lowb = 0;
+    int keyb = 4;  // bytes of the key part of a record
+    int auxb = 0;  // bytes of the auxiliary array per suffix
+    int recb = 0;  // record bytes per suffix of a group
+    uint32_t nb = 0;
+    std::vector<uint64_t> bstart;  // entry ranges of the buckets, in bucket order
+    // where every bucket crosses the text chunks: 2 MiB, so that the chunk all concurrent work items read
+    // fits every XCD's 4 MB L2
+    uint64_t chunk = 2ull << 20;  // (measured at 8 GiB: 1 MiB 61 ms, 2 MiB 60, 4 MiB 62, 16 MiB 88, 32 MiB 97)
+    uint32_t nch = 0;
+    DevBuf d_bstart, d_bounds;
+    // sweep form: array-wide tile bases of every bucket slot, the document of every tile's first position
+    DevBuf sweep_doc, d_codeslot;
+    const unsigned long long* sweep_base = nullptr;
+    double avail = 0;
+};
+
+// ---- segmented form (round 3): ONE launch per radix pass sorts every bucket of a group (radix_sort.h:
+// radix_sort_segmented), the last pass writes entries + group flags itself, the gather is planned on the
+// device and XCD-aware, and nothing in the group loop waits for the host.  Needs two record buffers per
+// group (the passes ping-pong over the whole group) and a bucket is never split across groups.
+template <typename V, typename W>
+void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Buckets& bk, RecordForm& rf, const BucketRecords& br,
+                   uint64_t seg_cap, const DevBuf& d_slotmap, DevBuf& E, InitialSort& out, SortStats& ss, double ta) {
+    if constexpr (sizeof(V) == 8) {
+        hipStream_t s = ix.stream;
+        const uint64_t n = ix.size, D = ix.ndocs;
+        BuildStats& st = ix.bstats;
+        const uint8_t* text = ix.d_text;
+        const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
+        const int nsym = kp.nsym;
+        const uint32_t nb = br.nb, nch = br.nch, bbase = rf.bbase;
+        const std::vector<uint64_t>& bstart = br.bstart;
+        const int blow = rf.blow, bpass = br.bpass, lowb = br.lowb, recb = br.recb;
+        const bool fuse_rec = rf.fuse_rec, sweep_rec = rf.sweep_rec, sweep_fused = rf.sweep_fused, tile_bytes = al.tile_bytes;
+        const bool pack_seg = rf.pack_E;
+        std::vector<Depth1Fold>& depth1 = out.depth1;
+        struct Group {
+            uint32_t b0, b1, tiles, cells;
+            uint64_t gstart, elems;
+            GatherPlan plan;
+        };
+        std::vector<Group> groups;
+        std::vector<SegInfo> h_segs(nb);
+        uint32_t max_tiles = 0, max_gb = 0, max_cells = 0;
+        uint64_t max_items = 0;
+        for (uint32_t b0 = 0; b0 < nb;) {
+            uint32_t b1 = b0 + 1;
+            while (b1 < nb && bstart[b1 + 1] - bstart[b0] <= seg_cap) ++b1;
+            Group g;
+            g.b0 = b0;
+            g.b1 = b1;
+            g.gstart = bstart[b0];
+            g.elems = bstart[b1] - bstart[b0];
+            uint32_t tiles = 0;
+            for (uint32_t b = b0; b < b1; ++b) {
+                h_segs[b] = SegInfo{(unsigned long long)(bstart[b] - g.gstart), (unsigned long long)(bstart[b + 1] - g.gstart), tiles, 0u, 0ull, 0ull};
+                if (!depth1.empty() && depth1[b].fold) {  // [end][low][high] is written as [end][high][low]
+                    h_segs[b].rot_a = depth1[b].nend;
+                    h_segs[b].rot_b = depth1[b].nend + depth1[b].nlow;
+                    depth1[b].done = true;
+                    st.compat_rotations += 1;
+                }
+                tiles += (uint32_t)ceil_div(bstart[b + 1] - bstart[b], (uint64_t)RS_SEG_TILE);
+            }
+            g.tiles = tiles;
+            const uint32_t gb = b1 - b0;
+            g.plan.cell_base[0] = 0;
+            for (uint32_t x = 0; x < 8; ++x) g.plan.cell_base[x + 1] = g.plan.cell_base[x] + (x < nch ? (nch - x + 7) / 8 : 0u) * gb;
+            g.cells = g.plan.cell_base[8];
+            max_tiles = std::max(max_tiles, tiles);
+            max_gb = std::max(max_gb, gb);
+            max_cells = std::max(max_cells, g.cells);
+            max_items = std::max<uint64_t>(max_items, g.elems / BR_ITEM + g.cells + 8);
+            groups.push_back(g);
+            b0 = b1;
+        }
+        uint64_t max_elems = 0;
+        for (const Group& g : groups) max_elems = std::max(max_elems, g.elems);
+        DevBuf kb[2], eb[2], wb[2], edges, d_starts, d_segs, tile_seg, cell_off, lists, d_items2, d_bh2;
+        uint32_t *kbp[2], *ebp[2];
+        // fused form: key and entry halves of a record buffer are ONE block, so that the last pass can write the
+        // finished 8-byte entries over the buffer it does not read (the passes ping-pong: pass p reads buffer p & 1)
+        // — that block then IS the suffix array, and no separate 8 n bytes are ever allocated
+        const int dead = bpass & 1;
+        for (int q = 0; q < 2; ++q) {
+            if (fuse_rec) {
+                kb[q] = std::move(rf.fr_kv[q]);  // (allocated when the fused form was chosen: max_elems = n)
+                kbp[q] = kb[q].as<uint32_t>();
+                if (out.packed_out) {
+                    eb[q] = std::move(rf.fr_e[q]);
+                    ebp[q] = eb[q].as<uint32_t>();
+                } else {
+                    ebp[q] = kbp[q] + max_elems;
+                }
+                wb[q] = std::move(rf.fr_w[q]);
+                continue;
+            } else {
+                kb[q].alloc(max_elems * sizeof(uint32_t));
+                eb[q].alloc(max_elems * sizeof(uint32_t));
+                kbp[q] = kb[q].as<uint32_t>();
+                ebp[q] = eb[q].as<uint32_t>();
+            }
+            wb[q].alloc(max_elems * sizeof(W));
+        }
+        edges.alloc((size_t)max_tiles * 256 * sizeof(SegEdge));
+        d_starts.alloc((size_t)max_gb * 8 * 256 * sizeof(uint64_t));
+        d_bh2.alloc((size_t)max_gb * 8 * 256 * sizeof(uint64_t));
+        d_segs.alloc((size_t)nb * sizeof(SegInfo));
+        tile_seg.alloc((size_t)max_tiles * sizeof(uint32_t));
+        cell_off.alloc((size_t)max_cells * sizeof(uint32_t));
+        lists.alloc(groups.size() * 16 * sizeof(uint32_t));  // per group: 8 list lengths, 8 tickets
+        d_items2.alloc((size_t)max_items * sizeof(BucketItem));
+        st.alloc_ms += now_ms() - ta;
+        CDB_HIP(hipMemcpyAsync(d_segs.p, h_segs.data(), (size_t)nb * sizeof(SegInfo), hipMemcpyHostToDevice, s));
+        CDB_HIP(hipMemsetAsync(lists.p, 0, groups.size() * 16 * sizeof(uint32_t), s));
+        const unsigned long long* bnd = br.d_bounds.as<unsigned long long>();
+        for (size_t gi = 0; gi < groups.size(); ++gi) {
+            const Group& g = groups[gi];
+            const uint32_t gb = g.b1 - g.b0;
+            uint32_t* list_len = lists.as<uint32_t>() + gi * 16;
+            uint32_t* tickets = list_len + 8;
+            if (fuse_rec && !sweep_fused) {
+                {
+                    hipLaunchKernelGGL(rs_seg_tilemap_kernel, dim3((unsigned)ceil_div(g.tiles, 256)), dim3(256), 0, s,
+                                       (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, tile_seg.as<uint32_t>());
+                    TextGen rg{text, doc_start, al.d_symmap.as<uint16_t>(), D, (int)ix.bits, bbase, nsym, 0, ix.text_padded};
+                    rg.slotmap = d_slotmap.as<uint8_t>();
+                    rg.rec_low_bits = blow;
+                    radix_gen_records<W>(s, ix.rws, ix.prof, kbp[0], ebp[0], wb[0].as<W>(), n,
+                                         bk.first_digit.data(), rg, (const uint32_t*)tile_seg.as<uint32_t>(),
+                                         (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, lowb, bpass,
+                                         d_bh2.as<unsigned long long>(), &ss,
+                                         tile_bytes ? (const uint32_t*)al.d_tbc.as<uint32_t>() : nullptr,
+                                         tile_bytes ? (const uint16_t*)bk.d_src_col.as<uint16_t>() : nullptr, tile_bytes ? &ix.tbw : nullptr);
+                    st.gen_prebased = tile_bytes ? 1 : 0;
+                }
+            } else if (sweep_rec || sweep_fused) {
+                hipLaunchKernelGGL(rs_seg_tilemap_kernel, dim3((unsigned)ceil_div(g.tiles, 256)), dim3(256), 0, s,
+                                   (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, tile_seg.as<uint32_t>());
+                TextGen rg{text, doc_start, al.d_symmap.as<uint16_t>(), D, (int)ix.bits, bbase, nsym, 0, ix.text_padded};
+                rg.slotmap = d_slotmap.as<uint8_t>();
+                rg.rec_low_bits = blow;
+                rg.part_m = rf.part_m;
+                rg.part_r = rf.part_gen.part_r;
+                rg.part_s = rf.part_gen.part_s;
+                rg.tile_doc = br.sweep_doc.as<uint64_t>();
+                rg.tile_base = br.sweep_base;
+                if (rf.vl_bits) {
+                    VlTables vt;
+                    vt.sym = rf.d_vl_sym.as<uint16_t>();
+                    vt.dec = rf.d_vl_dec.as<uint16_t>();
+                    vt.key_bits = rf.vl_bits;
+                    vt.end_len = rf.vlc.end_len;
+                    radix_sweep_records_vl<W>(s, ix.prof, kbp[0], ebp[0], wb[0].as<W>(), n, rg, (const uint16_t*)br.d_codeslot.as<uint16_t>(), vt,
+                                              g.b0, g.b1, g.gstart, g.elems, (const uint32_t*)tile_seg.as<uint32_t>(),
+                                              (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, lowb, bpass,
+                                              d_bh2.as<unsigned long long>(), &ss);
+                } else
+                radix_sweep_records<W>(s, ix.prof, kbp[0], ebp[0], wb[0].as<W>(), n, rg, (const uint16_t*)br.d_codeslot.as<uint16_t>(), g.b0, g.b1,
+                                       g.gstart, g.elems,
+                                       (const uint32_t*)tile_seg.as<uint32_t>(), (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb,
+                                       g.tiles, lowb, bpass, d_bh2.as<unsigned long long>(), &ss);
+                st.sweep_records = 1;
+                st.gen_prebased = 1;
+            } else {
+            CDB_HIP(hipMemsetAsync(d_bh2.p, 0, (size_t)gb * 8 * 256 * sizeof(uint64_t), s));
+            int t = ix.prof.begin(s);
+            hipLaunchKernelGGL(sa_gather_plan_kernel, dim3(8), dim3(1024), 0, s, bnd, nch, g.b0, gb, g.plan, cell_off.as<uint32_t>(),
+                               list_len);
+            hipLaunchKernelGGL(sa_gather_emit_kernel, dim3((unsigned)ceil_div(g.cells, 256)), dim3(256), 0, s, bnd, nch, g.b0, gb,
+                               g.plan, (const uint32_t*)cell_off.as<uint32_t>(), (const uint32_t*)list_len,
+                               d_items2.as<BucketItem>());
+            ix.prof.end(t, "sa_gather_plan", (uint64_t)g.cells * 24 + (g.elems / BR_ITEM) * sizeof(BucketItem), s);
+            t = ix.prof.begin(s);
+            constexpr unsigned gather_wgs = 256u * 8u;
+            if (pack_seg)
+            hipLaunchKernelGGL((sa_bucket_records_lists_kernel<W, Packed40>), dim3(gather_wgs), dim3(256), 0, s,
+                               Sa40{E.as<uint32_t>(), out.sa_hi_buf.as<uint8_t>()},
+                               (const BucketItem*)d_items2.as<BucketItem>(), (const uint32_t*)list_len, tickets, text, n, doc_start,
+                               (const uint16_t*)al.d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, bbase, blow, bpass, g.gstart,
+                               g.b0, kbp[0], wb[0].as<W>(), ebp[0], d_bh2.as<unsigned long long>());
+            else
+            hipLaunchKernelGGL((sa_bucket_records_lists_kernel<W>), dim3(gather_wgs), dim3(256), 0, s, (const uint64_t*)E.as<uint64_t>(),
+                               (const BucketItem*)d_items2.as<BucketItem>(), (const uint32_t*)list_len, tickets, text, n, doc_start,
+                               (const uint16_t*)al.d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, bbase, blow, bpass, g.gstart,
+                               g.b0, kbp[0], wb[0].as<W>(), ebp[0], d_bh2.as<unsigned long long>());
+            ix.prof.end(t, "sa_bucket_records", g.elems * ((uint64_t)nsym + recb + sizeof(V)), s);
+            st.gather_items += g.elems / BR_ITEM;
+            hipLaunchKernelGGL(rs_seg_tilemap_kernel, dim3((unsigned)ceil_div(g.tiles, 256)), dim3(256), 0, s,
+                               (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, tile_seg.as<uint32_t>());
+            }
+            SegFinalArgs fin;
+            if (pack_seg) {
+                fin.elo = E.as<uint32_t>() + g.gstart;
+                fin.ehi = out.sa_hi_buf.as<uint8_t>() + g.gstart;
+            } else if (out.packed_out) {
+                fin.elo = kbp[dead] + g.gstart;
+                fin.ehi = out.sa_hi_buf.as<uint8_t>() + g.gstart;
+            } else {
+                fin.eout = (fuse_rec ? kb[dead].as<uint64_t>() : E.as<uint64_t>()) + g.gstart;
+            }
+            fin.flags = out.flags.as<uint8_t>() + g.gstart;
+            fin.edges = edges.as<SegEdge>();
+            fin.hi_shift = blow;
+            fin.low_bits = blow;
+            fin.kbase = br.fbase;
+            fin.kmagic = br.bmagic;
+            radix_sort_segmented<W>(s, ix.rws, ix.prof, kbp[0], kbp[1], ebp[0], ebp[1], wb[0].as<W>(), wb[1].as<W>(), g.elems,
+                                    (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), (const uint32_t*)tile_seg.as<uint32_t>(), gb,
+                                    g.tiles, (const unsigned long long*)d_bh2.as<unsigned long long>(),
+                                    d_starts.as<unsigned long long>(), rf.bbits - blow, lowb, fin, &ss);
+            st.bucket_groups++;
+        }
+        CDB_HIP(hipStreamSynchronize(s));  // (h_segs and the group scratch go out of scope)
+        if (sweep_rec || sweep_fused) ix.tbw.base.release();
+        if (fuse_rec) E = std::move(kb[dead]);
+        if (pack_seg) out.packed_out = true;
+        st.segmented = 1;
+    }
+}
+
+// a bucket larger than the segmented sort's record memory: groups of buckets gather their records, and every bucket is sorted
+// by launches of its own
+template <typename V, typename I>
+void run_per_bucket(Index& ix, const Alphabet& al, const KeyPlan& kp, const Buckets& bk, const RecordForm& rf, const BucketRecords& br,
+                    DevBuf& E, InitialSort& out, SortStats& ss) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size;
+    BuildStats& st = ix.bstats;
+    const uint8_t* text = ix.d_text;
+    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
+    const int nsym = kp.nsym;
+    const uint32_t nb = br.nb, nch = br.nch, bbase = rf.bbase;
+    const std::vector<uint64_t>& bstart = br.bstart;
+    const int bbits = rf.bbits, blow = rf.blow, bpass = br.bpass, lowb = br.lowb, keyb = br.keyb, auxb = br.auxb, recb = br.recb;
+    const bool packed = rf.packed;
+    const uint64_t maxb = bk.maxb, bmagic = br.bmagic;
+    const double avail = br.avail;
+    std::vector<uint64_t> bounds((size_t)nb * (nch + 1));
+    CDB_HIP(hipMemcpyAsync(bounds.data(), br.d_bounds.p, bounds.size() * 8, hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipStreamSynchronize(s));
+    // (the third entry buffer is a luxury: without it an odd number of passes costs a copy back)
+    const bool third = !packed && avail > (double)maxb * (2.0 * (keyb + lowb) + 2 * sizeof(V)) * 1.15;
+    const double scratch = packed ? (double)maxb * recb
+                                  : (double)maxb * (keyb + lowb + (third ? 2 : 1) * sizeof(V)) +
+                                        (third ? (double)(n / 32) * (sizeof(I) + 16 + 2 * sizeof(V) + 1) : 0.0);
+    uint64_t gcap = (uint64_t)std::max(0.0, (avail - scratch) * 0.85 / recb);
+    if (ix.bucket_group_limit) gcap = std::min<uint64_t>(gcap, ix.bucket_group_limit);
+    gcap = std::max<uint64_t>(std::min<uint64_t>(gcap, n), maxb);
+    DevBuf k32g, lowg, k32t, lowt, ET, EX, elog, elot, d_bh, d_items;
+    k32g.alloc(gcap * keyb);
+    if (auxb) lowg.alloc(gcap * auxb);
+    k32t.alloc(maxb * keyb);
+    if (auxb) lowt.alloc(maxb * auxb);
+    if (packed) {
+        elog.alloc(gcap * sizeof(uint32_t));
+        elot.alloc(maxb * sizeof(uint32_t));
+    } else {
+        ET.alloc(maxb * sizeof(V));
+        if (third) EX.alloc(maxb * sizeof(V));  // third entry buffer: an odd number of passes still ends in place (radix_sort.h)
+    }
+    std::vector<uint64_t> bh;
+    std::vector<BucketItem> items;
+    auto run_group = [&](auto wtag, auto ktag, uint32_t b0, uint32_t b1) {  // buckets [b0, b1)
+        using W = decltype(wtag);
+        using K = decltype(ktag);
+        constexpr bool HAS_W = !std::is_same<W, NoVal>::value;
+        using FW = typename std::conditional<HAS_W, W, uint8_t>::type;
+        const uint64_t gstart = bstart[b0];
+        const uint32_t gb = b1 - b0;
+        d_bh.ensure((size_t)gb * 8 * 256 * sizeof(uint64_t));
+        CDB_HIP(hipMemsetAsync(d_bh.p, 0, (size_t)gb * 8 * 256 * sizeof(uint64_t), s));
+        items.clear();
+        for (uint32_t x = 0; x < nch; ++x)      // text chunk major: the group's buckets share the cached text
+            for (uint32_t b = b0; b < b1; ++b) {
+                const uint64_t lo = bounds[(size_t)b * (nch + 1) + x], hi = bounds[(size_t)b * (nch + 1) + x + 1];
+                for (uint64_t o = lo; o < hi; o += BR_ITEM)
+                    items.push_back(BucketItem{(unsigned long long)o, (uint32_t)std::min<uint64_t>(BR_ITEM, hi - o), b});
+            }
+        st.gather_items += items.size();
+        if (!items.empty()) {
+            d_items.ensure(items.size() * sizeof(BucketItem));
+            CDB_HIP(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(BucketItem), hipMemcpyHostToDevice, s));
+            int t = ix.prof.begin(s);
+            hipLaunchKernelGGL((sa_bucket_records_kernel<V, W, K>), dim3((unsigned)items.size()), dim3(256), 0, s,
+                               (const V*)E.as<V>(), (const BucketItem*)d_items.as<BucketItem>(), text, n, doc_start,
+                               (const uint16_t*)al.d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, bbase, blow, bpass,
+                               gstart, b0, k32g.as<K>(), lowg.as<W>(), d_bh.as<unsigned long long>());
+            ix.prof.end(t, "sa_bucket_records", (bstart[b1] - gstart) * ((uint64_t)nsym + keyb + lowb + sizeof(V)), s);
+        }
+        // (the per-bucket digit histograms stay on the device: the sorts below are queued without a single host
+        //  round trip; this one synchronisation per GROUP only protects `items`, rebuilt for the next group)
+        CDB_HIP(hipStreamSynchronize(s));
+        for (uint32_t b = b0; b < b1; ++b) {
+            const uint64_t start = bstart[b], cnt = bstart[b + 1] - start;
+            V* eb = E.as<V>() + start;
+            K* kb = k32g.as<K>() + (start - gstart);
+            FW* lb = HAS_W ? lowg.as<FW>() + (start - gstart) : (FW*)nullptr;
+            int r = 0;
+            if (bpass > 0 && cnt > 1) {
+                const unsigned long long* hb = d_bh.as<unsigned long long>() + (size_t)(b - b0) * 8 * 256;
+                ix.rws.value_spare = EX.p;  // (null without the third buffer)
+                if constexpr (HAS_W)
+                    r = radix_sort_split<V, W>(s, ix.rws, ix.prof, kb, k32t.as<uint32_t>(), eb, ET.as<V>(), lb, lowt.as<W>(), cnt,
+                                               bbits - blow, &ss, ix.sort_variant, 8, (const uint64_t*)nullptr,
+                                               (const TextGen*)nullptr, 0, hb);
+                else
+                    r = radix_sort<K, V>(s, ix.rws, ix.prof, kb, k32t.as<K>(), eb, ET.as<V>(), cnt, 0, bbits, &ss,
+                                         ix.sort_variant, 8, (const uint64_t*)nullptr, (const TextGen*)nullptr, hb);
+                if (ix.rws.value_result == 1) CDB_HIP(hipMemcpyAsync(eb, ET.p, cnt * sizeof(V), hipMemcpyDeviceToDevice, s));
+            }
+            if constexpr (sizeof(K) == 8)
+                hipLaunchKernelGGL(sa_initflags_kernel, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
+                                   (const uint64_t*)(r ? k32t.as<uint64_t>() : (uint64_t*)kb), cnt, bbase, bmagic,
+                                   out.flags.as<uint8_t>() + start, (start & 3) == 0);
+            else
+                hipLaunchKernelGGL(sa_initflags32_kernel<FW>, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
+                                   (const uint32_t*)(r ? k32t.as<uint32_t>() : (uint32_t*)kb),
+                                   HAS_W ? (const FW*)(r ? lowt.as<FW>() : lb) : (const FW*)nullptr, blow, cnt, bbase, bmagic,
+                                   out.flags.as<uint8_t>() + start, (start & 3) == 0);
+        }
+    };
+    auto run_group_packed = [&](auto wtag, uint32_t b0, uint32_t b1) {  // buckets [b0, b1), packed entries
+        using W = decltype(wtag);
+        if constexpr (sizeof(V) == 8) {
+            const uint64_t gstart = bstart[b0];
+            const uint32_t gb = b1 - b0;
+            d_bh.ensure((size_t)gb * 8 * 256 * sizeof(uint64_t));
+            CDB_HIP(hipMemsetAsync(d_bh.p, 0, (size_t)gb * 8 * 256 * sizeof(uint64_t), s));
+            items.clear();
+            for (uint32_t x = 0; x < nch; ++x)      // text chunk major: the group's buckets share the cached text
+                for (uint32_t b = b0; b < b1; ++b) {
+                    const uint64_t lo = bounds[(size_t)b * (nch + 1) + x], hi = bounds[(size_t)b * (nch + 1) + x + 1];
+                    for (uint64_t o = lo; o < hi; o += BR_ITEM)
+                        items.push_back(BucketItem{(unsigned long long)o, (uint32_t)std::min<uint64_t>(BR_ITEM, hi - o), b});
+                }
+            st.gather_items += items.size();
+            if (!items.empty()) {
+                d_items.ensure(items.size() * sizeof(BucketItem));
+                CDB_HIP(hipMemcpyAsync(d_items.p, items.data(), items.size() * sizeof(BucketItem), hipMemcpyHostToDevice, s));
+                int t = ix.prof.begin(s);
+                hipLaunchKernelGGL((sa_bucket_records_packed_kernel<W>), dim3((unsigned)items.size()), dim3(256), 0, s,
+                                   (const uint64_t*)E.as<uint64_t>(), (const BucketItem*)d_items.as<BucketItem>(), text, n,
+                                   doc_start, (const uint16_t*)al.d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, bbase,
+                                   blow, bpass, gstart, b0, k32g.as<uint32_t>(), lowg.as<W>(), elog.as<uint32_t>(),
+                                   d_bh.as<unsigned long long>());
+                ix.prof.end(t, "sa_bucket_records", (bstart[b1] - gstart) * ((uint64_t)nsym + recb + sizeof(V)), s);
+            }
+            CDB_HIP(hipStreamSynchronize(s));  // (protects `items`, rebuilt for the next group)
+            for (uint32_t b = b0; b < b1; ++b) {
+                const uint64_t start = bstart[b], cnt = bstart[b + 1] - start;
+                uint32_t* kb = k32g.as<uint32_t>() + (start - gstart);
+                uint32_t* vb = elog.as<uint32_t>() + (start - gstart);
+                W* lb = lowg.as<W>() + (start - gstart);
+                int r = 0, vr = 0;
+                if (bpass > 0 && cnt > 1) {
+                    const unsigned long long* hb = d_bh.as<unsigned long long>() + (size_t)(b - b0) * 8 * 256;
+                    ix.rws.value_spare = nullptr;
+                    r = radix_sort_split<uint32_t, W>(s, ix.rws, ix.prof, kb, k32t.as<uint32_t>(), vb, elot.as<uint32_t>(), lb,
+                                                      lowt.as<W>(), cnt, bbits - blow, &ss, ix.sort_variant, 8,
+                                                      (const uint64_t*)nullptr, (const TextGen*)nullptr, 0, hb, lowb);
+                    vr = ix.rws.value_result;
+                }
+                const W* ls = r ? lowt.as<W>() : lb;
+                int t = ix.prof.begin(s);
+                hipLaunchKernelGGL(sa_assemble_entries_kernel<W>, dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, s,
+                                   (const uint32_t*)(vr ? elot.as<uint32_t>() : vb), ls, blow, cnt, E.as<uint64_t>() + start);
+                ix.prof.end(t, "sa_assemble_entries", cnt * (4 + sizeof(W) + 8), s);
+                hipLaunchKernelGGL(sa_initflags32_kernel<W>, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
+                                   (const uint32_t*)(r ? k32t.as<uint32_t>() : kb), lowb ? ls : (const W*)nullptr, blow, cnt,
+                                   bbase, bmagic, out.flags.as<uint8_t>() + start, (start & 3) == 0);
+            }
+        }
+    };
+    for (uint32_t b0 = 0; b0 < nb;) {
+        uint32_t b1 = b0 + 1;
+        while (b1 < nb && bstart[b1 + 1] - bstart[b0] <= gcap) ++b1;
+        if (packed && lowb == 0) run_group_packed(uint8_t{}, b0, b1);
+        else if (packed && lowb == 1) run_group_packed(uint16_t{}, b0, b1);
+        else if (packed) run_group_packed(uint32_t{}, b0, b1);
+        else if (rf.bwide) run_group(NoVal{}, uint64_t{}, b0, b1);
+        else if (blow == 0) run_group(NoVal{}, uint32_t{}, b0, b1);
+        else if (blow == 8) run_group(uint8_t{}, uint32_t{}, b0, b1);
+        else run_group(uint16_t{}, uint32_t{}, b0, b1);
+        st.bucket_groups++;
+        b0 = b1;
+    }
+}
+
+// Builds of 2^32 suffixes and more: a streamed bucket-wise sort (a double-buffered LSD sort of (u64 key, u64 entry) pairs
+// would need 32 n bytes — 256 GiB at n = 2^33): ONE generated pass partitions the ENTRIES by first symbol — its keys exist
+// only inside the tile — and every bucket then gathers its keys from the text (its entries are still in text order, so the
+// gather walks the text front to back), LSD-sorts (key, entry) on the remaining symbols and writes its group flags.
+// Peak = 8 n (entries) + 24 x the largest bucket.
+template <typename V, typename I>
+InitialSort initial_sort_bucketwise(Index& ix, Alphabet& al, const KeyPlan& kp, SortStats& ss) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, D = ix.ndocs;
+    BuildStats& st = ix.bstats;
+    const uint8_t* text = ix.d_text;
+    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
+    const int sigma = al.sigma, symbits = al.symbits, nsym = kp.nsym, dbits = kp.dbits;
+    const uint32_t kbase = kp.kbase;
+    const uint64_t kmagic = kp.kmagic;
+    InitialSort out;
+    TextGen gen{text, doc_start, al.d_symmap.as<uint16_t>(), D, (int)ix.bits, kbase, nsym, 0, ix.text_padded};
+    double ta = now_ms();
+    out.flags.alloc(n);
+    DevBuf E, KT[2], ET;  // (E: allocated below, once it is known whether the entries are partitioned at all)
+    const int top_shift = (nsym - 1) * symbits;
+    Buckets bk;
+    make_buckets(ix, al, bk);
+    const uint64_t* h_first = bk.first_by_code.data();
+    const uint64_t maxb = bk.maxb;
+    RecordForm rf;
+    choose_record_form<V>(ix, al, kp, bk, rf, out);
+    const bool packed = rf.packed, brecords = rf.brecords, fuse_rec = rf.fuse_rec, pack_E = rf.pack_E;
+    const int blow = rf.blow;
+    if (pack_E) {
+        E.alloc(n * sizeof(uint32_t));
+        out.sa_hi_buf.alloc(n);
+    } else if (!fuse_rec) {
+        E.alloc(n * sizeof(V));
+    }
+    st.alloc_ms += now_ms() - ta;
+    st.fused_records = fuse_rec ? 1 : 0;
+    DevBuf d_slotmap;
+    if (fuse_rec || rf.sweep_rec) {
+        d_slotmap.alloc(260);
+        CDB_HIP(hipMemcpyAsync(d_slotmap.p, bk.h_slotmap, 260, hipMemcpyHostToDevice, s));
+        CDB_HIP(hipStreamSynchronize(s));
+    }
+    auto partition_entries = [&]() {
+        gen.first_only = true;
+        gen.symmap = bk.d_symmap_first.as<uint16_t>();
+        const int fbits = std::max(1, bit_width64((uint64_t)sigma - 1));
+        if (pack_E) gen.vout_hi = out.sa_hi_buf.as<uint8_t>();
+        (void)radix_sort<uint64_t, V>(s, ix.rws, ix.prof, (uint64_t*)nullptr, (uint64_t*)nullptr, (V*)nullptr, E.as<V>(), n, 0, fbits,
+                                      &ss, ix.sort_variant, fbits, bk.first_digit.data(), &gen);
+        radix_check_error(s, ix.rws);  // (the gathers below read the text through these entries)
+    };
+    if (!fuse_rec && !rf.sweep_rec) {
+        // partition + gather reads no per-tile byte counts: they (1 KiB per 8 Ki positions: 2 GiB at 16 GiB of text) and the
+        // tile-base workspace go back to the pool BEFORE the record memory of the groups is sized
+        al.d_tbc.release();
+        ix.tbw.partial.release();
+        ix.tbw.blockbase.release();
+        ix.tbw.base.release();
+        partition_entries();
+    }
+    if (bk.root_folded) fold_root_buckets(ix, al, bk, out);
+    st.bucket_low_digits = brecords && blow > 0 ? blow / 8 : 0;
+    st.key_layout = brecords ? (packed ? 5 : (rf.bwide ? 4 : (blow == 0 ? 1 : (blow == 8 ? 2 : 3)))) : 0;
+    if (brecords) {
+        BucketRecords br;
+        br.fbase = rf.vl_bits ? 2u : rf.bbase * rf.part_m;
+        br.bmagic = (br.fbase & (br.fbase - 1u)) ? (uint64_t)(~0ull / br.fbase) + 1ull : 0ull;
+        br.bpass = (int)ceil_div(rf.bbits, 8);
+        br.lowb = blow / 8;
+        br.keyb = rf.bwide ? 8 : 4;
+        // non-empty buckets and their entry ranges
+        const uint32_t nb = br.nb = (uint32_t)sigma;  // (every code stands for a byte that occurs)
+        br.bstart.assign(nb + 1, 0);
+        for (uint32_t b = 0; b < nb; ++b) br.bstart[b + 1] = br.bstart[b] + h_first[bk.border[b]];
+        const uint32_t nch = br.nch = (uint32_t)ceil_div(n, br.chunk);
+        br.d_bstart.alloc((nb + 1) * 8);
+        br.d_bounds.alloc(fuse_rec ? 8 : (size_t)nb * (nch + 1) * 8);
+        CDB_HIP(hipMemcpyAsync(br.d_bstart.p, br.bstart.data(), (nb + 1) * 8, hipMemcpyHostToDevice, s));
+        auto bucket_bounds = [&]() {
+        if (pack_E)
+        hipLaunchKernelGGL((sa_bucket_bounds_kernel<Packed40>), dim3((unsigned)ceil_div((uint64_t)nb * (nch + 1), 256)), dim3(256), 0, s,
+                           Sa40{E.as<uint32_t>(), out.sa_hi_buf.as<uint8_t>()}, (const unsigned long long*)br.d_bstart.as<unsigned long long>(), nb,
+                           nch, br.chunk, doc_start, (int)ix.bits, ix.mask, br.d_bounds.as<unsigned long long>());
+        else if (!fuse_rec)
+        hipLaunchKernelGGL((sa_bucket_bounds_kernel<V>), dim3((unsigned)ceil_div((uint64_t)nb * (nch + 1), 256)), dim3(256), 0, s,
+                           (const V*)E.as<V>(), (const unsigned long long*)br.d_bstart.as<unsigned long long>(), nb, nch, br.chunk,
+                           doc_start, (int)ix.bits, ix.mask, br.d_bounds.as<unsigned long long>());
+        };
+        if (!rf.sweep_rec) bucket_bounds();
+        // sweep form: array-wide tile bases of every bucket slot (4 GiB of them for 16 GiB of text: allocated BEFORE the record
+        // memory is sized; the counts they were made from go back to the pool), the document of every tile's first position
+        if (rf.sweep_rec || rf.sweep_fused) {
+            std::vector<uint16_t> codeslot(256, 0);  // byte -> symbol code | bucket slot << 8 (one lookup per text byte)
+            for (int b = 0; b < 256; ++b) codeslot[b] = (uint16_t)(al.h_map[b] | ((uint32_t)bk.h_slotmap[al.h_map[b]] << 8));
+            br.d_codeslot.alloc(256 * sizeof(uint16_t));
+            CDB_HIP(hipMemcpyAsync(br.d_codeslot.p, codeslot.data(), 256 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+            std::vector<uint64_t> slot_start(256, n);
+            for (uint32_t b = 0; b < nb; ++b) slot_start[b] = br.bstart[b];
+            DevBuf d_slot_start;
+            d_slot_start.alloc(256 * sizeof(uint64_t));
+            CDB_HIP(hipMemcpyAsync(d_slot_start.p, slot_start.data(), 256 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            int t = ix.prof.begin(s);
+            br.sweep_base = rs_tile_bases(s, ix.tbw, al.d_tbc.as<uint32_t>(), al.tiles8, bk.d_src_col.as<uint16_t>(),
+                                          (const unsigned long long*)d_slot_start.as<unsigned long long>());
+            br.sweep_doc.alloc(((size_t)al.tiles8 + 1) * sizeof(uint64_t));
+            hipLaunchKernelGGL(rs_tiledoc_kernel, dim3((unsigned)ceil_div((uint64_t)al.tiles8 + 1, 256)), dim3(256), 0, s, doc_start, D, n,
+                               (uint64_t)RS_SWEEP_TILE, (uint64_t)al.tiles8, br.sweep_doc.as<uint64_t>());
+            ix.prof.end(t, "rs_tile_bases", (uint64_t)al.tiles8 * 256 * (4 + 8), s);
+            CDB_HIP(hipStreamSynchronize(s));  // (slot_start, d_slot_start, codeslot)
+            al.d_tbc.release();
+            ix.tbw.partial.release();
+            ix.tbw.blockbase.release();
+        }
+        // groups of consecutive buckets whose records (4 + lowb bytes per suffix) fit the memory left
+        size_t fre = 0, tot = 0;
+        CDB_HIP(hipMemGetInfo(&fre, &tot));
+        br.avail = (double)fre + (double)DevPool::get().cached_bytes();
+        br.auxb = packed ? (br.lowb == 0 ? 1 : (br.lowb == 1 ? 2 : 4)) : br.lowb;
+        br.recb = br.keyb + br.auxb + (packed ? 4 : 0);
+        uint64_t seg_cap = 0;
+        if (packed && ix.segmented_sort && sizeof(V) == 8 && rs_atomic_rank_ok(s)) {
+            const double per = 2.0 * br.recb + 1.0;  // + edge records (32 B per tile and digit)
+            uint64_t cap = (uint64_t)std::max(0.0, br.avail * 0.85 / per);
+            if (cap >= maxb) {
+                if (ix.bucket_group_limit) cap = std::max<uint64_t>(std::min<uint64_t>(cap, ix.bucket_group_limit), maxb);
+                seg_cap = std::min<uint64_t>(cap, n);
+            }
+            if (fuse_rec) seg_cap = n;  // (decided with the same bound before the entries were NOT partitioned)
+        }
+        if (!fuse_rec && ix.debug_no_segcap) seg_cap = 0;  // (test hook: "a bucket does not fit the record memory")
+        if (fuse_rec && !seg_cap) throw Error("bucket-wise build: fused records without the segmented sort (internal)");
+        if ((rf.vl_bits || rf.part_m > 1) && !seg_cap) throw RetryWithDenseKeys(kVlRetry);
+        if (rf.sweep_rec && !seg_cap) {  // (a bucket larger than the record memory: partition + gather, bucket by bucket)
+            rf.sweep_rec = false;
+            br.sweep_doc.release();
+            ix.tbw.base.release();
+            partition_entries();
+            bucket_bounds();
+        }
+        if (pack_E && !seg_cap) {
+            // (a bucket larger than the record memory: the per-bucket forms below work on plain 8-byte entries)
+            if constexpr (sizeof(V) == 8) {
+                DevBuf wide;
+                wide.alloc(n * sizeof(uint64_t));
+                Index tmp_view;  // (sa_expand wants an Index: borrow the two arrays for one call)
+                tmp_view.stream = s;
+                tmp_view.d_sa = std::move(E);
+                tmp_view.d_sa_hi = std::move(out.sa_hi_buf);
+                tmp_view.sa_packed = true;
+                sa_expand(tmp_view, 0, n, wide.as<uint64_t>());
+                CDB_HIP(hipStreamSynchronize(s));
+                tmp_view.stream = nullptr;
+                E = std::move(wide);
+            }
+        }
+        if (seg_cap) {
+            if (br.lowb == 0) run_segmented<V, uint8_t>(ix, al, kp, bk, rf, br, seg_cap, d_slotmap, E, out, ss, ta);
+            else if (br.lowb == 1) run_segmented<V, uint16_t>(ix, al, kp, bk, rf, br, seg_cap, d_slotmap, E, out, ss, ta);
+            else run_segmented<V, uint32_t>(ix, al, kp, bk, rf, br, seg_cap, d_slotmap, E, out, ss, ta);
+        } else {
+            run_per_bucket<V, I>(ix, al, kp, bk, rf, br, E, out, ss);
+        }
+    } else {
+    KT[0].alloc(maxb * sizeof(uint64_t));
+    if (nsym > 1 && maxb > 1) {
+        KT[1].alloc(maxb * sizeof(uint64_t));
+        ET.alloc(maxb * sizeof(V));
+    }
+    uint64_t start = 0;
+    for (int k = 0; k < sigma; ++k) {
+        const uint64_t cnt = h_first[bk.border[k]];
+        if (!cnt) continue;
+        V* eb = E.as<V>() + start;
+        int t = ix.prof.begin(s);
+        hipLaunchKernelGGL((sa_bucket_keys_kernel<V>), dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, s, (const V*)eb, cnt,
+                           text, n, doc_start, (const uint16_t*)al.d_symmap.as<uint16_t>(), (int)ix.bits, ix.mask, nsym, symbits,
+                           KT[0].as<uint64_t>());
+        ix.prof.end(t, "sa_bucket_keys", cnt * ((uint64_t)nsym + 8 + sizeof(V)), s);
+        int r = 0;
+        if (nsym > 1 && cnt > 1) {
+            r = radix_sort<uint64_t, V>(s, ix.rws, ix.prof, KT[0].as<uint64_t>(), KT[1].as<uint64_t>(), eb, ET.as<V>(), cnt, 0,
+                                        top_shift, &ss, ix.sort_variant, dbits);
+            if (r == 1) CDB_HIP(hipMemcpyAsync(eb, ET.p, cnt * sizeof(V), hipMemcpyDeviceToDevice, s));
+        }
+        hipLaunchKernelGGL(sa_initflags_kernel, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
+                           (const uint64_t*)KT[r].as<uint64_t>(), cnt, kbase, kmagic, out.flags.as<uint8_t>() + start,
+                           (start & 3) == 0);
+        start += cnt;
+    }
+    }
+    CDB_HIP(hipStreamSynchronize(s));
+    st.bucketed = 1;
+    out.sa_buf = std::move(E);
+    return out;
+}
+
+// The sorted keys stay valid for the finished array: refinement only permutes entries inside groups
+// of equal keys.  They let a search probe decide on ONE load (query.hip) — kept when affordable.
+void hand_over_keys(Index& ix, bool big, InitialSort& is, const KeyPlan& kp) {
+    const double ta = now_ms();
+    ix.drop_keys();
+    if (ix.keep_keys && !big && ix.size * 8 <= (16ull << 30)) {
+        ix.d_keys = std::move(is.sorted_keys);
+        ix.d_keys32 = std::move(is.sorted_k32);
+        ix.d_keylow = std::move(is.sorted_low);
+        ix.key_low_bits = is.low_bits;
+        ix.key_low_bytes = is.low_bytes;
+        ix.key_nsym = kp.nsym;
+        ix.key_base = kp.kbase;
+    } else {
+        is.sorted_keys.release();
+        is.sorted_k32.release();
+        is.sorted_low.release();
+    }
+    ix.bstats.free_ms += now_ms() - ta;
+}
+
+// ---- 4. refinement rounds
+// (their buffers live until the build ends, as the reference-order finish sizes its second array against the memory left)
+struct RefineBuffers {
+    DevBuf d_order;
     DevBuf U, skey[2], sval[2], nh, rank, hcov;
+    DevBuf d_open;  // entries still unresolved after the last round (saves a full flag scan to learn "none")
+    DevBuf U2b, lf;       // list-based rounds: the other list of positions, the flag bytes of the current list in list order
+    DevBuf d_gs_state;  // sa_group_sort_kernel: [0] it gave up (groups too long for it), [1] members walked by its long walks
+};
+
+// slot order of the array as the bucket-wise build laid it out -> plain unsigned order (ranks of prefix doubling)
+SlotOrder make_slot_order(Index& ix, const InitialSort& is, const Alphabet& al, DevBuf& d_order) {
+    SlotOrder order;
+    if (is.folded_roots.empty()) return order;
+    const std::vector<Depth1Fold>& depth1 = is.depth1;
+    struct Blk { unsigned long long a, len; int code, cls; };  // cls: 0 = end of document, 1 = bytes < 0x80, 2 = bytes >= 0x80
+    std::vector<Blk> blks;
+    std::vector<int> code_of_root;  // first-symbol code of every root bucket, in array order
+    {
+        for (int b = 128; b < 256; ++b) if (al.h_map[b]) code_of_root.push_back(al.h_map[b]);
+        for (int b = 0; b < 128; ++b) if (al.h_map[b]) code_of_root.push_back(al.h_map[b]);
+    }
+    for (size_t b = 0; b < is.folded_roots.size(); ++b) {
+        const CompatBucket r = is.folded_roots[b];
+        if (!depth1.empty() && depth1[b].done) {  // written as [end][high][low]
+            blks.push_back(Blk{r.lo, depth1[b].nend, code_of_root[b], 0});
+            blks.push_back(Blk{r.lo + depth1[b].nend, depth1[b].nhigh, code_of_root[b], 2});
+            blks.push_back(Blk{r.lo + depth1[b].nend + depth1[b].nhigh, depth1[b].nlow, code_of_root[b], 1});
+        } else {
+            blks.push_back(Blk{r.lo, r.hi - r.lo, code_of_root[b], 0});
+        }
+    }
+    // unsigned order: by first-symbol code, inside a bucket [end][low][high]
+    std::vector<size_t> by_u(blks.size());
+    for (size_t i = 0; i < by_u.size(); ++i) by_u[i] = i;
+    std::sort(by_u.begin(), by_u.end(), [&](size_t x, size_t y) {
+        return blks[x].code != blks[y].code ? blks[x].code < blks[y].code : blks[x].cls < blks[y].cls;
+    });
+    std::vector<unsigned long long> tab(2 * blks.size());
+    unsigned long long at = 0;
+    for (size_t i : by_u) {
+        tab[blks.size() + i] = at;
+        at += blks[i].len;
+    }
+    for (size_t i = 0; i < blks.size(); ++i) tab[i] = blks[i].a;
+    d_order.alloc(tab.size() * sizeof(unsigned long long));
+    CDB_HIP(hipMemcpyAsync(d_order.p, tab.data(), tab.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ix.stream));
+    CDB_HIP(hipStreamSynchronize(ix.stream));
+    order.a_start = d_order.as<unsigned long long>();
+    order.u_start = d_order.as<unsigned long long>() + blks.size();
+    order.nseg = (uint32_t)blks.size();
+    return order;
+}
+
+// (generic over the array's storage: SaRW<V> = plain entries, Sa40RW = packed 5-byte entries, index_impl.h)
+// returns the depth every suffix is sorted to
+template <typename V, typename I, typename R, typename SAW>
+uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, const KeyPlan& kp, SortStats& ss, RefineBuffers& rb) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, D = ix.ndocs;
+    BuildStats& st = ix.bstats;
+    const uint8_t* text = ix.d_text;
+    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
+    const int symbits = al.symbits;
+    const DevBuf& flags = is.flags;
+    const uint32_t vl_kb1 = is.vl_kb1;
+    const SlotOrder order = make_slot_order(ix, is, al, rb.d_order);
+    DevBuf &U = rb.U, (&skey)[2] = rb.skey, (&sval)[2] = rb.sval, &nh = rb.nh, &rank = rb.rank, &hcov = rb.hcov;
+    DevBuf &d_open = rb.d_open, &U2b = rb.U2b, &lf = rb.lf, &d_gs_state = rb.d_gs_state;
     uint32_t h_acc = 0;  // symbols the text-extension rounds so far added behind every group's own depth (variable-length keys)
-    uint64_t h = refine_depth0 ? refine_depth0 : (uint64_t)nsym;
+    uint64_t h = is.refine_depth0 ? is.refine_depth0 : (uint64_t)kp.nsym;
     bool isa = false;
     uint64_t cap = 0;
-    DevBuf d_open;  // entries still unresolved after the last round (saves a full flag scan to learn "none")
     d_open.alloc(sizeof(uint64_t));
-    DevBuf U2b, lf;       // list-based rounds: the other list of positions, the flag bytes of the current list in list order
     bool have_list = false;  // the last round was a text-extension round: lf / U / sval[list_rs] describe its list
     uint64_t m_list = 0;
     int list_rs = 0;
-    DevBuf d_gs_state;  // sa_group_sort_kernel: [0] it gave up (groups too long for it), [1] members walked by its long walks
     d_gs_state.alloc(2 * sizeof(unsigned long long));
     bool group_sort_on = ix.group_sort;
-    // (generic over the array's storage: SaRW<V> = plain entries, Sa40RW = packed 5-byte entries, index_impl.h)
-    auto refine = [&](auto sa) {
-    using SAW = decltype(sa);
     for (;;) {
         if (st.rounds > 0) {
             uint64_t still = 0;
@@ -3431,11 +3518,11 @@ void build_typed(Index& ix, bool big) {
             hipLaunchKernelGGL(sa_flag_count_kernel, dim3((unsigned)ceil_div(nb, (uint64_t)(4 * FC_TILES_PER_WAVE))), dim3(256), 0, s,
                                (const uint8_t*)lf.as<uint8_t>(), m_list, nb, ix.scan_partials.as<U2>());
             ix.prof.end(t, "sa_flag_count", m_list, s);
-        } else if (!tile_sums_ready) {
+        } else if (!is.tile_sums_ready) {
             flag_tile_sums();
         }
         U2 tot = scan_totals_from_partials<U2>(s, ix.scan_partials, from_list ? m_list : n, OpAdd{}, U2{0, 0});
-        tile_sums_ready = false;
+        is.tile_sums_ready = false;
         uint64_t m = tot.a, G = tot.b;
         if (st.rounds == 0) st.unresolved_initial = m;
         st.unresolved_max = std::max(st.unresolved_max, m);
@@ -3505,13 +3592,13 @@ void build_typed(Index& ix, bool big) {
             }
             if (isa)
                 hipLaunchKernelGGL((sa_round_keys_kernel<V, R, true>), dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, s,
-                                   (const V*)sval[0].as<V>(), m, doc_start, text, (const uint16_t*)d_symmap.as<uint16_t>(),
+                                   (const V*)sval[0].as<V>(), m, doc_start, text, (const uint16_t*)al.d_symmap.as<uint16_t>(),
                                    (const R*)rank.as<R>(), (int)ix.bits, ix.mask, h, nsym2, symbits, skey[0].as<uint64_t>(), n);
             else
                 hipLaunchKernelGGL((sa_round_keys_kernel<V, R, false>), dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, s,
-                                   (const V*)sval[0].as<V>(), m, doc_start, text, (const uint16_t*)d_symmap.as<uint16_t>(),
+                                   (const V*)sval[0].as<V>(), m, doc_start, text, (const uint16_t*)al.d_symmap.as<uint16_t>(),
                                    (const R*)nullptr, (int)ix.bits, ix.mask, h, nsym2, symbits, skey[0].as<uint64_t>(), n,
-                                   vl_kb1 ? (const uint8_t*)d_vl_bytelen.as<uint8_t>() : nullptr, vl_kb1, h_acc, vl_kb1 ? hcov.as<uint8_t>() : nullptr);
+                                   vl_kb1 ? (const uint8_t*)is.d_vl_bytelen.as<uint8_t>() : nullptr, vl_kb1, h_acc, vl_kb1 ? hcov.as<uint8_t>() : nullptr);
             ix.prof.end(t, "sa_compact", n + m * (sizeof(I) + 8 + 2 * sizeof(V)), s);
         }
         int rs = -1;
@@ -3568,27 +3655,21 @@ void build_typed(Index& ix, bool big) {
         st.rounds++;
         if (st.rounds > 80) throw Error("suffix-array refinement did not converge (internal error)");
     }
-    };
-    if constexpr (sizeof(V) == 8) {
-        if (packed_out) refine(Sa40RW{sa_buf.as<uint32_t>(), sa_hi_buf.as<uint8_t>()});
-        else refine(SaRW<V>{sa_buf.as<V>()});
-    } else {
-        refine(SaRW<V>{sa_buf.as<V>()});
-    }
-    if (ix.debug_fail_build) throw Error("debug: build failure requested (test hook)");
-    if (ix.debug_starve_group == 1 && !ix.rws.plain_order) throw Error("radix sort look-back timed out (test hook)");
-    st.final_depth = h;
-    st.sort_passes = ss.passes_run;
-    st.sort_passes_skipped = ss.passes_skipped;
-    radix_check_error(s, ix.rws);
-    CDB_HIP(hipStreamSynchronize(s));
-    ix.sa_sorted = !(ix.reference_compat && high_bytes);
+    return h;
+}
+
+// the array goes to the index — on text with bytes >= 0x80 first into the reference's order
+template <typename V>
+void finish_reference_order(Index& ix, InitialSort& is, Alphabet& al) {
+    ix.sa_sorted = !(ix.reference_compat && al.high_bytes);
     ix.pivot_levels = 0;  // the pivot table belongs to the previous suffix array
     if (ix.key_nsym) {  // the code table the kept keys were built with
-        ix.d_symmap_q = std::move(d_symmap);
-        std::memcpy(ix.h_symmap_q, h_map, sizeof(h_map));
+        ix.d_symmap_q = std::move(al.d_symmap);
+        std::memcpy(ix.h_symmap_q, al.h_map, sizeof(al.h_map));
     }
-    if (ix.reference_compat && high_bytes) {
+    if (ix.reference_compat && al.high_bytes) {
+        std::vector<CompatBucket>& folded_roots = is.folded_roots;
+        const std::vector<Depth1Fold>& depth1 = is.depth1;
         // buckets whose two byte blocks were swapped by the sort enter the walk as their two blocks (each sorted by the
         // second symbol and with all children on one side of 0x80: no rotation there, their big children are walked)
         if (!folded_roots.empty() && !depth1.empty()) {
@@ -3611,17 +3692,74 @@ void build_typed(Index& ix, bool big) {
         const std::vector<CompatBucket>* roots = folded_roots.empty() ? nullptr : &folded_roots;
         auto reorder = [&](auto tag) {
             using T = decltype(tag);
-            if (!apply_reference_order_oop<T>(ix, sa_buf, &sa_hi_buf, roots)) {
-                apply_reference_order<T>(ix, sa_buf, &sa_hi_buf, roots);  // in place when no second array fits
-                ix.drop_keys();                                           // ... which moves the entries away from their keys
+            if (!apply_reference_order_oop<T>(ix, is.sa_buf, &is.sa_hi_buf, roots)) {
+                apply_reference_order<T>(ix, is.sa_buf, &is.sa_hi_buf, roots);  // in place when no second array fits
+                ix.drop_keys();                                                 // ... which moves the entries away from their keys
             }
         };
-        if (packed_out) reorder(Packed40{});
+        if (is.packed_out) reorder(Packed40{});
         else reorder(V{});
     }
-    ix.d_sa = std::move(sa_buf);
-    ix.d_sa_hi = std::move(sa_hi_buf);
-    ix.sa_packed = packed_out;
+    ix.d_sa = std::move(is.sa_buf);
+    ix.d_sa_hi = std::move(is.sa_hi_buf);
+    ix.sa_packed = is.packed_out;
+}
+
+// I = type of suffix-array slot numbers, R = type of ranks / extended text positions: u32 while
+// n + D < 2^32, u64 beyond.  `big` additionally selects the bucket-wise initial sort that keeps the
+// working set inside HBM for multi-GiB corpora with 8-byte entries.
+template <typename V, typename I, typename R>
+void build_typed(Index& ix, bool big) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, D = ix.ndocs;
+    BuildStats& st = ix.bstats;
+    st = BuildStats{};
+    {
+        // the previous suffix array and kept keys go back to the block cache first: a rebuild of the same
+        // corpus shape then finds every buffer it needs there instead of asking the driver for fresh memory
+        const double tf = now_ms();
+        ix.release_sa();
+        ix.drop_keys();
+        ix.d_pivots.release();
+        ix.pivot_levels = 0;
+        st.free_ms += now_ms() - tf;
+    }
+    if (n == 0) {
+        ix.d_sa.alloc(16);
+        ix.sa_sorted = true;
+        ix.pivot_levels = 0;
+        ix.drop_keys();
+        return;
+    }
+    if (sizeof(R) == 4 && n + D + 2 >= (1ull << 32)) throw Error("internal: 32-bit ranks selected for a corpus >= 2^32");
+    Alphabet al;
+    count_alphabet<V>(ix, big, al);
+    TopCounts tc;
+    count_top_digits_aside<V>(ix, big, al, tc);
+    const KeyPlan kp = plan_keys<V>(ix, big, al);
+    const DigitHist dh = digit_histograms<V>(ix, big, al, kp, tc);
+    SortStats ss;
+    InitialSort is = big ? initial_sort_bucketwise<V, I>(ix, al, kp, ss) : initial_sort_direct<V>(ix, al, kp, dh, tc, ss);
+    // (a starved pass of the initial sort left garbage entries: the refinement below would index the text with them —
+    //  the error surfaces HERE, before anything dereferences an entry; build_suffix_array redoes the build in plain order)
+    radix_check_error(s, ix.rws);
+    hand_over_keys(ix, big, is, kp);
+    RefineBuffers rb;
+    uint64_t h;
+    if constexpr (sizeof(V) == 8) {
+        if (is.packed_out) h = refine_groups<V, I, R>(ix, Sa40RW{is.sa_buf.as<uint32_t>(), is.sa_hi_buf.as<uint8_t>()}, is, al, kp, ss, rb);
+        else h = refine_groups<V, I, R>(ix, SaRW<V>{is.sa_buf.as<V>()}, is, al, kp, ss, rb);
+    } else {
+        h = refine_groups<V, I, R>(ix, SaRW<V>{is.sa_buf.as<V>()}, is, al, kp, ss, rb);
+    }
+    if (ix.debug_fail_build) throw Error("debug: build failure requested (test hook)");
+    if (ix.debug_starve_group == 1 && !ix.rws.plain_order) throw Error("radix sort look-back timed out (test hook)");
+    st.final_depth = h;
+    st.sort_passes = ss.passes_run;
+    st.sort_passes_skipped = ss.passes_skipped;
+    radix_check_error(s, ix.rws);
+    CDB_HIP(hipStreamSynchronize(s));
+    finish_reference_order<V>(ix, is, al);
 }
 
 }  // namespace
@@ -3648,16 +3786,25 @@ void build_suffix_array(Index& ix) {
             else build_typed<uint64_t, uint64_t, uint64_t>(ix, true);
         }
     };
+    // The array and its keys go, after the stream has drained (its queued kernels may still use them).  A build that failed
+    // for good also goes back to "never built": queries answer {} instead of touching a half-built array.
+    auto discard = [&](bool failed) {
+        (void)hipStreamSynchronize(ix.stream);
+        ix.prof.resolve();
+        ix.release_sa();
+        ix.drop_keys();
+        if (failed) {
+            ix.width = 0;
+            ix.size = 0;
+        }
+    };
     ix.vl_off_once = false;
     auto run_dense_after_vl = [&]() {
         try {
             run();
         } catch (const RetryWithDenseKeys&) {
             ix.dense_key_retries += 1;  // (visible: a column that pays two build prologues on every build is a regression)
-            (void)hipStreamSynchronize(ix.stream);
-            ix.prof.resolve();
-            ix.release_sa();
-            ix.drop_keys();
+            discard(false);
             ix.vl_off_once = true;
             run();
         }
@@ -3670,10 +3817,7 @@ void build_suffix_array(Index& ix) {
             // other kernels on the device can starve it, which ends in the (bounded) look-back timeout.  The plain
             // ticket order needs one resident workgroup: rebuild with it, and keep it for this handle.
             if (ix.rws.plain_order || std::strstr(e.what(), "look-back timed out") == nullptr) throw;
-            (void)hipStreamSynchronize(ix.stream);
-            ix.prof.resolve();
-            ix.release_sa();
-            ix.drop_keys();
+            discard(false);
             ix.rws.plain_order = true;
             if (!ix.debug_starve_group) rs_group_order_disable(ix.device);  // (the test hook leaves the device alone)
             ix.group_fallbacks += 1;
@@ -3682,12 +3826,7 @@ void build_suffix_array(Index& ix) {
     } catch (...) {
         // (the scratch buffers went back to the block cache while the stack unwound; they carry an event of this
         //  stream, so no other stream gets them before the kernels queued here have finished — common.h: DevPool)
-        (void)hipStreamSynchronize(ix.stream);
-        ix.prof.resolve();
-        ix.release_sa();
-        ix.drop_keys();
-        ix.width = 0;  // back to "never built": queries answer {} instead of touching a half-built array
-        ix.size = 0;
+        discard(true);
         throw;
     }
     CDB_HIP(hipStreamSynchronize(ix.stream));
@@ -3729,27 +3868,20 @@ void build_suffix_array(Index& ix) {
             const bool was_atomic = rs_atomic_rank_ok(ix.stream);
             if (was_atomic && !ix.debug_fail_self_check) rs_atomic_rank_disable(ix.device);  // (the test hook leaves the device alone)
             ix.self_check_fallbacks += 1;
-            ix.release_sa();  // (the failed array and its keys go first: the rebuild needs their memory on large corpora)
-            ix.drop_keys();
+            // (the failed array and its keys go first: the rebuild needs their memory on large corpora; check() has drained the
+            //  stream and queued nothing profiled, so the drain here finds nothing to wait for)
+            discard(false);
             try {
                 run_dense_after_vl();
                 CDB_HIP(hipStreamSynchronize(ix.stream));
                 ix.prof.resolve();
                 pack_now();
             } catch (...) {
-                (void)hipStreamSynchronize(ix.stream);
-                ix.prof.resolve();
-                ix.release_sa();
-                ix.drop_keys();
-                ix.width = 0;
-                ix.size = 0;
+                discard(true);
                 throw;
             }
             if (!check()) {
-                ix.release_sa();
-                ix.drop_keys();
-                ix.width = 0;
-                ix.size = 0;
+                discard(true);
                 throw Error("suffix array self-check failed: " + std::to_string(sc[0]) + " pairs out of order, " + std::to_string(sc[1]) +
                             " invalid entries among the sampled pairs (internal error)");
             }
