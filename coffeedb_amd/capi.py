@@ -30,6 +30,7 @@ EXPORTS = [
     "cdb_comm_world", "cdb_comm_transport", "cdb_reserve", "cdb_reserve_wait",
     "cdb_column_create", "cdb_column_destroy", "cdb_column_last_error", "cdb_column_add_bulk", "cdb_column_build", "cdb_column_query",
     "cdb_column_query_any", "cdb_query_and_columns", "cdb_column_get_stat", "cdb_debug_column_set_option", "cdb_debug_column_profile_dump",
+    "cdb_column_cluster", "cdb_cluster", "cdb_clusters_free",
 ]
 
 
@@ -64,6 +65,11 @@ class CdbKeyQuery(C.Structure):
 
 class CdbColumnKey(C.Structure):
     _fields_ = [("column", C.c_void_p), ("blob", C.c_void_p), ("offsets", C.c_void_p), ("nranges", C.c_uint64)]
+
+
+class CdbClusters(C.Structure):
+    _fields_ = [("ngroups", C.c_uint64), ("missing", C.c_uint64), ("counts", C.POINTER(C.c_int64)), ("rep_ids", C.POINTER(C.c_int64)),
+                ("values", C.POINTER(C.c_uint64)), ("value_ptr", C.POINTER(C.c_uint64)), ("value_blob", C.POINTER(C.c_char))]
 
 
 class CdbDeviceHits(C.Structure):
@@ -217,8 +223,20 @@ def load_library():
     lib.cdb_column_get_stat.argtypes = [vp, cp, C.POINTER(C.c_double)]
     lib.cdb_debug_column_set_option.argtypes = [vp, cp, i64]
     lib.cdb_debug_column_profile_dump.argtypes = [vp, C.c_char_p, C.c_size_t]
+    lib.cdb_column_cluster.argtypes = [vp, vp, u64, C.POINTER(CdbClusters)]
+    lib.cdb_cluster.argtypes = [vp, vp, u64, C.c_int, C.POINTER(CdbClusters)]
+    lib.cdb_clusters_free.argtypes = [C.POINTER(CdbClusters)]
+    lib.cdb_clusters_free.restype = None
     _LIB = lib
     return lib
+
+
+def _array(ptr, n, dtype):
+    """copy of a C result array of n elements"""
+    n = int(n)
+    if n == 0:
+        return np.empty(0, dtype=dtype)
+    return np.ctypeslib.as_array(ptr, shape=(n,)).view(dtype).copy()
 
 
 def _ptr(a):
@@ -482,6 +500,24 @@ class GpuStringIndex:
         self._check(self._lib.cdb_debug_query_latency(self._h, blob, _ptr(offs), len(keywords), reps, _ptr(out)))
         return out
 
+    def cluster(self, ids, with_values=True):
+        """cdb_cluster (database.cpp:442-460 for this string field): the rows `ids` grouped by their document, groups in
+        std::string order.  Returns (values: list of bytes, or None without with_values; counts int64; rep_ids int64: the smallest
+        id of each group among the rows; missing: rows whose id the index does not hold)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        r = CdbClusters()
+        self._check(self._lib.cdb_cluster(self._h, _ptr(ids) if len(ids) else None, len(ids), 1 if with_values else 0, C.byref(r)))
+        try:
+            ng = int(r.ngroups)
+            values = None
+            if with_values:
+                vp_ = _array(r.value_ptr, ng + 1, np.uint64)
+                blob = C.string_at(r.value_blob, int(vp_[ng])) if ng else b""
+                values = [blob[int(vp_[g]):int(vp_[g + 1])] for g in range(ng)]
+            return values, _array(r.counts, ng, np.int64), _array(r.rep_ids, ng, np.int64), int(r.missing)
+        finally:
+            self._lib.cdb_clusters_free(C.byref(r))
+
     def set_option(self, name, value):
         self._check(self._lib.cdb_set_option(self._h, name.encode(), int(value)))
 
@@ -719,6 +755,21 @@ class GpuColumn:
         finally:
             self._lib.cdb_free(ids)
 
+    def cluster(self, ids):
+        """cdb_column_cluster (database.cpp:442-460 for this field): the rows `ids` grouped by value, ascending.  Returns
+        (values: int64 / float64 / bool array, counts int64, rep_ids int64: the smallest id of each group among the rows,
+        missing: rows whose id the column does not hold)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        r = CdbClusters()
+        self._check(self._lib.cdb_column_cluster(self._h, _ptr(ids) if len(ids) else None, len(ids), C.byref(r)))
+        try:
+            ng = int(r.ngroups)
+            raw = _array(r.values, ng, np.uint64)
+            values = raw.astype(np.bool_) if self.kind == 0 else raw.view(np.int64 if self.kind == 1 else np.float64)
+            return values, _array(r.counts, ng, np.int64), _array(r.rep_ids, ng, np.int64), int(r.missing)
+        finally:
+            self._lib.cdb_clusters_free(C.byref(r))
+
     def stat(self, name):
         v = C.c_double(0)
         if self._lib.cdb_column_get_stat(self._h, name.encode(), C.byref(v)) != 0:
@@ -726,7 +777,7 @@ class GpuColumn:
         return v.value
 
     def set_option(self, name, value):
-        """Test / measurement hook (cdb_debug_column_set_option): "profile", "debug_query_path"."""
+        """Test / measurement hook (cdb_debug_column_set_option): "profile", "debug_query_path", "debug_cluster_path"."""
         self._check(self._lib.cdb_debug_column_set_option(self._h, name.encode(), int(value)))
 
     def profile(self):

@@ -247,51 +247,6 @@ struct Windows {
     uint64_t k = 0;                  // sum of b - a (overlaps counted)
 };
 
-}  // namespace
-
-struct cdb_column {
-    int kind = 1;
-    Index ws;  // stream, device, lock, error text, radix / scan work spaces, profiler; result rows of an AND it leads (q_ids / q_counts)
-    std::vector<int64_t> staged_ids;
-    std::vector<uint64_t> staged_raw;
-    uint64_t n = 0;
-    uint64_t n_false = 0;  // bool: rows with value false (they come first in key order)
-    DevBuf keys_v, ids_v, id_sorted, vpos;
-    DevBuf d_bounds;  // scratch: bound values, tags, positions
-    double build_ms = 0;
-    double last_union_ms = 0;  // the last materialisation (windows uploaded .. ids on the device), host wall clock
-    int id_sort_skipped = 0;
-    int debug_query_path = 0;
-    uint64_t sparse_queries = 0, dense_queries = 0, probe_filters = 0, materialised_keys = 0, last_k = 0;
-};
-
-namespace {
-
-void set_err(Index& ix, const char* msg) {
-    std::lock_guard<std::mutex> g(ix.err_mu);
-    ix.err = msg;
-}
-
-template <typename F>
-int guarded_ix(Index& ix, F&& f) {
-    ForegroundCall fg;
-    try {
-        f();
-        return CDB_OK;
-    } catch (const Error& e) {
-        set_err(ix, e.what());
-        const bool dev = std::strncmp(e.what(), "HIP error", 9) == 0;
-        const bool internal = std::strstr(e.what(), "internal") != nullptr;
-        return dev ? CDB_E_DEVICE : (internal ? CDB_E_INTERNAL : CDB_E_INVALID);
-    } catch (const std::bad_alloc&) {
-        set_err(ix, "out of host memory");
-        return CDB_E_DEVICE;
-    } catch (const std::exception& e) {
-        set_err(ix, e.what());
-        return CDB_E_INTERNAL;
-    }
-}
-
 struct ColumnScope {
     StreamScope ss;
     explicit ColumnScope(cdb_column* c) : ss(c->ws.stream) { CDB_HIP(hipSetDevice(c->ws.device)); }
@@ -422,6 +377,7 @@ void column_build(cdb_column* c) {
     c->vpos = std::move(vpos);
     c->n = n;
     c->n_false = n_false;
+    ++c->generation;  // (cluster.hip keeps a table per build)
     c->staged_ids.clear();
     c->staged_ids.shrink_to_fit();
     c->staged_raw.clear();
@@ -903,7 +859,8 @@ int cdb_column_get_stat(const cdb_column* c, const char* name, double* value) {
         {"id_sort_skipped", (double)c->id_sort_skipped}, {"sparse_queries", (double)c->sparse_queries},
         {"dense_queries", (double)c->dense_queries}, {"probe_filters", (double)c->probe_filters},
         {"materialised_keys", (double)c->materialised_keys}, {"last_k", (double)c->last_k}, {"kind", (double)c->kind},
-        {"last_union_ms", c->last_union_ms},
+        {"last_union_ms", c->last_union_ms}, {"sparse_clusters", (double)c->sparse_clusters}, {"dense_clusters", (double)c->dense_clusters},
+        {"cluster_ms", c->cluster_ms},
     };
     for (auto& e : tab)
         if (!std::strcmp(e.n, name)) {
@@ -922,6 +879,10 @@ int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value) 
     }
     if (!std::strcmp(name, "debug_query_path") && value >= 0 && value <= 2) {
         c->debug_query_path = (int)value;
+        return CDB_OK;
+    }
+    if (!std::strcmp(name, "debug_cluster_path") && value >= 0 && value <= 2) {
+        c->debug_cluster_path = (int)value;
         return CDB_OK;
     }
     return CDB_E_INVALID;

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/coffeedb_gpu.h"
 #include "common.h"
 #include "radix_sort.h"
 
@@ -178,6 +179,7 @@ struct Index {
         d_sa.release();
         d_sa_hi.release();
         sa_packed = false;
+        clu.drop();  // (the class table of cdb_cluster describes the array that just went)
     }
     template <typename T> typename SaOf<T>::ptr sa_view() const;  // (below)
     bool sa_sorted = false;           // SA is globally sorted in unsigned byte order (false only for
@@ -300,6 +302,29 @@ struct Index {
     int key_coding = 0;           // initial sort keys: 0 = dense when that saves a pass, 1 = bit-aligned symbols, 2 = dense
     uint64_t query_hit_budget = 1ull << 31;  // hits resolved per chunk of a batch (16 B of scratch each)
 
+    // ---- cluster tables (cluster.hip): built under ix.mu at the first cdb_cluster on a built array, dropped where the array goes
+    // (release_sa above: reset_unbuilt, every build, and the order proof's repair of a damaged array — a table made from an array the
+    // proof later judges wrong must not outlive it).  4 * ndocs + 4 * nclasses bytes, plus 12 * ndocs when the ids do not ascend.
+    struct ClusterTables {
+        bool valid = false;
+        uint64_t nclasses = 0;     // distinct documents (the empty document included when there is one)
+        bool ids_ascend = true;    // d_ids is its own id -> document table
+        bool resorted = false;     // classes were put into std::string order on the host (array in the reference's order)
+        DevBuf class_of_doc;       // u32[ndocs]
+        DevBuf class_rep;          // u32[nclasses]: one document of every class
+        DevBuf id_sorted, id_doc;  // !ids_ascend: the ids ascending (i64) and the document of each (u32)
+        double prepare_ms = 0, last_ms = 0;
+        uint64_t bytes() const { return class_of_doc.bytes + class_rep.bytes + id_sorted.bytes + id_doc.bytes; }
+        void drop() {
+            valid = false;
+            nclasses = 0;
+            class_of_doc.release();
+            class_rep.release();
+            id_sorted.release();
+            id_doc.release();
+        }
+    } clu;
+
     double host_upload_ms = 0, host_free_ms = 0;  // cdb_build: staged column to the device / staging copy released
     Profiler prof;
     BuildStats bstats;
@@ -408,8 +433,62 @@ template <typename F> inline auto sa_dispatch(const Index& ix, F&& f) {
 struct cdb_index {
     cdb::Index ix;
 };
+// ... and behind cdb_column (columns.hip builds and queries it, cluster.hip groups by it)
+struct cdb_column {
+    int kind = 1;
+    cdb::Index ws;  // stream, device, lock, error text, radix / scan work spaces, profiler; result rows of an AND it leads (q_ids / q_counts)
+    std::vector<int64_t> staged_ids;
+    std::vector<uint64_t> staged_raw;
+    uint64_t n = 0;
+    uint64_t n_false = 0;  // bool: rows with value false (they come first in key order)
+    cdb::DevBuf keys_v, ids_v, id_sorted, vpos;
+    cdb::DevBuf d_bounds;  // scratch: bound values, tags, positions
+    double build_ms = 0;
+    double last_union_ms = 0;  // the last materialisation (windows uploaded .. ids on the device), host wall clock
+    int id_sort_skipped = 0;
+    int debug_query_path = 0;
+    uint64_t sparse_queries = 0, dense_queries = 0, probe_filters = 0, materialised_keys = 0, last_k = 0;
+    // cluster.hip: where every run of equal keys starts (u64[runs + 1]), made at the first dense cluster of this build
+    uint64_t generation = 0;  // counts builds
+    uint64_t clu_generation = UINT64_MAX, clu_runs = 0;
+    cdb::DevBuf clu_run_start;
+    int debug_cluster_path = 0;  // 0 = automatic, 1 = always sparse, 2 = always dense
+    uint64_t sparse_clusters = 0, dense_clusters = 0;
+    double cluster_ms = 0;
+};
 struct cdb_key_query;
 namespace cdb {
+// the value (bit pattern) behind a column's order-preserving key (columns.hip: order_key; kind: 0 bool, 1 int64, 2 double)
+__host__ __device__ __forceinline__ uint64_t column_key_raw(int kind, uint64_t key) {
+    constexpr uint64_t S = 1ull << 63;
+    if (kind == 1) return key ^ S;
+    if (kind == 2) return (key & S) ? (key ^ S) : ~key;
+    return key;
+}
+// body of a C-ABI entry point that reports through an Index (columns, clusters): exceptions -> CDB_E_* + last-error text
+template <typename F>
+int guarded_ix(Index& ix, F&& f) {
+    ForegroundCall fg;
+    auto set_err = [&ix](const char* msg) {
+        std::lock_guard<std::mutex> g(ix.err_mu);
+        ix.err = msg;
+    };
+    try {
+        f();
+        return CDB_OK;
+    } catch (const Error& e) {
+        set_err(e.what());
+        const bool dev = std::strncmp(e.what(), "HIP error", 9) == 0;
+        const bool internal = std::strstr(e.what(), "internal") != nullptr;
+        return dev ? CDB_E_DEVICE : (internal ? CDB_E_INTERNAL : CDB_E_INVALID);
+    } catch (const std::bad_alloc&) {
+        set_err("out of host memory");
+        return CDB_E_DEVICE;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return CDB_E_INTERNAL;
+    }
+}
 int query_and_with_lead(cdb_index* lead, const cdb_key_query* keys, int nkeys, int ranked, int64_t corr_lo, int64_t corr_hi,
                         uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows);
 }

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "../../../include/coffeedb_gpu.h"
+#include "cluster.h"
 #ifdef CDB_USE_REFERENCE_UTILITY
 #include "utility.h"  // the reference's own parse_range (src/utility.h:69-86)
 #else
@@ -45,6 +46,20 @@ index::result_type column_query(cdb_column* c, const std::string& range) {
     cdb_free(ids);
     return out;
 }
+struct clusters_guard {  // releases the library's arrays also when printing the groups throws
+    cdb_clusters cl{};
+    ~clusters_guard() { cdb_clusters_free(&cl); }
+};
+index::cluster_type column_cluster(cdb_column* c, int kind, const index::result_type& rows) {
+    if (!c) throw std::logic_error("cluster: this index is not a GPU column (COFFEEDB_GPU_NUMERIC=1)");
+    std::vector<int64_t> ids;
+    ids.reserve(rows.size());
+    for (const auto& r : rows) ids.push_back(r.first);
+    clusters_guard g;
+    const int rc = cdb_column_cluster(c, ids.data(), ids.size(), &g.cl);
+    if (rc != CDB_OK) rethrow_column(c, rc);
+    return cdb_shim::cluster_rows(g.cl, kind);
+}
 }  // namespace
 
 // ---- numeric indexes: sorted (value, id) pairs, half-open lower_bound window (index.cpp:63-74, 129-173)
@@ -79,6 +94,10 @@ index::result_type numeric_index<T, Tag>::query(const std::string& range) const 
     if (first < last) out.reserve((size_t)(last - first));
     for (auto it = first; it < last; ++it) out.emplace_back(it->second, 0);
     return out;
+}
+template <typename T, int8_t Tag>
+index::cluster_type numeric_index<T, Tag>::cluster(const result_type& rows) const {
+    return column_cluster(col, Tag, rows);
 }
 template class numeric_index<int64_t, 1>;
 template class numeric_index<double, 2>;
@@ -118,6 +137,8 @@ index::result_type bool_index::query(const std::string& range) const {
     for (int64_t id : data[which]) out.emplace_back(id, 0);
     return out;
 }
+
+index::cluster_type bool_index::cluster(const result_type& rows) const { return column_cluster(col, number, rows); }
 
 // ---- string index: forwards to the GPU library
 namespace {
@@ -230,6 +251,17 @@ index::result_type string_index::query(const std::string& keyword) const {
     cdb_free(ids);
     cdb_free(counts);
     return out;
+}
+
+index::cluster_type string_index::cluster(const result_type& rows) const {
+    if (!handle) throw std::logic_error("cluster: not available on a sharded string index (COFFEEDB_GPUS)");
+    std::vector<int64_t> ids;
+    ids.reserve(rows.size());
+    for (const auto& r : rows) ids.push_back(r.first);
+    clusters_guard g;
+    const int rc = cdb_cluster(handle, ids.data(), ids.size(), 1, &g.cl);
+    if (rc != CDB_OK) rethrow(handle, rc);
+    return cdb_shim::cluster_rows(g.cl);
 }
 
 std::vector<index::result_type> string_index::query_batch(const std::vector<std::string>& keywords) const {

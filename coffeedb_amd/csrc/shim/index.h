@@ -25,6 +25,8 @@ struct cdb_column;  // opaque GPU numeric / bool column (COFFEEDB_GPU_NUMERIC=1)
 class index {
 public:
     using result_type = std::vector<std::pair<int64_t, int64_t>>;
+    // what database.cpp's cluster() returns (database.cpp:442): (printed value, rows that hold it), ordered by the string
+    using cluster_type = std::vector<std::pair<const std::string, int64_t>>;
     index() = default;
     index(const index&) = delete;
     index(index&&) = delete;
@@ -49,6 +51,10 @@ public:
     void build() override;
     result_type query(const std::string& range) const override;
     cdb_column* column() const { return col; }
+    // NEW: database.cpp:442-460 for this field — the result rows grouped by their value on the device (cdb_column_cluster +
+    // cluster.h).  GPU column only (std::logic_error otherwise: the CPU classes keep the reference's surface).  Rows whose id
+    // the column does not hold are skipped (undefined behaviour in the reference).
+    cluster_type cluster(const result_type& rows) const;
 
 private:
     std::array<std::vector<int64_t>, 2> data;
@@ -77,6 +83,7 @@ public:
     void build() override;
     result_type query(const std::string& range) const override;
     cdb_column* column() const { return col; }
+    cluster_type cluster(const result_type& rows) const;  // NEW: as bool_index::cluster
 
 protected:
     std::vector<std::pair<T, int64_t>> rows;
@@ -120,6 +127,9 @@ public:
     // Render with cdb_shim::render_spans (highlight.h).
     std::vector<std::pair<int64_t, std::vector<std::pair<uint64_t, uint64_t>>>> highlight_spans(
         const std::vector<std::string>& keywords) const;
+    // NEW: database.cpp:442-460 for this field — the result rows grouped by their whole document on the device (cdb_cluster),
+    // in std::string order.  One GPU only (std::logic_error with COFFEEDB_GPUS).
+    cluster_type cluster(const result_type& rows) const;
     // NEW (no counterpart in the reference): announce a string column of roughly `bytes` bytes BEFORE the data is loaded —
     // start_server() calls init() and then build() (server.cpp:43-44); called at the start of init() with the size of the raw
     // directory (and any document as a sample of the alphabet) it lets the GPU map the first build's working set on a helper

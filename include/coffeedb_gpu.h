@@ -218,7 +218,8 @@ int cdb_query_and_columns(const cdb_key_query* keys, int nkeys, const cdb_column
                           int64_t corr_hi, uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows);
 /* "rows", "staged_rows", "build_ms", "id_sort_skipped", "sparse_queries", "dense_queries", "probe_filters",
  * "materialised_keys", "last_k" (rows inside the last query's windows), "last_union_ms" (the last query_any's or
- * materialised key's union on the device, result download excluded) */
+ * materialised key's union on the device, result download excluded), "sparse_clusters", "dense_clusters", "cluster_ms" (the last
+ * cdb_column_cluster: ids uploaded .. groups on the host) */
 int cdb_column_get_stat(const cdb_column* c, const char* name, double* value);
 /* Test and measurement hooks of the columns — NOT part of the stable ABI (like the other cdb_debug_* entry points they may change
  * or go without notice; the library chooses every path itself, a caller never needs them):
@@ -227,6 +228,46 @@ int cdb_column_get_stat(const cdb_column* c, const char* name, double* value);
  * union paths and the crossover measurement of tools/bench_columns.py). */
 int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value);
 int cdb_debug_column_profile_dump(cdb_column* c, char* buf, size_t cap);
+
+/* ---- cluster (cluster.hip) ---------------------------------------------------------------------------
+ * replaces database.cpp:442-460 (`cluster`, driven by interface.cpp:249-273): "how many of the rows filter() left over have
+ * which value in field F".  The reference walks the rows through its host object store into a std::map<std::string, int64_t>;
+ * here the rows are grouped on the device by the column / string index that already holds the field.
+ *
+ * Input: the ids of the rows (the counts of a result row play no part).  nrows = 0 is valid and yields zero groups; so does a
+ * column / index that was never built (every row is then `missing`, the choice cdb_query makes for an unbuilt index).
+ * An id the column / index does not hold is skipped and counted in `missing` (the reference dereferences data[id].find(field)
+ * unchecked there: undefined behaviour); sum(counts) + missing == nrows always.  A repeated id counts as often as it is given.
+ * Group order — column: ascending by value, compared as the column compares; string index: ascending by
+ * std::string::operator< (unsigned bytes, a proper prefix first, the empty string first of all) whatever reference_compat is
+ * and whatever bytes the text holds.
+ * KNOWN DIVERGENCE: a double column folds -0.0 onto +0.0 when it is built, so the two zeros form ONE group whose value is
+ * +0.0; the reference would print "-0.000000" and "0.000000" separately.
+ * The strings the reference prints for numeric values (std::to_string, with distinct values that print alike merged) are
+ * made on the host by cdb_shim::cluster_rows (coffeedb_amd/csrc/shim/cluster.h).
+ * All arrays are host memory owned by the library (pinned result cache when large): release with cdb_clusters_free only.
+ * Both calls are queries: several host threads may run them on one handle, they wait out a rebuild; the string index's class
+ * table (4 bytes per document + 4 per distinct document, stats "cluster_table_bytes", "cluster_classes",
+ * "cluster_prepare_ms", "cluster_ms"; "cluster_resorted" = 1 when its classes had to be ordered on the host) is made once per
+ * built array under the handle's lock, at the first cdb_cluster, and goes wherever that array goes: every build and load, and the
+ * order proof's repair of a damaged array.  Cost to know: when the array is in the reference's order (reference_compat = 1 and text
+ * with bytes >= 0x80) the classes are put into std::string order on the HOST — one document per class is downloaded and sorted
+ * while the handle's lock is held; for a column of mostly distinct documents that is nearly the whole text (254 ms for 256 MiB
+ * of distinct 256-byte documents on an MI355X host), once per build.  Pure ASCII text and reference_compat = 0 skip that step.
+ * cdb_debug_column_set_option "debug_cluster_path" (0 automatic, 1 sort + run lengths, 2 counters per position) forces one of
+ * the column's two paths (tests, tools/bench_cluster.py).  Not available on cdb_shards. */
+typedef struct cdb_clusters {
+    uint64_t ngroups;
+    uint64_t missing;      /* input rows whose id the column / index does not hold (skipped) */
+    int64_t* counts;       /* ngroups: input rows in the group */
+    int64_t* rep_ids;      /* ngroups: the smallest object id of the group among the input rows */
+    uint64_t* values;      /* column: ngroups raw values (int64 / double bit pattern / 0, 1); string index: NULL */
+    uint64_t* value_ptr;   /* string index with with_values != 0: ngroups + 1 offsets into value_blob; else NULL */
+    char* value_blob;      /* the groups' strings, concatenated */
+} cdb_clusters;
+int cdb_column_cluster(cdb_column* c, const int64_t* ids, uint64_t nrows, cdb_clusters* out);
+int cdb_cluster(cdb_index* h, const int64_t* ids, uint64_t nrows, int with_values, cdb_clusters* out);
+void cdb_clusters_free(cdb_clusters* r);
 
 /* Highlight spans — replaces the per-document re-scan of ac_automaton::render (database.cpp:58-76) that
  * select() runs for every returned object (database.cpp:394-441): for the keyword list of ONE string
