@@ -89,7 +89,7 @@ void commit_layout(Index& ix, const Layout& L) {
     ix.ndocs = L.ndocs;
 }
 
-// document tables into fresh device blocks (committed by the caller once everything else succeeded)
+// document tables into fresh device blocks (installed once everything else succeeded: replace_column)
 void upload_tables(Index& ix, const std::vector<uint64_t>& doc_start, const std::vector<int64_t>& ids, uint64_t ndocs,
                    DevBuf& d_start, DevBuf& d_ids) {
     hipStream_t s = ix.stream;
@@ -117,70 +117,19 @@ void upload_fork(hipStream_t s, hipStream_t s2) {
     (void)hipEventDestroy(ev);
     CDB_HIP(e2);
 }
-void upload_pageable(void* dst, const char* src, size_t bytes, hipStream_t s, int device, hipStream_t s2 = nullptr) {
-    constexpr size_t CHUNK = 16u << 20;
-    // (a host thread fills pinned chunks at ~10 GB/s: four of them stay below the link's 57 GB/s, eight do not)
-    static const int t_env = getenv("CDB_UPLOAD_THREADS") ? std::atoi(getenv("CDB_UPLOAD_THREADS")) : 0;
-    const int T = std::max(2, std::min({t_env > 0 ? t_env : 8, (int)std::thread::hardware_concurrency() / 2, (int)(bytes / (2 * CHUNK))}));
-    if (bytes < 4 * CHUNK) {
-        if (bytes) CDB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-        return;
-    }
-    upload_fork(s, s2);
-    const size_t nchunks = (bytes + CHUNK - 1) / CHUNK;
-    std::string failure;
-    std::mutex fmu;
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t)
-        th.emplace_back([&, t] {
-            void* pin[2] = {nullptr, nullptr};
-            hipEvent_t ev[2] = {nullptr, nullptr};
-            try {
-                CDB_HIP(hipSetDevice(device));
-                for (int k = 0; k < 2; ++k) {
-                    pin[k] = HostPool::get().alloc(CHUNK);
-                    if (!pin[k]) throw Error("HIP error: no pinned staging memory");
-                    CDB_HIP(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-                }
-                int k = 0;
-                bool used[2] = {false, false};
-                for (size_t c = t; c < nchunks; c += T, k ^= 1) {
-                    const size_t off = c * CHUNK, len = std::min(CHUNK, bytes - off);
-                    if (used[k]) CDB_HIP(hipEventSynchronize(ev[k]));  // the DMA out of this block has finished
-                    std::memcpy(pin[k], src + off, len);
-                    hipStream_t cs = (s2 && (t & 1)) ? s2 : s;
-                    CDB_HIP(hipMemcpyAsync(static_cast<char*>(dst) + off, pin[k], len, hipMemcpyHostToDevice, cs));
-                    CDB_HIP(hipEventRecord(ev[k], cs));
-                    used[k] = true;
-                }
-                for (int q = 0; q < 2; ++q)
-                    if (used[q]) CDB_HIP(hipEventSynchronize(ev[q]));
-            } catch (const std::exception& e) {
-                (void)hipStreamSynchronize(s);  // a DMA out of the pinned blocks may still be in flight: it ends before they go back
-                if (s2) (void)hipStreamSynchronize(s2);
-                std::lock_guard<std::mutex> g(fmu);
-                if (failure.empty()) failure = e.what();
-            }
-            for (int q = 0; q < 2; ++q) {
-                if (ev[q]) (void)hipEventDestroy(ev[q]);
-                if (pin[q]) (void)HostPool::get().release(pin[q]);
-            }
-        });
-    for (auto& x : th) x.join();
-    if (!failure.empty()) throw Error(failure);
-}
-
-// The same for a column that is NOT contiguous on the host: document d is the lens[d] bytes at ptrs[d] — string_index's own
-// state (index.h:58: non-owning string_views into database.cpp's strings).  The gather into the pinned chunks IS the
-// staging copy (there is no other one); doc_start = the running sum of lens.
-void upload_views(void* dst, const char* const* ptrs, const uint64_t* doc_start, uint64_t ndocs, size_t bytes, hipStream_t s,
-                  int device, hipStream_t s2 = nullptr) {
-    constexpr size_t CHUNK = 16u << 20;
-    // (the gather of scattered 1 KiB strings runs at ~5 GB/s per host thread: four threads would make it — not the PCIe link
-    //  at ~52 GB/s — the bound of the shim's build(); up to twelve keep the link busy)
+// The pipeline both uploads share.  Every host thread owns UPLOAD_BLOCKS pinned blocks of UPLOAD_CHUNK bytes and an event per block;
+// chunk c belongs to thread c % T, which has `fill(pin, off, len)` write the chunk's bytes into a block and queues the DMA behind it.
+// Odd threads queue on s2.  T = the CDB_UPLOAD_THREADS override or `default_threads`, at most half the cores and one thread per two
+// chunks, at least `min_threads`; below four chunks ONE chunk loop runs on the calling thread, on s alone.
+constexpr size_t UPLOAD_CHUNK = 16u << 20;
+constexpr int UPLOAD_BLOCKS = 2;
+constexpr int UPLOAD_THREADS_PAGEABLE = 8, UPLOAD_THREADS_VIEWS = 12;  // (the defaults: measured below)
+template <typename Fill>
+void upload_chunked(void* dst, size_t bytes, hipStream_t s, int device, hipStream_t s2, int min_threads, int default_threads, Fill&& fill) {
+    constexpr size_t CHUNK = UPLOAD_CHUNK;
     const int hw = (int)std::thread::hardware_concurrency();
     static const int t_env = getenv("CDB_UPLOAD_THREADS") ? std::atoi(getenv("CDB_UPLOAD_THREADS")) : 0;  // (measurements)
-    const int T = bytes >= 4 * CHUNK ? std::max(4, std::min({t_env > 0 ? t_env : 12, hw / 2, (int)(bytes / (2 * CHUNK))})) : 1;
+    const int T = bytes >= 4 * CHUNK ? std::max(min_threads, std::min({t_env > 0 ? t_env : default_threads, hw / 2, (int)(bytes / (2 * CHUNK))})) : 1;
     const size_t nchunks = (bytes + CHUNK - 1) / CHUNK;
     if (T > 1) upload_fork(s, s2);
     else s2 = nullptr;
@@ -188,38 +137,27 @@ void upload_views(void* dst, const char* const* ptrs, const uint64_t* doc_start,
     std::mutex fmu;
     std::vector<std::thread> th;
     auto work = [&](int t) {
-        void* pin[2] = {nullptr, nullptr};
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        void* pin[UPLOAD_BLOCKS] = {};
+        hipEvent_t ev[UPLOAD_BLOCKS] = {};
         try {
             CDB_HIP(hipSetDevice(device));
-            for (int k = 0; k < 2; ++k) {
+            for (int k = 0; k < UPLOAD_BLOCKS; ++k) {
                 pin[k] = HostPool::get().alloc(CHUNK);
                 if (!pin[k]) throw Error("HIP error: no pinned staging memory");
                 CDB_HIP(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
             }
             int k = 0;
-            bool used[2] = {false, false};
-            for (size_t c = t; c < nchunks; c += T, k ^= 1) {
+            bool used[UPLOAD_BLOCKS] = {};
+            for (size_t c = t; c < nchunks; c += T, k = (k + 1) % UPLOAD_BLOCKS) {
                 const size_t off = c * CHUNK, len = std::min(CHUNK, bytes - off);
                 if (used[k]) CDB_HIP(hipEventSynchronize(ev[k]));  // the DMA out of this block has finished
-                // documents overlapping [off, off + len): the first one is the last d with doc_start[d] <= off
-                uint64_t d = std::upper_bound(doc_start, doc_start + ndocs + 1, (uint64_t)off) - doc_start - 1;
-                size_t at = 0;
-                while (at < len) {
-                    const uint64_t ds = doc_start[d], de = doc_start[d + 1];
-                    const uint64_t from = std::max<uint64_t>(ds, off + at), to = std::min<uint64_t>(de, off + len);
-                    if (to > from) {
-                        std::memcpy(static_cast<char*>(pin[k]) + at, ptrs[d] + (from - ds), to - from);
-                        at += to - from;
-                    }
-                    ++d;
-                }
+                fill(static_cast<char*>(pin[k]), off, len);
                 hipStream_t cs = (s2 && (t & 1)) ? s2 : s;
                 CDB_HIP(hipMemcpyAsync(static_cast<char*>(dst) + off, pin[k], len, hipMemcpyHostToDevice, cs));
                 CDB_HIP(hipEventRecord(ev[k], cs));
                 used[k] = true;
             }
-            for (int q = 0; q < 2; ++q)
+            for (int q = 0; q < UPLOAD_BLOCKS; ++q)
                 if (used[q]) CDB_HIP(hipEventSynchronize(ev[q]));
         } catch (const std::exception& e) {
             (void)hipStreamSynchronize(s);  // a DMA out of the pinned blocks may still be in flight: it ends before they go back
@@ -227,7 +165,7 @@ void upload_views(void* dst, const char* const* ptrs, const uint64_t* doc_start,
             std::lock_guard<std::mutex> g(fmu);
             if (failure.empty()) failure = e.what();
         }
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < UPLOAD_BLOCKS; ++q) {
             if (ev[q]) (void)hipEventDestroy(ev[q]);
             if (pin[q]) (void)HostPool::get().release(pin[q]);
         }
@@ -239,6 +177,37 @@ void upload_views(void* dst, const char* const* ptrs, const uint64_t* doc_start,
         for (auto& x : th) x.join();
     }
     if (!failure.empty()) throw Error(failure);
+}
+void upload_pageable(void* dst, const char* src, size_t bytes, hipStream_t s, int device, hipStream_t s2 = nullptr) {
+    if (bytes < 4 * UPLOAD_CHUNK) {
+        if (bytes) CDB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+        return;
+    }
+    // (a host thread fills pinned chunks at ~10 GB/s: four of them stay below the link's 57 GB/s, eight do not)
+    upload_chunked(dst, bytes, s, device, s2, 2, UPLOAD_THREADS_PAGEABLE, [src](char* pin, size_t off, size_t len) { std::memcpy(pin, src + off, len); });
+}
+
+// The same for a column that is NOT contiguous on the host: document d is the lens[d] bytes at ptrs[d] — string_index's own
+// state (index.h:58: non-owning string_views into database.cpp's strings).  The gather into the pinned chunks IS the
+// staging copy (there is no other one); doc_start = the running sum of lens.
+void upload_views(void* dst, const char* const* ptrs, const uint64_t* doc_start, uint64_t ndocs, size_t bytes, hipStream_t s,
+                  int device, hipStream_t s2 = nullptr) {
+    // (the gather of scattered 1 KiB strings runs at ~5 GB/s per host thread: four threads would make it — not the PCIe link
+    //  at ~52 GB/s — the bound of the shim's build(); up to twelve keep the link busy)
+    upload_chunked(dst, bytes, s, device, s2, 4, UPLOAD_THREADS_VIEWS, [=](char* pin, size_t off, size_t len) {
+        // documents overlapping [off, off + len): the first one is the last d with doc_start[d] <= off
+        uint64_t d = std::upper_bound(doc_start, doc_start + ndocs + 1, (uint64_t)off) - doc_start - 1;
+        size_t at = 0;
+        while (at < len) {
+            const uint64_t ds = doc_start[d], de = doc_start[d + 1];
+            const uint64_t from = std::max<uint64_t>(ds, off + at), to = std::min<uint64_t>(de, off + len);
+            if (to > from) {
+                std::memcpy(pin + at, ptrs[d] + (from - ds), to - from);
+                at += to - from;
+            }
+            ++d;
+        }
+    });
 }
 
 // back to "never built" (queries answer {}): a failed build or load must not leave new parameters over an old array
@@ -254,6 +223,100 @@ void reset_unbuilt(Index& ix) {
     ix.width = 0;
     ix.size = 0;
     ix.q_spec_cap = 0;
+}
+
+// Everything a handle needs to serve a new column, gathered BEFORE the handle is touched: every cdb_build* and cdb_load fill one
+// of these ("prepare") and hand it to replace_column.
+struct NewColumn {
+    Layout L;
+    DevBuf text;                        // the library's own copy of the text (TEXT_PAD readable zero bytes behind it), or ...
+    const uint8_t* borrowed = nullptr;  // ... the caller's device memory (no padding promised)
+    DevBuf d_start, d_ids;
+    enum { HOST_KEPT, HOST_NEW, HOST_NONE } host = HOST_KEPT;  // the handle's staging copy stays (cdb_build) / ids + doc_start below
+    std::vector<int64_t> ids;                                  // replace it / tables and text live on the device only
+    std::vector<uint64_t> doc_start;
+    double upload_t0 = -1;  // wall_ms() when the upload of the text began (host_upload_ms); < 0: nothing was uploaded
+    // cdb_load only: the array comes with the column instead of being built (sa_hi: the packed storage's fifth bytes)
+    DevBuf sa, sa_hi;
+    bool reference_compat = true, sa_sorted = true;
+};
+
+void alloc_padded_text(Index& ix, DevBuf& text, uint64_t n) {
+    text.alloc(n + TEXT_PAD);
+    CDB_HIP(hipMemsetAsync((uint8_t*)text.p + n, 0, TEXT_PAD, ix.stream));
+}
+
+// the caller's tables on the origin of its first document, into host copies the handle will keep
+void rebase_tables(const uint64_t* doc_start, const int64_t* ids, uint64_t ndocs, uint64_t first, NewColumn& c) {
+    c.ids.assign(ids, ids + ndocs);
+    c.doc_start.resize(ndocs + 1);
+    c.doc_start[0] = 0;
+    for (uint64_t d = 0; d < ndocs; ++d) {
+        if (doc_start[d + 1] < doc_start[d]) throw Error("doc_start must be non-decreasing");
+        c.doc_start[d + 1] = doc_start[d + 1] - first;
+    }
+    c.host = NewColumn::HOST_NEW;
+}
+
+// The commit point: the old index stops serving here, and from here on a failure leaves a "never built" handle.
+void install(Index& ix, NewColumn& c) {
+    const bool loaded = c.sa.p != nullptr;
+    try {
+        reset_unbuilt(ix);  // (waits for the stream: the old arrays are idle; ix.mu keeps queries out)
+        if (!loaded) ix.host_upload_ms = c.upload_t0 >= 0 ? wall_ms() - c.upload_t0 : 0;  // (a build's statistic: a load keeps them all)
+        commit_layout(ix, c.L);
+        if (c.host == NewColumn::HOST_NEW) {
+            ix.ids.swap(c.ids);
+            ix.doc_start.swap(c.doc_start);
+            ix.host_tables_valid = true;
+        } else if (c.host == NewColumn::HOST_NONE) {
+            ix.ids.clear();
+            ix.doc_start.assign(1, 0);
+            ix.host_tables_valid = false;  // fetched back on demand (ensure_host_tables)
+        }
+        if (c.host != NewColumn::HOST_KEPT) {  // the column lives on the device (and with the caller): cdb_add* fetch it back
+            std::string().swap(ix.host_text);
+            ix.host_text_valid = false;
+        }
+        ix.d_text_owned = std::move(c.text);  // (empty for a borrowed text: the previous copy is released)
+        ix.d_text = c.borrowed ? c.borrowed : ix.d_text_owned.as<uint8_t>();
+        ix.text_padded = !c.borrowed;
+        ix.d_doc_start = std::move(c.d_start);
+        ix.d_ids = std::move(c.d_ids);
+        if (!loaded) {
+            build_suffix_array(ix);
+            return;
+        }
+        ix.reference_compat = c.reference_compat;
+        ix.sa_sorted = c.sa_sorted;  // a reference-compat ordering keeps the reference's exact probe sequence
+        ix.d_sa = std::move(c.sa);
+        if (c.sa_hi.p) {
+            ix.d_sa_hi = std::move(c.sa_hi);
+            ix.sa_packed = true;
+        }
+        // a file's entries were checked one by one (each names a real suffix), their ORDER was not: the proof behind a build runs
+        // behind a load as well (damage -> the array is rebuilt from the loaded text)
+        if (ix.self_check >= 3 || ix.premap_generation) {
+            ix.proof.of_loaded_file = true;
+            proof_start(ix);
+        }
+    } catch (...) {
+        reset_unbuilt(ix);
+        throw;
+    }
+}
+
+// prepare(c) validates, allocates and uploads into c; a failure in it (allocation, upload) leaves the previous index serving
+template <typename Prepare>
+void replace_column(Index& ix, Prepare&& prepare) {
+    NewColumn c;
+    try {
+        prepare(c);
+    } catch (...) {
+        (void)hipStreamSynchronize(ix.stream);  // (copies into blocks of c may be queued: they end before the blocks go back)
+        throw;
+    }
+    install(ix, c);
 }
 
 // every entry point that touches the device: make the handle's device current and tell the block cache which
@@ -662,96 +725,76 @@ int cdb_load(cdb_index* h, const char* path) {
         FILE* fp = std::fopen(path, "rb");
         if (!fp) throw Error(std::string("Cannot open file: ") + path);
         struct Closer { FILE* f; ~Closer() { std::fclose(f); } } closer{fp};
-        // ---- everything is read and checked into locals; the handle changes only when the file proved consistent
-        SaveHeader hd{};
-        if (std::fread(&hd, sizeof(hd), 1, fp) != 1 || hd.magic != SAVE_MAGIC || (hd.width != 4 && hd.width != 8))
-            throw Error(std::string("Not a saved index: ") + path);
-        if (std::fseek(fp, 0, SEEK_END) != 0) throw Error(std::string("Cannot read file: ") + path);
-        const long long fsize = std::ftell(fp);
-        if (hd.ndocs >= (1ull << 33) || hd.size >= (1ull << 48) ||
-            fsize < 0 || (unsigned long long)fsize != sizeof(hd) + 8 * hd.ndocs + 8 * (hd.ndocs + 1) + hd.size + hd.size * hd.width)
-            throw Error(std::string("Truncated index file: ") + path);
-        if (std::fseek(fp, (long)sizeof(hd), SEEK_SET) != 0) throw Error(std::string("Cannot read file: ") + path);
-        std::vector<int64_t> ids(hd.ndocs);
-        std::vector<uint64_t> doc_start(hd.ndocs + 1);
-        bool ok = hd.ndocs == 0 || std::fread(ids.data(), 8, hd.ndocs, fp) == hd.ndocs;
-        ok = ok && std::fread(doc_start.data(), 8, hd.ndocs + 1, fp) == hd.ndocs + 1;
-        if (!ok) throw Error(std::string("Truncated index file: ") + path);
-        if (doc_start[0] != 0 || doc_start[hd.ndocs] != hd.size) throw Error(std::string("Corrupt index file (document table): ") + path);
-        const Layout L = layout_of(doc_start, hd.ndocs);  // (also: doc_start non-decreasing)
-        if (L.size != hd.size || L.bits != hd.bits || L.mask != hd.mask || (uint64_t)L.width != hd.width)
-            throw Error(std::string("Corrupt index file (entry layout): ") + path);
-        DevBuf text, sa, sa_hi, d_start, d_ids;
-        text.alloc(hd.size + TEXT_PAD);
-        CDB_HIP(hipMemsetAsync((uint8_t*)text.p + hd.size, 0, TEXT_PAD, ix.stream));
-        // 8-byte entries below 2^40 are stored packed (the storage a build of this column would leave): they are packed chunk by
-        // chunk while the file is read, so the plain array never exists on the device and nothing can fail after the commit
-        const bool pack = ix.pack_sa && hd.width == 8 && (int)L.bits + L.off_bits <= 40 && hd.size > 0;
-        if (pack) {
-            sa.alloc(hd.size * sizeof(uint32_t));
-            sa_hi.alloc(hd.size);
-        } else {
-            sa.alloc(std::max<uint64_t>(hd.size * hd.width, 16));
-        }
-        std::vector<char> buf(std::min<uint64_t>(std::max<uint64_t>(hd.size * hd.width, 1), 256ull << 20));
-        auto fill = [&](void* dptr, uint64_t bytes) {
-            for (uint64_t o = 0; o < bytes; o += buf.size()) {
-                const uint64_t c = std::min<uint64_t>(buf.size(), bytes - o);
-                if (std::fread(buf.data(), 1, c, fp) != c) throw Error(std::string("Truncated index file: ") + path);
-                CDB_HIP(hipMemcpyAsync(static_cast<char*>(dptr) + o, buf.data(), c, hipMemcpyHostToDevice, ix.stream));
-                CDB_HIP(hipStreamSynchronize(ix.stream));
+        // ---- everything is read and checked into a NewColumn; the handle changes only when the file proved consistent
+        replace_column(ix, [&](NewColumn& col) {
+            SaveHeader hd{};
+            if (std::fread(&hd, sizeof(hd), 1, fp) != 1 || hd.magic != SAVE_MAGIC || (hd.width != 4 && hd.width != 8))
+                throw Error(std::string("Not a saved index: ") + path);
+            if (std::fseek(fp, 0, SEEK_END) != 0) throw Error(std::string("Cannot read file: ") + path);
+            const long long fsize = std::ftell(fp);
+            if (hd.ndocs >= (1ull << 33) || hd.size >= (1ull << 48) ||
+                fsize < 0 || (unsigned long long)fsize != sizeof(hd) + 8 * hd.ndocs + 8 * (hd.ndocs + 1) + hd.size + hd.size * hd.width)
+                throw Error(std::string("Truncated index file: ") + path);
+            if (std::fseek(fp, (long)sizeof(hd), SEEK_SET) != 0) throw Error(std::string("Cannot read file: ") + path);
+            std::vector<int64_t>& ids = col.ids;
+            std::vector<uint64_t>& doc_start = col.doc_start;
+            ids.resize(hd.ndocs);
+            doc_start.resize(hd.ndocs + 1);
+            bool ok = hd.ndocs == 0 || std::fread(ids.data(), 8, hd.ndocs, fp) == hd.ndocs;
+            ok = ok && std::fread(doc_start.data(), 8, hd.ndocs + 1, fp) == hd.ndocs + 1;
+            if (!ok) throw Error(std::string("Truncated index file: ") + path);
+            if (doc_start[0] != 0 || doc_start[hd.ndocs] != hd.size) throw Error(std::string("Corrupt index file (document table): ") + path);
+            const Layout L = layout_of(doc_start, hd.ndocs);  // (also: doc_start non-decreasing)
+            if (L.size != hd.size || L.bits != hd.bits || L.mask != hd.mask || (uint64_t)L.width != hd.width)
+                throw Error(std::string("Corrupt index file (entry layout): ") + path);
+            DevBuf &text = col.text, &sa = col.sa, &sa_hi = col.sa_hi, &d_start = col.d_start, &d_ids = col.d_ids;
+            alloc_padded_text(ix, text, hd.size);
+            // 8-byte entries below 2^40 are stored packed (the storage a build of this column would leave): they are packed chunk by
+            // chunk while the file is read, so the plain array never exists on the device and nothing can fail after the commit
+            const bool pack = ix.pack_sa && hd.width == 8 && (int)L.bits + L.off_bits <= 40 && hd.size > 0;
+            if (pack) {
+                sa.alloc(hd.size * sizeof(uint32_t));
+                sa_hi.alloc(hd.size);
+            } else {
+                sa.alloc(std::max<uint64_t>(hd.size * hd.width, 16));
             }
-        };
-        fill(text.p, hd.size);
-        upload_tables(ix, doc_start, ids, hd.ndocs, d_start, d_ids);
-        // every entry must name a real (document, offset): queries decode entries without further checks
-        const char* bad_sa = "Corrupt index file (suffix array): ";
-        if (pack) {
-            DevBuf chunk;
-            const uint64_t per = buf.size() / 8;
-            chunk.alloc(std::max<uint64_t>(per * 8, 16));
-            for (uint64_t first = 0; first < hd.size; first += per) {
-                const uint64_t cnt = std::min<uint64_t>(per, hd.size - first);
-                if (std::fread(buf.data(), 8, cnt, fp) != cnt) throw Error(std::string("Truncated index file: ") + path);
-                CDB_HIP(hipMemcpyAsync(chunk.p, buf.data(), cnt * 8, hipMemcpyHostToDevice, ix.stream));
-                if (count_invalid_entries(ix.stream, chunk.p, 8, cnt, d_start.as<uint64_t>(), hd.ndocs, (int)L.bits, L.mask) != 0)
+            std::vector<char> buf(std::min<uint64_t>(std::max<uint64_t>(hd.size * hd.width, 1), 256ull << 20));
+            auto fill = [&](void* dptr, uint64_t bytes) {
+                for (uint64_t o = 0; o < bytes; o += buf.size()) {
+                    const uint64_t c = std::min<uint64_t>(buf.size(), bytes - o);
+                    if (std::fread(buf.data(), 1, c, fp) != c) throw Error(std::string("Truncated index file: ") + path);
+                    CDB_HIP(hipMemcpyAsync(static_cast<char*>(dptr) + o, buf.data(), c, hipMemcpyHostToDevice, ix.stream));
+                    CDB_HIP(hipStreamSynchronize(ix.stream));
+                }
+            };
+            fill(text.p, hd.size);
+            upload_tables(ix, doc_start, ids, hd.ndocs, d_start, d_ids);
+            // every entry must name a real (document, offset): queries decode entries without further checks
+            const char* bad_sa = "Corrupt index file (suffix array): ";
+            if (pack) {
+                DevBuf chunk;
+                const uint64_t per = buf.size() / 8;
+                chunk.alloc(std::max<uint64_t>(per * 8, 16));
+                for (uint64_t first = 0; first < hd.size; first += per) {
+                    const uint64_t cnt = std::min<uint64_t>(per, hd.size - first);
+                    if (std::fread(buf.data(), 8, cnt, fp) != cnt) throw Error(std::string("Truncated index file: ") + path);
+                    CDB_HIP(hipMemcpyAsync(chunk.p, buf.data(), cnt * 8, hipMemcpyHostToDevice, ix.stream));
+                    if (count_invalid_entries(ix.stream, chunk.p, 8, cnt, d_start.as<uint64_t>(), hd.ndocs, (int)L.bits, L.mask) != 0)
+                        throw Error(std::string(bad_sa) + path);
+                    sa_pack_chunk(ix.stream, chunk.as<uint64_t>(), cnt, sa.as<uint32_t>(), sa_hi.as<uint8_t>(), first);
+                    CDB_HIP(hipStreamSynchronize(ix.stream));  // (buf and chunk are reused)
+                }
+            } else {
+                fill(sa.p, hd.size * hd.width);
+                if (count_invalid_entries(ix.stream, sa.p, (int)hd.width, hd.size, d_start.as<uint64_t>(), hd.ndocs, (int)L.bits, L.mask) != 0)
                     throw Error(std::string(bad_sa) + path);
-                sa_pack_chunk(ix.stream, chunk.as<uint64_t>(), cnt, sa.as<uint32_t>(), sa_hi.as<uint8_t>(), first);
-                CDB_HIP(hipStreamSynchronize(ix.stream));  // (buf and chunk are reused)
             }
-        } else {
-            fill(sa.p, hd.size * hd.width);
-            if (count_invalid_entries(ix.stream, sa.p, (int)hd.width, hd.size, d_start.as<uint64_t>(), hd.ndocs, (int)L.bits, L.mask) != 0)
-                throw Error(std::string(bad_sa) + path);
-        }
-        CDB_HIP(hipStreamSynchronize(ix.stream));
-        // ---- commit
-        reset_unbuilt(ix);
-        commit_layout(ix, L);
-        ix.ids.swap(ids);
-        ix.doc_start.swap(doc_start);
-        ix.host_tables_valid = true;
-        ix.host_text.clear();
-        ix.host_text.shrink_to_fit();
-        ix.host_text_valid = false;  // the text lives on the device (cdb_add* fetch it back)
-        ix.reference_compat = hd.compat != 0;
-        ix.sa_sorted = hd.sorted != 0;  // a reference-compat ordering keeps the reference's exact probe sequence
-        ix.d_text_owned = std::move(text);
-        ix.d_text = ix.d_text_owned.as<uint8_t>();
-        ix.text_padded = true;
-        ix.d_sa = std::move(sa);
-        if (pack) {
-            ix.d_sa_hi = std::move(sa_hi);
-            ix.sa_packed = true;
-        }
-        ix.d_doc_start = std::move(d_start);
-        ix.d_ids = std::move(d_ids);
-        // a file's entries were checked one by one (each names a real suffix), their ORDER was not: the proof behind a build runs
-        // behind a load as well (damage -> the array is rebuilt from the loaded text)
-        if (ix.self_check >= 3 || ix.premap_generation) {
-            ix.proof.of_loaded_file = true;
-            proof_start(ix);
-        }
+            CDB_HIP(hipStreamSynchronize(ix.stream));
+            col.L = L;
+            col.host = NewColumn::HOST_NEW;
+            col.reference_compat = hd.compat != 0;
+            col.sa_sorted = hd.sorted != 0;
+        });
     });
 }
 
@@ -820,10 +863,11 @@ int cdb_reserve(int device, uint64_t text_bytes, uint64_t ndocs, const char* sam
                 hipLaunchKernelGGL(reserve_fill_kernel, dim3(4096), dim3(256), 0, ix.stream, text.as<uint8_t>(), text_bytes,
                                    (const uint8_t*)d_table.as<uint8_t>(), d_start.as<uint64_t>(), d_ids.as<int64_t>(), ndocs);
                 CDB_HIP(hipStreamSynchronize(ix.stream));
-                {   // the pinned staging chunks of the first upload (upload_views / upload_pageable: two 16 MiB blocks per copy thread)
+                {   // the pinned staging blocks of the first upload (upload_chunked: as many as upload_views takes by default)
+                    static_assert(UPLOAD_THREADS_VIEWS >= UPLOAD_THREADS_PAGEABLE);
                     std::vector<void*> pins;
-                    for (int k = 0; k < 24; ++k)
-                        if (void* q = HostPool::get().alloc(16u << 20)) pins.push_back(q);
+                    for (int k = 0; k < UPLOAD_THREADS_VIEWS * UPLOAD_BLOCKS; ++k)
+                        if (void* q = HostPool::get().alloc(UPLOAD_CHUNK)) pins.push_back(q);
                     for (void* q : pins) (void)HostPool::get().release(q);
                 }
                 const int rc = cdb_build_resident(h, text.p, d_start.as<uint64_t>(), d_ids.as<int64_t>(), ndocs);
@@ -865,30 +909,13 @@ int cdb_build(cdb_index* h) {
         std::lock_guard<std::mutex> g(ix.mu);
         DeviceScope dscope(ix);
         const Layout L = layout_of(ix.doc_start, ix.ids.size());  // throws the reference's capacity errors: nothing changed yet
-        const uint64_t n = L.size;
-        bool committed = false;  // a failure before the commit point (allocation, upload) leaves the previous index serving
-        try {
-            DevBuf text, d_start, d_ids;
-            text.alloc(n + TEXT_PAD);
-            CDB_HIP(hipMemsetAsync((uint8_t*)text.p + n, 0, TEXT_PAD, ix.stream));
-            const double tu = wall_ms();
-            upload_pageable(text.p, ix.host_text.data(), n, ix.stream, ix.device, upload_stream(ix));
-            upload_tables(ix, ix.doc_start, ix.ids, L.ndocs, d_start, d_ids);
-            committed = true;
-            reset_unbuilt(ix);  // (waits for the stream: the old arrays are idle; ix.mu keeps queries out)
-            ix.host_upload_ms = wall_ms() - tu;
-            commit_layout(ix, L);
-            ix.d_text_owned = std::move(text);
-            ix.d_text = ix.d_text_owned.as<uint8_t>();
-            ix.text_padded = true;
-            ix.d_doc_start = std::move(d_start);
-            ix.d_ids = std::move(d_ids);
-            build_suffix_array(ix);
-        } catch (...) {
-            if (committed) reset_unbuilt(ix);
-            else (void)hipStreamSynchronize(ix.stream);
-            throw;
-        }
+        replace_column(ix, [&](NewColumn& col) {
+            col.L = L;
+            alloc_padded_text(ix, col.text, L.size);
+            col.upload_t0 = wall_ms();
+            upload_pageable(col.text.p, ix.host_text.data(), L.size, ix.stream, ix.device, upload_stream(ix));
+            upload_tables(ix, ix.doc_start, ix.ids, L.ndocs, col.d_start, col.d_ids);
+        });
         // the staging copy has done its job (database.cpp builds a fresh index object per build and never adds to a
         // built one); cdb_add* fetch the column back from the device if they are called again
         if (ix.host_text.size() >= (1u << 20)) {
@@ -913,41 +940,15 @@ int cdb_build_device(cdb_index* h, const void* d_text, const uint64_t* doc_start
         Index& ix = h->ix;
         std::lock_guard<std::mutex> g(ix.mu);
         DeviceScope dscope(ix);
-        // ---- validate first
         if (((uintptr_t)d_text & 15u) != 0) throw Error("device text must be 16-byte aligned");
         const uint64_t first = ndocs ? doc_start[0] : 0;
         if (first & 15u) throw Error("first document must start 16-byte aligned");
-        std::vector<int64_t> hid(ids, ids + ndocs);
-        std::vector<uint64_t> hstart(ndocs + 1);
-        hstart[0] = 0;
-        for (uint64_t d = 0; d < ndocs; ++d) {
-            if (doc_start[d + 1] < doc_start[d]) throw Error("doc_start must be non-decreasing");
-            hstart[d + 1] = doc_start[d + 1] - first;
-        }
-        const Layout L = layout_of(hstart, ndocs);
-        bool committed = false;
-        try {
-            DevBuf d_start, d_ids;
-            upload_tables(ix, hstart, hid, ndocs, d_start, d_ids);
-            committed = true;
-            reset_unbuilt(ix);
-            commit_layout(ix, L);
-            ix.ids.swap(hid);
-            ix.doc_start.swap(hstart);
-            ix.host_tables_valid = true;
-            std::string().swap(ix.host_text);
-            ix.host_text_valid = false;
-            ix.d_text_owned.release();
-            ix.d_text = static_cast<const uint8_t*>(d_text) + first;
-            ix.text_padded = false;
-            ix.d_doc_start = std::move(d_start);
-            ix.d_ids = std::move(d_ids);
-            build_suffix_array(ix);
-        } catch (...) {
-            if (committed) reset_unbuilt(ix);
-            else (void)hipStreamSynchronize(ix.stream);
-            throw;
-        }
+        replace_column(ix, [&](NewColumn& col) {
+            rebase_tables(doc_start, ids, ndocs, first, col);
+            col.L = layout_of(col.doc_start, ndocs);
+            col.borrowed = static_cast<const uint8_t*>(d_text) + first;
+            upload_tables(ix, col.doc_start, col.ids, ndocs, col.d_start, col.d_ids);
+        });
     });
 }
 
@@ -981,60 +982,31 @@ int cdb_build_view(cdb_index* h, const int64_t* ids, const char* blob, const uin
                 (void)hipGetLastError();
             }
         }
-        DevBuf text;
-        text.alloc(n_claimed + TEXT_PAD);
-        CDB_HIP(hipMemsetAsync((uint8_t*)text.p + n_claimed, 0, TEXT_PAD, ix.stream));
-        const double tu = wall_ms();
-        std::string uerr;
-        hipStream_t s2 = upload_stream(ix);
-        std::thread up([&] {
-            try {
-                CDB_HIP(hipSetDevice(ix.device));
-                if (n_claimed) upload_pageable(text.p, blob + first, n_claimed, ix.stream, ix.device, s2);
-            } catch (const std::exception& e) {
-                uerr = e.what();
-            }
-        });
-        struct Joiner {
-            std::thread& t;
-            ~Joiner() { if (t.joinable()) t.join(); }
-        } joiner{up};
-        std::vector<int64_t> hid(ids, ids + ndocs);
-        std::vector<uint64_t> hstart(ndocs + 1);
-        hstart[0] = 0;
-        for (uint64_t d = 0; d < ndocs; ++d) {
-            if (doc_start[d + 1] < doc_start[d]) throw Error("doc_start must be non-decreasing");
-            hstart[d + 1] = doc_start[d + 1] - first;
-        }
-        const Layout L = layout_of(hstart, ndocs);  // (throws the reference's capacity errors: nothing changed yet)
-        bool committed = false;
-        try {
-            DevBuf d_start, d_ids;
+        replace_column(ix, [&](NewColumn& col) {
+            alloc_padded_text(ix, col.text, n_claimed);
+            col.upload_t0 = wall_ms();
+            std::string uerr;
+            hipStream_t s2 = upload_stream(ix);
+            std::thread up([&] {
+                try {
+                    CDB_HIP(hipSetDevice(ix.device));
+                    if (n_claimed) upload_pageable(col.text.p, blob + first, n_claimed, ix.stream, ix.device, s2);
+                } catch (const std::exception& e) {
+                    uerr = e.what();
+                }
+            });
+            struct Joiner {
+                std::thread& t;
+                ~Joiner() { if (t.joinable()) t.join(); }
+            } joiner{up};
+            rebase_tables(doc_start, ids, ndocs, first, col);
+            col.L = layout_of(col.doc_start, ndocs);  // (throws the reference's capacity errors: nothing changed yet)
             up.join();
             if (!uerr.empty()) throw Error(uerr);
             // (tried: the 16 MB of document tables on a helper thread beside the text — the runtime's pageable staging then competes
             //  with the chunk copies: 21.4 instead of 20.1 ms)
-            upload_tables(ix, hstart, hid, ndocs, d_start, d_ids);
-            committed = true;
-            reset_unbuilt(ix);
-            ix.host_upload_ms = wall_ms() - tu;
-            commit_layout(ix, L);
-            ix.ids.swap(hid);
-            ix.doc_start.swap(hstart);
-            ix.host_tables_valid = true;
-            std::string().swap(ix.host_text);
-            ix.host_text_valid = false;  // the column lives on the device (and with the caller)
-            ix.d_text_owned = std::move(text);
-            ix.d_text = ix.d_text_owned.as<uint8_t>();
-            ix.text_padded = true;
-            ix.d_doc_start = std::move(d_start);
-            ix.d_ids = std::move(d_ids);
-            build_suffix_array(ix);
-        } catch (...) {
-            if (committed) reset_unbuilt(ix);
-            else (void)hipStreamSynchronize(ix.stream);
-            throw;
-        }
+            upload_tables(ix, col.doc_start, col.ids, ndocs, col.d_start, col.d_ids);
+        });
     });
 }
 
@@ -1047,43 +1019,22 @@ int cdb_build_views(cdb_index* h, const int64_t* ids, const char* const* ptrs, c
         Index& ix = h->ix;
         std::lock_guard<std::mutex> g(ix.mu);
         DeviceScope dscope(ix);
-        std::vector<int64_t> hid(ids, ids + ndocs);
-        std::vector<uint64_t> hstart(ndocs + 1);
-        hstart[0] = 0;
-        for (uint64_t d = 0; d < ndocs; ++d) {
-            if (lens[d] && !ptrs[d]) throw Error("cdb_build_views: null document");
-            hstart[d + 1] = hstart[d] + lens[d];
-        }
-        const Layout L = layout_of(hstart, ndocs);  // (throws the reference's capacity errors: nothing changed yet)
-        const uint64_t n = L.size;
-        bool committed = false;
-        try {
-            DevBuf text, d_start, d_ids;
-            text.alloc(n + TEXT_PAD);
-            CDB_HIP(hipMemsetAsync((uint8_t*)text.p + n, 0, TEXT_PAD, ix.stream));
-            const double tu = wall_ms();
-            if (n) upload_views(text.p, ptrs, hstart.data(), ndocs, n, ix.stream, ix.device, upload_stream(ix));
-            upload_tables(ix, hstart, hid, ndocs, d_start, d_ids);
-            committed = true;
-            reset_unbuilt(ix);
-            ix.host_upload_ms = wall_ms() - tu;
-            commit_layout(ix, L);
-            ix.ids.swap(hid);
-            ix.doc_start.swap(hstart);
-            ix.host_tables_valid = true;
-            std::string().swap(ix.host_text);
-            ix.host_text_valid = false;  // the column lives on the device (and with the caller)
-            ix.d_text_owned = std::move(text);
-            ix.d_text = ix.d_text_owned.as<uint8_t>();
-            ix.text_padded = true;
-            ix.d_doc_start = std::move(d_start);
-            ix.d_ids = std::move(d_ids);
-            build_suffix_array(ix);
-        } catch (...) {
-            if (committed) reset_unbuilt(ix);
-            else (void)hipStreamSynchronize(ix.stream);
-            throw;
-        }
+        replace_column(ix, [&](NewColumn& col) {
+            col.host = NewColumn::HOST_NEW;
+            col.ids.assign(ids, ids + ndocs);
+            col.doc_start.resize(ndocs + 1);
+            col.doc_start[0] = 0;
+            for (uint64_t d = 0; d < ndocs; ++d) {
+                if (lens[d] && !ptrs[d]) throw Error("cdb_build_views: null document");
+                col.doc_start[d + 1] = col.doc_start[d] + lens[d];
+            }
+            col.L = layout_of(col.doc_start, ndocs);  // (throws the reference's capacity errors: nothing changed yet)
+            const uint64_t n = col.L.size;
+            alloc_padded_text(ix, col.text, n);
+            col.upload_t0 = wall_ms();
+            if (n) upload_views(col.text.p, ptrs, col.doc_start.data(), ndocs, n, ix.stream, ix.device, upload_stream(ix));
+            upload_tables(ix, col.doc_start, col.ids, ndocs, col.d_start, col.d_ids);
+        });
     });
 }
 
@@ -1096,41 +1047,27 @@ int cdb_build_resident(cdb_index* h, const void* d_text, const uint64_t* d_doc_s
         std::lock_guard<std::mutex> g(ix.mu);
         DeviceScope dscope(ix);
         if (((uintptr_t)d_text & 15u) != 0) throw Error("device text must be 16-byte aligned");
-        hipStream_t s = ix.stream;
-        DevBuf d_start, d_id, d_out;
-        d_start.alloc((ndocs + 1) * sizeof(uint64_t));
-        d_id.alloc(std::max<uint64_t>(ndocs, 1) * sizeof(int64_t));
-        d_out.alloc(2 * sizeof(uint64_t));
-        CDB_HIP(hipMemsetAsync(d_out.p, 0, 2 * sizeof(uint64_t), s));
-        const int grid = (int)std::min<uint64_t>(ceil_div(ndocs + 1, 256), 1024);
-        hipLaunchKernelGGL(layout_kernel, dim3(grid), dim3(256), 0, s, d_doc_start, d_ids, ndocs, d_start.as<uint64_t>(),
-                           d_id.as<int64_t>(), d_out.as<unsigned long long>());
-        uint64_t out[2] = {0, 0}, first = 0, total = 0;
-        CDB_HIP(hipMemcpyAsync(out, d_out.p, sizeof(out), hipMemcpyDeviceToHost, s));
-        CDB_HIP(hipMemcpyAsync(&first, d_doc_start, 8, hipMemcpyDeviceToHost, s));
-        CDB_HIP(hipMemcpyAsync(&total, d_start.as<uint64_t>() + ndocs, 8, hipMemcpyDeviceToHost, s));
-        CDB_HIP(hipStreamSynchronize(s));
-        if (out[1]) throw Error("doc_start must be non-decreasing");
-        if (first != 0) throw Error("d_doc_start[0] must be 0");
-        const Layout L = layout_from(ndocs, total, out[0]);  // bits / mask / size / entry width exactly as index.cpp:182-208
-        try {  // (nothing can fail between here and the commit: the tables are already on the device)
-            reset_unbuilt(ix);
-            commit_layout(ix, L);
-            ix.ids.clear();
-            ix.doc_start.assign(1, 0);
-            std::string().swap(ix.host_text);
-            ix.host_tables_valid = false;  // tables and text live on the device (fetched back on demand)
-            ix.host_text_valid = false;
-            ix.d_text_owned.release();
-            ix.d_text = static_cast<const uint8_t*>(d_text);
-            ix.text_padded = false;
-            ix.d_doc_start = std::move(d_start);
-            ix.d_ids = std::move(d_id);
-            build_suffix_array(ix);
-        } catch (...) {
-            reset_unbuilt(ix);
-            throw;
-        }
+        replace_column(ix, [&](NewColumn& col) {
+            hipStream_t s = ix.stream;
+            DevBuf d_out;
+            col.d_start.alloc((ndocs + 1) * sizeof(uint64_t));
+            col.d_ids.alloc(std::max<uint64_t>(ndocs, 1) * sizeof(int64_t));
+            d_out.alloc(2 * sizeof(uint64_t));
+            CDB_HIP(hipMemsetAsync(d_out.p, 0, 2 * sizeof(uint64_t), s));
+            const int grid = (int)std::min<uint64_t>(ceil_div(ndocs + 1, 256), 1024);
+            hipLaunchKernelGGL(layout_kernel, dim3(grid), dim3(256), 0, s, d_doc_start, d_ids, ndocs, col.d_start.as<uint64_t>(),
+                               col.d_ids.as<int64_t>(), d_out.as<unsigned long long>());
+            uint64_t out[2] = {0, 0}, first = 0, total = 0;
+            CDB_HIP(hipMemcpyAsync(out, d_out.p, sizeof(out), hipMemcpyDeviceToHost, s));
+            CDB_HIP(hipMemcpyAsync(&first, d_doc_start, 8, hipMemcpyDeviceToHost, s));
+            CDB_HIP(hipMemcpyAsync(&total, col.d_start.as<uint64_t>() + ndocs, 8, hipMemcpyDeviceToHost, s));
+            CDB_HIP(hipStreamSynchronize(s));
+            if (out[1]) throw Error("doc_start must be non-decreasing");
+            if (first != 0) throw Error("d_doc_start[0] must be 0");
+            col.L = layout_from(ndocs, total, out[0]);  // bits / mask / size / entry width exactly as index.cpp:182-208
+            col.host = NewColumn::HOST_NONE;            // tables and text live on the device (fetched back on demand)
+            col.borrowed = static_cast<const uint8_t*>(d_text);
+        });
     });
 }
 

@@ -842,6 +842,78 @@ def test_failed_build_leaves_index_unbuilt(G):
     assert g.query(bytes(blob[:2]))
 
 
+@pytest.mark.parametrize("entry", ["build", "build_view", "build_views", "build_device", "build_resident", "load"])
+def test_every_entry_point_keeps_the_commit_protocol(G, entry, tmp_path):
+    # every way to give a handle a new column follows one protocol: a failure BEFORE the commit point (validation, upload)
+    # leaves the old index serving; a failure after it (test hook: the build throws after its sorts) leaves a queryable
+    # "never built" handle, and the same call then builds
+    import ctypes as C
+    import torch
+    from coffeedb_amd import capi
+    n = 300
+    blob, ds = W.ascii_corpus(n, 64, seed=3, lo=0x00, hi=0xFF)
+    old_ids, new_ids = np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64) + 1000
+    kw = bytes(blob[:2])
+    g = _gpu(G, blob, ds, old_ids)
+    old_rows, width = g.query(kw), g.sa_width
+    assert old_rows and width
+    new_rows = old_rows if entry == "build" else [(i + 1000, c) for i, c in old_rows]
+    bad_ds = ds.copy()
+    bad_ds[5] = bad_ds[6] + 1                                        # runs backwards
+    docs = [bytes(blob[int(ds[d]):int(ds[d + 1])]) for d in range(n)]
+    d_text = torch.from_numpy(np.concatenate([blob, np.zeros(16, dtype=np.uint8)])).cuda()
+    d_ds, d_bad, d_ids = (torch.from_numpy(a).cuda() for a in (ds.astype(np.int64), bad_ds.astype(np.int64), new_ids))
+    torch.cuda.synchronize()
+
+    def views(with_null):
+        ptrs = (C.c_char_p * n)(*docs)
+        if with_null:
+            ptrs[5] = None                                           # (the binding takes bytes objects: the raw call can say it)
+        lens = np.array([len(d) for d in docs], dtype=np.uint64)
+        assert lens[5] > 0
+        g._check(g._lib.cdb_build_views(g._h, capi._ptr(new_ids), C.cast(ptrs, C.c_void_p), capi._ptr(lens), n))
+
+    def call(bad):
+        if entry == "build":
+            assert not bad
+            g.build()
+        elif entry == "build_view":
+            g.build_view(new_ids, blob, bad_ds if bad else ds)
+        elif entry == "build_views":
+            views(bad)
+        elif entry == "build_device":
+            g.build_device(d_text.data_ptr(), bad_ds if bad else ds, new_ids)
+        elif entry == "build_resident":
+            g.build_resident(d_text.data_ptr(), (d_bad if bad else d_ds).data_ptr(), d_ids.data_ptr(), n)
+        else:
+            path = tmp_path / "col.idx"
+            other = G()
+            other.build_view(new_ids, blob, ds)
+            other.save(path)
+            if bad:
+                path.write_bytes(path.read_bytes()[:-7])
+            g.load(path)
+
+    # (a) before the commit
+    if entry != "build":                                             # (cdb_build validates nothing a caller can get wrong)
+        match = {"build_views": "null document", "load": "Truncated"}.get(entry, "non-decreasing")
+        with pytest.raises(RuntimeError, match=match):
+            call(True)
+        assert g.query(kw) == old_rows and g.sa_width == width
+    # (b) after the commit
+    if entry == "load":                                              # (a load builds nothing: it installs the file's array)
+        call(False)
+        assert g.query(kw) == new_rows and g.sa_width == width
+        return
+    g.set_option("debug_fail_build", 1)
+    with pytest.raises(RuntimeError, match="build failure requested"):
+        call(False)
+    assert g.sa_width == 0 and g.query(kw) == []
+    g.set_option("debug_fail_build", 0)
+    call(False)
+    assert g.query(kw) == new_rows and g.sa_width == width
+
+
 def test_bucket_wise_path_with_all_256_byte_values(G):
     # corpora of 4 GiB and more (here: the same code path forced at small size) with every byte value present: the
     # first-symbol partition runs on code - 1 (8 bits), the keys behind it carry 9-bit codes (reference: 257 buckets,
