@@ -31,6 +31,7 @@ EXPORTS = [
     "cdb_column_create", "cdb_column_destroy", "cdb_column_last_error", "cdb_column_add_bulk", "cdb_column_build", "cdb_column_query",
     "cdb_column_query_any", "cdb_query_and_columns", "cdb_column_get_stat", "cdb_debug_column_set_option", "cdb_debug_column_profile_dump",
     "cdb_column_cluster", "cdb_cluster", "cdb_clusters_free",
+    "cdb_render_rows", "cdb_shards_render_rows", "cdb_rendered_free",
 ]
 
 
@@ -70,6 +71,15 @@ class CdbColumnKey(C.Structure):
 class CdbClusters(C.Structure):
     _fields_ = [("ngroups", C.c_uint64), ("missing", C.c_uint64), ("counts", C.POINTER(C.c_int64)), ("rep_ids", C.POINTER(C.c_int64)),
                 ("values", C.POINTER(C.c_uint64)), ("value_ptr", C.POINTER(C.c_uint64)), ("value_blob", C.POINTER(C.c_char))]
+
+
+class CdbRendered(C.Structure):
+    _fields_ = [("nrows", C.c_uint64), ("missing", C.c_uint64), ("nspans", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("found", C.POINTER(C.c_uint8)), ("text_ptr", C.POINTER(C.c_uint64)), ("text_blob", C.POINTER(C.c_char)),
+                ("span_ptr", C.POINTER(C.c_uint64)), ("begin", C.POINTER(C.c_uint64)), ("end", C.POINTER(C.c_uint64))]
+
+
+RENDER_TEXT, RENDER_SPANS = 1, 2
 
 
 class CdbDeviceHits(C.Structure):
@@ -227,6 +237,11 @@ def load_library():
     lib.cdb_cluster.argtypes = [vp, vp, u64, C.c_int, C.POINTER(CdbClusters)]
     lib.cdb_clusters_free.argtypes = [C.POINTER(CdbClusters)]
     lib.cdb_clusters_free.restype = None
+    render_args = [vp, vp, u64, vp, vp, u64, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.POINTER(CdbRendered)]
+    lib.cdb_render_rows.argtypes = render_args
+    lib.cdb_shards_render_rows.argtypes = render_args
+    lib.cdb_rendered_free.argtypes = [C.POINTER(CdbRendered)]
+    lib.cdb_rendered_free.restype = None
     _LIB = lib
     return lib
 
@@ -241,6 +256,38 @@ def _array(ptr, n, dtype):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _render_rows(self, fn, ids, keywords, left, right, text, spans, raw):
+    """cdb_render_rows / cdb_shards_render_rows behind GpuStringIndex.render_rows and GpuShards.render_rows"""
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    blob = np.frombuffer(b"".join(keywords), dtype=np.uint8)
+    offs = np.zeros(len(keywords) + 1, dtype=np.uint64)
+    np.cumsum([len(k) for k in keywords], out=offs[1:])
+    left, right = bytes(left), bytes(right)
+    r = CdbRendered()
+    self._check(fn(self._h, _ptr(ids) if len(ids) else None, len(ids), _ptr(blob) if len(blob) else None, _ptr(offs), len(keywords),
+                   left if left else None, len(left), right if right else None, len(right),
+                   (RENDER_TEXT if text else 0) | (RENDER_SPANS if spans else 0), C.byref(r)))
+    try:
+        n = int(r.nrows)
+        found = _array(r.found, n, np.uint8).astype(bool)
+        tp = tb = sp = sb = se = None
+        if r.text_ptr:
+            tp = _array(r.text_ptr, n + 1, np.uint64)
+            tb = C.string_at(r.text_blob, int(r.text_bytes))
+        if r.span_ptr:
+            sp = _array(r.span_ptr, n + 1, np.uint64)
+            sb = _array(r.begin, int(r.nspans), np.uint64)
+            se = _array(r.end, int(r.nspans), np.uint64)
+        if raw:
+            return {"found": found, "missing": int(r.missing), "nspans": int(r.nspans), "text_bytes": int(r.text_bytes), "text_ptr": tp,
+                    "text_blob": tb, "span_ptr": sp, "begin": sb, "end": se}
+        texts = None if tp is None else [tb[int(tp[i]):int(tp[i + 1])] for i in range(n)]
+        spans_ = None if sp is None else [[(int(sb[k]), int(se[k])) for k in range(int(sp[i]), int(sp[i + 1]))] for i in range(n)]
+        return found, texts, spans_, int(r.missing)
+    finally:
+        self._lib.cdb_rendered_free(C.byref(r))
 
 
 class GpuStringIndex:
@@ -518,6 +565,13 @@ class GpuStringIndex:
         finally:
             self._lib.cdb_clusters_free(C.byref(r))
 
+    def render_rows(self, ids, keywords, left=b"", right=b"", text=True, spans=True, raw=False):
+        """cdb_render_rows (the tail of select(), database.cpp:394-441): the rows `ids` in the caller's order, each rendered as
+        ac_automaton::render does for this key's keyword list.  Returns (found bool[nrows]; texts: list of bytes, None without
+        `text`; spans: per row a list of (begin, end_inclusive) inside the original document, None without `spans`; missing).
+        raw=True returns the C arrays (text_ptr, text_blob, span_ptr, begin, end, ...) in a dict instead."""
+        return _render_rows(self, self._lib.cdb_render_rows, ids, keywords, left, right, text, spans, raw)
+
     def set_option(self, name, value):
         self._check(self._lib.cdb_set_option(self._h, name.encode(), int(value)))
 
@@ -646,6 +700,10 @@ class GpuShards:
             return [(r.ids[d], [(r.begin[k], r.end[k]) for k in range(r.span_ptr[d], r.span_ptr[d + 1])]) for d in range(r.ndocs)]
         finally:
             self._lib.cdb_spans_free(C.byref(r))
+
+    def render_rows(self, ids, keywords, left=b"", right=b"", text=True, spans=True, raw=False):
+        """GpuStringIndex.render_rows over all shards"""
+        return _render_rows(self, self._lib.cdb_shards_render_rows, ids, keywords, left, right, text, spans, raw)
 
     def query_batch(self, blob, offsets):
         blob = np.ascontiguousarray(blob, dtype=np.uint8)

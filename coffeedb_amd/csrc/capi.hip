@@ -1673,8 +1673,9 @@ int cdb_get_stat(const cdb_index* h, const char* name, double* value) {
         {"compat_depth", (double)b.compat_depth},
         {"host_upload_ms", h->ix.host_upload_ms}, {"host_free_ms", h->ix.host_free_ms},
         {"resident_answers", (double)h->ix.res_answers}, {"launched_answers", (double)h->ix.launched_answers}, {"resident_mode", (double)h->ix.resident_mode},
-        {"cluster_table_bytes", h->ix.clu.valid ? (double)h->ix.clu.bytes() : 0.0}, {"cluster_classes", (double)h->ix.clu.nclasses},
+        {"cluster_table_bytes", h->ix.clu.valid ? (double)(h->ix.clu.bytes() + h->ix.idt.bytes()) : 0.0}, {"cluster_classes", (double)h->ix.clu.nclasses},
         {"cluster_prepare_ms", h->ix.clu.prepare_ms}, {"cluster_ms", h->ix.clu.last_ms}, {"cluster_resorted", h->ix.clu.resorted ? 1.0 : 0.0},
+        {"render_ms", h->ix.rnd.last_ms}, {"render_page_bytes", (double)h->ix.rnd.page_bytes}, {"render_spans", (double)h->ix.rnd.spans},
         {"query_ms", q.query_ms}, {"query_upload_ms", q.upload_ms}, {"query_device_ms", q.device_ms}, {"query_download_ms", q.download_ms}, {"query_hits", (double)q.nhits}, {"query_rows", (double)q.nrows},
     };
     for (auto& e : tab)

@@ -54,16 +54,6 @@ __device__ __forceinline__ uint64_t wave_min(uint64_t v) {
     }
     return v;
 }
-// first slot of the ascending ids[0 .. n) that is not below id (n: none)
-__device__ __forceinline__ uint64_t lower_bound_id(const int64_t* __restrict__ ids, uint64_t n, int64_t id) {
-    uint64_t a = 0, b = n;
-    while (a < b) {
-        const uint64_t m = (a + b) >> 1;
-        if (ids[m] < id) a = m + 1;
-        else b = m;
-    }
-    return a;
-}
 
 // ---- columns -------------------------------------------------------------------------------------------------------------------
 // row i -> its position in (value, id) order: key[i] = p (sparse; n for an id the column does not hold, which sorts behind every
@@ -546,6 +536,49 @@ void column_cluster(cdb_column* c, const int64_t* ids, uint64_t nrows, Result& r
     c->cluster_ms = wall_ms() - t0;
 }
 
+}  // namespace
+
+// id -> document: the ids are insertion timestamps and usually ascend; otherwise a sorted copy
+void cdb::id_table_prepare(Index& ix) {
+    Index::IdTable& it = ix.idt;
+    if (it.valid) return;
+    hipStream_t s = ix.stream;
+    const uint64_t ndocs = ix.ndocs;
+    it.drop();
+    DevBuf flag, id_sorted, id_doc;
+    flag.alloc(16);
+    CDB_HIP(hipMemsetAsync(flag.p, 0, 16, s));
+    hipLaunchKernelGGL(clu_id_order_kernel, dim3(grid_for(ndocs)), dim3(256), 0, s, (const int64_t*)ix.d_ids.as<int64_t>(), ndocs, flag.as<unsigned int>());
+    CDB_HIP(hipGetLastError());
+    unsigned int unordered = 0;
+    CDB_HIP(hipMemcpyAsync(&unordered, flag.p, 4, hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipStreamSynchronize(s));
+    if (unordered) {
+        DevBuf k0, k1, v0, v1;
+        k0.alloc(ndocs * 8);
+        k1.alloc(ndocs * 8);
+        v0.alloc(ndocs * 4);
+        v1.alloc(ndocs * 4);
+        hipLaunchKernelGGL(clu_id_keys_kernel, dim3(grid_for(ndocs)), dim3(256), 0, s, (const int64_t*)ix.d_ids.as<int64_t>(), ndocs, k0.as<uint64_t>(),
+                           v0.as<uint32_t>());
+        const int sel = radix_sort<uint64_t, uint32_t>(s, ix.rws, ix.prof, k0.as<uint64_t>(), k1.as<uint64_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(),
+                                                       ndocs, 0, 64, nullptr);
+        id_sorted.alloc(ndocs * 8);
+        hipLaunchKernelGGL(clu_unflip_kernel, dim3(grid_for(ndocs)), dim3(256), 0, s, (const uint64_t*)(sel ? k1 : k0).as<uint64_t>(), ndocs,
+                           id_sorted.as<int64_t>());
+        CDB_HIP(hipGetLastError());
+        radix_check_error(s, ix.rws);
+        CDB_HIP(hipStreamSynchronize(s));
+        id_doc = std::move(sel ? v1 : v0);
+    }
+    it.id_sorted = std::move(id_sorted);
+    it.id_doc = std::move(id_doc);
+    it.ids_ascend = !unordered;
+    it.valid = true;
+}
+
+namespace {
+
 // ---- string indexes: host side -----------------------------------------------------------------------------------------------------
 void cluster_prepare(Index& ix) {
     Index::ClusterTables& ct = ix.clu;
@@ -640,40 +673,12 @@ void cluster_prepare(Index& ix) {
         CDB_HIP(hipStreamSynchronize(s));  // (the host vectors are read by the copies)
         resorted = true;
     }
-    // 4. id -> document: the ids are insertion timestamps and usually ascend; otherwise a sorted copy
-    DevBuf flag, id_sorted, id_doc;
-    flag.alloc(16);
-    CDB_HIP(hipMemsetAsync(flag.p, 0, 16, s));
-    hipLaunchKernelGGL(clu_id_order_kernel, dim3(grid_for(ndocs)), dim3(256), 0, s, (const int64_t*)ix.d_ids.as<int64_t>(), ndocs, flag.as<unsigned int>());
-    CDB_HIP(hipGetLastError());
-    unsigned int unordered = 0;
-    CDB_HIP(hipMemcpyAsync(&unordered, flag.p, 4, hipMemcpyDeviceToHost, s));
-    CDB_HIP(hipStreamSynchronize(s));
-    if (unordered) {
-        DevBuf k0, k1, v0, v1;
-        k0.alloc(ndocs * 8);
-        k1.alloc(ndocs * 8);
-        v0.alloc(ndocs * 4);
-        v1.alloc(ndocs * 4);
-        hipLaunchKernelGGL(clu_id_keys_kernel, dim3(grid_for(ndocs)), dim3(256), 0, s, (const int64_t*)ix.d_ids.as<int64_t>(), ndocs, k0.as<uint64_t>(),
-                           v0.as<uint32_t>());
-        const int sel = radix_sort<uint64_t, uint32_t>(s, ix.rws, ix.prof, k0.as<uint64_t>(), k1.as<uint64_t>(), v0.as<uint32_t>(), v1.as<uint32_t>(),
-                                                       ndocs, 0, 64, nullptr);
-        id_sorted.alloc(ndocs * 8);
-        hipLaunchKernelGGL(clu_unflip_kernel, dim3(grid_for(ndocs)), dim3(256), 0, s, (const uint64_t*)(sel ? k1 : k0).as<uint64_t>(), ndocs,
-                           id_sorted.as<int64_t>());
-        CDB_HIP(hipGetLastError());
-        radix_check_error(s, ix.rws);
-        CDB_HIP(hipStreamSynchronize(s));
-        id_doc = std::move(sel ? v1 : v0);
-    }
+    // 4. id -> document: its own once-per-array piece (cdb_render_rows needs it without the classes)
+    id_table_prepare(ix);
     ix.prof.resolve();
     ct.class_of_doc = std::move(class_of_doc);
     ct.class_rep = std::move(class_rep);
-    ct.id_sorted = std::move(id_sorted);
-    ct.id_doc = std::move(id_doc);
     ct.nclasses = nclasses;
-    ct.ids_ascend = !unordered;
     ct.resorted = resorted;
     ct.prepare_ms = wall_ms() - t0;
     ct.valid = true;
@@ -705,8 +710,8 @@ void index_cluster(Index& ix, const int64_t* ids, uint64_t nrows, bool with_valu
     const uint64_t ndocs = ix.ndocs, nclasses = ct.nclasses;
     const int rbits = std::max(1, bit_width64(ndocs - 1)), cbits = bit_width64(nclasses);
     if (rbits + cbits > 64) throw Error("cdb_cluster: too many distinct documents for one sort key");
-    const int64_t* id_tab = ct.ids_ascend ? ix.d_ids.as<int64_t>() : ct.id_sorted.as<int64_t>();
-    const uint32_t* id_doc = ct.ids_ascend ? nullptr : ct.id_doc.as<uint32_t>();
+    const int64_t* id_tab = ix.idt.ids_ascend ? ix.d_ids.as<int64_t>() : ix.idt.id_sorted.as<int64_t>();
+    const uint32_t* id_doc = ix.idt.ids_ascend ? nullptr : ix.idt.id_doc.as<uint32_t>();
     DevBuf d_ids, d_out, k0, k1, start, d_counts, d_rep, d_repdoc;
     upload_ids(s, d_ids, ids, nrows);
     d_out.alloc(16);

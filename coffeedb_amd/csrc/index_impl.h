@@ -180,6 +180,7 @@ struct Index {
         d_sa_hi.release();
         sa_packed = false;
         clu.drop();  // (the class table of cdb_cluster describes the array that just went)
+        idt.drop();  // (... and the id table goes with it: every build and load passes here, so it never outlives d_ids)
     }
     template <typename T> typename SaOf<T>::ptr sa_view() const;  // (below)
     bool sa_sorted = false;           // SA is globally sorted in unsigned byte order (false only for
@@ -304,26 +305,42 @@ struct Index {
 
     // ---- cluster tables (cluster.hip): built under ix.mu at the first cdb_cluster on a built array, dropped where the array goes
     // (release_sa above: reset_unbuilt, every build, and the order proof's repair of a damaged array — a table made from an array the
-    // proof later judges wrong must not outlive it).  4 * ndocs + 4 * nclasses bytes, plus 12 * ndocs when the ids do not ascend.
+    // proof later judges wrong must not outlive it).  4 * ndocs + 4 * nclasses bytes, plus the id table below.
     struct ClusterTables {
         bool valid = false;
         uint64_t nclasses = 0;     // distinct documents (the empty document included when there is one)
-        bool ids_ascend = true;    // d_ids is its own id -> document table
         bool resorted = false;     // classes were put into std::string order on the host (array in the reference's order)
         DevBuf class_of_doc;       // u32[ndocs]
         DevBuf class_rep;          // u32[nclasses]: one document of every class
-        DevBuf id_sorted, id_doc;  // !ids_ascend: the ids ascending (i64) and the document of each (u32)
         double prepare_ms = 0, last_ms = 0;
-        uint64_t bytes() const { return class_of_doc.bytes + class_rep.bytes + id_sorted.bytes + id_doc.bytes; }
+        uint64_t bytes() const { return class_of_doc.bytes + class_rep.bytes; }
         void drop() {
             valid = false;
             nclasses = 0;
             class_of_doc.release();
             class_rep.release();
+        }
+    } clu;
+    // ---- id -> document (cluster.hip: id_table_prepare; read by cdb_cluster and cdb_render_rows): the ids are insertion timestamps
+    // and usually ascend, then d_ids is the table; otherwise a sorted (id, document) copy, 12 * ndocs bytes.  Made under ix.mu by the
+    // first call that needs it, without the class table (a render never pays for that), dropped with it in release_sa.
+    struct IdTable {
+        bool valid = false;
+        bool ids_ascend = true;    // d_ids is its own id -> document table
+        DevBuf id_sorted, id_doc;  // !ids_ascend: the ids ascending (i64) and the document of each (u32)
+        uint64_t bytes() const { return id_sorted.bytes + id_doc.bytes; }
+        void drop() {
+            valid = false;
+            ids_ascend = true;
             id_sorted.release();
             id_doc.release();
         }
-    } clu;
+    } idt;
+    // ---- cdb_render_rows (render.hip): the last call's wall time, page positions (bytes of the found rows' documents) and spans
+    struct RenderStats {
+        double last_ms = 0;
+        uint64_t page_bytes = 0, spans = 0;
+    } rnd;
 
     double host_upload_ms = 0, host_free_ms = 0;  // cdb_build: staged column to the device / staging copy released
     Profiler prof;
@@ -343,6 +360,19 @@ void read_raw_dir(const char* dir, const char* key, std::vector<int64_t>& ids, s
 
 // sa_build.hip
 void build_suffix_array(Index& ix);
+
+// cluster.hip — fills ix.idt on ix.stream (ix.mu held, device set); a no-op while the table is valid
+void id_table_prepare(Index& ix);
+// first slot of the ascending ids[0 .. n) that is not below id (n: none)
+__device__ __forceinline__ uint64_t lower_bound_id(const int64_t* __restrict__ ids, uint64_t n, int64_t id) {
+    uint64_t a = 0, b = n;
+    while (a < b) {
+        const uint64_t m = (a + b) >> 1;
+        if (ids[m] < id) a = m + 1;
+        else b = m;
+    }
+    return a;
+}
 
 // verify.hip — out = {inversions, tie-order violations, wrapped sum of entries, invalid entries, expected sum}
 void verify_suffix_array(Index& ix, uint64_t out[5]);

@@ -1242,6 +1242,76 @@ int cdb_shards_query_spans(cdb_shards* h, const char* blob, const uint64_t* offs
     return rc;
 }
 
+// every shard renders the rows it holds (ids are disjoint across shards); the answers go back into the caller's row order
+int cdb_shards_render_rows(cdb_shards* h, const int64_t* ids, uint64_t nrows, const char* blob, const uint64_t* offsets, uint64_t nkw, const char* left,
+                           size_t left_len, const char* right, size_t right_len, int what, cdb_rendered* out) {
+    if (!h || !out || (nrows && !ids) || (nkw && !offsets) || (left_len && !left) || (right_len && !right)) return CDB_E_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    const int rc = guarded_on(h, [&] {
+        std::shared_lock<StateLock> st(h->state);
+        std::vector<cdb_rendered> parts(std::max(h->used, 1));
+        for (auto& x : parts) std::memset(&x, 0, sizeof(cdb_rendered));
+        struct Cleanup {
+            std::vector<cdb_rendered>& p;
+            ~Cleanup() { for (auto& x : p) cdb_rendered_free(&x); }
+        } cleanup{parts};
+        parallel_shards((int)parts.size(), [&](int i) {
+            check_shard(h, i, cdb_render_rows(h->shard[i], ids, nrows, blob, offsets, nkw, left, left_len, right, right_len, what, &parts[i]));
+        });
+        const bool want_text = (what & CDB_RENDER_TEXT) != 0, want_spans = (what & CDB_RENDER_SPANS) != 0;
+        std::vector<int> owner(nrows, -1);  // the shard that holds row i
+        uint64_t ns = 0, tb = 0;
+        for (const cdb_rendered& p : parts) {
+            ns += p.nspans;
+            tb += p.text_bytes;
+        }
+        out->nrows = nrows;
+        out->nspans = ns;
+        out->text_bytes = tb;
+        out->found = (uint8_t*)host_alloc(nrows, true);
+        for (uint64_t i = 0; i < nrows; ++i) {
+            for (size_t g = 0; g < parts.size() && owner[i] < 0; ++g)
+                if (parts[g].found[i]) owner[i] = (int)g;
+            out->found[i] = owner[i] >= 0 ? 1 : 0;
+            out->missing += owner[i] < 0 ? 1 : 0;
+        }
+        if (want_text) {
+            out->text_ptr = (uint64_t*)host_alloc((nrows + 1) * 8, true);
+            out->text_blob = (char*)host_alloc(tb);
+            uint64_t o = 0;
+            for (uint64_t i = 0; i < nrows; ++i) {
+                out->text_ptr[i] = o;
+                if (owner[i] < 0) continue;
+                const cdb_rendered& p = parts[owner[i]];
+                const uint64_t len = p.text_ptr[i + 1] - p.text_ptr[i];
+                if (len) std::memcpy(out->text_blob + o, p.text_blob + p.text_ptr[i], len);
+                o += len;
+            }
+            out->text_ptr[nrows] = o;
+        }
+        if (want_spans) {
+            out->span_ptr = (uint64_t*)host_alloc((nrows + 1) * 8, true);
+            out->begin = (uint64_t*)host_alloc(ns * 8);
+            out->end = (uint64_t*)host_alloc(ns * 8);
+            uint64_t o = 0;
+            for (uint64_t i = 0; i < nrows; ++i) {
+                out->span_ptr[i] = o;
+                if (owner[i] < 0) continue;
+                const cdb_rendered& p = parts[owner[i]];
+                const uint64_t a = p.span_ptr[i], len = p.span_ptr[i + 1] - a;
+                if (len) {
+                    std::memcpy(out->begin + o, p.begin + a, len * 8);
+                    std::memcpy(out->end + o, p.end + a, len * 8);
+                }
+                o += len;
+            }
+            out->span_ptr[nrows] = o;
+        }
+    });
+    if (rc != CDB_OK) cdb_rendered_free(out);
+    return rc;
+}
+
 namespace {
 // Host merge of the shards' CSR answers (the consumer of the C ABI is the host: SURVEY §8e — every GPU hands over its own
 // slice, nothing is replicated on the devices).  Every shard answers the whole batch through its own host entry point

@@ -343,3 +343,25 @@ std::vector<std::pair<int64_t, std::vector<std::pair<uint64_t, uint64_t>>>> stri
     cdb_spans_free(&sp);
     return out;
 }
+
+std::vector<std::optional<std::string>> string_index::render_rows(const result_type& rows, const std::vector<std::string>& keywords,
+                                                                  const std::string& left, const std::string& right) const {
+    const auto [blob, offs] = pack(keywords);
+    std::vector<int64_t> page(rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) page[i] = rows[i].first;
+    cdb_rendered r;
+    if (shards) {
+        const int rc = cdb_shards_render_rows(shards, page.data(), page.size(), blob.data(), offs.data(), keywords.size(), left.data(), left.size(),
+                                              right.data(), right.size(), CDB_RENDER_TEXT, &r);
+        if (rc != CDB_OK) rethrow(shards, rc);
+    } else {
+        const int rc = cdb_render_rows(handle, page.data(), page.size(), blob.data(), offs.data(), keywords.size(), left.data(), left.size(),
+                                       right.data(), right.size(), CDB_RENDER_TEXT, &r);
+        if (rc != CDB_OK) rethrow(handle, rc);
+    }
+    std::vector<std::optional<std::string>> out(rows.size());
+    for (size_t i = 0; i < rows.size(); ++i)
+        if (r.found[i]) out[i].emplace(r.text_blob + r.text_ptr[i], (size_t)(r.text_ptr[i + 1] - r.text_ptr[i]));
+    cdb_rendered_free(&r);
+    return out;
+}

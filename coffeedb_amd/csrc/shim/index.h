@@ -13,6 +13,7 @@
 #include <array>
 #include <cstdint>
 #include <stdexcept>
+#include <optional>
 #include <string>
 #include <string_view>
 #include <utility>
@@ -127,6 +128,13 @@ public:
     // Render with cdb_shim::render_spans (highlight.h).
     std::vector<std::pair<int64_t, std::vector<std::pair<uint64_t, uint64_t>>>> highlight_spans(
         const std::vector<std::string>& keywords) const;
+    // NEW: the tail of select() for this field (database.cpp:394-441 with ac_automaton::render, :58-90) — the page `rows` (in
+    // the caller's order, as `span` cut it from the ranked list) rendered on the device from the resident text: entry i is the
+    // document of rows[i].first with `left` / `right` around its merged keyword occurrences, or nullopt when the index does not
+    // hold that id.  No keywords: the plain documents.  One GPU call whose cost follows the page (cdb_render_rows);
+    // highlight_spans above is the whole-column form.
+    std::vector<std::optional<std::string>> render_rows(const result_type& rows, const std::vector<std::string>& keywords,
+                                                        const std::string& left, const std::string& right) const;
     // NEW: database.cpp:442-460 for this field — the result rows grouped by their whole document on the device (cdb_cluster),
     // in std::string order.  One GPU only (std::logic_error with COFFEEDB_GPUS).
     cluster_type cluster(const result_type& rows) const;

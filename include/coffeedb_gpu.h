@@ -285,6 +285,43 @@ typedef struct cdb_spans {
 int cdb_query_spans(cdb_index* h, const char* blob, const uint64_t* offsets, uint64_t nkw, cdb_spans* out);
 void cdb_spans_free(cdb_spans* r);
 
+/* A page of result rows rendered on the device — the tail of select() (database.cpp:394-441): for the rows `ids` (the page that
+ * `span` cut from the ranked list) and the keyword list of ONE string key, every row's document, its merged highlight spans and the
+ * document with `left` / `right` put around them, as ac_automaton::render does (database.cpp:58-90).  Only the resident text of
+ * those documents is read: the cost follows the page, not the corpus, and a caller that built from device memory (cdb_build_device,
+ * cdb_build_resident, shards) needs no host copy of the column.  It is a text scan like the reference's highlighter, so it reports the
+ * true occurrences whatever order the suffix array is in (reference_compat, bytes >= 0x80); the array is never read.
+ *   Rows.  Output row i belongs to ids[i], in the caller's order (rank order, not id order); a repeated id is rendered as often as
+ * it is given.  An id the index does not hold gets found[i] = 0, an empty string and no spans, and is counted in `missing`; an index
+ * that was never built answers all rows missing (as cdb_cluster does).  nrows = 0 is valid.
+ *   Keywords.  nkw = 0 returns the plain documents (select without highlight).  An empty keyword fails the call with CDB_E_INVALID
+ * and "Empty keywords are not allowed", like every other keyword entry point.  There is no limit on the number or length of keywords.
+ *   Occurrences.  A keyword of m bytes occurs at offset p of a document of L bytes iff p + m <= L and the bytes are equal;
+ * occurrences never cross into the next document.
+ *   Spans.  The union of all occurrences of the document: overlapping occurrences fuse, merely adjacent ones stay apart; `end` is
+ * inclusive (the reference's pop / extend / append rule, database.cpp:62-77; the same spans as cdb_query_spans).
+ *   Rendering.  `left` goes before byte `begin`, `right` after byte `end` (database.cpp:78-90); either may be empty, neither need be
+ * text.  Row i's string is text_blob[text_ptr[i] .. text_ptr[i + 1]), its spans are [span_ptr[i], span_ptr[i + 1]).
+ *   `what` selects the arrays filled (CDB_RENDER_TEXT | CDB_RENDER_SPANS); the others stay NULL.  `found` is always filled.
+ * The call is a query: several host threads may call it on one handle, and it waits out a rebuild under the handle's lock.  Large
+ * result arrays are pinned blocks of the result cache (below); release them with cdb_rendered_free.  Stats: "render_ms",
+ * "render_page_bytes" (bytes of the found rows' documents), "render_spans"; with option profile the kernels are timed as rnd_*.
+ * Documents of 4 GiB and more are refused.  One key per call: the reference keeps one automaton per key. */
+#define CDB_RENDER_TEXT  1   /* fill text_ptr / text_blob */
+#define CDB_RENDER_SPANS 2   /* fill span_ptr / begin / end */
+typedef struct cdb_rendered {
+    uint64_t nrows, missing, nspans, text_bytes;
+    uint8_t*  found;      /* nrows: 1 = the index holds ids[i] */
+    uint64_t* text_ptr;   /* nrows + 1 offsets into text_blob, or NULL */
+    char*     text_blob;  /* rendered documents, concatenated in input order */
+    uint64_t* span_ptr;   /* nrows + 1, or NULL */
+    uint64_t* begin;      /* nspans, byte offsets inside the ORIGINAL document */
+    uint64_t* end;        /* nspans, inclusive, as ac_automaton's spans */
+} cdb_rendered;
+int cdb_render_rows(cdb_index* h, const int64_t* ids, uint64_t nrows, const char* blob, const uint64_t* offsets, uint64_t nkw,
+                    const char* left, size_t left_len, const char* right, size_t right_len, int what, cdb_rendered* out);
+void cdb_rendered_free(cdb_rendered* r);
+
 /* Batched query with patterns and results left in device memory (multi-GPU merge over RCCL, HBM-
  * resident timing).  d_blob/d_offsets are device pointers.  On return the library-owned device arrays
  * d_row_ptr (npat+1 u64), d_ids (nrows i64), d_counts (nrows i64) stay valid until the next query on
@@ -338,6 +375,10 @@ int cdb_shards_query_or(cdb_shards* h, const char* blob, const uint64_t* offsets
 int cdb_shards_query_ranked(cdb_shards* h, const char* blob, const uint64_t* offsets, uint64_t nkw, int64_t corr_lo, int64_t corr_hi,
                             uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows);
 int cdb_shards_query_spans(cdb_shards* h, const char* blob, const uint64_t* offsets, uint64_t nkw, cdb_spans* out);
+/* cdb_render_rows over all shards: every shard renders the rows it holds, the answers are put back into the caller's row order; a
+ * row no shard holds is missing */
+int cdb_shards_render_rows(cdb_shards* h, const int64_t* ids, uint64_t nrows, const char* blob, const uint64_t* offsets, uint64_t nkw,
+                           const char* left, size_t left_len, const char* right, size_t right_len, int what, cdb_rendered* out);
 /* cdb_query_batch_offsets over all shards (occurrence offsets are relative to their document, so they need no re-basing) */
 int cdb_shards_query_batch_offsets(cdb_shards* h, const char* blob, const uint64_t* offsets, uint64_t npat, cdb_result* out,
                                    cdb_hits* hits);
