@@ -1677,6 +1677,9 @@ int cdb_get_stat(const cdb_index* h, const char* name, double* value) {
         {"cluster_prepare_ms", h->ix.clu.prepare_ms}, {"cluster_ms", h->ix.clu.last_ms}, {"cluster_resorted", h->ix.clu.resorted ? 1.0 : 0.0},
         {"render_ms", h->ix.rnd.last_ms}, {"render_page_bytes", (double)h->ix.rnd.page_bytes}, {"render_spans", (double)h->ix.rnd.spans},
         {"query_ms", q.query_ms}, {"query_upload_ms", q.upload_ms}, {"query_device_ms", q.device_ms}, {"query_download_ms", q.download_ms}, {"query_hits", (double)q.nhits}, {"query_rows", (double)q.nrows},
+        {"query_batches", (double)q.batches}, {"query_spec_batches", (double)q.spec_batches}, {"query_spec_spills", (double)q.spec_spills},
+        {"query_wave_batches", (double)q.wave_batches}, {"query_sort_batches", (double)q.sort_batches}, {"query_sort_chunks", (double)q.sort_chunks},
+        {"query_empty_batches", (double)q.empty_batches},
     };
     for (auto& e : tab)
         if (!std::strcmp(e.n, name)) {

@@ -54,6 +54,13 @@ struct QueryStats {
     double query_ms = 0;
     double upload_ms = 0, device_ms = 0, download_ms = 0;  // host batches: patterns in, search + rows, results out
     uint64_t nhits = 0, nrows = 0;
+    // which row builder answered the batched queries of this handle (query.hip: query_typed), counted since the handle was
+    // created — builds, loads and proof repairs leave them alone.  spec + wave + sort + empty - spec_spills == batches.
+    uint64_t batches = 0;
+    uint64_t spec_batches = 0, spec_spills = 0;  // speculation attempted / attempted and redone the ordinary way
+    uint64_t wave_batches = 0;                   // one wavefront per pattern with the totals known
+    uint64_t sort_batches = 0, sort_chunks = 0;  // expand + radix sort + runs, and the chunks it was cut into
+    uint64_t empty_batches = 0;                  // nothing to look up (no pattern, no text) or no hit at all
 };
 
 // kept sort keys for the lone-keyword kernels (query.hip): suffixes starting with the keyword's first min(m, nsym) symbols

@@ -835,7 +835,9 @@ DeviceCsr query_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, 
     DeviceCsr out;
     out.npat = npat;
     ix.q_rowptr.ensure((npat + 1) * 8);
+    ix.qstats.batches++;
     if (npat == 0 || ix.size == 0 || ix.width == 0) {
+        ix.qstats.empty_batches++;
         CDB_HIP(hipMemsetAsync(ix.q_rowptr.p, 0, (npat + 1) * 8, s));
         ix.q_ids.ensure(16);
         ix.q_counts.ensure(16);
@@ -857,6 +859,7 @@ DeviceCsr query_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, 
     // redone below with the totals known.
     if (!with_offsets && ix.use_wave_rows && ix.ndocs < 0xFFFFFFFFull && ix.q_spec_cap > 0) {
         const uint64_t cap = ix.q_spec_cap;
+        ix.qstats.spec_batches++;
         scan_totals_device<U2>(s, ix.scan_partials, hin, npat, OpSumMax{}, U2{0, 0});
         const uint64_t nb1 = ceil_div(npat, SC_TILE);
         ix.q_spec.ensure(4 * sizeof(uint64_t));  // {H, maxh, spill flag, nrows}
@@ -893,12 +896,14 @@ DeviceCsr query_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, 
             return out;
         }
         ix.q_spec_cap = 0;  // this batch is not of that kind: the ordinary path below decides again
+        ix.qstats.spec_spills++;
     }
     const U2 tot = scan_totals<U2>(s, ix.scan_partials, hin, npat, OpSumMax{}, U2{0, 0});
     scan_apply<U2>(s, ix.scan_partials, hin, npat, OpSumMax{}, U2{0, 0}, HitsOut2{ix.q_hoff.as<uint64_t>(), npat});
     const uint64_t H = tot.a, maxh = tot.b;
     out.nhits = H;
     if (H == 0) {
+        ix.qstats.empty_batches++;
         CDB_HIP(hipMemsetAsync(ix.q_rowptr.p, 0, (npat + 1) * 8, s));
         ix.q_ids.ensure(16);
         ix.q_counts.ensure(16);
@@ -907,6 +912,7 @@ DeviceCsr query_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, 
     }
     if (!with_offsets && maxh <= 64 && ix.use_wave_rows && ix.ndocs < 0xFFFFFFFFull && H <= (1ull << 28)) {
         // every pattern's hit list fits one wavefront: sort + run-length encode per pattern in registers
+        ix.qstats.wave_batches++;
         ix.q_keys0.ensure(H * 4);   // row_doc
         ix.q_keys1.ensure(H * 4);   // row_cnt
         ix.q_flags.ensure(npat * 8);  // rows per pattern
@@ -957,6 +963,8 @@ DeviceCsr query_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, 
         }
         cut.push_back(npat);
     }
+    ix.qstats.sort_batches++;
+    ix.qstats.sort_chunks += cut.size() - 1;
     uint64_t rows_total = 0, hits_done = 0;
     for (size_t c = 0; c + 1 < cut.size(); ++c) {
         const uint64_t j0 = cut[c], j1 = cut[c + 1];

@@ -457,7 +457,13 @@ int cdb_sa_copy(cdb_index* h, void* host_out, uint64_t capacity_bytes);
 int cdb_set_option(cdb_index* h, const char* name, int64_t value);
 
 /* statistic by name: "build_ms", "rounds", "unresolved_after_initial", "sort_passes", "isa_built",
- * "key_symbols", "symbol_bits", "query_ms", ... returns CDB_E_INVALID for unknown names */
+ * "key_symbols", "symbol_bits", "query_ms", ... returns CDB_E_INVALID for unknown names.
+ * Which row builder answered the batched queries (cdb_query_batch*, and lone keywords handed over to them), counted per handle
+ * since cdb_create and left alone by builds, loads and proof repairs: "query_batches"; "query_spec_batches" (run speculatively
+ * in buffers sized from the previous batch) and "query_spec_spills" (of those, redone because a hit list or the total did not
+ * fit); "query_wave_batches" (one wavefront per pattern, totals known); "query_sort_batches" and "query_sort_chunks" (expand +
+ * radix sort, and the chunks query_hit_budget cut them into); "query_empty_batches" (nothing to look up, or no hit).
+ * spec + wave + sort + empty - spills == batches.  Shards: through cdb_shards_get(i), as every other statistic. */
 int cdb_get_stat(const cdb_index* h, const char* name, double* value);
 
 /* accumulated HIP-event time of one kernel family since cdb_profile_reset (needs option profile=1).
