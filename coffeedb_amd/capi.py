@@ -32,6 +32,7 @@ EXPORTS = [
     "cdb_column_query_any", "cdb_query_and_columns", "cdb_column_get_stat", "cdb_debug_column_set_option", "cdb_debug_column_profile_dump",
     "cdb_column_cluster", "cdb_cluster", "cdb_clusters_free",
     "cdb_render_rows", "cdb_shards_render_rows", "cdb_rendered_free",
+    "cdb_remove", "cdb_column_remove",
 ]
 
 
@@ -242,6 +243,8 @@ def load_library():
     lib.cdb_shards_render_rows.argtypes = render_args
     lib.cdb_rendered_free.argtypes = [C.POINTER(CdbRendered)]
     lib.cdb_rendered_free.restype = None
+    lib.cdb_remove.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    lib.cdb_column_remove.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     _LIB = lib
     return lib
 
@@ -572,6 +575,15 @@ class GpuStringIndex:
         raw=True returns the C arrays (text_ptr, text_blob, span_ptr, begin, end, ...) in a dict instead."""
         return _render_rows(self, self._lib.cdb_render_rows, ids, keywords, left, right, text, spans, raw)
 
+    def remove(self, ids):
+        """cdb_remove: the documents `ids` leave the built index on the device (no rebuild, nothing uploaded but the ids); the handle
+        then equals a fresh one built over the survivors.  Returns (removed: distinct documents dropped, missing: entries of `ids`
+        the index does not hold)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        removed, missing = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.cdb_remove(self._h, _ptr(ids) if len(ids) else None, len(ids), C.byref(removed), C.byref(missing)))
+        return int(removed.value), int(missing.value)
+
     def set_option(self, name, value):
         self._check(self._lib.cdb_set_option(self._h, name.encode(), int(value)))
 
@@ -812,6 +824,14 @@ class GpuColumn:
             return np.ctypeslib.as_array(ids, shape=(n.value,)).copy() if n.value else np.empty(0, dtype=np.int64)
         finally:
             self._lib.cdb_free(ids)
+
+    def remove(self, ids):
+        """cdb_column_remove: the rows `ids` leave the column (built and staged rows alike), which is rebuilt over the rest.
+        Returns (removed, missing) as GpuStringIndex.remove does."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        removed, missing = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.cdb_column_remove(self._h, _ptr(ids) if len(ids) else None, len(ids), C.byref(removed), C.byref(missing)))
+        return int(removed.value), int(missing.value)
 
     def cluster(self, ids):
         """cdb_column_cluster (database.cpp:442-460 for this field): the rows `ids` grouped by value, ascending.  Returns

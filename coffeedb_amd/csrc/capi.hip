@@ -239,6 +239,13 @@ struct NewColumn {
     // cdb_load only: the array comes with the column instead of being built (sa_hi: the packed storage's fifth bytes)
     DevBuf sa, sa_hi;
     bool reference_compat = true, sa_sorted = true;
+    // cdb_remove only: the array was compacted on this device, out of one that was built here — damage the order proof finds in it
+    // is treated like damage behind a build; and the search keys come along, compacted slot for slot, with the parameters they
+    // were made with (the symbol maps of the handle stay as they are)
+    bool from_file = true;
+    DevBuf keys, keys32, keylow;
+    int key_nsym = 0, key_low_bits = 0, key_low_bytes = 0;
+    uint32_t key_base = 0;
 };
 
 void alloc_padded_text(Index& ix, DevBuf& text, uint64_t n) {
@@ -294,10 +301,19 @@ void install(Index& ix, NewColumn& c) {
             ix.d_sa_hi = std::move(c.sa_hi);
             ix.sa_packed = true;
         }
+        if (c.key_nsym) {
+            ix.d_keys = std::move(c.keys);
+            ix.d_keys32 = std::move(c.keys32);
+            ix.d_keylow = std::move(c.keylow);
+            ix.key_nsym = c.key_nsym;
+            ix.key_base = c.key_base;
+            ix.key_low_bits = c.key_low_bits;
+            ix.key_low_bytes = c.key_low_bytes;
+        }
         // a file's entries were checked one by one (each names a real suffix), their ORDER was not: the proof behind a build runs
         // behind a load as well (damage -> the array is rebuilt from the loaded text)
         if (ix.self_check >= 3 || ix.premap_generation) {
-            ix.proof.of_loaded_file = true;
+            ix.proof.of_loaded_file = c.from_file;
             proof_start(ix);
         }
     } catch (...) {
@@ -1071,6 +1087,77 @@ int cdb_build_resident(cdb_index* h, const void* d_text, const uint64_t* d_doc_s
     });
 }
 
+// Documents leave a built index without a rebuild (remove.hip).  The survivors' array is the old one with the removed documents'
+// entries dropped and the rest re-encoded in the same order; an array in the reference's order (bytes >= 0x80 under
+// reference_compat) depends on bucket sizes that change with n, so there only text and tables are compacted and the array is
+// built over them on the device.  Either way nothing is uploaded but the ids.
+int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
+    if (!h || (nids && !ids)) return CDB_E_INVALID;
+    if (removed) *removed = 0;
+    if (missing) *missing = 0;
+    reserve_join();
+    return guarded(h, [&] {
+        Index& ix = h->ix;
+        std::lock_guard<std::mutex> g(ix.mu);
+        DeviceScope dscope(ix);
+        const double t0 = wall_ms();
+        const uint64_t built_docs = ix.width ? ix.ndocs : 0;
+        if (ix.host_text_valid && ix.ids.size() > built_docs) throw Error("remove: documents were added since the last build");
+        if (!nids) return;
+        if (!built_docs) {  // never built, or built over nothing: the index holds no id
+            if (missing) *missing = nids;
+            return;
+        }
+        RemovePlan p;
+        try {
+            remove_mark(ix, ids, nids, p);
+        } catch (...) {
+            (void)hipStreamSynchronize(ix.stream);
+            throw;
+        }
+        if (removed) *removed = p.removed;
+        if (missing) *missing = p.missing;
+        if (!p.removed) {  // (the scan's total synchronised the stream and nothing was queued behind it)
+            ix.prof.resolve();
+            return;
+        }
+        const Layout L = layout_from(p.ndocs, p.size, p.longest);  // (a smaller column: the capacity errors cannot fire)
+        const bool compact = ix.sa_sorted;
+        const uint64_t old_size = ix.size;
+        replace_column(ix, [&](NewColumn& col) {
+            col.L = L;
+            col.host = NewColumn::HOST_NONE;  // (a staging copy that equals the built column goes: cdb_add* fetch the survivors back)
+            remove_text(ix, p);
+            if (compact) {
+                const bool pack = ix.pack_sa && L.width == 8 && (int)L.bits + L.off_bits <= 40 && L.size > 0;
+                remove_compact(ix, p, (int)L.bits, L.width, pack);
+                col.sa = std::move(p.sa);
+                col.sa_hi = std::move(p.sa_hi);
+                col.keys = std::move(p.keys);
+                col.keys32 = std::move(p.keys32);
+                col.keylow = std::move(p.keylow);
+                col.key_nsym = p.key_nsym;
+                col.key_base = p.key_base;
+                col.key_low_bits = p.key_low_bits;
+                col.key_low_bytes = p.key_low_bytes;
+                col.reference_compat = ix.reference_compat;
+                col.sa_sorted = true;
+                col.from_file = false;
+            }
+            CDB_HIP(hipStreamSynchronize(ix.stream));
+            ix.prof.resolve();
+            col.text = std::move(p.text);
+            col.d_start = std::move(p.d_start);
+            col.d_ids = std::move(p.d_ids);
+        });
+        ix.rm.calls += 1;
+        (compact ? ix.rm.compactions : ix.rm.rebuilds) += 1;
+        ix.rm.docs = p.removed;
+        ix.rm.bytes = old_size - L.size;
+        ix.rm.last_ms = wall_ms() - t0;
+    });
+}
+
 void cdb_free(void* p) { host_free(p); }
 
 namespace {
@@ -1675,6 +1762,8 @@ int cdb_get_stat(const cdb_index* h, const char* name, double* value) {
         {"resident_answers", (double)h->ix.res_answers}, {"launched_answers", (double)h->ix.launched_answers}, {"resident_mode", (double)h->ix.resident_mode},
         {"cluster_table_bytes", h->ix.clu.valid ? (double)(h->ix.clu.bytes() + h->ix.idt.bytes()) : 0.0}, {"cluster_classes", (double)h->ix.clu.nclasses},
         {"cluster_prepare_ms", h->ix.clu.prepare_ms}, {"cluster_ms", h->ix.clu.last_ms}, {"cluster_resorted", h->ix.clu.resorted ? 1.0 : 0.0},
+        {"removes", (double)h->ix.rm.calls}, {"remove_compactions", (double)h->ix.rm.compactions}, {"remove_rebuilds", (double)h->ix.rm.rebuilds},
+        {"remove_docs", (double)h->ix.rm.docs}, {"remove_bytes", (double)h->ix.rm.bytes}, {"remove_ms", h->ix.rm.last_ms},
         {"render_ms", h->ix.rnd.last_ms}, {"render_page_bytes", (double)h->ix.rnd.page_bytes}, {"render_spans", (double)h->ix.rnd.spans},
         {"query_ms", q.query_ms}, {"query_upload_ms", q.upload_ms}, {"query_device_ms", q.device_ms}, {"query_download_ms", q.download_ms}, {"query_hits", (double)q.nhits}, {"query_rows", (double)q.nrows},
         {"query_batches", (double)q.batches}, {"query_spec_batches", (double)q.spec_batches}, {"query_spec_spills", (double)q.spec_spills},

@@ -651,6 +651,61 @@ int cdb_column_build(cdb_column* c) {
     });
 }
 
+// Rows leave a column: the built rows come back in key order (bool: insertion order within each value, which the stable sort by
+// value restores), join the rows staged since, the removed ids are dropped and the column's own build runs over the rest — a
+// device sort of milliseconds, so its derived arrays are not compacted one by one.  A failed build leaves the column as it was.
+int cdb_column_remove(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
+    if (!c || (nids && !ids)) return CDB_E_INVALID;
+    if (removed) *removed = 0;
+    if (missing) *missing = 0;
+    return guarded_ix(c->ws, [&] {
+        std::lock_guard<std::mutex> g(c->ws.mu);
+        ColumnScope cs(c);
+        if (!nids) return;
+        hipStream_t s = c->ws.stream;
+        const uint64_t n_old = c->n, n_staged = c->staged_ids.size();
+        std::vector<int64_t> all_ids(n_old + n_staged);
+        std::vector<uint64_t> all_raw(n_old + n_staged);
+        if (n_old) {
+            CDB_HIP(hipMemcpyAsync(all_ids.data(), c->ids_v.p, n_old * 8, hipMemcpyDeviceToHost, s));
+            CDB_HIP(hipMemcpyAsync(all_raw.data(), c->keys_v.p, n_old * 8, hipMemcpyDeviceToHost, s));
+            CDB_HIP(hipStreamSynchronize(s));
+            for (uint64_t i = 0; i < n_old; ++i) all_raw[i] = column_key_raw(c->kind, all_raw[i]);
+        }
+        std::copy(c->staged_ids.begin(), c->staged_ids.end(), all_ids.begin() + n_old);
+        std::copy(c->staged_raw.begin(), c->staged_raw.end(), all_raw.begin() + n_old);
+        std::vector<int64_t> held(all_ids), gone(ids, ids + nids);
+        std::sort(held.begin(), held.end());
+        std::sort(gone.begin(), gone.end());
+        uint64_t miss = 0;
+        for (int64_t id : gone) miss += std::binary_search(held.begin(), held.end(), id) ? 0 : 1;
+        gone.erase(std::unique(gone.begin(), gone.end()), gone.end());
+        uint64_t kept = 0;
+        for (uint64_t i = 0; i < all_ids.size(); ++i) {
+            if (std::binary_search(gone.begin(), gone.end(), all_ids[i])) continue;
+            all_ids[kept] = all_ids[i];
+            all_raw[kept++] = all_raw[i];
+        }
+        const uint64_t dropped = all_ids.size() - kept;
+        if (removed) *removed = dropped;
+        if (missing) *missing = miss;
+        if (!dropped) return;
+        all_ids.resize(kept);
+        all_raw.resize(kept);
+        c->staged_ids.swap(all_ids);  // (all_ids / all_raw now hold the rows staged before the call)
+        c->staged_raw.swap(all_raw);
+        c->n = 0;
+        try {
+            column_build(c);
+        } catch (...) {
+            c->n = n_old;
+            c->staged_ids.swap(all_ids);
+            c->staged_raw.swap(all_raw);
+            throw;
+        }
+    });
+}
+
 int cdb_column_query(cdb_column* c, const char* range, size_t len, int64_t** ids, size_t* nrows) {
     if (!c || !ids || !nrows || (len && !range)) return CDB_E_INVALID;
     *ids = nullptr;

@@ -349,6 +349,13 @@ struct Index {
         uint64_t page_bytes = 0, spans = 0;
     } rnd;
 
+    // ---- cdb_remove (remove.hip): calls that dropped something, by the path they took; the last call's documents, text bytes and wall time
+    struct RemoveStats {
+        uint64_t calls = 0, compactions = 0, rebuilds = 0;
+        uint64_t docs = 0, bytes = 0;
+        double last_ms = 0;
+    } rm;
+
     double host_upload_ms = 0, host_free_ms = 0;  // cdb_build: staged column to the device / staging copy released
     Profiler prof;
     BuildStats bstats;
@@ -380,6 +387,21 @@ __device__ __forceinline__ uint64_t lower_bound_id(const int64_t* __restrict__ i
     }
     return a;
 }
+
+// remove.hip — the pieces of cdb_remove (capi.hip commits them), all on ix.stream with ix.mu held.  Everything is made in fresh
+// blocks of the plan while the old index stands.
+struct RemovePlan {
+    uint64_t removed = 0, missing = 0;         // distinct documents dropped, entries of ids the index does not hold
+    uint64_t ndocs = 0, size = 0, longest = 0;  // the surviving column
+    DevBuf drop, newdoc, src_start;            // u8[old ndocs] flag, u32[old ndocs] old -> new document, u64[ndocs] old start of every survivor
+    DevBuf d_start, d_ids, text;               // the new tables and the new padded text
+    DevBuf sa, sa_hi, keys, keys32, keylow;    // the compacted array and search keys
+    int key_nsym = 0, key_low_bits = 0, key_low_bytes = 0;
+    uint32_t key_base = 0;
+};
+void remove_mark(Index& ix, const int64_t* ids, uint64_t nids, RemovePlan& p);  // flags, counts, and (something to drop) the new tables; synchronises
+void remove_text(Index& ix, RemovePlan& p);                                      // the kept documents gathered into p.text
+void remove_compact(Index& ix, RemovePlan& p, int new_bits, int new_width, bool new_packed);  // the array and its keys in the new layout
 
 // verify.hip — out = {inversions, tie-order violations, wrapped sum of entries, invalid entries, expected sum}
 void verify_suffix_array(Index& ix, uint64_t out[5]);

@@ -60,6 +60,28 @@ index::cluster_type column_cluster(cdb_column* c, int kind, const index::result_
     if (rc != CDB_OK) rethrow_column(c, rc);
     return cdb_shim::cluster_rows(g.cl, kind);
 }
+// rows staged on this side whose id is in `gone` (sorted) are forgotten
+template <typename V>
+void forget_staged(std::vector<int64_t>& ids, std::vector<V>& vals, const std::vector<int64_t>& gone) {
+    size_t k = 0;
+    for (size_t i = 0; i < ids.size(); ++i) {
+        if (std::binary_search(gone.begin(), gone.end(), ids[i])) continue;
+        ids[k] = ids[i];
+        vals[k++] = vals[i];
+    }
+    ids.resize(k);
+    vals.resize(k);
+}
+template <typename V>
+bool column_remove(cdb_column* c, std::vector<int64_t>& staged_ids, std::vector<V>& staged_vals, const std::vector<int64_t>& ids) {
+    if (!c) return false;
+    const int rc = cdb_column_remove(c, ids.data(), ids.size(), nullptr, nullptr);
+    if (rc != CDB_OK) rethrow_column(c, rc);
+    std::vector<int64_t> gone(ids);
+    std::sort(gone.begin(), gone.end());
+    forget_staged(staged_ids, staged_vals, gone);
+    return true;
+}
 }  // namespace
 
 // ---- numeric indexes: sorted (value, id) pairs, half-open lower_bound window (index.cpp:63-74, 129-173)
@@ -98,6 +120,10 @@ index::result_type numeric_index<T, Tag>::query(const std::string& range) const 
 template <typename T, int8_t Tag>
 index::cluster_type numeric_index<T, Tag>::cluster(const result_type& rows) const {
     return column_cluster(col, Tag, rows);
+}
+template <typename T, int8_t Tag>
+bool numeric_index<T, Tag>::remove(const std::vector<int64_t>& ids) {
+    return column_remove(col, staged_ids, staged_vals, ids);
 }
 template class numeric_index<int64_t, 1>;
 template class numeric_index<double, 2>;
@@ -139,6 +165,7 @@ index::result_type bool_index::query(const std::string& range) const {
 }
 
 index::cluster_type bool_index::cluster(const result_type& rows) const { return column_cluster(col, number, rows); }
+bool bool_index::remove(const std::vector<int64_t>& ids) { return column_remove(col, staged_ids, staged_vals, ids); }
 
 // ---- string index: forwards to the GPU library
 namespace {
@@ -233,6 +260,27 @@ void string_index::build() {
     }
     const int rc = cdb_build_views(handle, ids.data(), ptrs.data(), lens.data(), ids.size());
     if (rc != CDB_OK) rethrow(handle, rc);
+    built = ids.size();
+}
+
+bool string_index::remove(const std::vector<int64_t>& gone_ids) {
+    if (!handle || ids.size() != built) return false;
+    const int rc = cdb_remove(handle, gone_ids.data(), gone_ids.size(), nullptr, nullptr);
+    if (rc != CDB_OK) rethrow(handle, rc);
+    std::vector<int64_t> gone(gone_ids);
+    std::sort(gone.begin(), gone.end());
+    size_t k = 0;
+    for (size_t i = 0; i < ids.size(); ++i) {
+        if (std::binary_search(gone.begin(), gone.end(), ids[i])) continue;
+        ids[k] = ids[i];
+        ptrs[k] = ptrs[i];
+        lens[k++] = lens[i];
+    }
+    ids.resize(k);
+    ptrs.resize(k);
+    lens.resize(k);
+    built = k;
+    return true;
 }
 
 index::result_type string_index::query(const std::string& keyword) const {

@@ -56,6 +56,9 @@ public:
     // cluster.h).  GPU column only (std::logic_error otherwise: the CPU classes keep the reference's surface).  Rows whose id
     // the column does not hold are skipped (undefined behaviour in the reference).
     cluster_type cluster(const result_type& rows) const;
+    // NEW: the rows `ids` leave the column on the device (cdb_column_remove; rows staged since the last build() go too).  false = not
+    // available (the CPU class): the caller rebuilds as the reference does (database.cpp:461-466, then build()).
+    bool remove(const std::vector<int64_t>& ids);
 
 private:
     std::array<std::vector<int64_t>, 2> data;
@@ -85,6 +88,7 @@ public:
     result_type query(const std::string& range) const override;
     cdb_column* column() const { return col; }
     cluster_type cluster(const result_type& rows) const;  // NEW: as bool_index::cluster
+    bool remove(const std::vector<int64_t>& ids);          // NEW: as bool_index::remove
 
 protected:
     std::vector<std::pair<T, int64_t>> rows;
@@ -138,6 +142,11 @@ public:
     // NEW: database.cpp:442-460 for this field — the result rows grouped by their whole document on the device (cdb_cluster),
     // in std::string order.  One GPU only (std::logic_error with COFFEEDB_GPUS).
     cluster_type cluster(const result_type& rows) const;
+    // NEW: "remove + build" for this field (interface.cpp:274-285, database.cpp:461-466 followed by :170-282) without the build — the
+    // documents `ids` leave the built index on the device (cdb_remove) and the views add() collected for them are forgotten, so a
+    // later build() does not bring them back.  Ids the index does not hold are ignored.  false = not available — a sharded index
+    // (COFFEEDB_GPUS), or documents were added since the last build(): nothing changed, the caller rebuilds as the reference does.
+    bool remove(const std::vector<int64_t>& ids);
     // NEW (no counterpart in the reference): announce a string column of roughly `bytes` bytes BEFORE the data is loaded —
     // start_server() calls init() and then build() (server.cpp:43-44); called at the start of init() with the size of the raw
     // directory (and any document as a sample of the alphabet) it lets the GPU map the first build's working set on a helper
@@ -152,6 +161,7 @@ private:
     std::vector<int64_t> ids;        // index.h:58-59: ids and (non-owning) views of the documents, in add() order
     std::vector<const char*> ptrs;
     std::vector<uint64_t> lens;
+    size_t built = 0;              // documents the last build() handed over
     cdb_index* handle = nullptr;   // one GPU
     cdb_shards* shards = nullptr;  // several GPUs (environment COFFEEDB_GPUS; the library shards a column only when it
                                    // exceeds one GPU's share)

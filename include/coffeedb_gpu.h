@@ -322,6 +322,40 @@ int cdb_render_rows(cdb_index* h, const int64_t* ids, uint64_t nrows, const char
                     const char* left, size_t left_len, const char* right, size_t right_len, int what, cdb_rendered* out);
 void cdb_rendered_free(cdb_rendered* r);
 
+/* Documents leave a built index on the device, without a rebuild — replaces "remove + build" (interface.cpp:274-285,
+ * database.cpp:461-466 followed by :170-282) for one string key.  The reference deletes the raw files and the objects stay visible until
+ * the next build re-reads every file and rebuilds every index; here the resident text, tables and array are enough: suffixes never
+ * cross documents, equal suffixes ascend by document and the survivors keep their order, so the survivors' array is the old one with the
+ * removed documents' entries dropped and the rest re-encoded (remove.hip: a stable compaction, nothing but `ids` is uploaded).
+ *   Result.  After a successful call the handle cannot be told from a fresh handle built over the surviving documents in their
+ * original order: cdb_size / cdb_bits / cdb_mask / cdb_sa_width / cdb_sa_copy, every query entry point, cdb_cluster, cdb_render_rows,
+ * cdb_save and the cdb_debug_verify* hooks.  The layout is recomputed with the build's own rule (index.cpp:182-208): bits, mask, the
+ * entry width and the packed storage may all change.
+ *   Counting.  *removed = distinct documents dropped; *missing = entries of `ids` the index does not hold — every such entry counts,
+ * as cdb_cluster counts them; a held id given twice is removed once and is not missing (either pointer may be NULL).  nids = 0 is
+ * valid and changes nothing.  On a handle that was never built every id is missing.  Removing every document leaves what cdb_build
+ * leaves for an empty column.
+ *   Pending additions.  If documents were added since the last build the call fails with CDB_E_INVALID and "remove: documents were
+ * added since the last build"; nothing changes.  A host staging copy that equals the built column is dropped (cdb_add* fetch the
+ * survivors back on demand: "remove, add, rebuild" works).
+ *   Borrowed text.  For a handle built with cdb_build_device / cdb_build_resident the compacted text goes into a library-owned block:
+ * after a removal that dropped at least one document the handle NO LONGER READS THE CALLER'S BUFFER.
+ *   Locking and failure.  The call is exclusive, like a build: queries wait under the handle's lock.  Everything new is made in fresh
+ * blocks while the old index stands; a failure before the commit leaves the old index serving (cdb_last_error tells why).
+ *   Paths.  A sorted array (pure ASCII text, or reference_compat = 0) is compacted, and its search keys with it.  An array in the
+ * reference's order (reference_compat = 1 and bytes >= 0x80) depends on bucket sizes that change with n (index.cpp:96-126,218): there
+ * text and tables are compacted on the device and the array is built over them — a failure of that build leaves a "never built"
+ * handle, as after any failed build.  With self_check >= 3 the order proof runs behind either path; damage found in a compacted
+ * array is treated like damage behind a build.
+ *   Stats: "removes" (calls that dropped something), "remove_compactions", "remove_rebuilds", and of the last such call "remove_docs",
+ * "remove_bytes" (text bytes dropped), "remove_ms" (wall, under the lock); with option profile the kernels are timed as rm_*.
+ * Not available on cdb_shards (each shard's document bounds would have to be re-cut): rebuild there. */
+int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
+/* The same for a column, with the same counting rules: the rows leave the built and the staged rows, and the column's own build (a
+ * device sort of milliseconds) runs over the rest.  The result equals a fresh column built from the surviving rows; a failed build
+ * leaves the column as it was. */
+int cdb_column_remove(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
+
 /* Batched query with patterns and results left in device memory (multi-GPU merge over RCCL, HBM-
  * resident timing).  d_blob/d_offsets are device pointers.  On return the library-owned device arrays
  * d_row_ptr (npat+1 u64), d_ids (nrows i64), d_counts (nrows i64) stay valid until the next query on
