@@ -33,6 +33,7 @@ EXPORTS = [
     "cdb_column_cluster", "cdb_cluster", "cdb_clusters_free",
     "cdb_render_rows", "cdb_shards_render_rows", "cdb_rendered_free",
     "cdb_remove", "cdb_column_remove",
+    "cdb_append", "cdb_debug_verify_keys",
 ]
 
 
@@ -245,6 +246,8 @@ def load_library():
     lib.cdb_rendered_free.restype = None
     lib.cdb_remove.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     lib.cdb_column_remove.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    lib.cdb_append.argtypes = [vp, vp, vp, vp, u64, C.POINTER(u64)]
+    lib.cdb_debug_verify_keys.argtypes = [vp, C.POINTER(u64)]
     _LIB = lib
     return lib
 
@@ -583,6 +586,28 @@ class GpuStringIndex:
         removed, missing = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.cdb_remove(self._h, _ptr(ids) if len(ids) else None, len(ids), C.byref(removed), C.byref(missing)))
         return int(removed.value), int(missing.value)
+
+    def append(self, ids, blob, doc_start):
+        """cdb_append: the documents (ids, blob, doc_start as for build_view) join the built index on the device — only they are
+        uploaded and sorted; the handle then equals a fresh one built over the old documents followed by the new ones.  Returns the
+        number of documents that joined."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        doc_start = np.ascontiguousarray(doc_start, dtype=np.uint64)
+        assert len(doc_start) == len(ids) + 1
+        if len(doc_start) and int(doc_start[-1]) > len(blob):   # (the C ABI takes plain pointers: a short blob would be read past its end)
+            raise ValueError(f"blob holds {len(blob)} bytes, doc_start[-1] = {int(doc_start[-1])}")
+        if not len(blob):
+            blob = np.zeros(1, dtype=np.uint8)   # (empty documents only: the C ABI still wants a pointer)
+        appended = C.c_uint64(0)
+        self._check(self._lib.cdb_append(self._h, _ptr(ids) if len(ids) else None, _ptr(blob), _ptr(doc_start), len(ids), C.byref(appended)))
+        return int(appended.value)
+
+    def verify_keys(self):
+        """GPU-side check of the kept search keys against the text (cdb_debug_verify_keys); checked = 0: no keys are kept."""
+        out = (C.c_uint64 * 2)()
+        self._check(self._lib.cdb_debug_verify_keys(self._h, out))
+        return {"mismatches": int(out[0]), "checked": int(out[1])}
 
     def set_option(self, name, value):
         self._check(self._lib.cdb_set_option(self._h, name.encode(), int(value)))

@@ -1,0 +1,570 @@
+// append.hip — documents join a built index on the device (cdb_append, include/coffeedb_gpu.h; capi.hip holds the entry point,
+// the upload and the commit).  Suffixes never cross documents, so the old suffixes keep their mutual order and the new ones get
+// theirs from a build over the new documents alone; equal suffixes ascend by document and every new document is numbered behind
+// every old one, so a new suffix that equals an old one goes behind it.  The array over "old documents, then new documents" is
+// therefore the stable two-way merge of the old array and the new documents' array, ties old first — a merge instead of a sort.
+//
+//   1. tables    old ids / doc_start copied on the device, the new ones (re-based by the old size) uploaded behind them; the old
+//                column's longest document by a reduce; the set of byte values the new text holds
+//   2. new array the m new suffixes sorted by the existing build (a throw-away inner Index on this stream), decoded into entries
+//                of the NEW layout
+//   3. rank      pos_j = #{old suffixes <= new suffix j}: a sparse sample searches the whole old array, the rest between their
+//                bracketing samples; a probe is decided by the kept search key where the handle has one and resumes its byte
+//                comparison at the prefix both bounds already share (Manber-Myers)
+//   4. merge     output slot pos_j + j belongs to new suffix j: one flag per output slot, a count per tile, a scan, and a tile
+//                kernel that ranks with ballots (no atomics: the order is exact) and re-encodes both kinds of entry
+// Everything is written into fresh blocks of an AppendPlan while the old index stands.  64-bit indices throughout.
+#include <memory>
+#include <type_traits>
+
+#include "index_impl.h"
+#include "scan.h"
+
+namespace cdb {
+namespace {
+
+constexpr int AP_ROUNDS = 16;             // output slots per thread and tile
+constexpr int AP_TILE = 256 * AP_ROUNDS;  // output slots per tile (one workgroup)
+constexpr uint64_t AP_SAMPLE = 64;        // every AP_SAMPLE-th new suffix (and the last) searches the whole old array
+
+unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 256), 8192)); }
+
+// ---- 1. tables and text -----------------------------------------------------------------------------------------------------
+// the longest document (as rm_longest_kernel, without a drop flag)
+__global__ __launch_bounds__(256) void ap_longest_kernel(const uint64_t* __restrict__ doc_start, uint64_t ndocs, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long s_max[4];
+    uint64_t mx = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t d = (uint64_t)blockIdx.x * 256 + threadIdx.x; d < ndocs; d += stride) {
+        const uint64_t len = doc_start[d + 1] - doc_start[d];
+        mx = len > mx ? len : mx;
+    }
+    for (int off = 32; off; off >>= 1) {
+        const uint64_t o = __shfl_xor(mx, off);
+        mx = o > mx ? o : mx;
+    }
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) mx = s_max[w] > mx ? s_max[w] : mx;
+        if (mx) atomicMax(out, (unsigned long long)mx);
+    }
+}
+
+// out[b >> 5] bit (b & 31) = byte value b occurs in text[0 .. m)
+__global__ __launch_bounds__(256) void ap_bytes_kernel(const uint8_t* __restrict__ text, uint64_t m, uint32_t* __restrict__ out) {
+    __shared__ uint32_t s_set[8];
+    if (threadIdx.x < 8) s_set[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t mine[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += stride) {
+        const uint32_t b = text[i], w = b >> 5, bit = 1u << (b & 31u);
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) mine[k] |= w == k ? bit : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (mine[k]) atomicOr(&s_set[k], mine[k]);
+    __syncthreads();
+    if (threadIdx.x < 8 && s_set[threadIdx.x]) atomicOr(out + threadIdx.x, s_set[threadIdx.x]);
+}
+
+// dst[d] = src[d] - base (the new documents' starts on the origin of the new text, for the inner build)
+__global__ __launch_bounds__(256) void ap_rebase_kernel(const uint64_t* __restrict__ src, uint64_t cnt, uint64_t base, uint64_t* __restrict__ dst) {
+    const uint64_t d = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d < cnt) dst[d] = src[d] - base;
+}
+
+// ---- 2. the new documents' array in the new layout --------------------------------------------------------------------------
+template <typename Tag>
+__global__ __launch_bounds__(256) void ap_decode_kernel(typename SaOf<Tag>::ptr sa, uint64_t m, int in_bits, uint64_t in_mask, int new_bits,
+                                                        uint64_t doc_base, uint64_t* __restrict__ out) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const uint64_t e = (uint64_t)sa[j];
+    out[j] = ((e >> in_bits) << new_bits) | ((e & in_mask) + doc_base);
+}
+
+// ---- search keys ------------------------------------------------------------------------------------------------------------
+// the key the build keeps for a suffix (sa_build.hip: sa_keygen_kernel): its first nsym symbol codes as a number in base kbase,
+// code 0 behind the end of the document.  Reads rem bytes at most.
+__device__ __forceinline__ uint64_t suffix_key(const uint8_t* __restrict__ p, uint64_t rem, const uint16_t* map, int nsym, uint32_t kbase) {
+    uint64_t key = 0;
+    for (int k = 0; k < nsym; ++k) key = key * kbase + ((uint64_t)k < rem ? (uint64_t)map[p[k]] : 0ull);
+    return key;
+}
+struct KeysIn {  // the kept keys of a handle in whichever form it holds them (index_impl.h: d_keys / d_keys32 + d_keylow)
+    const uint64_t* k64;
+    const uint32_t* k32;
+    const uint8_t* low;
+    int low_bits, low_bytes;
+    __device__ __forceinline__ uint64_t at(uint64_t i) const {
+        if (k64) return k64[i];
+        const uint64_t h = k32[i];
+        if (!low_bits) return h;
+        return (h << low_bits) | (low_bytes == 2 ? (uint64_t)reinterpret_cast<const uint16_t*>(low)[i] : (uint64_t)low[i]);
+    }
+};
+// ... with the form known at compile time (ap_rank_kernel: 1 = u64 keys, 2 = u32 keys, 3 / 4 = u32 keys + one / two low bytes)
+template <int KF>
+__device__ __forceinline__ uint64_t key_at(const KeysIn& k, uint64_t i) {
+    if constexpr (KF == 1) return k.k64[i];
+    else if constexpr (KF == 2) return k.k32[i];
+    else if constexpr (KF == 3) return ((uint64_t)k.k32[i] << k.low_bits) | (uint64_t)k.low[i];
+    else return ((uint64_t)k.k32[i] << k.low_bits) | (uint64_t)reinterpret_cast<const uint16_t*>(k.low)[i];
+}
+struct KeysOut {
+    uint64_t* o64;
+    uint32_t* o32;
+    uint8_t* olow;
+    int low_bits, low_bytes;
+    __device__ __forceinline__ void put(uint64_t i, uint64_t key) const {
+        if (o64) o64[i] = key;
+        if (o32) o32[i] = (uint32_t)(key >> low_bits);
+        if (olow) {
+            const uint64_t l = key & ((1ull << low_bits) - 1ull);
+            if (low_bytes == 2) reinterpret_cast<uint16_t*>(olow)[i] = (uint16_t)l;
+            else olow[i] = (uint8_t)l;
+        }
+    }
+};
+
+// ---- 3. rank ----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t load_be8(const uint8_t* p) {
+    uint64_t v;
+    __builtin_memcpy(&v, p, 8);
+    return __builtin_bswap64(v);
+}
+// s <= t ?  (cmp_common's rule: unsigned bytes, shorter first, equal counts as "<=").  The first k bytes of both are known to be
+// equal; lcp = the length of their common prefix.  Neither suffix is read past its end.
+__device__ __forceinline__ bool suffix_le(const uint8_t* __restrict__ s, uint64_t sl, const uint8_t* __restrict__ t, uint64_t tl, uint64_t k,
+                                          uint64_t& lcp) {
+    const uint64_t len = sl < tl ? sl : tl;
+    uint64_t i = k < len ? k : len;
+    for (; i + 8 <= len; i += 8) {
+        const uint64_t a = load_be8(s + i), b = load_be8(t + i);
+        if (a != b) {
+            lcp = i + (uint64_t)(__clzll((long long)(a ^ b)) >> 3);
+            return a < b;
+        }
+    }
+    for (; i < len; ++i) {
+        const uint8_t a = s[i], b = t[i];
+        if (a != b) {
+            lcp = i;
+            return a < b;
+        }
+    }
+    lcp = len;
+    return sl <= tl;
+}
+
+// phase 0: the samples (j = 0, AP_SAMPLE, 2 AP_SAMPLE, ... and m - 1) search [0, n]; phase 1: every other j searches
+// [pos of the sample in front of it, pos of the sample behind it] — pos is non-decreasing in j.  pos[j] = first slot whose old
+// suffix is greater than new suffix j.  Invariant of the bisection: every slot in front of lo holds a suffix <= t and shares at
+// least ll bytes with it, every slot from hi on a suffix > t sharing at least rl bytes; a slot between them shares at least
+// min(ll, rl) bytes with t, which is where its comparison resumes.  A probe the keys decide leaves ll / rl as they are: the
+// bound moves towards t, so what it shared before it still shares.
+// KF = the form of the kept keys (0: none, the text decides every probe).  One new suffix per thread, no loop around the
+// bisection: wave-uniform switches are template parameters or used in front of it only.
+template <typename Tag, int KF>
+__global__ __launch_bounds__(256) void ap_rank_kernel(typename SaOf<Tag>::ptr sa, uint64_t n, const uint8_t* __restrict__ otext,
+                                                      const uint64_t* __restrict__ ostart, int obits, uint64_t omask,
+                                                      const uint64_t* __restrict__ nent, uint64_t m, const uint8_t* __restrict__ ctext,
+                                                      const uint64_t* __restrict__ cstart, int nbits, uint64_t nmask, KeysIn keys,
+                                                      const uint16_t* __restrict__ symmap, int nsym, uint32_t kbase, int phase,
+                                                      uint64_t* __restrict__ pos, uint64_t* __restrict__ newkey) {
+    __shared__ uint16_t s_map[256];
+    if constexpr (KF != 0) s_map[threadIdx.x] = symmap[threadIdx.x];
+    __syncthreads();
+    const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint64_t j = q, lo = 0, hi = n;
+    bool active;
+    if (phase == 0) {
+        const uint64_t nsamples = (m - 1) / AP_SAMPLE + 1 + ((m - 1) % AP_SAMPLE ? 1 : 0);
+        active = q < nsamples;
+        j = q * AP_SAMPLE < m ? q * AP_SAMPLE : m - 1;
+    } else {
+        active = j < m && j % AP_SAMPLE != 0 && j != m - 1;
+        if (active) {
+            const uint64_t a = j - j % AP_SAMPLE, b = a + AP_SAMPLE < m ? a + AP_SAMPLE : m - 1;
+            lo = pos[a];
+            hi = pos[b];
+        }
+    }
+    if (!active) return;
+    const uint64_t e = nent[j];
+    const uint64_t td = e & nmask, tb = cstart[td] + (e >> nbits), tl = cstart[td + 1] - tb;
+    const uint8_t* t = ctext + tb;
+    uint64_t tkey = 0;
+    if constexpr (KF != 0) {
+        tkey = suffix_key(t, tl, s_map, nsym, kbase);
+        newkey[j] = tkey;
+    }
+    uint64_t ll = 0, rl = 0;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        bool le = false, decided = false;
+        if constexpr (KF != 0) {
+            const uint64_t sk = key_at<KF>(keys, mid);
+            le = sk < tkey;
+            decided = sk != tkey;
+        }
+        if (!decided) {
+            const uint64_t se = (uint64_t)sa[mid];
+            const uint64_t sd = se & omask, sb = ostart[sd] + (se >> obits), sl = ostart[sd + 1] - sb;
+            uint64_t lcp = 0;
+            le = suffix_le(otext + sb, sl, t, tl, ll < rl ? ll : rl, lcp);
+            if (le) ll = lcp;
+            else rl = lcp;
+        }
+        if (le) lo = mid + 1;
+        else hi = mid;
+    }
+    pos[j] = lo;
+}
+
+// ---- 4. merge ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ap_flag_kernel(const uint64_t* __restrict__ pos, uint64_t m, uint8_t* __restrict__ flag) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < m) flag[pos[j] + j] = 1;
+}
+// pass A: new entries per tile of output slots
+__global__ __launch_bounds__(256) void ap_count_kernel(const uint8_t* __restrict__ flag, uint64_t N, uint64_t* __restrict__ tile_count) {
+    __shared__ uint32_t s_w[4];
+    const uint64_t base = (uint64_t)blockIdx.x * AP_TILE;
+    uint32_t c = 0;
+#pragma unroll 4
+    for (int k = 0; k < AP_ROUNDS; ++k) {
+        const uint64_t o = base + (uint64_t)k * 256 + threadIdx.x;
+        if (o < N) c += flag[o] ? 1u : 0u;
+    }
+    for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+struct TileBaseOut {
+    uint64_t* base;
+    __device__ __forceinline__ void operator()(uint64_t t, uint64_t ex, uint64_t) const { base[t] = ex; }
+};
+// pass B: output slot o of the tile's round k is new entry number r or old entry number o - r, where r = new entries in front of
+// o = tile base + new in earlier rounds + new in earlier waves of this round + new in earlier lanes of its wave (ballot)
+template <typename SrcTag, typename Dst>
+__global__ __launch_bounds__(256) void ap_merge_kernel(typename SaOf<SrcTag>::ptr sa, uint64_t N, int old_bits, uint64_t old_mask, int new_bits,
+                                                       const uint8_t* __restrict__ flag, const uint64_t* __restrict__ nent,
+                                                       const uint64_t* __restrict__ newkey, const uint64_t* __restrict__ tile_base, Dst out,
+                                                       KeysIn kin, KeysOut kout, bool with_keys) {
+    __shared__ uint32_t s_w[2][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t base = (uint64_t)blockIdx.x * AP_TILE;
+    uint64_t run = tile_base[blockIdx.x];
+    for (int k = 0; k < AP_ROUNDS; ++k) {
+        const uint64_t o = base + (uint64_t)k * 256 + threadIdx.x;
+        const bool valid = o < N;
+        const bool isnew = valid && flag[o] != 0;
+        const uint64_t bal = __ballot(isnew);
+        if (lane == 0) s_w[k & 1][wave] = (uint32_t)__popcll(bal);
+        __syncthreads();  // (the other half of s_w is still being read by the slowest wave of round k - 1: two halves, one barrier)
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t c = s_w[k & 1][w];
+            before += w < wave ? c : 0u;
+            all += c;
+        }
+        if (valid) {
+            const uint64_t r = run + before + (uint64_t)__popcll(bal & ((1ull << lane) - 1));
+            if (isnew) {
+                out.store(o, (typename Dst::val)nent[r]);
+                if (with_keys) kout.put(o, newkey[r]);
+            } else {
+                const uint64_t i = o - r;
+                const uint64_t e = (uint64_t)sa[i];
+                out.store(o, (typename Dst::val)(((e >> old_bits) << new_bits) | (e & old_mask)));
+                if (with_keys) kout.put(o, kin.at(i));
+            }
+        }
+        run += all;
+    }
+}
+
+// ---- cdb_debug_verify_keys ----------------------------------------------------------------------------------------------------
+template <typename Tag>
+__global__ __launch_bounds__(256) void ap_verify_keys_kernel(typename SaOf<Tag>::ptr sa, uint64_t n, const uint8_t* __restrict__ text,
+                                                             const uint64_t* __restrict__ doc_start, int bits, uint64_t mask, KeysIn keys,
+                                                             const uint16_t* __restrict__ symmap, int nsym, uint32_t kbase,
+                                                             unsigned long long* __restrict__ out) {
+    __shared__ uint16_t s_map[256];
+    s_map[threadIdx.x] = symmap[threadIdx.x];
+    __syncthreads();
+    uint64_t bad = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const uint64_t e = (uint64_t)sa[i];
+        const uint64_t d = e & mask, b = doc_start[d] + (e >> bits), sl = doc_start[d + 1] - b;
+        bad += suffix_key(text + b, sl, s_map, nsym, kbase) != keys.at(i) ? 1 : 0;
+    }
+    for (int off = 32; off; off >>= 1) bad += __shfl_xor(bad, off);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, (unsigned long long)bad);
+}
+
+bool keys_recomputable(const Index& ix) {  // the handle holds keys, their code table, and every part of a split key
+    return ix.key_nsym > 0 && (ix.d_keys.p || ix.d_keys32.p) && ix.d_symmap_q.p && ix.key_low_bytes >= 0 && ix.key_low_bytes <= 2 &&
+           (ix.d_keys.p || ix.key_low_bits == 0 || (ix.d_keylow.p && ix.key_low_bytes >= 1));
+}
+KeysIn keys_of(const Index& ix) {
+    return KeysIn{ix.d_keys.p ? ix.d_keys.as<uint64_t>() : nullptr, ix.d_keys32.p ? ix.d_keys32.as<uint32_t>() : nullptr,
+                  ix.d_keylow.p ? ix.d_keylow.as<uint8_t>() : nullptr, ix.d_keys.p ? 0 : ix.key_low_bits, ix.key_low_bytes};
+}
+
+}  // namespace
+
+void append_old_longest(Index& ix, AppendPlan& p) {
+    hipStream_t s = ix.stream;
+    DevBuf d_out;
+    d_out.alloc(8);
+    CDB_HIP(hipMemsetAsync(d_out.p, 0, 8, s));
+    int t = ix.prof.begin(s);
+    hipLaunchKernelGGL(ap_longest_kernel, dim3(grid_for(ix.ndocs)), dim3(256), 0, s, (const uint64_t*)ix.d_doc_start.as<uint64_t>(), ix.ndocs,
+                       d_out.as<unsigned long long>());
+    ix.prof.end(t, "ap_longest", ix.ndocs * 8, s);
+    CDB_HIP(hipGetLastError());
+    uint64_t out = 0;
+    CDB_HIP(hipMemcpyAsync(&out, d_out.p, 8, hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipStreamSynchronize(s));
+    p.old_longest = out;
+}
+
+void append_tables(Index& ix, AppendPlan& p, const int64_t* ids, const uint64_t* new_start) {
+    hipStream_t s = ix.stream;
+    const uint64_t D = ix.ndocs;
+    p.d_start.alloc((D + p.ndocs + 1) * 8);
+    p.d_ids.alloc((D + p.ndocs) * 8);
+    CDB_HIP(hipMemcpyAsync(p.d_start.p, ix.d_doc_start.p, D * 8, hipMemcpyDeviceToDevice, s));
+    CDB_HIP(hipMemcpyAsync(p.d_start.as<uint64_t>() + D, new_start, (p.ndocs + 1) * 8, hipMemcpyHostToDevice, s));
+    CDB_HIP(hipMemcpyAsync(p.d_ids.p, ix.d_ids.p, D * 8, hipMemcpyDeviceToDevice, s));
+    CDB_HIP(hipMemcpyAsync(p.d_ids.as<int64_t>() + D, ids, p.ndocs * 8, hipMemcpyHostToDevice, s));
+}
+
+void append_text_old(Index& ix, AppendPlan& p) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size;
+    p.text.alloc(n + p.size + TEXT_PAD);
+    CDB_HIP(hipMemsetAsync(p.text.as<uint8_t>() + n + p.size, 0, TEXT_PAD, s));
+    if (n) CDB_HIP(hipMemcpyAsync(p.text.p, ix.d_text, n, hipMemcpyDeviceToDevice, s));
+}
+
+void append_scan_bytes(Index& ix, AppendPlan& p) {
+    hipStream_t s = ix.stream;
+    uint32_t set[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (p.size) {
+        DevBuf d_set;
+        d_set.alloc(32);
+        CDB_HIP(hipMemsetAsync(d_set.p, 0, 32, s));
+        int t = ix.prof.begin(s);
+        hipLaunchKernelGGL(ap_bytes_kernel, dim3(grid_for(ceil_div(p.size, 16))), dim3(256), 0, s, (const uint8_t*)p.text.as<uint8_t>() + ix.size, p.size,
+                           d_set.as<uint32_t>());
+        ix.prof.end(t, "ap_bytes", p.size, s);
+        CDB_HIP(hipGetLastError());
+        CDB_HIP(hipMemcpyAsync(set, d_set.p, 32, hipMemcpyDeviceToHost, s));
+    }
+    CDB_HIP(hipStreamSynchronize(s));
+    p.high_bytes = (set[4] | set[5] | set[6] | set[7]) != 0;
+    p.unmapped_bytes = false;
+    for (int b = 0; b < 256; ++b)
+        if (((set[b >> 5] >> (b & 31)) & 1u) && ix.h_symmap_q[b] == 0) p.unmapped_bytes = true;
+}
+
+void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int new_width, bool new_packed) {
+    hipStream_t s = ix.stream;
+    const uint64_t n = ix.size, m = p.size, N = n + m, D = ix.ndocs;
+    if (new_packed) {
+        p.sa.alloc(std::max<uint64_t>(N, 4) * 4);
+        p.sa_hi.alloc(std::max<uint64_t>(N, 16));
+    } else {
+        p.sa.alloc(std::max<uint64_t>(N * (uint64_t)new_width, 16));
+    }
+    p.key_nsym = 0;
+    p.keys_kept = false;
+    if (!N) return;
+    // ---- the new documents' own array, decoded into entries of the new layout
+    DevBuf nent, pos, newkey;
+    nent.alloc(std::max<uint64_t>(m, 2) * 8);
+    const bool with_keys = keys_recomputable(ix) && !p.unmapped_bytes;
+    if (m) {
+        auto inner = std::make_unique<Index>();
+        Index& in = *inner;
+        in.device = ix.device;
+        in.stream = s;
+        in.aux_stream = ix.aux_stream;  // (lent: the build's second stream and its events belong to the handle)
+        in.aux_ev[0] = ix.aux_ev[0];
+        in.aux_ev[1] = ix.aux_ev[1];
+        struct GiveBack {
+            Index& ix;
+            Index& in;
+            ~GiveBack() {
+                ix.aux_stream = in.aux_stream;
+                ix.aux_ev[0] = in.aux_ev[0];
+                ix.aux_ev[1] = in.aux_ev[1];
+            }
+        } give_back{ix, in};
+        in.reference_compat = ix.reference_compat;
+        in.self_check = std::min(ix.self_check, 1);
+        in.premap_generation = false;
+        in.keep_keys = false;
+        in.pack_sa = ix.pack_sa;
+        in.force_big_path = ix.force_big_path;
+        in.debug_fail_build = ix.debug_fail_build;
+        in.rws.plain_order = ix.rws.plain_order;
+        in.host_tables_valid = false;
+        in.host_text_valid = false;
+        in.size = m;
+        in.ndocs = p.ndocs;
+        in.bits = p.in_bits;
+        in.mask = p.in_mask;
+        in.width = p.in_width;
+        in.off_bits = p.in_off_bits;
+        in.d_text_owned.alloc(m + TEXT_PAD);  // (a block of its own: the build wants its text 16-byte aligned)
+        CDB_HIP(hipMemcpyAsync(in.d_text_owned.p, p.text.as<uint8_t>() + n, m, hipMemcpyDeviceToDevice, s));
+        CDB_HIP(hipMemsetAsync(in.d_text_owned.as<uint8_t>() + m, 0, TEXT_PAD, s));
+        in.d_text = in.d_text_owned.as<uint8_t>();
+        in.text_padded = true;
+        in.d_doc_start.alloc((p.ndocs + 1) * 8);
+        in.d_ids.alloc(16);
+        hipLaunchKernelGGL(ap_rebase_kernel, dim3((unsigned)ceil_div(p.ndocs + 1, 256)), dim3(256), 0, s,
+                           (const uint64_t*)p.d_start.as<uint64_t>() + D, p.ndocs + 1, n, in.d_doc_start.as<uint64_t>());
+        CDB_HIP(hipGetLastError());
+        build_suffix_array(in);  // (synchronises; a failure here is a failure before the commit)
+        if (!in.sa_sorted) throw Error("append: the new documents' array is not sorted (internal)");
+        const unsigned blocks = (unsigned)ceil_div(m, 256);
+        int t = ix.prof.begin(s);
+        sa_dispatch(in, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL((ap_decode_kernel<T>), dim3(blocks), dim3(256), 0, s, in.sa_view<T>(), m, (int)in.bits, in.mask, new_bits, D,
+                               nent.as<uint64_t>());
+        });
+        ix.prof.end(t, "ap_decode", m * (8 + (in.sa_packed ? 5 : (uint64_t)in.width)), s);
+        CDB_HIP(hipGetLastError());
+        CDB_HIP(hipStreamSynchronize(s));  // (the inner index goes: its blocks return to the cache idle)
+    }
+    // ---- rank
+    pos.alloc(std::max<uint64_t>(m, 2) * 8);
+    if (with_keys) newkey.alloc(std::max<uint64_t>(m, 2) * 8);
+    const KeysIn kin = with_keys ? keys_of(ix) : KeysIn{nullptr, nullptr, nullptr, 0, 0};
+    const int nsym = with_keys ? ix.key_nsym : 0;
+    const uint16_t* symmap = with_keys ? (const uint16_t*)ix.d_symmap_q.as<uint16_t>() : (const uint16_t*)nullptr;
+    if (m) {
+        const uint64_t nsamples = (m - 1) / AP_SAMPLE + 2;
+        if (ceil_div(m, 256) >= (1ull << 31)) throw Error("append: too many new suffixes for one launch (internal)");
+        const int kf = !with_keys ? 0 : kin.k64 ? 1 : !kin.low_bits ? 2 : kin.low_bytes == 2 ? 4 : 3;
+        for (int phase = 0; phase < 2; ++phase) {
+            const unsigned blocks = (unsigned)ceil_div(phase == 0 ? nsamples : m, 256);
+            int t = ix.prof.begin(s);
+            sa_dispatch(ix, [&](auto tag) {
+                using T = decltype(tag);
+                auto launch = [&](auto kform) {
+                    constexpr int KF = decltype(kform)::value;
+                    hipLaunchKernelGGL((ap_rank_kernel<T, KF>), dim3(blocks), dim3(256), 0, s, ix.sa_view<T>(), n, ix.d_text,
+                                       (const uint64_t*)ix.d_doc_start.as<uint64_t>(), (int)ix.bits, ix.mask, (const uint64_t*)nent.as<uint64_t>(), m,
+                                       (const uint8_t*)p.text.as<uint8_t>(), (const uint64_t*)p.d_start.as<uint64_t>(), new_bits, new_mask, kin,
+                                       symmap, nsym, ix.key_base, phase, pos.as<uint64_t>(), newkey.as<uint64_t>());
+                };
+                if (kf == 0) launch(std::integral_constant<int, 0>{});
+                else if (kf == 1) launch(std::integral_constant<int, 1>{});
+                else if (kf == 2) launch(std::integral_constant<int, 2>{});
+                else if (kf == 3) launch(std::integral_constant<int, 3>{});
+                else launch(std::integral_constant<int, 4>{});
+            });
+            ix.prof.end(t, phase == 0 ? "ap_rank_samples" : "ap_rank", (phase == 0 ? nsamples : m) * (uint64_t)bit_width64(n + 1) * 64, s);
+            CDB_HIP(hipGetLastError());
+        }
+    }
+    // ---- merge
+    DevBuf flag, tile_count, tile_base;
+    flag.alloc(N);
+    CDB_HIP(hipMemsetAsync(flag.p, 0, N, s));
+    if (m) {
+        int t = ix.prof.begin(s);
+        hipLaunchKernelGGL(ap_flag_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, s, (const uint64_t*)pos.as<uint64_t>(), m, flag.as<uint8_t>());
+        ix.prof.end(t, "ap_flag", m * 9, s);
+        CDB_HIP(hipGetLastError());
+    }
+    const uint64_t ntiles = ceil_div(N, AP_TILE);
+    if (ntiles >= (1ull << 31)) throw Error("append: the array has too many tiles for one launch (internal)");
+    tile_count.alloc(ntiles * 8);
+    tile_base.alloc(ntiles * 8);
+    int t = ix.prof.begin(s);
+    hipLaunchKernelGGL(ap_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, (const uint8_t*)flag.as<uint8_t>(), N, tile_count.as<uint64_t>());
+    ix.prof.end(t, "ap_count", N + ntiles * 8, s);
+    CDB_HIP(hipGetLastError());
+    PartialsIn<uint64_t> tin{tile_count.as<uint64_t>()};
+    const uint64_t joined = scan_totals<uint64_t>(s, ix.scan_partials, tin, ntiles, OpAdd{}, (uint64_t)0);
+    if (joined != m) throw Error("append: new entries and new bytes differ (internal)");
+    scan_apply<uint64_t>(s, ix.scan_partials, tin, ntiles, OpAdd{}, (uint64_t)0, TileBaseOut{tile_base.as<uint64_t>()});
+    CDB_HIP(hipGetLastError());
+    KeysOut kout{nullptr, nullptr, nullptr, 0, 0};
+    if (with_keys) {
+        p.key_nsym = ix.key_nsym;
+        p.key_base = ix.key_base;
+        p.key_low_bits = ix.key_low_bits;
+        p.key_low_bytes = ix.key_low_bytes;
+        p.keys_kept = true;
+        if (ix.d_keys.p) {
+            p.keys.alloc(N * 8);
+            kout.o64 = p.keys.as<uint64_t>();
+        }
+        if (ix.d_keys32.p) {
+            p.keys32.alloc(N * 4);
+            kout.o32 = p.keys32.as<uint32_t>();
+            kout.low_bits = ix.key_low_bits;
+        }
+        if (ix.d_keylow.p) {
+            kout.low_bytes = std::max(ix.key_low_bytes, 1);
+            p.keylow.alloc(N * (uint64_t)kout.low_bytes);
+            kout.olow = p.keylow.as<uint8_t>();
+            kout.low_bits = ix.key_low_bits;
+        }
+    }
+    const uint64_t key_bytes = (kout.o64 ? 8 : 0) + (kout.o32 ? 4 : 0) + (kout.olow ? kout.low_bytes : 0);
+    const int old_bytes = ix.sa_packed ? 5 : ix.width;
+    t = ix.prof.begin(s);
+    sa_dispatch(ix, [&](auto src_tag) {
+        using S = decltype(src_tag);
+        auto launch = [&](auto dst) {
+            using Dd = decltype(dst);
+            hipLaunchKernelGGL((ap_merge_kernel<S, Dd>), dim3((unsigned)ntiles), dim3(256), 0, s, ix.sa_view<S>(), N, (int)ix.bits, ix.mask, new_bits,
+                               (const uint8_t*)flag.as<uint8_t>(), (const uint64_t*)nent.as<uint64_t>(), (const uint64_t*)newkey.as<uint64_t>(),
+                               (const uint64_t*)tile_base.as<uint64_t>(), dst, kin, kout, with_keys);
+        };
+        if (new_packed) launch(Sa40RW{p.sa.as<uint32_t>(), p.sa_hi.as<uint8_t>()});
+        else if (new_width == 8) launch(SaRW<uint64_t>{p.sa.as<uint64_t>()});
+        else launch(SaRW<uint32_t>{p.sa.as<uint32_t>()});
+    });
+    ix.prof.end(t, "ap_merge", n * (uint64_t)old_bytes + m * 8 + N * (1 + (new_packed ? 5 : (uint64_t)new_width) + 2 * key_bytes) + ntiles * 8, s);
+    CDB_HIP(hipGetLastError());
+    CDB_HIP(hipStreamSynchronize(s));  // (the scratch blocks above go back to the cache idle)
+}
+
+void verify_kept_keys(Index& ix, uint64_t out[2]) {
+    out[0] = out[1] = 0;
+    if (!ix.size || !keys_recomputable(ix)) return;
+    hipStream_t s = ix.stream;
+    DevBuf d_out;
+    d_out.alloc(8);
+    CDB_HIP(hipMemsetAsync(d_out.p, 0, 8, s));
+    const KeysIn kin = keys_of(ix);
+    sa_dispatch(ix, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((ap_verify_keys_kernel<T>), dim3(grid_for(ix.size)), dim3(256), 0, s, ix.sa_view<T>(), ix.size, ix.d_text,
+                           (const uint64_t*)ix.d_doc_start.as<uint64_t>(), (int)ix.bits, ix.mask, kin, (const uint16_t*)ix.d_symmap_q.as<uint16_t>(),
+                           ix.key_nsym, ix.key_base, d_out.as<unsigned long long>());
+    });
+    CDB_HIP(hipGetLastError());
+    CDB_HIP(hipMemcpyAsync(out, d_out.p, 8, hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipStreamSynchronize(s));
+    out[1] = ix.size;
+}
+
+}  // namespace cdb

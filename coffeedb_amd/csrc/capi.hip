@@ -972,6 +972,56 @@ int cdb_build_device(cdb_index* h, const void* d_text, const uint64_t* doc_start
  * non-owning string_views into database.cpp's map, database.cpp:262-264) — without the staging copy of cdb_add_bulk
  * (a memcpy into fresh pages: 180 ms per GiB, 3x the build it feeds).  The column goes to the device through the
  * chunked pinned upload; afterwards the handle owns device copies only (cdb_add* fetch them back when needed). */
+namespace {
+// the body of cdb_build_view, with ix.mu held and the device set (cdb_append on a handle that holds nothing is this build)
+void build_view_locked(Index& ix, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs) {
+    const uint64_t first = ndocs ? doc_start[0] : 0;
+    // The text starts travelling FIRST, on a helper thread, into a block nothing refers to yet; the document tables are
+    // copied and validated meanwhile (1-2 ms per million documents on one core — it used to sit in front of the upload).
+    // A column that fails validation is simply dropped after the copy.
+    const uint64_t n_claimed = ndocs ? doc_start[ndocs] - first : 0;
+    if (ndocs && (doc_start[ndocs] < first || n_claimed >= (1ull << 48))) throw Error("doc_start must be non-decreasing");
+    // O(1) checks BEFORE anything is allocated or uploaded: the longest document has at least n / ndocs bytes, so a
+    // column the width rule refuses for that length gets the reference's capacity error (index.cpp:195-200), not a hipMalloc
+    // error after the block cache was trimmed; and a text that does not fit the device is refused without trimming it
+    if (ndocs) (void)layout_from(ndocs, n_claimed, (n_claimed + ndocs - 1) / ndocs);
+    {
+        size_t fre = 0, tot = 0;
+        if (hipMemGetInfo(&fre, &tot) == hipSuccess) {
+            if ((double)n_claimed + (double)TEXT_PAD > (double)fre + (double)cdb_cached_memory_bytes())
+                throw Error("HIP error: the column does not fit the device memory that is free");
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    replace_column(ix, [&](NewColumn& col) {
+        alloc_padded_text(ix, col.text, n_claimed);
+        col.upload_t0 = wall_ms();
+        std::string uerr;
+        hipStream_t s2 = upload_stream(ix);
+        std::thread up([&] {
+            try {
+                CDB_HIP(hipSetDevice(ix.device));
+                if (n_claimed) upload_pageable(col.text.p, blob + first, n_claimed, ix.stream, ix.device, s2);
+            } catch (const std::exception& e) {
+                uerr = e.what();
+            }
+        });
+        struct Joiner {
+            std::thread& t;
+            ~Joiner() { if (t.joinable()) t.join(); }
+        } joiner{up};
+        rebase_tables(doc_start, ids, ndocs, first, col);
+        col.L = layout_of(col.doc_start, ndocs);  // (throws the reference's capacity errors: nothing changed yet)
+        up.join();
+        if (!uerr.empty()) throw Error(uerr);
+        // (tried: the 16 MB of document tables on a helper thread beside the text — the runtime's pageable staging then competes
+        //  with the chunk copies: 21.4 instead of 20.1 ms)
+        upload_tables(ix, col.doc_start, col.ids, ndocs, col.d_start, col.d_ids);
+    });
+}
+}  // namespace
+
 int cdb_build_view(cdb_index* h, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs) {
     reserve_join();
     if (!h || (ndocs && (!ids || !doc_start || (!blob && doc_start[ndocs] > doc_start[0])))) return CDB_E_INVALID;
@@ -979,50 +1029,7 @@ int cdb_build_view(cdb_index* h, const int64_t* ids, const char* blob, const uin
         Index& ix = h->ix;
         std::lock_guard<std::mutex> g(ix.mu);
         DeviceScope dscope(ix);
-        const uint64_t first = ndocs ? doc_start[0] : 0;
-        // The text starts travelling FIRST, on a helper thread, into a block nothing refers to yet; the document tables are
-        // copied and validated meanwhile (1-2 ms per million documents on one core — it used to sit in front of the upload).
-        // A column that fails validation is simply dropped after the copy.
-        const uint64_t n_claimed = ndocs ? doc_start[ndocs] - first : 0;
-        if (ndocs && (doc_start[ndocs] < first || n_claimed >= (1ull << 48))) throw Error("doc_start must be non-decreasing");
-        // O(1) checks BEFORE anything is allocated or uploaded: the longest document has at least n / ndocs bytes, so a
-        // column the width rule refuses for that length gets the reference's capacity error (index.cpp:195-200), not a hipMalloc
-        // error after the block cache was trimmed; and a text that does not fit the device is refused without trimming it
-        if (ndocs) (void)layout_from(ndocs, n_claimed, (n_claimed + ndocs - 1) / ndocs);
-        {
-            size_t fre = 0, tot = 0;
-            if (hipMemGetInfo(&fre, &tot) == hipSuccess) {
-                if ((double)n_claimed + (double)TEXT_PAD > (double)fre + (double)cdb_cached_memory_bytes())
-                    throw Error("HIP error: the column does not fit the device memory that is free");
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        replace_column(ix, [&](NewColumn& col) {
-            alloc_padded_text(ix, col.text, n_claimed);
-            col.upload_t0 = wall_ms();
-            std::string uerr;
-            hipStream_t s2 = upload_stream(ix);
-            std::thread up([&] {
-                try {
-                    CDB_HIP(hipSetDevice(ix.device));
-                    if (n_claimed) upload_pageable(col.text.p, blob + first, n_claimed, ix.stream, ix.device, s2);
-                } catch (const std::exception& e) {
-                    uerr = e.what();
-                }
-            });
-            struct Joiner {
-                std::thread& t;
-                ~Joiner() { if (t.joinable()) t.join(); }
-            } joiner{up};
-            rebase_tables(doc_start, ids, ndocs, first, col);
-            col.L = layout_of(col.doc_start, ndocs);  // (throws the reference's capacity errors: nothing changed yet)
-            up.join();
-            if (!uerr.empty()) throw Error(uerr);
-            // (tried: the 16 MB of document tables on a helper thread beside the text — the runtime's pageable staging then competes
-            //  with the chunk copies: 21.4 instead of 20.1 ms)
-            upload_tables(ix, col.doc_start, col.ids, ndocs, col.d_start, col.d_ids);
-        });
+        build_view_locked(ix, ids, blob, doc_start, ndocs);
     });
 }
 
@@ -1155,6 +1162,100 @@ int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* remove
         ix.rm.docs = p.removed;
         ix.rm.bytes = old_size - L.size;
         ix.rm.last_ms = wall_ms() - t0;
+    });
+}
+
+// Documents join a built index without a rebuild (append.hip).  The array over "old documents, then new documents" is the stable
+// merge of the old array and the new documents' own array, ties old first; an array in the reference's order (bytes >= 0x80 under
+// reference_compat) depends on bucket sizes that change with n, so there text and tables are extended on the device and the array
+// is built over them.  Either way only the new documents are uploaded.
+int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs, uint64_t* appended) {
+    if (!h || (ndocs && (!ids || !blob || !doc_start))) return CDB_E_INVALID;
+    if (appended) *appended = 0;
+    reserve_join();
+    return guarded(h, [&] {
+        Index& ix = h->ix;
+        std::lock_guard<std::mutex> g(ix.mu);
+        DeviceScope dscope(ix);
+        const double t0 = wall_ms();
+        const uint64_t built_docs = ix.width ? ix.ndocs : 0;
+        if (ix.host_text_valid && ix.ids.size() > built_docs) throw Error("append: documents were added since the last build");
+        if (!ndocs) return;
+        const uint64_t first = doc_start[0];
+        if (doc_start[ndocs] < first || doc_start[ndocs] - first >= (1ull << 48)) throw Error("doc_start must be non-decreasing");
+        const uint64_t m = doc_start[ndocs] - first;
+        auto count = [&](bool merged, int keys_kept) {
+            ix.ap.calls += 1;
+            (merged ? ix.ap.merges : ix.ap.rebuilds) += 1;
+            ix.ap.docs = ndocs;
+            ix.ap.bytes = m;
+            ix.ap.keys_kept = keys_kept;
+            ix.ap.last_ms = wall_ms() - t0;
+            if (appended) *appended = ndocs;
+        };
+        if (!built_docs) {  // never built, or built over nothing: a build of the given documents
+            build_view_locked(ix, ids, blob, doc_start, ndocs);
+            count(false, ix.key_nsym ? 1 : 0);
+            return;
+        }
+        const uint64_t n = ix.size, D = ix.ndocs;
+        AppendPlan p;
+        std::vector<uint64_t> new_start(ndocs + 1);  // the new documents behind the old text
+        new_start[0] = n;
+        for (uint64_t d = 0; d < ndocs; ++d) {
+            if (doc_start[d + 1] < doc_start[d]) throw Error("doc_start must be non-decreasing");
+            p.longest = std::max(p.longest, doc_start[d + 1] - doc_start[d]);
+            new_start[d + 1] = n + (doc_start[d + 1] - first);
+        }
+        p.ndocs = ndocs;
+        p.size = m;
+        try {
+            append_old_longest(ix, p);
+        } catch (...) {
+            (void)hipStreamSynchronize(ix.stream);
+            throw;
+        }
+        // the reference's capacity errors (index.cpp:195-200): nothing has been touched yet
+        const Layout L = layout_from(D + ndocs, n + m, std::max(p.old_longest, p.longest));
+        const Layout Li = layout_from(ndocs, m, p.longest);
+        p.in_bits = Li.bits;
+        p.in_mask = Li.mask;
+        p.in_width = Li.width;
+        p.in_off_bits = Li.off_bits;
+        bool merged = false;
+        replace_column(ix, [&](NewColumn& col) {
+            col.L = L;
+            col.host = NewColumn::HOST_NONE;  // (a staging copy that equals the built column goes: cdb_add* / cdb_save fetch the column back)
+            append_tables(ix, p, ids, new_start.data());
+            append_text_old(ix, p);
+            if (m) upload_pageable(p.text.as<uint8_t>() + n, blob + first, m, ix.stream, ix.device, upload_stream(ix));
+            append_scan_bytes(ix, p);
+            // the merge is exact where the fresh array would be globally sorted; the reference's order is rebuilt
+            const bool valid = n > 0 && ix.sa_sorted && (!ix.reference_compat || !p.high_bytes);
+            merged = valid && ix.debug_append_path != 2;
+            if (merged) {
+                const bool pack = ix.pack_sa && L.width == 8 && (int)L.bits + L.off_bits <= 40 && L.size > 0;
+                append_merge(ix, p, (int)L.bits, L.mask, L.width, pack);
+                col.sa = std::move(p.sa);
+                col.sa_hi = std::move(p.sa_hi);
+                col.keys = std::move(p.keys);
+                col.keys32 = std::move(p.keys32);
+                col.keylow = std::move(p.keylow);
+                col.key_nsym = p.key_nsym;
+                col.key_base = p.key_base;
+                col.key_low_bits = p.key_low_bits;
+                col.key_low_bytes = p.key_low_bytes;
+                col.reference_compat = ix.reference_compat;
+                col.sa_sorted = true;
+                col.from_file = false;
+            }
+            CDB_HIP(hipStreamSynchronize(ix.stream));
+            ix.prof.resolve();
+            col.text = std::move(p.text);
+            col.d_start = std::move(p.d_start);
+            col.d_ids = std::move(p.d_ids);
+        });
+        count(merged, merged ? (p.keys_kept ? 1 : 0) : (ix.key_nsym ? 1 : 0));
     });
 }
 
@@ -1708,6 +1809,7 @@ int cdb_set_option(cdb_index* h, const char* name, int64_t value) {
     else if (!std::strcmp(name, "fuse_keygen")) ix.fuse_keygen = value != 0;
     else if (!std::strcmp(name, "force_big_path")) ix.force_big_path = value != 0;
     else if (!std::strcmp(name, "debug_fail_build")) ix.debug_fail_build = value != 0;
+    else if (!std::strcmp(name, "debug_append_path")) ix.debug_append_path = value == 1 || value == 2 ? (int)value : 0;  // cdb_append: 0 automatic, 1 merge where valid, 2 rebuild
     else if (!std::strcmp(name, "debug_no_segcap")) ix.debug_no_segcap = value != 0;  // test hook: "a bucket does not fit the record memory"
     else if (!std::strcmp(name, "debug_starve_group")) ix.debug_starve_group = (int)value;  // 1 = reported after the sorts, 2 = error flag up before the initial sort
     else if (!std::strcmp(name, "self_check")) ix.self_check = value < 0 ? 0 : value > 3 ? 3 : (int)value;  // 0 off, 1 sample, 2 every pair inline, 3 sample + proof after publish
@@ -1764,6 +1866,9 @@ int cdb_get_stat(const cdb_index* h, const char* name, double* value) {
         {"cluster_prepare_ms", h->ix.clu.prepare_ms}, {"cluster_ms", h->ix.clu.last_ms}, {"cluster_resorted", h->ix.clu.resorted ? 1.0 : 0.0},
         {"removes", (double)h->ix.rm.calls}, {"remove_compactions", (double)h->ix.rm.compactions}, {"remove_rebuilds", (double)h->ix.rm.rebuilds},
         {"remove_docs", (double)h->ix.rm.docs}, {"remove_bytes", (double)h->ix.rm.bytes}, {"remove_ms", h->ix.rm.last_ms},
+        {"appends", (double)h->ix.ap.calls}, {"append_merges", (double)h->ix.ap.merges}, {"append_rebuilds", (double)h->ix.ap.rebuilds},
+        {"append_docs", (double)h->ix.ap.docs}, {"append_bytes", (double)h->ix.ap.bytes}, {"append_ms", h->ix.ap.last_ms},
+        {"append_keys_kept", (double)h->ix.ap.keys_kept},
         {"render_ms", h->ix.rnd.last_ms}, {"render_page_bytes", (double)h->ix.rnd.page_bytes}, {"render_spans", (double)h->ix.rnd.spans},
         {"query_ms", q.query_ms}, {"query_upload_ms", q.upload_ms}, {"query_device_ms", q.device_ms}, {"query_download_ms", q.download_ms}, {"query_hits", (double)q.nhits}, {"query_rows", (double)q.nrows},
         {"query_batches", (double)q.batches}, {"query_spec_batches", (double)q.spec_batches}, {"query_spec_spills", (double)q.spec_spills},
@@ -1846,6 +1951,17 @@ int cdb_debug_verify_reference(cdb_index* h, uint64_t out[4]) {
         DeviceScope dscope(ix);
         if (ix.width == 0) throw Error("index has not been built");
         verify_reference_order(ix, out);
+    });
+}
+
+int cdb_debug_verify_keys(cdb_index* h, uint64_t out[2]) {
+    if (!h || !out) return CDB_E_INVALID;
+    return guarded(h, [&] {
+        Index& ix = h->ix;
+        std::lock_guard<std::mutex> g(ix.mu);
+        DeviceScope dscope(ix);
+        if (ix.width == 0) throw Error("index has not been built");
+        verify_kept_keys(ix, out);
     });
 }
 

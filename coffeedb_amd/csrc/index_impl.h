@@ -355,6 +355,15 @@ struct Index {
         uint64_t docs = 0, bytes = 0;
         double last_ms = 0;
     } rm;
+    // ---- cdb_append (append.hip): calls that added something, by the path they took; the last call's documents, text bytes, wall
+    // time and whether the search keys came along
+    struct AppendStats {
+        uint64_t calls = 0, merges = 0, rebuilds = 0;
+        uint64_t docs = 0, bytes = 0;
+        double last_ms = 0;
+        int keys_kept = 0;
+    } ap;
+    int debug_append_path = 0;  // test hook: 0 = automatic, 1 = merge where it is valid, 2 = always rebuild
 
     double host_upload_ms = 0, host_free_ms = 0;  // cdb_build: staged column to the device / staging copy released
     Profiler prof;
@@ -402,6 +411,28 @@ struct RemovePlan {
 void remove_mark(Index& ix, const int64_t* ids, uint64_t nids, RemovePlan& p);  // flags, counts, and (something to drop) the new tables; synchronises
 void remove_text(Index& ix, RemovePlan& p);                                      // the kept documents gathered into p.text
 void remove_compact(Index& ix, RemovePlan& p, int new_bits, int new_width, bool new_packed);  // the array and its keys in the new layout
+
+// append.hip — the pieces of cdb_append (capi.hip uploads the new text between them and commits), all on ix.stream with ix.mu held.
+// Everything is made in fresh blocks of the plan while the old index stands.
+struct AppendPlan {
+    uint64_t ndocs = 0, size = 0, longest = 0;  // the new documents (filled by the caller) ...
+    uint64_t in_bits = 1, in_mask = 1;          // ... and the layout of an index over them alone (the inner build)
+    int in_width = 4, in_off_bits = 1;
+    uint64_t old_longest = 0;                        // the built column's longest document
+    bool high_bytes = false, unmapped_bytes = false;  // the new text holds bytes >= 0x80 / bytes the handle's symbol map codes as 0
+    DevBuf d_start, d_ids, text;                // old then new: the tables and the padded text
+    DevBuf sa, sa_hi, keys, keys32, keylow;     // the merged array and search keys
+    int key_nsym = 0, key_low_bits = 0, key_low_bytes = 0;
+    uint32_t key_base = 0;
+    bool keys_kept = false;
+};
+void append_old_longest(Index& ix, AppendPlan& p);  // synchronises
+void append_tables(Index& ix, AppendPlan& p, const int64_t* ids, const uint64_t* new_start);  // new_start[ndocs + 1]: based at the old size
+void append_text_old(Index& ix, AppendPlan& p);     // p.text allocated, the old bytes copied in front, the padding zeroed
+void append_scan_bytes(Index& ix, AppendPlan& p);   // the byte values of the new text (behind its upload); synchronises
+void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int new_width, bool new_packed);  // inner build, rank, merge; synchronises
+// out = {slots whose kept key differs from the key recomputed from the suffix, slots checked (0: no keys kept)}
+void verify_kept_keys(Index& ix, uint64_t out[2]);
 
 // verify.hip — out = {inversions, tie-order violations, wrapped sum of entries, invalid entries, expected sum}
 void verify_suffix_array(Index& ix, uint64_t out[5]);

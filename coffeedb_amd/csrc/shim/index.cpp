@@ -283,6 +283,20 @@ bool string_index::remove(const std::vector<int64_t>& gone_ids) {
     return true;
 }
 
+bool string_index::append() {
+    if (!handle || ids.size() == built) return false;
+    const size_t fresh = ids.size() - built;
+    std::string blob;  // (cdb_append takes one blob: the staging copy of the NEW documents only)
+    std::vector<uint64_t> doc_start(fresh + 1, 0);
+    for (size_t k = 0; k < fresh; ++k) doc_start[k + 1] = doc_start[k] + lens[built + k];
+    blob.reserve(doc_start[fresh] + 1);
+    for (size_t k = 0; k < fresh; ++k) blob.append(ptrs[built + k], lens[built + k]);
+    const int rc = cdb_append(handle, ids.data() + built, blob.data(), doc_start.data(), fresh, nullptr);
+    if (rc != CDB_OK) rethrow(handle, rc);
+    built = ids.size();
+    return true;
+}
+
 index::result_type string_index::query(const std::string& keyword) const {
     int64_t *ids = nullptr, *counts = nullptr;
     size_t rows = 0;

@@ -147,6 +147,11 @@ public:
     // later build() does not bring them back.  Ids the index does not hold are ignored.  false = not available — a sharded index
     // (COFFEEDB_GPUS), or documents were added since the last build(): nothing changed, the caller rebuilds as the reference does.
     bool remove(const std::vector<int64_t>& ids);
+    // NEW: "insert ... build" for this field (interface.cpp:157-180, :286-288) without the rebuild — the views add() collected since
+    // the last build() join the built index on the device (cdb_append: only they are gathered, uploaded and sorted).  The strings
+    // must stay valid until the call has returned, as for build().  false = nothing was pending, or not available (a sharded index,
+    // COFFEEDB_GPUS): nothing changed, the caller builds as the reference does.
+    bool append();
     // NEW (no counterpart in the reference): announce a string column of roughly `bytes` bytes BEFORE the data is loaded —
     // start_server() calls init() and then build() (server.cpp:43-44); called at the start of init() with the size of the raw
     // directory (and any document as a sample of the alphabet) it lets the GPU map the first build's working set on a helper

@@ -356,6 +356,46 @@ int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* remove
  * leaves the column as it was. */
 int cdb_column_remove(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
 
+/* Documents join a built index on the device, without a rebuild — replaces "insert ... build" (interface.cpp:157-180, :286-288, and
+ * database.cpp:276-280, which constructs the next generation beside the serving one) for one string key.  The arguments are those of
+ * cdb_build_view: doc_start[ndocs + 1] holds non-decreasing offsets into `blob`.  Suffixes never cross documents, so the old suffixes
+ * keep their mutual order and the new ones get theirs from a build over the new documents alone; equal suffixes ascend by document and
+ * every new document is numbered behind every old one.  The array over "old documents, then new documents" is therefore the stable
+ * merge of the old array and the new documents' array, ties old first (append.hip: only the new documents are uploaded and sorted).
+ *   Result.  After a successful call the handle cannot be told from a fresh handle built over the old documents in their order
+ * followed by the new ones in theirs: cdb_size / cdb_bits / cdb_mask / cdb_sa_width / cdb_sa_copy, every query entry point, cdb_cluster,
+ * cdb_render_rows, cdb_save and the cdb_debug_verify* hooks.
+ *   Layout.  It is recomputed with the build's own rule (index.cpp:182-208; the longest document is the maximum of old and new): bits,
+ * mask, the entry width and the packed storage may all grow.
+ *   Capacity.  The reference's capacity errors (index.cpp:195-200) can fire; they fire before anything is touched, and the old index
+ * goes on serving.
+ *   Edges.  ndocs = 0 is valid and changes nothing.  On a handle that was never built, or was built over nothing, the call is
+ * cdb_build_view of the given documents.  Ids are assumed unique, as everywhere: there is no check.  *appended (may be NULL) = the
+ * number of documents that joined.  With ndocs > 0 none of ids, blob and doc_start may be NULL (CDB_E_INVALID).
+ *   Pending additions.  If documents were staged with cdb_add* since the last build the call fails with CDB_E_INVALID and "append:
+ * documents were added since the last build"; nothing changes.  A host staging copy that equals the built column is dropped (cdb_add*
+ * and cdb_save fetch the column back on demand).
+ *   Borrowed text.  Old and new text go into one library-owned padded block (a device copy of the old bytes, a chunked upload of the
+ * new ones): after an append that added at least one document a cdb_build_device / cdb_build_resident handle NO LONGER READS THE
+ * CALLER'S BUFFER.
+ *   Locking and failure.  The call is exclusive, like a build: queries wait under the handle's lock.  Everything new is made in fresh
+ * blocks while the old index stands; a failure before the commit leaves the old index serving (cdb_last_error tells why).
+ *   Paths.  The merge runs only where the fresh array would be globally sorted: reference_compat = 0, or the old array is sorted and
+ * the new text holds no byte >= 0x80.  Otherwise the array is in the reference's order, which depends on bucket sizes max(4096, n / 256)
+ * (index.cpp:96-126,218): text and tables are extended on the device and the array is built over them — only there a failed build
+ * leaves a "never built" handle, as after any failed build.  With self_check >= 3 the order proof runs behind either path; damage
+ * found in a merged array is treated like damage behind a build.  Option "debug_append_path" (test hook): 0 = automatic, 1 = merge
+ * where it is valid, 2 = always rebuild.
+ *   Search keys.  Where the handle keeps search keys and its symbol map codes every byte of the new text, the new suffixes' keys are
+ * computed under that map and merged with the old ones ("append_keys_kept" = 1).  New text with a byte the old text never held is
+ * installed without keys, as after cdb_load ("append_keys_kept" = 0): queries stay exact, lone keywords lose the key shortcut until
+ * the next build.
+ *   Stats: "appends" (calls that added something), "append_merges", "append_rebuilds", and of the last such call "append_docs",
+ * "append_bytes" (text bytes added), "append_ms" (wall, under the lock), "append_keys_kept"; with option profile the kernels are
+ * timed as ap_*.
+ * Not available on cdb_shards (each shard's document bounds would have to be re-cut): rebuild there. */
+int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs, uint64_t* appended);
+
 /* Batched query with patterns and results left in device memory (multi-GPU merge over RCCL, HBM-
  * resident timing).  d_blob/d_offsets are device pointers.  On return the library-owned device arrays
  * d_row_ptr (npat+1 u64), d_ids (nrows i64), d_counts (nrows i64) stay valid until the next query on
@@ -557,6 +597,10 @@ int cdb_debug_verify_reference(cdb_index* h, uint64_t out[4]);
 /* Test hook: the check every build ends with (option self_check), run on the index as it stands — on 2^15 random adjacent
  * pairs, or (full != 0) on every adjacent pair.  out[0] = pairs out of order, out[1] = entries that are no valid (doc, off). */
 int cdb_debug_self_check(cdb_index* h, int full, uint64_t out[2]);
+/* Test hook: the kept search keys against the text.  out[0] = slots whose kept key (in whichever of the three arrays the handle
+ * holds: 64-bit keys, 32-bit keys, 32-bit keys + low digits) differs from the key recomputed from that suffix's bytes under the
+ * handle's symbol map; out[1] = slots checked, 0 when no keys are kept (after cdb_load, or an append that dropped them). */
+int cdb_debug_verify_keys(cdb_index* h, uint64_t out[2]);
 
 /* The order proof behind a published build (option self_check = 3, the default).  The reference's array is sorted by
  * construction (std::sort leaves, index.cpp:86-95); this library's passes rest on an observed LDS lane order, so after
