@@ -11,46 +11,22 @@
 //   3. rank      pos_j = #{old suffixes <= new suffix j}: a sparse sample searches the whole old array, the rest between their
 //                bracketing samples; a probe is decided by the kept search key where the handle has one and resumes its byte
 //                comparison at the prefix both bounds already share (Manber-Myers)
-//   4. merge     output slot pos_j + j belongs to new suffix j: one flag per output slot, a count per tile, a scan, and a tile
-//                kernel that ranks with ballots (no atomics: the order is exact) and re-encodes both kinds of entry
+//   4. merge     output slot pos_j + j belongs to new suffix j: one flag per output slot, the flagged slots ranked stably tile by
+//                tile (stable_tiles.h: count, scan, ballot ranks), and both kinds of entry re-encoded
 // Everything is written into fresh blocks of an AppendPlan while the old index stands.  64-bit indices throughout.
 #include <memory>
 #include <type_traits>
 
 #include "index_impl.h"
 #include "scan.h"
+#include "stable_tiles.h"
 
 namespace cdb {
 namespace {
 
-constexpr int AP_ROUNDS = 16;             // output slots per thread and tile
-constexpr int AP_TILE = 256 * AP_ROUNDS;  // output slots per tile (one workgroup)
-constexpr uint64_t AP_SAMPLE = 64;        // every AP_SAMPLE-th new suffix (and the last) searches the whole old array
-
-unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 256), 8192)); }
+constexpr uint64_t AP_SAMPLE = 64;  // every AP_SAMPLE-th new suffix (and the last) searches the whole old array
 
 // ---- 1. tables and text -----------------------------------------------------------------------------------------------------
-// the longest document (as rm_longest_kernel, without a drop flag)
-__global__ __launch_bounds__(256) void ap_longest_kernel(const uint64_t* __restrict__ doc_start, uint64_t ndocs, unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long s_max[4];
-    uint64_t mx = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t d = (uint64_t)blockIdx.x * 256 + threadIdx.x; d < ndocs; d += stride) {
-        const uint64_t len = doc_start[d + 1] - doc_start[d];
-        mx = len > mx ? len : mx;
-    }
-    for (int off = 32; off; off >>= 1) {
-        const uint64_t o = __shfl_xor(mx, off);
-        mx = o > mx ? o : mx;
-    }
-    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) mx = s_max[w] > mx ? s_max[w] : mx;
-        if (mx) atomicMax(out, (unsigned long long)mx);
-    }
-}
-
 // out[b >> 5] bit (b & 31) = byte value b occurs in text[0 .. m)
 __global__ __launch_bounds__(256) void ap_bytes_kernel(const uint8_t* __restrict__ text, uint64_t m, uint32_t* __restrict__ out) {
     __shared__ uint32_t s_set[8];
@@ -94,42 +70,14 @@ __device__ __forceinline__ uint64_t suffix_key(const uint8_t* __restrict__ p, ui
     for (int k = 0; k < nsym; ++k) key = key * kbase + ((uint64_t)k < rem ? (uint64_t)map[p[k]] : 0ull);
     return key;
 }
-struct KeysIn {  // the kept keys of a handle in whichever form it holds them (index_impl.h: d_keys / d_keys32 + d_keylow)
-    const uint64_t* k64;
-    const uint32_t* k32;
-    const uint8_t* low;
-    int low_bits, low_bytes;
-    __device__ __forceinline__ uint64_t at(uint64_t i) const {
-        if (k64) return k64[i];
-        const uint64_t h = k32[i];
-        if (!low_bits) return h;
-        return (h << low_bits) | (low_bytes == 2 ? (uint64_t)reinterpret_cast<const uint16_t*>(low)[i] : (uint64_t)low[i]);
-    }
-};
-// ... with the form known at compile time (ap_rank_kernel: 1 = u64 keys, 2 = u32 keys, 3 / 4 = u32 keys + one / two low bytes)
+// KeptKeys::at with the form known at compile time (ap_rank_kernel: 1 = u64 keys, 2 = u32 keys, 3 / 4 = u32 keys + one / two low bytes)
 template <int KF>
-__device__ __forceinline__ uint64_t key_at(const KeysIn& k, uint64_t i) {
+__device__ __forceinline__ uint64_t key_at(const KeptKeys& k, uint64_t i) {
     if constexpr (KF == 1) return k.k64[i];
     else if constexpr (KF == 2) return k.k32[i];
     else if constexpr (KF == 3) return ((uint64_t)k.k32[i] << k.low_bits) | (uint64_t)k.low[i];
     else return ((uint64_t)k.k32[i] << k.low_bits) | (uint64_t)reinterpret_cast<const uint16_t*>(k.low)[i];
 }
-struct KeysOut {
-    uint64_t* o64;
-    uint32_t* o32;
-    uint8_t* olow;
-    int low_bits, low_bytes;
-    __device__ __forceinline__ void put(uint64_t i, uint64_t key) const {
-        if (o64) o64[i] = key;
-        if (o32) o32[i] = (uint32_t)(key >> low_bits);
-        if (olow) {
-            const uint64_t l = key & ((1ull << low_bits) - 1ull);
-            if (low_bytes == 2) reinterpret_cast<uint16_t*>(olow)[i] = (uint16_t)l;
-            else olow[i] = (uint8_t)l;
-        }
-    }
-};
-
 // ---- 3. rank ----------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t load_be8(const uint8_t* p) {
     uint64_t v;
@@ -172,7 +120,7 @@ template <typename Tag, int KF>
 __global__ __launch_bounds__(256) void ap_rank_kernel(typename SaOf<Tag>::ptr sa, uint64_t n, const uint8_t* __restrict__ otext,
                                                       const uint64_t* __restrict__ ostart, int obits, uint64_t omask,
                                                       const uint64_t* __restrict__ nent, uint64_t m, const uint8_t* __restrict__ ctext,
-                                                      const uint64_t* __restrict__ cstart, int nbits, uint64_t nmask, KeysIn keys,
+                                                      const uint64_t* __restrict__ cstart, int nbits, uint64_t nmask, KeptKeys keys,
                                                       const uint16_t* __restrict__ symmap, int nsym, uint32_t kbase, int phase,
                                                       uint64_t* __restrict__ pos, uint64_t* __restrict__ newkey) {
     __shared__ uint16_t s_map[256];
@@ -230,52 +178,24 @@ __global__ __launch_bounds__(256) void ap_flag_kernel(const uint64_t* __restrict
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j < m) flag[pos[j] + j] = 1;
 }
-// pass A: new entries per tile of output slots
-__global__ __launch_bounds__(256) void ap_count_kernel(const uint8_t* __restrict__ flag, uint64_t N, uint64_t* __restrict__ tile_count) {
-    __shared__ uint32_t s_w[4];
-    const uint64_t base = (uint64_t)blockIdx.x * AP_TILE;
-    uint32_t c = 0;
-#pragma unroll 4
-    for (int k = 0; k < AP_ROUNDS; ++k) {
-        const uint64_t o = base + (uint64_t)k * 256 + threadIdx.x;
-        if (o < N) c += flag[o] ? 1u : 0u;
-    }
-    for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-struct TileBaseOut {
-    uint64_t* base;
-    __device__ __forceinline__ void operator()(uint64_t t, uint64_t ex, uint64_t) const { base[t] = ex; }
+// the flag of the ranking (stable_tiles.h): output slot o takes a new entry
+struct SlotIsNew {
+    const uint8_t* flag;
+    __device__ __forceinline__ bool operator()(uint64_t o) const { return flag[o] != 0; }
 };
-// pass B: output slot o of the tile's round k is new entry number r or old entry number o - r, where r = new entries in front of
-// o = tile base + new in earlier rounds + new in earlier waves of this round + new in earlier lanes of its wave (ballot)
+// output slot o is new entry number r or old entry number o - r, where r = new entries in front of o
 template <typename SrcTag, typename Dst>
 __global__ __launch_bounds__(256) void ap_merge_kernel(typename SaOf<SrcTag>::ptr sa, uint64_t N, int old_bits, uint64_t old_mask, int new_bits,
                                                        const uint8_t* __restrict__ flag, const uint64_t* __restrict__ nent,
                                                        const uint64_t* __restrict__ newkey, const uint64_t* __restrict__ tile_base, Dst out,
-                                                       KeysIn kin, KeysOut kout, bool with_keys) {
-    __shared__ uint32_t s_w[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t base = (uint64_t)blockIdx.x * AP_TILE;
-    uint64_t run = tile_base[blockIdx.x];
-    for (int k = 0; k < AP_ROUNDS; ++k) {
-        const uint64_t o = base + (uint64_t)k * 256 + threadIdx.x;
+                                                       KeptKeys kin, KeptKeys kout, bool with_keys) {
+    TileRanker ranker(tile_base);
+    for (int k = 0; k < ST_ROUNDS; ++k) {
+        const uint64_t o = tile_slot(k);
         const bool valid = o < N;
         const bool isnew = valid && flag[o] != 0;
-        const uint64_t bal = __ballot(isnew);
-        if (lane == 0) s_w[k & 1][wave] = (uint32_t)__popcll(bal);
-        __syncthreads();  // (the other half of s_w is still being read by the slowest wave of round k - 1: two halves, one barrier)
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const uint32_t c = s_w[k & 1][w];
-            before += w < wave ? c : 0u;
-            all += c;
-        }
+        const uint64_t r = ranker.before(k, isnew);
         if (valid) {
-            const uint64_t r = run + before + (uint64_t)__popcll(bal & ((1ull << lane) - 1));
             if (isnew) {
                 out.store(o, (typename Dst::val)nent[r]);
                 if (with_keys) kout.put(o, newkey[r]);
@@ -286,14 +206,13 @@ __global__ __launch_bounds__(256) void ap_merge_kernel(typename SaOf<SrcTag>::pt
                 if (with_keys) kout.put(o, kin.at(i));
             }
         }
-        run += all;
     }
 }
 
 // ---- cdb_debug_verify_keys ----------------------------------------------------------------------------------------------------
 template <typename Tag>
 __global__ __launch_bounds__(256) void ap_verify_keys_kernel(typename SaOf<Tag>::ptr sa, uint64_t n, const uint8_t* __restrict__ text,
-                                                             const uint64_t* __restrict__ doc_start, int bits, uint64_t mask, KeysIn keys,
+                                                             const uint64_t* __restrict__ doc_start, int bits, uint64_t mask, KeptKeys keys,
                                                              const uint16_t* __restrict__ symmap, int nsym, uint32_t kbase,
                                                              unsigned long long* __restrict__ out) {
     __shared__ uint16_t s_map[256];
@@ -310,15 +229,6 @@ __global__ __launch_bounds__(256) void ap_verify_keys_kernel(typename SaOf<Tag>:
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(out, (unsigned long long)bad);
 }
 
-bool keys_recomputable(const Index& ix) {  // the handle holds keys, their code table, and every part of a split key
-    return ix.key_nsym > 0 && (ix.d_keys.p || ix.d_keys32.p) && ix.d_symmap_q.p && ix.key_low_bytes >= 0 && ix.key_low_bytes <= 2 &&
-           (ix.d_keys.p || ix.key_low_bits == 0 || (ix.d_keylow.p && ix.key_low_bytes >= 1));
-}
-KeysIn keys_of(const Index& ix) {
-    return KeysIn{ix.d_keys.p ? ix.d_keys.as<uint64_t>() : nullptr, ix.d_keys32.p ? ix.d_keys32.as<uint32_t>() : nullptr,
-                  ix.d_keylow.p ? ix.d_keylow.as<uint8_t>() : nullptr, ix.d_keys.p ? 0 : ix.key_low_bits, ix.key_low_bytes};
-}
-
 }  // namespace
 
 void append_old_longest(Index& ix, AppendPlan& p) {
@@ -327,8 +237,7 @@ void append_old_longest(Index& ix, AppendPlan& p) {
     d_out.alloc(8);
     CDB_HIP(hipMemsetAsync(d_out.p, 0, 8, s));
     int t = ix.prof.begin(s);
-    hipLaunchKernelGGL(ap_longest_kernel, dim3(grid_for(ix.ndocs)), dim3(256), 0, s, (const uint64_t*)ix.d_doc_start.as<uint64_t>(), ix.ndocs,
-                       d_out.as<unsigned long long>());
+    longest_document(s, nullptr, ix.d_doc_start.as<uint64_t>(), ix.ndocs, d_out.as<unsigned long long>());
     ix.prof.end(t, "ap_longest", ix.ndocs * 8, s);
     CDB_HIP(hipGetLastError());
     uint64_t out = 0;
@@ -380,14 +289,7 @@ void append_scan_bytes(Index& ix, AppendPlan& p) {
 void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int new_width, bool new_packed) {
     hipStream_t s = ix.stream;
     const uint64_t n = ix.size, m = p.size, N = n + m, D = ix.ndocs;
-    if (new_packed) {
-        p.sa.alloc(std::max<uint64_t>(N, 4) * 4);
-        p.sa_hi.alloc(std::max<uint64_t>(N, 16));
-    } else {
-        p.sa.alloc(std::max<uint64_t>(N * (uint64_t)new_width, 16));
-    }
-    p.key_nsym = 0;
-    p.keys_kept = false;
+    p.arr.alloc(N, new_width, new_packed);
     if (!N) return;
     // ---- the new documents' own array, decoded into entries of the new layout
     DevBuf nent, pos, newkey;
@@ -452,7 +354,7 @@ void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int
     // ---- rank
     pos.alloc(std::max<uint64_t>(m, 2) * 8);
     if (with_keys) newkey.alloc(std::max<uint64_t>(m, 2) * 8);
-    const KeysIn kin = with_keys ? keys_of(ix) : KeysIn{nullptr, nullptr, nullptr, 0, 0};
+    const KeptKeys kin = with_keys ? keys_of(ix) : KeptKeys{};
     const int nsym = with_keys ? ix.key_nsym : 0;
     const uint16_t* symmap = with_keys ? (const uint16_t*)ix.d_symmap_q.as<uint16_t>() : (const uint16_t*)nullptr;
     if (m) {
@@ -482,7 +384,7 @@ void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int
         }
     }
     // ---- merge
-    DevBuf flag, tile_count, tile_base;
+    DevBuf flag, tile_base;
     flag.alloc(N);
     CDB_HIP(hipMemsetAsync(flag.p, 0, N, s));
     if (m) {
@@ -491,45 +393,12 @@ void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int
         ix.prof.end(t, "ap_flag", m * 9, s);
         CDB_HIP(hipGetLastError());
     }
-    const uint64_t ntiles = ceil_div(N, AP_TILE);
-    if (ntiles >= (1ull << 31)) throw Error("append: the array has too many tiles for one launch (internal)");
-    tile_count.alloc(ntiles * 8);
-    tile_base.alloc(ntiles * 8);
-    int t = ix.prof.begin(s);
-    hipLaunchKernelGGL(ap_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, (const uint8_t*)flag.as<uint8_t>(), N, tile_count.as<uint64_t>());
-    ix.prof.end(t, "ap_count", N + ntiles * 8, s);
-    CDB_HIP(hipGetLastError());
-    PartialsIn<uint64_t> tin{tile_count.as<uint64_t>()};
-    const uint64_t joined = scan_totals<uint64_t>(s, ix.scan_partials, tin, ntiles, OpAdd{}, (uint64_t)0);
-    if (joined != m) throw Error("append: new entries and new bytes differ (internal)");
-    scan_apply<uint64_t>(s, ix.scan_partials, tin, ntiles, OpAdd{}, (uint64_t)0, TileBaseOut{tile_base.as<uint64_t>()});
-    CDB_HIP(hipGetLastError());
-    KeysOut kout{nullptr, nullptr, nullptr, 0, 0};
-    if (with_keys) {
-        p.key_nsym = ix.key_nsym;
-        p.key_base = ix.key_base;
-        p.key_low_bits = ix.key_low_bits;
-        p.key_low_bytes = ix.key_low_bytes;
-        p.keys_kept = true;
-        if (ix.d_keys.p) {
-            p.keys.alloc(N * 8);
-            kout.o64 = p.keys.as<uint64_t>();
-        }
-        if (ix.d_keys32.p) {
-            p.keys32.alloc(N * 4);
-            kout.o32 = p.keys32.as<uint32_t>();
-            kout.low_bits = ix.key_low_bits;
-        }
-        if (ix.d_keylow.p) {
-            kout.low_bytes = std::max(ix.key_low_bytes, 1);
-            p.keylow.alloc(N * (uint64_t)kout.low_bytes);
-            kout.olow = p.keylow.as<uint8_t>();
-            kout.low_bits = ix.key_low_bits;
-        }
-    }
-    const uint64_t key_bytes = (kout.o64 ? 8 : 0) + (kout.o32 ? 4 : 0) + (kout.olow ? kout.low_bytes : 0);
+    const uint64_t ntiles = ceil_div(N, ST_TILE);
+    if (tile_bases(ix, "append", SlotIsNew{flag.as<uint8_t>()}, N, tile_base, "ap_count", N + ntiles * 8) != m)
+        throw Error("append: new entries and new bytes differ (internal)");
+    const KeptKeys kout = with_keys ? p.arr.alloc_keys_like(ix, N) : KeptKeys{};
     const int old_bytes = ix.sa_packed ? 5 : ix.width;
-    t = ix.prof.begin(s);
+    const int t = ix.prof.begin(s);
     sa_dispatch(ix, [&](auto src_tag) {
         using S = decltype(src_tag);
         auto launch = [&](auto dst) {
@@ -538,11 +407,11 @@ void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int
                                (const uint8_t*)flag.as<uint8_t>(), (const uint64_t*)nent.as<uint64_t>(), (const uint64_t*)newkey.as<uint64_t>(),
                                (const uint64_t*)tile_base.as<uint64_t>(), dst, kin, kout, with_keys);
         };
-        if (new_packed) launch(Sa40RW{p.sa.as<uint32_t>(), p.sa_hi.as<uint8_t>()});
-        else if (new_width == 8) launch(SaRW<uint64_t>{p.sa.as<uint64_t>()});
-        else launch(SaRW<uint32_t>{p.sa.as<uint32_t>()});
+        if (new_packed) launch(Sa40RW{p.arr.sa.as<uint32_t>(), p.arr.sa_hi.as<uint8_t>()});
+        else if (new_width == 8) launch(SaRW<uint64_t>{p.arr.sa.as<uint64_t>()});
+        else launch(SaRW<uint32_t>{p.arr.sa.as<uint32_t>()});
     });
-    ix.prof.end(t, "ap_merge", n * (uint64_t)old_bytes + m * 8 + N * (1 + (new_packed ? 5 : (uint64_t)new_width) + 2 * key_bytes) + ntiles * 8, s);
+    ix.prof.end(t, "ap_merge", n * (uint64_t)old_bytes + m * 8 + N * (1 + (new_packed ? 5 : (uint64_t)new_width) + 2 * kout.bytes_per_slot()) + ntiles * 8, s);
     CDB_HIP(hipGetLastError());
     CDB_HIP(hipStreamSynchronize(s));  // (the scratch blocks above go back to the cache idle)
 }
@@ -554,7 +423,7 @@ void verify_kept_keys(Index& ix, uint64_t out[2]) {
     DevBuf d_out;
     d_out.alloc(8);
     CDB_HIP(hipMemsetAsync(d_out.p, 0, 8, s));
-    const KeysIn kin = keys_of(ix);
+    const KeptKeys kin = keys_of(ix);
     sa_dispatch(ix, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL((ap_verify_keys_kernel<T>), dim3(grid_for(ix.size)), dim3(256), 0, s, ix.sa_view<T>(), ix.size, ix.d_text,

@@ -70,6 +70,8 @@ Layout layout_from(uint64_t ndocs, uint64_t size, uint64_t longest) {
     L.ndocs = ndocs;
     return L;
 }
+// sa_packable (index_impl.h) for a layout the handle does not have yet; an empty array is stored plain
+bool layout_packable(const Index& ix, const Layout& L) { return ix.pack_sa && L.width == 8 && (int)L.bits + L.off_bits <= 40 && L.size > 0; }
 Layout layout_of(const std::vector<uint64_t>& doc_start, uint64_t ndocs) {
     uint64_t size = 0, longest = 0;
     for (uint64_t d = 0; d < ndocs; ++d) {
@@ -227,25 +229,18 @@ void reset_unbuilt(Index& ix) {
 
 // Everything a handle needs to serve a new column, gathered BEFORE the handle is touched: every cdb_build* and cdb_load fill one
 // of these ("prepare") and hand it to replace_column.
-struct NewColumn {
+struct NewColumn : ColumnBlocks {        // text: the library's own copy (TEXT_PAD readable zero bytes behind it), or ...
     Layout L;
-    DevBuf text;                        // the library's own copy of the text (TEXT_PAD readable zero bytes behind it), or ...
     const uint8_t* borrowed = nullptr;  // ... the caller's device memory (no padding promised)
-    DevBuf d_start, d_ids;
     enum { HOST_KEPT, HOST_NEW, HOST_NONE } host = HOST_KEPT;  // the handle's staging copy stays (cdb_build) / ids + doc_start below
     std::vector<int64_t> ids;                                  // replace it / tables and text live on the device only
     std::vector<uint64_t> doc_start;
     double upload_t0 = -1;  // wall_ms() when the upload of the text began (host_upload_ms); < 0: nothing was uploaded
-    // cdb_load only: the array comes with the column instead of being built (sa_hi: the packed storage's fifth bytes)
-    DevBuf sa, sa_hi;
+    // cdb_load, cdb_remove, cdb_append: the array comes with the column (arr) instead of being built, in this order
     bool reference_compat = true, sa_sorted = true;
-    // cdb_remove only: the array was compacted on this device, out of one that was built here — damage the order proof finds in it
-    // is treated like damage behind a build; and the search keys come along, compacted slot for slot, with the parameters they
-    // were made with (the symbol maps of the handle stay as they are)
+    // cdb_remove, cdb_append: the array was made on this device, out of one that was built here — damage the order proof finds in it
+    // is treated like damage behind a build
     bool from_file = true;
-    DevBuf keys, keys32, keylow;
-    int key_nsym = 0, key_low_bits = 0, key_low_bytes = 0;
-    uint32_t key_base = 0;
 };
 
 void alloc_padded_text(Index& ix, DevBuf& text, uint64_t n) {
@@ -267,7 +262,8 @@ void rebase_tables(const uint64_t* doc_start, const int64_t* ids, uint64_t ndocs
 
 // The commit point: the old index stops serving here, and from here on a failure leaves a "never built" handle.
 void install(Index& ix, NewColumn& c) {
-    const bool loaded = c.sa.p != nullptr;
+    ArrivedArray& a = c.arr;
+    const bool loaded = a.sa.p != nullptr;
     try {
         reset_unbuilt(ix);  // (waits for the stream: the old arrays are idle; ix.mu keeps queries out)
         if (!loaded) ix.host_upload_ms = c.upload_t0 >= 0 ? wall_ms() - c.upload_t0 : 0;  // (a build's statistic: a load keeps them all)
@@ -296,19 +292,19 @@ void install(Index& ix, NewColumn& c) {
         }
         ix.reference_compat = c.reference_compat;
         ix.sa_sorted = c.sa_sorted;  // a reference-compat ordering keeps the reference's exact probe sequence
-        ix.d_sa = std::move(c.sa);
-        if (c.sa_hi.p) {
-            ix.d_sa_hi = std::move(c.sa_hi);
+        ix.d_sa = std::move(a.sa);
+        if (a.sa_hi.p) {
+            ix.d_sa_hi = std::move(a.sa_hi);
             ix.sa_packed = true;
         }
-        if (c.key_nsym) {
-            ix.d_keys = std::move(c.keys);
-            ix.d_keys32 = std::move(c.keys32);
-            ix.d_keylow = std::move(c.keylow);
-            ix.key_nsym = c.key_nsym;
-            ix.key_base = c.key_base;
-            ix.key_low_bits = c.key_low_bits;
-            ix.key_low_bytes = c.key_low_bytes;
+        if (a.key_nsym) {
+            ix.d_keys = std::move(a.keys);
+            ix.d_keys32 = std::move(a.keys32);
+            ix.d_keylow = std::move(a.keylow);
+            ix.key_nsym = a.key_nsym;
+            ix.key_base = a.key_base;
+            ix.key_low_bits = a.key_low_bits;
+            ix.key_low_bytes = a.key_low_bytes;
         }
         // a file's entries were checked one by one (each names a real suffix), their ORDER was not: the proof behind a build runs
         // behind a load as well (damage -> the array is rebuilt from the loaded text)
@@ -322,17 +318,40 @@ void install(Index& ix, NewColumn& c) {
     }
 }
 
+// f() queues work on blocks that go back to the cache when it throws: the stream drains first
+template <typename F>
+void drained_on_failure(Index& ix, F&& f) {
+    try {
+        f();
+    } catch (...) {
+        (void)hipStreamSynchronize(ix.stream);
+        throw;
+    }
+}
 // prepare(c) validates, allocates and uploads into c; a failure in it (allocation, upload) leaves the previous index serving
 template <typename Prepare>
 void replace_column(Index& ix, Prepare&& prepare) {
     NewColumn c;
-    try {
-        prepare(c);
-    } catch (...) {
-        (void)hipStreamSynchronize(ix.stream);  // (copies into blocks of c may be queued: they end before the blocks go back)
-        throw;
-    }
+    drained_on_failure(ix, [&] { prepare(c); });
     install(ix, c);
+}
+// cdb_remove / cdb_append change a built column only.  Returns its documents (0: never built, or built over nothing)
+uint64_t built_docs_or_refuse(const Index& ix, const char* op) {
+    const uint64_t built_docs = ix.width ? ix.ndocs : 0;
+    if (ix.host_text_valid && ix.ids.size() > built_docs) throw Error(std::string(op) + ": documents were added since the last build");
+    return built_docs;
+}
+// ... and end their prepare here: what the plan made beside the old index becomes the column, once the stream is idle
+// (made.arr empty: only text and tables were made, the array is built over them)
+void adopt_blocks(Index& ix, NewColumn& col, ColumnBlocks& made) {
+    if (made.arr.sa.p) {
+        col.reference_compat = ix.reference_compat;
+        col.sa_sorted = true;
+        col.from_file = false;
+    }
+    CDB_HIP(hipStreamSynchronize(ix.stream));
+    ix.prof.resolve();
+    static_cast<ColumnBlocks&>(col) = std::move(made);
 }
 
 // every entry point that touches the device: make the handle's device current and tell the block cache which
@@ -763,17 +782,12 @@ int cdb_load(cdb_index* h, const char* path) {
             const Layout L = layout_of(doc_start, hd.ndocs);  // (also: doc_start non-decreasing)
             if (L.size != hd.size || L.bits != hd.bits || L.mask != hd.mask || (uint64_t)L.width != hd.width)
                 throw Error(std::string("Corrupt index file (entry layout): ") + path);
-            DevBuf &text = col.text, &sa = col.sa, &sa_hi = col.sa_hi, &d_start = col.d_start, &d_ids = col.d_ids;
+            DevBuf &text = col.text, &sa = col.arr.sa, &sa_hi = col.arr.sa_hi, &d_start = col.d_start, &d_ids = col.d_ids;
             alloc_padded_text(ix, text, hd.size);
             // 8-byte entries below 2^40 are stored packed (the storage a build of this column would leave): they are packed chunk by
             // chunk while the file is read, so the plain array never exists on the device and nothing can fail after the commit
-            const bool pack = ix.pack_sa && hd.width == 8 && (int)L.bits + L.off_bits <= 40 && hd.size > 0;
-            if (pack) {
-                sa.alloc(hd.size * sizeof(uint32_t));
-                sa_hi.alloc(hd.size);
-            } else {
-                sa.alloc(std::max<uint64_t>(hd.size * hd.width, 16));
-            }
+            const bool pack = layout_packable(ix, L);  // (L.width and L.size are the header's: checked above)
+            col.arr.alloc(hd.size, (int)hd.width, pack);
             std::vector<char> buf(std::min<uint64_t>(std::max<uint64_t>(hd.size * hd.width, 1), 256ull << 20));
             auto fill = [&](void* dptr, uint64_t bytes) {
                 for (uint64_t o = 0; o < bytes; o += buf.size()) {
@@ -1108,20 +1122,14 @@ int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* remove
         std::lock_guard<std::mutex> g(ix.mu);
         DeviceScope dscope(ix);
         const double t0 = wall_ms();
-        const uint64_t built_docs = ix.width ? ix.ndocs : 0;
-        if (ix.host_text_valid && ix.ids.size() > built_docs) throw Error("remove: documents were added since the last build");
+        const uint64_t built_docs = built_docs_or_refuse(ix, "remove");
         if (!nids) return;
         if (!built_docs) {  // never built, or built over nothing: the index holds no id
             if (missing) *missing = nids;
             return;
         }
         RemovePlan p;
-        try {
-            remove_mark(ix, ids, nids, p);
-        } catch (...) {
-            (void)hipStreamSynchronize(ix.stream);
-            throw;
-        }
+        drained_on_failure(ix, [&] { remove_mark(ix, ids, nids, p); });
         if (removed) *removed = p.removed;
         if (missing) *missing = p.missing;
         if (!p.removed) {  // (the scan's total synchronised the stream and nothing was queued behind it)
@@ -1135,27 +1143,8 @@ int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* remove
             col.L = L;
             col.host = NewColumn::HOST_NONE;  // (a staging copy that equals the built column goes: cdb_add* fetch the survivors back)
             remove_text(ix, p);
-            if (compact) {
-                const bool pack = ix.pack_sa && L.width == 8 && (int)L.bits + L.off_bits <= 40 && L.size > 0;
-                remove_compact(ix, p, (int)L.bits, L.width, pack);
-                col.sa = std::move(p.sa);
-                col.sa_hi = std::move(p.sa_hi);
-                col.keys = std::move(p.keys);
-                col.keys32 = std::move(p.keys32);
-                col.keylow = std::move(p.keylow);
-                col.key_nsym = p.key_nsym;
-                col.key_base = p.key_base;
-                col.key_low_bits = p.key_low_bits;
-                col.key_low_bytes = p.key_low_bytes;
-                col.reference_compat = ix.reference_compat;
-                col.sa_sorted = true;
-                col.from_file = false;
-            }
-            CDB_HIP(hipStreamSynchronize(ix.stream));
-            ix.prof.resolve();
-            col.text = std::move(p.text);
-            col.d_start = std::move(p.d_start);
-            col.d_ids = std::move(p.d_ids);
+            if (compact) remove_compact(ix, p, (int)L.bits, L.width, layout_packable(ix, L));
+            adopt_blocks(ix, col, p);
         });
         ix.rm.calls += 1;
         (compact ? ix.rm.compactions : ix.rm.rebuilds) += 1;
@@ -1178,24 +1167,23 @@ int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_
         std::lock_guard<std::mutex> g(ix.mu);
         DeviceScope dscope(ix);
         const double t0 = wall_ms();
-        const uint64_t built_docs = ix.width ? ix.ndocs : 0;
-        if (ix.host_text_valid && ix.ids.size() > built_docs) throw Error("append: documents were added since the last build");
+        const uint64_t built_docs = built_docs_or_refuse(ix, "append");
         if (!ndocs) return;
         const uint64_t first = doc_start[0];
         if (doc_start[ndocs] < first || doc_start[ndocs] - first >= (1ull << 48)) throw Error("doc_start must be non-decreasing");
         const uint64_t m = doc_start[ndocs] - first;
-        auto count = [&](bool merged, int keys_kept) {
+        auto count = [&](bool merged) {  // (behind the build or the commit: the handle's keys are the new column's)
             ix.ap.calls += 1;
             (merged ? ix.ap.merges : ix.ap.rebuilds) += 1;
             ix.ap.docs = ndocs;
             ix.ap.bytes = m;
-            ix.ap.keys_kept = keys_kept;
+            ix.ap.with_keys = ix.key_nsym ? 1 : 0;
             ix.ap.last_ms = wall_ms() - t0;
             if (appended) *appended = ndocs;
         };
         if (!built_docs) {  // never built, or built over nothing: a build of the given documents
             build_view_locked(ix, ids, blob, doc_start, ndocs);
-            count(false, ix.key_nsym ? 1 : 0);
+            count(false);
             return;
         }
         const uint64_t n = ix.size, D = ix.ndocs;
@@ -1209,12 +1197,7 @@ int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_
         }
         p.ndocs = ndocs;
         p.size = m;
-        try {
-            append_old_longest(ix, p);
-        } catch (...) {
-            (void)hipStreamSynchronize(ix.stream);
-            throw;
-        }
+        drained_on_failure(ix, [&] { append_old_longest(ix, p); });
         // the reference's capacity errors (index.cpp:195-200): nothing has been touched yet
         const Layout L = layout_from(D + ndocs, n + m, std::max(p.old_longest, p.longest));
         const Layout Li = layout_from(ndocs, m, p.longest);
@@ -1233,29 +1216,10 @@ int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_
             // the merge is exact where the fresh array would be globally sorted; the reference's order is rebuilt
             const bool valid = n > 0 && ix.sa_sorted && (!ix.reference_compat || !p.high_bytes);
             merged = valid && ix.debug_append_path != 2;
-            if (merged) {
-                const bool pack = ix.pack_sa && L.width == 8 && (int)L.bits + L.off_bits <= 40 && L.size > 0;
-                append_merge(ix, p, (int)L.bits, L.mask, L.width, pack);
-                col.sa = std::move(p.sa);
-                col.sa_hi = std::move(p.sa_hi);
-                col.keys = std::move(p.keys);
-                col.keys32 = std::move(p.keys32);
-                col.keylow = std::move(p.keylow);
-                col.key_nsym = p.key_nsym;
-                col.key_base = p.key_base;
-                col.key_low_bits = p.key_low_bits;
-                col.key_low_bytes = p.key_low_bytes;
-                col.reference_compat = ix.reference_compat;
-                col.sa_sorted = true;
-                col.from_file = false;
-            }
-            CDB_HIP(hipStreamSynchronize(ix.stream));
-            ix.prof.resolve();
-            col.text = std::move(p.text);
-            col.d_start = std::move(p.d_start);
-            col.d_ids = std::move(p.d_ids);
+            if (merged) append_merge(ix, p, (int)L.bits, L.mask, L.width, layout_packable(ix, L));
+            adopt_blocks(ix, col, p);
         });
-        count(merged, merged ? (p.keys_kept ? 1 : 0) : (ix.key_nsym ? 1 : 0));
+        count(merged);
     });
 }
 
@@ -1868,7 +1832,7 @@ int cdb_get_stat(const cdb_index* h, const char* name, double* value) {
         {"remove_docs", (double)h->ix.rm.docs}, {"remove_bytes", (double)h->ix.rm.bytes}, {"remove_ms", h->ix.rm.last_ms},
         {"appends", (double)h->ix.ap.calls}, {"append_merges", (double)h->ix.ap.merges}, {"append_rebuilds", (double)h->ix.ap.rebuilds},
         {"append_docs", (double)h->ix.ap.docs}, {"append_bytes", (double)h->ix.ap.bytes}, {"append_ms", h->ix.ap.last_ms},
-        {"append_keys_kept", (double)h->ix.ap.keys_kept},
+        {"append_keys_kept", (double)h->ix.ap.with_keys},
         {"render_ms", h->ix.rnd.last_ms}, {"render_page_bytes", (double)h->ix.rnd.page_bytes}, {"render_spans", (double)h->ix.rnd.spans},
         {"query_ms", q.query_ms}, {"query_upload_ms", q.upload_ms}, {"query_device_ms", q.device_ms}, {"query_download_ms", q.download_ms}, {"query_hits", (double)q.nhits}, {"query_rows", (double)q.nrows},
         {"query_batches", (double)q.batches}, {"query_spec_batches", (double)q.spec_batches}, {"query_spec_spills", (double)q.spec_spills},

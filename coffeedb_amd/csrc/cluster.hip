@@ -41,7 +41,6 @@ double wall_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
-unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 256), 8192)); }
 
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
     for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);

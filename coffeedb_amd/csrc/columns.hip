@@ -37,8 +37,6 @@ double wall_ms() {
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 256), 8192)); }
-
 // ---- keys --------------------------------------------------------------------------------------------------------------
 // int64: v ^ 2^63; double: sign-flip order with -0.0 folded onto +0.0 (the two zeros compare equal in the reference's pairs and
 // then order by id); bool: 0 / 1.  `raw` is the value's bit pattern.

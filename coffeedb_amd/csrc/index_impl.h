@@ -361,7 +361,7 @@ struct Index {
         uint64_t calls = 0, merges = 0, rebuilds = 0;
         uint64_t docs = 0, bytes = 0;
         double last_ms = 0;
-        int keys_kept = 0;
+        int with_keys = 0;
     } ap;
     int debug_append_path = 0;  // test hook: 0 = automatic, 1 = merge where it is valid, 2 = always rebuild
 
@@ -397,34 +397,103 @@ __device__ __forceinline__ uint64_t lower_bound_id(const int64_t* __restrict__ i
     return a;
 }
 
+// ---- the kept search keys as kernels see them, slot for slot beside the array, in whichever form a handle holds them (d_keys, or
+// d_keys32 = key >> low_bits with the low digits in one or two bytes of d_keylow; a form that is absent is a null pointer)
+struct KeptKeys {
+    uint64_t* k64 = nullptr;
+    uint32_t* k32 = nullptr;
+    uint8_t* low = nullptr;
+    int low_bits = 0, low_bytes = 0;
+    __device__ __forceinline__ uint64_t at(uint64_t i) const {
+        if (k64) return k64[i];
+        const uint64_t h = k32[i];
+        if (!low_bits) return h;
+        return (h << low_bits) | (low_bytes == 2 ? (uint64_t)reinterpret_cast<const uint16_t*>(low)[i] : (uint64_t)low[i]);
+    }
+    __device__ __forceinline__ void put(uint64_t i, uint64_t key) const {
+        if (k64) k64[i] = key;
+        if (k32) k32[i] = (uint32_t)(key >> low_bits);
+        if (low) {
+            const uint64_t l = key & ((1ull << low_bits) - 1ull);
+            if (low_bytes == 2) reinterpret_cast<uint16_t*>(low)[i] = (uint16_t)l;
+            else low[i] = (uint8_t)l;
+        }
+    }
+    // slot `from` of src into slot `to`, every stored form as it is (src holds the same forms)
+    __device__ __forceinline__ void copy(const KeptKeys& src, uint64_t from, uint64_t to) const {
+        if (k64) k64[to] = src.k64[from];
+        if (k32) k32[to] = src.k32[from];
+        if (low) {
+            if (low_bytes == 2) reinterpret_cast<uint16_t*>(low)[to] = reinterpret_cast<const uint16_t*>(src.low)[from];
+            else low[to] = src.low[from];
+        }
+    }
+    uint64_t bytes_per_slot() const { return (k64 ? 8 : 0) + (k32 ? 4 : 0) + (low ? low_bytes : 0); }
+};
+inline KeptKeys keys_of(const Index& ix) {
+    return KeptKeys{ix.d_keys.as<uint64_t>(), ix.d_keys32.as<uint32_t>(), ix.d_keylow.as<uint8_t>(), ix.key_low_bits,
+                    ix.d_keylow.p ? std::max(ix.key_low_bytes, 1) : 0};
+}
+inline bool keys_recomputable(const Index& ix) {  // the handle holds keys, their code table, and every part of a split key
+    return ix.key_nsym > 0 && (ix.d_keys.p || ix.d_keys32.p) && ix.d_symmap_q.p && ix.key_low_bytes >= 0 && ix.key_low_bytes <= 2 &&
+           (ix.d_keys.p || ix.key_low_bits == 0 || (ix.d_keylow.p && ix.key_low_bytes >= 1));
+}
+
+// An array that arrives with its column instead of being built over it (cdb_load, cdb_remove, cdb_append), and the search keys that
+// come along with the parameters they were made with (key_nsym = 0: none; the symbol maps of the handle stay as they are)
+struct ArrivedArray {
+    DevBuf sa, sa_hi;  // sa_hi: the packed storage's fifth bytes
+    DevBuf keys, keys32, keylow;
+    int key_nsym = 0, key_low_bits = 0, key_low_bytes = 0;
+    uint32_t key_base = 0;
+    void alloc(uint64_t n, int width, bool packed) {
+        if (packed) {
+            sa.alloc(std::max<uint64_t>(n, 4) * 4);
+            sa_hi.alloc(std::max<uint64_t>(n, 16));
+        } else {
+            sa.alloc(std::max<uint64_t>(n * (uint64_t)width, 16));
+        }
+    }
+    // key blocks of n slots in the forms ix holds, under its parameters
+    KeptKeys alloc_keys_like(const Index& ix, uint64_t n) {
+        const KeptKeys src = keys_of(ix);
+        key_nsym = ix.key_nsym;
+        key_base = ix.key_base;
+        key_low_bits = ix.key_low_bits;
+        key_low_bytes = ix.key_low_bytes;
+        if (src.k64) keys.alloc(n * 8);
+        if (src.k32) keys32.alloc(n * 4);
+        if (src.low) keylow.alloc(n * (uint64_t)src.low_bytes);
+        return KeptKeys{keys.as<uint64_t>(), keys32.as<uint32_t>(), keylow.as<uint8_t>(), src.low_bits, src.low_bytes};
+    }
+};
+// the device blocks of a column: what cdb_remove and cdb_append make beside the old index and the commit (capi.hip) takes as a whole
+struct ColumnBlocks {
+    DevBuf d_start, d_ids, text;  // the tables and the library's own padded text
+    ArrivedArray arr;             // empty: the array is built over them
+};
+
 // remove.hip — the pieces of cdb_remove (capi.hip commits them), all on ix.stream with ix.mu held.  Everything is made in fresh
 // blocks of the plan while the old index stands.
-struct RemovePlan {
+struct RemovePlan : ColumnBlocks {
     uint64_t removed = 0, missing = 0;         // distinct documents dropped, entries of ids the index does not hold
     uint64_t ndocs = 0, size = 0, longest = 0;  // the surviving column
     DevBuf drop, newdoc, src_start;            // u8[old ndocs] flag, u32[old ndocs] old -> new document, u64[ndocs] old start of every survivor
-    DevBuf d_start, d_ids, text;               // the new tables and the new padded text
-    DevBuf sa, sa_hi, keys, keys32, keylow;    // the compacted array and search keys
-    int key_nsym = 0, key_low_bits = 0, key_low_bytes = 0;
-    uint32_t key_base = 0;
 };
 void remove_mark(Index& ix, const int64_t* ids, uint64_t nids, RemovePlan& p);  // flags, counts, and (something to drop) the new tables; synchronises
 void remove_text(Index& ix, RemovePlan& p);                                      // the kept documents gathered into p.text
 void remove_compact(Index& ix, RemovePlan& p, int new_bits, int new_width, bool new_packed);  // the array and its keys in the new layout
+// out (zeroed by the caller) = the longest document among those whose drop flag is 0 (drop = nullptr: among all), queued on s
+void longest_document(hipStream_t s, const uint8_t* drop, const uint64_t* doc_start, uint64_t ndocs, unsigned long long* out);
 
 // append.hip — the pieces of cdb_append (capi.hip uploads the new text between them and commits), all on ix.stream with ix.mu held.
-// Everything is made in fresh blocks of the plan while the old index stands.
-struct AppendPlan {
+// Everything is made in fresh blocks of the plan while the old index stands (old then new: the tables and the padded text).
+struct AppendPlan : ColumnBlocks {
     uint64_t ndocs = 0, size = 0, longest = 0;  // the new documents (filled by the caller) ...
     uint64_t in_bits = 1, in_mask = 1;          // ... and the layout of an index over them alone (the inner build)
     int in_width = 4, in_off_bits = 1;
     uint64_t old_longest = 0;                        // the built column's longest document
     bool high_bytes = false, unmapped_bytes = false;  // the new text holds bytes >= 0x80 / bytes the handle's symbol map codes as 0
-    DevBuf d_start, d_ids, text;                // old then new: the tables and the padded text
-    DevBuf sa, sa_hi, keys, keys32, keylow;     // the merged array and search keys
-    int key_nsym = 0, key_low_bits = 0, key_low_bytes = 0;
-    uint32_t key_base = 0;
-    bool keys_kept = false;
 };
 void append_old_longest(Index& ix, AppendPlan& p);  // synchronises
 void append_tables(Index& ix, AppendPlan& p, const int64_t* ids, const uint64_t* new_start);  // new_start[ndocs + 1]: based at the old size

@@ -7,20 +7,17 @@
 //   2. tables    a scan over the flags numbers the survivors and sums their lengths: new ids, new doc_start, the old
 //                start of every survivor, the old -> new document table (the flag stays separate: no value of it is spent)
 //   3. text      gather of the kept documents, cut by OUTPUT bytes (a 3 GiB document spreads over all workgroups)
-//   4. array     pass A counts the kept entries of every tile, a scan bases the tiles, pass B ranks inside the tile with
-//                ballots and an LDS prefix (stable) and writes entries and kept search keys in the new storage form
+//   4. array     the kept entries are ranked stably tile by tile (stable_tiles.h: count, scan, ballot ranks) and written with the
+//                kept search keys in the new storage form
 // Everything is written into fresh blocks of a RemovePlan while the old index stands.  64-bit indices throughout.
 #include "index_impl.h"
 #include "scan.h"
+#include "stable_tiles.h"
 
 namespace cdb {
 namespace {
 
-constexpr int RM_ROUNDS = 16;                 // entries per thread and tile
-constexpr int RM_TILE = 256 * RM_ROUNDS;      // entries per tile (one workgroup)
 constexpr uint64_t RM_TEXT_RANGE = 64u << 10;  // output bytes per workgroup step of the gather
-
-unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 256), 8192)); }
 
 // ---- 1. mark ----------------------------------------------------------------------------------------------------------------
 // out[0] += entries of ids the index does not hold; a held id given twice sets the same flag twice
@@ -67,14 +64,14 @@ struct TablesOut {
         if (d + 1 == ndocs) new_start[in.a] = in.b;
     }
 };
-// the longest kept document (as layout_kernel finds the longest of a resident column)
-__global__ __launch_bounds__(256) void rm_longest_kernel(const uint8_t* __restrict__ drop, const uint64_t* __restrict__ doc_start, uint64_t ndocs,
-                                                         unsigned long long* __restrict__ out) {
+// the longest document that is not dropped (drop = nullptr: of all; as layout_kernel finds the longest of a resident column)
+__global__ __launch_bounds__(256) void longest_document_kernel(const uint8_t* __restrict__ drop, const uint64_t* __restrict__ doc_start,
+                                                               uint64_t ndocs, unsigned long long* __restrict__ out) {
     __shared__ unsigned long long s_max[4];
     uint64_t mx = 0;
     const uint64_t stride = (uint64_t)gridDim.x * 256;
     for (uint64_t d = (uint64_t)blockIdx.x * 256 + threadIdx.x; d < ndocs; d += stride) {
-        const uint64_t len = drop[d] ? 0 : doc_start[d + 1] - doc_start[d];
+        const uint64_t len = drop && drop[d] ? 0 : doc_start[d + 1] - doc_start[d];
         mx = len > mx ? len : mx;
     }
     for (int off = 32; off; off >>= 1) {
@@ -147,50 +144,24 @@ __global__ __launch_bounds__(256) void rm_text_kernel(const uint8_t* __restrict_
 }
 
 // ---- 4. suffix array --------------------------------------------------------------------------------------------------------
-// pass A: kept entries per tile.  The document field lies below bit 32 in every layout: `lo` + i * stride is the entry's low word
-// (stride 1: u32 entries and the packed form's low words; 2: u64 entries)
-__global__ __launch_bounds__(256) void rm_count_kernel(const uint32_t* __restrict__ lo, int stride, uint64_t n, uint32_t mask,
-                                                       const uint8_t* __restrict__ drop, uint64_t* __restrict__ tile_count) {
-    __shared__ uint32_t s_w[4];
-    const uint64_t base = (uint64_t)blockIdx.x * RM_TILE;
-    uint32_t c = 0;
-#pragma unroll 4
-    for (int k = 0; k < RM_ROUNDS; ++k) {
-        const uint64_t i = base + (uint64_t)k * 256 + threadIdx.x;
-        if (i < n) c += drop[lo[i * (uint64_t)stride] & mask] ? 0u : 1u;
-    }
-    for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-struct TileBaseOut {
-    uint64_t* base;
-    __device__ __forceinline__ void operator()(uint64_t t, uint64_t ex, uint64_t) const { base[t] = ex; }
+// the flag of the ranking (stable_tiles.h): entry i is kept.  The document field lies below bit 32 in every layout: `lo` + i * stride
+// is the entry's low word (stride 1: u32 entries and the packed form's low words; 2: u64 entries)
+struct EntryKept {
+    const uint32_t* lo;
+    int stride;
+    uint32_t mask;
+    const uint8_t* drop;
+    __device__ __forceinline__ bool operator()(uint64_t i) const { return drop[lo[i * (uint64_t)stride] & mask] == 0; }
 };
 
-struct KeyArrays {  // the kept search keys beside the array, slot for slot (any of them may be absent)
-    const uint64_t* k64;
-    const uint32_t* k32;
-    const uint8_t* low;
-    int low_bytes;
-    uint64_t* o64;
-    uint32_t* o32;
-    uint8_t* olow;
-};
-
-// pass B: entry i of the tile's round k keeps its place among the kept: tile base + kept in earlier rounds + kept in earlier
-// waves of this round + kept in earlier lanes of its wave (ballot) — no atomics, so the order is the input's
+// kept entry number r of the input is entry r of the output, re-encoded; its stored search keys go with it as they are
 template <typename SrcTag, typename Dst>
 __global__ __launch_bounds__(256) void rm_compact_kernel(typename SaOf<SrcTag>::ptr sa, uint64_t n, int old_bits, uint64_t old_mask, int new_bits,
                                                          const uint8_t* __restrict__ drop, const uint32_t* __restrict__ newdoc,
-                                                         const uint64_t* __restrict__ tile_base, Dst out, KeyArrays keys) {
-    __shared__ uint32_t s_w[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t base = (uint64_t)blockIdx.x * RM_TILE;
-    uint64_t run = tile_base[blockIdx.x];
-    for (int k = 0; k < RM_ROUNDS; ++k) {
-        const uint64_t i = base + (uint64_t)k * 256 + threadIdx.x;
+                                                         const uint64_t* __restrict__ tile_base, Dst out, KeptKeys keys_in, KeptKeys keys_out) {
+    TileRanker ranker(tile_base);
+    for (int k = 0; k < ST_ROUNDS; ++k) {
+        const uint64_t i = tile_slot(k);
         uint64_t e = 0, d = 0;
         bool keep = false;
         if (i < n) {
@@ -198,31 +169,19 @@ __global__ __launch_bounds__(256) void rm_compact_kernel(typename SaOf<SrcTag>::
             d = e & old_mask;
             keep = drop[d] == 0;
         }
-        const uint64_t bal = __ballot(keep);
-        if (lane == 0) s_w[k & 1][wave] = (uint32_t)__popcll(bal);
-        __syncthreads();  // (the other half of s_w is still being read by the slowest wave of round k - 1: two halves, one barrier)
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const uint32_t c = s_w[k & 1][w];
-            before += w < wave ? c : 0u;
-            all += c;
-        }
+        const uint64_t at = ranker.before(k, keep);
         if (keep) {
-            const uint64_t at = run + before + (uint64_t)__popcll(bal & ((1ull << lane) - 1));
             out.store(at, (typename Dst::val)(((e >> old_bits) << new_bits) | (uint64_t)newdoc[d]));
-            if (keys.k64) keys.o64[at] = keys.k64[i];
-            if (keys.k32) keys.o32[at] = keys.k32[i];
-            if (keys.low) {
-                if (keys.low_bytes == 2) reinterpret_cast<uint16_t*>(keys.olow)[at] = reinterpret_cast<const uint16_t*>(keys.low)[i];
-                else keys.olow[at] = keys.low[i];
-            }
+            keys_out.copy(keys_in, i, at);
         }
-        run += all;
     }
 }
 
 }  // namespace
+
+void longest_document(hipStream_t s, const uint8_t* drop, const uint64_t* doc_start, uint64_t ndocs, unsigned long long* out) {
+    hipLaunchKernelGGL(longest_document_kernel, dim3(grid_for(ndocs)), dim3(256), 0, s, drop, doc_start, ndocs, out);
+}
 
 void remove_mark(Index& ix, const int64_t* ids, uint64_t nids, RemovePlan& p) {
     hipStream_t s = ix.stream;
@@ -246,8 +205,7 @@ void remove_mark(Index& ix, const int64_t* ids, uint64_t nids, RemovePlan& p) {
     // survivors and their bytes (the host sizes the new tables from them)
     KeptIn kin{p.drop.as<uint8_t>(), doc_start};
     t = ix.prof.begin(s);
-    hipLaunchKernelGGL(rm_longest_kernel, dim3(grid_for(ndocs)), dim3(256), 0, s, (const uint8_t*)p.drop.as<uint8_t>(), doc_start, ndocs,
-                       d_out.as<unsigned long long>() + 1);
+    longest_document(s, p.drop.as<uint8_t>(), doc_start, ndocs, d_out.as<unsigned long long>() + 1);
     uint64_t out[2] = {0, 0};
     CDB_HIP(hipMemcpyAsync(out, d_out.p, 16, hipMemcpyDeviceToHost, s));
     const U2 tot = scan_totals<U2>(s, ix.scan_partials, kin, ndocs, OpAdd{}, U2{0, 0});  // (synchronises: out is here)
@@ -287,68 +245,31 @@ void remove_text(Index& ix, RemovePlan& p) {
 void remove_compact(Index& ix, RemovePlan& p, int new_bits, int new_width, bool new_packed) {
     hipStream_t s = ix.stream;
     const uint64_t n = ix.size, m = p.size;
-    if (new_packed) {
-        p.sa.alloc(std::max<uint64_t>(m, 4) * 4);
-        p.sa_hi.alloc(std::max<uint64_t>(m, 16));
-    } else {
-        p.sa.alloc(std::max<uint64_t>(m * (uint64_t)new_width, 16));
-    }
-    p.key_nsym = 0;
+    p.arr.alloc(m, new_width, new_packed);
     if (!m) return;  // (what a build leaves for an empty column: a block, no keys)
-    KeyArrays keys{};
-    if (ix.key_nsym && (ix.d_keys.p || ix.d_keys32.p)) {
-        p.key_nsym = ix.key_nsym;
-        p.key_base = ix.key_base;
-        p.key_low_bits = ix.key_low_bits;
-        p.key_low_bytes = ix.key_low_bytes;
-        if (ix.d_keys.p) {
-            p.keys.alloc(m * 8);
-            keys.k64 = ix.d_keys.as<uint64_t>();
-            keys.o64 = p.keys.as<uint64_t>();
-        }
-        if (ix.d_keys32.p) {
-            p.keys32.alloc(m * 4);
-            keys.k32 = ix.d_keys32.as<uint32_t>();
-            keys.o32 = p.keys32.as<uint32_t>();
-        }
-        if (ix.d_keylow.p) {
-            keys.low_bytes = std::max(ix.key_low_bytes, 1);
-            p.keylow.alloc(m * (uint64_t)keys.low_bytes);
-            keys.low = ix.d_keylow.as<uint8_t>();
-            keys.olow = p.keylow.as<uint8_t>();
-        }
-    }
-    const uint64_t key_bytes = (keys.k64 ? 8 : 0) + (keys.k32 ? 4 : 0) + (keys.low ? keys.low_bytes : 0);
-    const uint64_t ntiles = ceil_div(n, RM_TILE);
-    if (ntiles >= (1ull << 31)) throw Error("remove: the array has too many tiles for one launch (internal)");
-    DevBuf tile_count, tile_base;
-    tile_count.alloc(ntiles * 8);
-    tile_base.alloc(ntiles * 8);
+    const bool with_keys = ix.key_nsym && (ix.d_keys.p || ix.d_keys32.p);
+    const KeptKeys keys_in = with_keys ? keys_of(ix) : KeptKeys{}, keys_out = with_keys ? p.arr.alloc_keys_like(ix, m) : KeptKeys{};
+    const uint64_t ntiles = ceil_div(n, ST_TILE);
+    DevBuf tile_base;
+    const EntryKept kept{ix.d_sa.as<uint32_t>(), (!ix.sa_packed && ix.width == 8) ? 2 : 1, (uint32_t)ix.mask, p.drop.as<uint8_t>()};
+    if (tile_bases(ix, "remove", kept, n, tile_base, "rm_count", n * (4 + 1) + ntiles * 8) != m)
+        throw Error("remove: kept entries and kept bytes differ (internal)");
     const int old_bytes = ix.sa_packed ? 5 : ix.width;
-    int t = ix.prof.begin(s);
-    hipLaunchKernelGGL(rm_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, (const uint32_t*)ix.d_sa.as<uint32_t>(),
-                       (!ix.sa_packed && ix.width == 8) ? 2 : 1, n, (uint32_t)ix.mask, (const uint8_t*)p.drop.as<uint8_t>(), tile_count.as<uint64_t>());
-    ix.prof.end(t, "rm_count", n * (4 + 1) + ntiles * 8, s);
-    CDB_HIP(hipGetLastError());
-    PartialsIn<uint64_t> tin{tile_count.as<uint64_t>()};
-    const uint64_t kept = scan_totals<uint64_t>(s, ix.scan_partials, tin, ntiles, OpAdd{}, (uint64_t)0);
-    if (kept != m) throw Error("remove: kept entries and kept bytes differ (internal)");
-    scan_apply<uint64_t>(s, ix.scan_partials, tin, ntiles, OpAdd{}, (uint64_t)0, TileBaseOut{tile_base.as<uint64_t>()});
-    CDB_HIP(hipGetLastError());
-    t = ix.prof.begin(s);
+    const int t = ix.prof.begin(s);
     sa_dispatch(ix, [&](auto src_tag) {
         using S = decltype(src_tag);
         auto launch = [&](auto dst) {
             using D = decltype(dst);
             hipLaunchKernelGGL((rm_compact_kernel<S, D>), dim3((unsigned)ntiles), dim3(256), 0, s, ix.sa_view<S>(), n, (int)ix.bits, ix.mask, new_bits,
                                (const uint8_t*)p.drop.as<uint8_t>(), (const uint32_t*)p.newdoc.as<uint32_t>(),
-                               (const uint64_t*)tile_base.as<uint64_t>(), dst, keys);
+                               (const uint64_t*)tile_base.as<uint64_t>(), dst, keys_in, keys_out);
         };
-        if (new_packed) launch(Sa40RW{p.sa.as<uint32_t>(), p.sa_hi.as<uint8_t>()});
-        else if (new_width == 8) launch(SaRW<uint64_t>{p.sa.as<uint64_t>()});
-        else launch(SaRW<uint32_t>{p.sa.as<uint32_t>()});
+        if (new_packed) launch(Sa40RW{p.arr.sa.as<uint32_t>(), p.arr.sa_hi.as<uint8_t>()});
+        else if (new_width == 8) launch(SaRW<uint64_t>{p.arr.sa.as<uint64_t>()});
+        else launch(SaRW<uint32_t>{p.arr.sa.as<uint32_t>()});
     });
-    ix.prof.end(t, "rm_compact", n * ((uint64_t)old_bytes + 1) + m * ((new_packed ? 5 : (uint64_t)new_width) + 4 + 2 * key_bytes) + ntiles * 8, s);
+    ix.prof.end(t, "rm_compact",
+                n * ((uint64_t)old_bytes + 1) + m * ((new_packed ? 5 : (uint64_t)new_width) + 4 + 2 * keys_out.bytes_per_slot()) + ntiles * 8, s);
     CDB_HIP(hipGetLastError());
 }
 

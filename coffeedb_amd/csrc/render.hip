@@ -42,7 +42,6 @@ double wall_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
-unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 256), 8192)); }
 
 // row i -> doc[i] (RN_NODOC: the index does not hold ids[i]) and found[i]; out[0] += rows missed, out[1] = longest document met
 __global__ __launch_bounds__(256) void rnd_lookup_kernel(const int64_t* __restrict__ ids, uint64_t nrows, const int64_t* __restrict__ id_tab,

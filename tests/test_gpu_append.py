@@ -124,6 +124,28 @@ def test_many_tiles_equal_fresh_build(corpus_b, count):
     assert g.stat("append_docs") == count and g.stat("append_bytes") == sum(len(d) for d in new)
 
 
+# ---- 2b. merged lengths on the edges of a round (256 slots) and of a tile (4096) ------------------------------------------------
+def split(total, parts, rng):
+    """`parts` lengths >= 0 that sum to `total`"""
+    cuts = np.sort(rng.integers(0, total + 1, size=parts - 1))
+    return [int(x) for x in np.diff(np.concatenate([[0], cuts, [total]]))]
+
+
+@pytest.mark.parametrize("where", ["below", "above"])
+@pytest.mark.parametrize("total", [255, 256, 257, 4095, 4096, 4097, 8192])
+def test_round_and_tile_edges_equal_fresh_build(total, where):
+    # every new byte sorts below (above) every old byte: all new entries take the first (last) slots of the merged array
+    rng = np.random.default_rng(total)
+    m = total // 4
+    lo = 0x02 if where == "below" else ord("}")
+    docs = [bytes(rng.integers(0, 4, size=k, dtype=np.uint8) + ord("a")) for k in split(total - m, 12, rng)]
+    new = [bytes(rng.integers(0, 2, size=k, dtype=np.uint8) + lo) for k in split(m, 4, rng)]
+    g, f = append_and_compare(list(range(100, 112)), docs, list(range(500, 504)), new)
+    assert (f.size, g.sa_width) == (total, 4) and g.stat("append_merges") == 1
+    new_slots = np.flatnonzero((g.sa().astype(np.uint64) & np.uint64(g.mask)) >= 12)
+    assert np.array_equal(new_slots, np.arange(m) + (0 if where == "below" else total - m))
+
+
 # ---- 3. layout growth ----------------------------------------------------------------------------------------------------
 def _edge(name):
     rng = np.random.default_rng(3)

@@ -136,6 +136,33 @@ def test_empty_id_list_changes_nothing(corpus_b):
     assert np.array_equal(g.sa(), before)
 
 
+# ---- 1b. array lengths on the edges of a round (256 entries) and of a tile (4096) ---------------------------------------------
+def split(total, parts, rng):
+    """`parts` lengths >= 0 that sum to `total`"""
+    cuts = np.sort(rng.integers(0, total + 1, size=parts - 1))
+    return [int(x) for x in np.diff(np.concatenate([[0], cuts, [total]]))]
+
+
+EDGE_N = [255, 256, 257, 4095, 4096, 4097, 8192]
+# (old length, which documents go, kept length): half and nearly all of every old length, and the kept length itself on a tile edge
+EDGE_CASES = ([(n, "every_second", n // 2) for n in EDGE_N] + [(n, "last", n - 1 - n // 16) for n in EDGE_N] +
+              [(8192, "last", 4097), (4097, "last", 4096), (8192, "every_second", 4097)])
+
+
+@pytest.mark.parametrize("n,which,kept", EDGE_CASES)
+def test_round_and_tile_edges_equal_fresh_build(n, which, kept):
+    rng = np.random.default_rng(n * 3 + kept)
+    if which == "every_second":   # documents 0, 2, 4, ... go
+        lens = [x for pair in zip(split(n - kept, 8, rng), split(kept, 8, rng)) for x in pair]
+    else:
+        lens = split(kept, 15, rng) + [n - kept]
+    docs = [bytes(rng.integers(0, 4, size=m, dtype=np.uint8) + ord("a")) for m in lens]
+    ids = list(range(100, 100 + len(docs)))
+    gone = ids[::2] if which == "every_second" else [ids[-1]]
+    g, f = remove_and_compare(ids, docs, gone)
+    assert (sum(lens), f.size, g.sa_width) == (n, kept, 4) and g.stat("remove_compactions") == 1
+
+
 # ---- 2. layout edges ---------------------------------------------------------------------------------------------------
 def _edge(name):
     rng = np.random.default_rng(3)
