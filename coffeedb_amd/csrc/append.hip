@@ -79,11 +79,6 @@ __device__ __forceinline__ uint64_t key_at(const KeptKeys& k, uint64_t i) {
     else return ((uint64_t)k.k32[i] << k.low_bits) | (uint64_t)reinterpret_cast<const uint16_t*>(k.low)[i];
 }
 // ---- 3. rank ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t load_be8(const uint8_t* p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return __builtin_bswap64(v);
-}
 // s <= t ?  (cmp_common's rule: unsigned bytes, shorter first, equal counts as "<=").  The first k bytes of both are known to be
 // equal; lcp = the length of their common prefix.  Neither suffix is read past its end.
 __device__ __forceinline__ bool suffix_le(const uint8_t* __restrict__ s, uint64_t sl, const uint8_t* __restrict__ t, uint64_t tl, uint64_t k,

@@ -36,6 +36,12 @@ inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 inline int bit_width64(uint64_t x) { return x == 0 ? 0 : 64 - __builtin_clzll(x); }
 // workgroups of 256 threads for a grid-stride loop over n items
 inline unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n, 256), 8192)); }
+// 8 text bytes as a big-endian integer: integer order == unsigned lexicographic order
+__device__ __forceinline__ uint64_t load_be8(const uint8_t* p) {
+    uint64_t v;
+    __builtin_memcpy(&v, p, 8);
+    return __builtin_bswap64(v);
+}
 
 // The stream the calling thread is currently issuing device work on (set by every C-ABI entry point through
 // StreamScope).  DevPool uses it to make block reuse stream-aware: a block released while kernels of that stream

@@ -63,13 +63,72 @@ struct QueryStats {
     uint64_t empty_batches = 0;                  // nothing to look up (no pattern, no text) or no hit at all
 };
 
-// kept sort keys for the lone-keyword kernels (query.hip): suffixes starting with the keyword's first min(m, nsym) symbols
-// are exactly those with key in [klo, khi] (coded on the host); decisive = the keyword has at most nsym symbols
+// ---- the kept search keys as kernels see them, slot for slot beside the array, in whichever form a handle holds them (d_keys, or
+// d_keys32 = key >> low_bits with the low digits in one or two bytes of d_keylow; a form that is absent is a null pointer; a handle
+// without keys gives the empty view: keys_of below)
+struct KeptKeys {
+    uint64_t* k64 = nullptr;
+    uint32_t* k32 = nullptr;
+    uint8_t* low = nullptr;
+    int low_bits = 0, low_bytes = 0;
+    __host__ __device__ __forceinline__ bool present() const { return k64 != nullptr || k32 != nullptr; }
+    __device__ __forceinline__ uint64_t low_at(uint64_t i) const {
+        return low_bytes == 2 ? (uint64_t)reinterpret_cast<const uint16_t*>(low)[i] : (uint64_t)low[i];
+    }
+    __device__ __forceinline__ uint64_t at(uint64_t i) const {
+        if (k64) return k64[i];
+        const uint64_t h = k32[i];
+        if (!low_bits) return h;
+        return (h << low_bits) | low_at(i);
+    }
+    // slot i against the key range [klo, khi]: -1 its key lies below, +1 above, 0 inside (the suffix starts with the symbols the
+    // range was coded from: query.hip, key_range).  Split keys: the 32-bit part alone decides unless it equals the truncated range
+    // end it is compared with, and the low digits are fetched only then.  (The lone-keyword kernels fetch them beside the high
+    // part and keep their own compare: query.hip, q_single_answer.)
+    __device__ __forceinline__ int cmp_range(uint64_t i, uint64_t klo, uint64_t khi) const {
+        uint64_t key;
+        if (k64) {
+            key = k64[i];
+        } else {
+            const uint64_t h = k32[i];
+            if (low) {
+                const uint64_t a = klo >> low_bits, b = khi >> low_bits;
+                if (h < a) return -1;
+                if (h > b) return 1;
+                if (h > a && h < b) return 0;
+                key = (h << low_bits) | low_at(i);
+            } else {
+                key = h;
+            }
+        }
+        return key < klo ? -1 : (key > khi ? 1 : 0);
+    }
+    __device__ __forceinline__ void put(uint64_t i, uint64_t key) const {
+        if (k64) k64[i] = key;
+        if (k32) k32[i] = (uint32_t)(key >> low_bits);
+        if (low) {
+            const uint64_t l = key & ((1ull << low_bits) - 1ull);
+            if (low_bytes == 2) reinterpret_cast<uint16_t*>(low)[i] = (uint16_t)l;
+            else low[i] = (uint8_t)l;
+        }
+    }
+    // slot `from` of src into slot `to`, every stored form as it is (src holds the same forms)
+    __device__ __forceinline__ void copy(const KeptKeys& src, uint64_t from, uint64_t to) const {
+        if (k64) k64[to] = src.k64[from];
+        if (k32) k32[to] = src.k32[from];
+        if (low) {
+            if (low_bytes == 2) reinterpret_cast<uint16_t*>(low)[to] = reinterpret_cast<const uint16_t*>(src.low)[from];
+            else low[to] = src.low[from];
+        }
+    }
+    uint64_t bytes_per_slot() const { return (k64 ? 8 : 0) + (k32 ? 4 : 0) + (low ? low_bytes : 0); }
+};
+// the kept keys for the lone-keyword kernels (query.hip): suffixes starting with the keyword's first min(m, nsym) symbols are exactly
+// those with key in [klo, khi] (coded on the host); decisive = the keyword has at most nsym symbols.  nsym = 0: no keys, the text
+// decides every probe
 struct SingleKeys {
-    const uint64_t* keys64 = nullptr;
-    const uint32_t* keys32 = nullptr;
-    const void* keylow = nullptr;
-    int low_bits = 0, low_bytes = 0, nsym = 0;
+    KeptKeys keys;
+    int nsym = 0;
     bool decisive = false;
     uint64_t klo = 0, khi = 0;
     // slots the lower bound can lie in, from the host-side key directory (query.hip: query_keydir_ensure): every slot in
@@ -397,39 +456,6 @@ __device__ __forceinline__ uint64_t lower_bound_id(const int64_t* __restrict__ i
     return a;
 }
 
-// ---- the kept search keys as kernels see them, slot for slot beside the array, in whichever form a handle holds them (d_keys, or
-// d_keys32 = key >> low_bits with the low digits in one or two bytes of d_keylow; a form that is absent is a null pointer)
-struct KeptKeys {
-    uint64_t* k64 = nullptr;
-    uint32_t* k32 = nullptr;
-    uint8_t* low = nullptr;
-    int low_bits = 0, low_bytes = 0;
-    __device__ __forceinline__ uint64_t at(uint64_t i) const {
-        if (k64) return k64[i];
-        const uint64_t h = k32[i];
-        if (!low_bits) return h;
-        return (h << low_bits) | (low_bytes == 2 ? (uint64_t)reinterpret_cast<const uint16_t*>(low)[i] : (uint64_t)low[i]);
-    }
-    __device__ __forceinline__ void put(uint64_t i, uint64_t key) const {
-        if (k64) k64[i] = key;
-        if (k32) k32[i] = (uint32_t)(key >> low_bits);
-        if (low) {
-            const uint64_t l = key & ((1ull << low_bits) - 1ull);
-            if (low_bytes == 2) reinterpret_cast<uint16_t*>(low)[i] = (uint16_t)l;
-            else low[i] = (uint8_t)l;
-        }
-    }
-    // slot `from` of src into slot `to`, every stored form as it is (src holds the same forms)
-    __device__ __forceinline__ void copy(const KeptKeys& src, uint64_t from, uint64_t to) const {
-        if (k64) k64[to] = src.k64[from];
-        if (k32) k32[to] = src.k32[from];
-        if (low) {
-            if (low_bytes == 2) reinterpret_cast<uint16_t*>(low)[to] = reinterpret_cast<const uint16_t*>(src.low)[from];
-            else low[to] = src.low[from];
-        }
-    }
-    uint64_t bytes_per_slot() const { return (k64 ? 8 : 0) + (k32 ? 4 : 0) + (low ? low_bytes : 0); }
-};
 inline KeptKeys keys_of(const Index& ix) {
     return KeptKeys{ix.d_keys.as<uint64_t>(), ix.d_keys32.as<uint32_t>(), ix.d_keylow.as<uint8_t>(), ix.key_low_bits,
                     ix.d_keylow.p ? std::max(ix.key_low_bytes, 1) : 0};

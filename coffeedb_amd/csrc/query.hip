@@ -19,13 +19,6 @@
 namespace cdb {
 namespace {
 
-__device__ __forceinline__ uint64_t load_be8(const uint8_t* p) {
-    // 8 text bytes as a big-endian integer: integer order == unsigned lexicographic order
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return __builtin_bswap64(v);
-}
-
 // three-way compare of keyword k[0..m) against suffix s[0..sl) on their common length, then the
 // reference's two predicates are derived from (c, m, sl):
 //   keyword <= suffix  <=>  c < 0 || (c == 0 && m <= sl)          (index.cpp:267, string_view <=)
@@ -45,45 +38,67 @@ __device__ __forceinline__ int cmp_common(const uint8_t* __restrict__ k, uint64_
     return 0;
 }
 
+// a suffix-array entry -> the suffix it names: where its text starts and how many bytes its document has left from there
+struct SuffixText {
+    const uint8_t* text;
+    const uint64_t* doc_start;
+    int bits;
+    uint64_t mask;
+    template <typename E>
+    __device__ __forceinline__ const uint8_t* at(E e, uint64_t& sl) const {
+        const uint64_t d = (uint64_t)e & mask, off = (uint64_t)e >> bits;
+        const uint64_t b = doc_start[d] + off;
+        sl = doc_start[d + 1] - b;
+        return text + b;
+    }
+};
+inline SuffixText suffix_text(const Index& ix) { return SuffixText{ix.d_text, ix.d_doc_start.as<uint64_t>(), (int)ix.bits, ix.mask}; }
+
+// what every search kernel is launched with (launch_search): the array over its text, the batch, and where the bounds go
 template <typename V>
-__global__ __launch_bounds__(256) void q_search_kernel(typename SaOf<V>::ptr sa, uint64_t n,
-                                                       const uint8_t* __restrict__ text,
-                                                       const uint64_t* __restrict__ doc_start, int bits, uint64_t mask,
-                                                       const uint8_t* __restrict__ blob,
-                                                       const uint64_t* __restrict__ offs, uint64_t npat,
-                                                       int64_t* __restrict__ left_out, uint64_t* __restrict__ hits_out) {
+struct SearchArgs {
+    typename SaOf<V>::ptr sa;
+    uint64_t n;
+    SuffixText st;
+    const uint8_t* blob;
+    const uint64_t* offs;
+    uint64_t npat;
+    int64_t* left_out;
+    uint64_t* hits_out;
+};
+
+template <typename V>
+__global__ __launch_bounds__(256) void q_search_kernel(SearchArgs<V> a) {
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= npat) return;
-    const uint8_t* k = blob + offs[j];
-    const uint64_t m = offs[j + 1] - offs[j];
-    if (m == 0 || offs[j + 1] < offs[j]) {  // empty pattern (device batches are not pre-validated): no rows
-        left_out[j] = 0;
-        hits_out[j] = 0;
+    if (j >= a.npat) return;
+    const uint8_t* k = a.blob + a.offs[j];
+    const uint64_t m = a.offs[j + 1] - a.offs[j];
+    if (m == 0 || a.offs[j + 1] < a.offs[j]) {  // empty pattern (device batches are not pre-validated): no rows
+        a.left_out[j] = 0;
+        a.hits_out[j] = 0;
         return;
     }
-    int64_t L = 0, R = (int64_t)n - 1;
+    int64_t L = 0, R = (int64_t)a.n - 1;
     while (L < R) {
         const int64_t M = L + (R - L) / 2;
-        const auto e = sa[M];
-        const uint64_t d = (uint64_t)e & mask, off = (uint64_t)e >> bits;
-        const uint64_t b = doc_start[d] + off, sl = doc_start[d + 1] - b;
-        const int c = cmp_common(k, m, text + b, sl);
+        uint64_t sl;
+        const uint8_t* sp = a.st.at(a.sa[M], sl);
+        const int c = cmp_common(k, m, sp, sl);
         if (c < 0 || (c == 0 && m <= sl)) R = M; else L = M + 1;
     }
     const int64_t left = L;
     L = left - 1;
-    R = (int64_t)n - 1;
+    R = (int64_t)a.n - 1;
     while (L < R) {
         const int64_t M = L + (R - L + 1) / 2;
-        const auto e = sa[M];
-        const uint64_t d = (uint64_t)e & mask, off = (uint64_t)e >> bits;
-        const uint64_t b = doc_start[d] + off, sl = doc_start[d + 1] - b;
-        const bool pref = sl >= m && cmp_common(k, m, text + b, sl) == 0;
+        uint64_t sl;
+        const uint8_t* sp = a.st.at(a.sa[M], sl);
+        const bool pref = sl >= m && cmp_common(k, m, sp, sl) == 0;
         if (pref) L = M; else R = M - 1;
     }
     const int64_t right = L + 1;
-    left_out[j] = left;
-    hits_out[j] = right > left ? (uint64_t)(right - left) : 0ull;
+    a.left_out[j] = left;
+    a.hits_out[j] = right > left ? (uint64_t)(right - left) : 0ull;
 }
 
 // ---- fast search for globally sorted suffix arrays ---------------------------------------------------
@@ -104,10 +119,8 @@ struct Pivot {
 };
 
 template <typename V>
-__global__ __launch_bounds__(256) void q_pivots_kernel(typename SaOf<V>::ptr sa, uint64_t n,
-                                                       const uint8_t* __restrict__ text,
-                                                       const uint64_t* __restrict__ doc_start, int bits, uint64_t mask,
-                                                       int levels, Pivot* __restrict__ piv) {
+__global__ __launch_bounds__(256) void q_pivots_kernel(typename SaOf<V>::ptr sa, uint64_t n, SuffixText st, int levels,
+                                                       Pivot* __restrict__ piv) {
     const uint32_t id = blockIdx.x * 256 + threadIdx.x + 1;  // heap order: root 1, children 2id (R = M), 2id+1 (L = M+1)
     if (id >= (1u << levels)) return;
     int depth = 31 - __clz(id);
@@ -121,11 +134,10 @@ __global__ __launch_bounds__(256) void q_pivots_kernel(typename SaOf<V>::ptr sa,
     Pivot p{0, 0, 0};
     if (!dead && L < R) {
         const int64_t M = L + (R - L) / 2;
-        const auto e = sa[M];
-        const uint64_t d = (uint64_t)e & mask, off = (uint64_t)e >> bits;
-        const uint64_t b0 = doc_start[d] + off, sl = doc_start[d + 1] - b0;
+        uint64_t sl;
+        const uint8_t* sp = st.at(sa[M], sl);
         uint64_t w[2] = {0, 0};
-        for (int k = 0; k < 16 && (uint64_t)k < sl; ++k) w[k >> 3] |= (uint64_t)text[b0 + k] << (56 - 8 * (k & 7));
+        for (int k = 0; k < 16 && (uint64_t)k < sl; ++k) w[k >> 3] |= (uint64_t)sp[k] << (56 - 8 * (k & 7));
         p = Pivot{w[0], w[1], sl};
     }
     piv[id] = p;
@@ -146,101 +158,71 @@ __device__ __forceinline__ int kw_le_pivot(uint64_t khi, uint64_t klo, uint64_t 
     return 2;
 }
 
+// A keyword in the key alphabet: its first min(m, nsym) symbol codes as a number in base kbase, packed like the kept keys.  The
+// suffixes that start with those symbols are exactly those with key in [klo, khi]; decisive = the keys hold the whole keyword
+// (m <= nsym: a key inside the range is a match); absent = the keyword holds a byte that does not occur in the text (code 0),
+// so it occurs nowhere.  Coded on the device for a batch and on the host for a lone keyword.
+struct KeyRange {
+    bool absent;
+    uint64_t klo, khi;
+    bool decisive;
+};
+__host__ __device__ __forceinline__ KeyRange key_range(const uint16_t* code, const uint8_t* k, uint64_t m, int nsym, uint32_t kbase) {
+    const int kc = (int)(m < (uint64_t)nsym ? m : (uint64_t)nsym);
+    uint64_t kwc = 0;
+    bool absent = false;
+    for (int q = 0; q < kc; ++q) {
+        const uint64_t c = code[k[q]];
+        absent |= c == 0;
+        kwc = kwc * kbase + c;
+    }
+    for (uint64_t q = kc; q < m; ++q) absent |= code[k[q]] == 0;
+    uint64_t kpw = 1;
+    for (int q = kc; q < nsym; ++q) kpw *= kbase;
+    const uint64_t klo = kwc * kpw;
+    return KeyRange{absent, klo, klo + (kpw - 1), m <= (uint64_t)nsym};
+}
+
 // G = lanes per keyword.  G = 1: plain bisection below the pivot levels.  G = 8: the lanes of a group probe G slots per
 // round, which split the range G + 1 ways — log9 instead of log2 rounds of DEPENDENT loads (6 instead of 19 below the
 // pivot levels at 2^30 suffixes) for G times the loads: the better trade while a batch is too small to fill the GPU
 // with one thread per keyword.  The array is sorted, so every search strategy finds the same bounds.
 template <typename V, int G>
-__global__ __launch_bounds__(256) void q_search_fast_kernel(typename SaOf<V>::ptr sa, uint64_t n,
-                                                            const uint8_t* __restrict__ text,
-                                                            const uint64_t* __restrict__ doc_start, int bits,
-                                                            uint64_t mask, const uint8_t* __restrict__ blob,
-                                                            const uint64_t* __restrict__ offs, uint64_t npat,
-                                                            const Pivot* __restrict__ piv, int levels,
-                                                            const uint64_t* __restrict__ keys64,
-                                                            const uint32_t* __restrict__ keys32,
-                                                            const void* __restrict__ keylow, int low_bits, int low_bytes,
+__global__ __launch_bounds__(256) void q_search_fast_kernel(SearchArgs<V> a, const Pivot* __restrict__ piv, int levels, KeptKeys kk,
                                                             const uint16_t* __restrict__ symmap, int nsym, uint32_t kbase,
-                                                            bool refseq, int64_t* __restrict__ left_out,
-                                                            uint64_t* __restrict__ hits_out) {
+                                                            bool refseq) {
     __shared__ Pivot s_piv[PIVOT_NODES + 1];
     __shared__ uint16_t s_code[256];
-    const bool keys = keys64 != nullptr || keys32 != nullptr;  // sorted initial keys available
+    const uint64_t n = a.n;
+    const bool keys = kk.present();  // sorted initial keys available
     // (refseq: a reference-compat ordering — not globally sorted — is searched with the reference's own two
     //  bisections, levels = 0; the kept keys, reordered with the array, still decide most probes from one load)
     for (int i = threadIdx.x; levels > 0 && i < (1 << levels); i += 256) s_piv[i] = piv[i];
     if (keys) s_code[threadIdx.x] = symmap[threadIdx.x];
     __syncthreads();
     const uint64_t j = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / G;
-    if (j >= npat) return;
+    if (j >= a.npat) return;
     const int sub = (int)(threadIdx.x & (G - 1));             // this lane's place in its group
     const int gshift = (int)((threadIdx.x & 63) & ~(G - 1));  // first lane of the group inside the wavefront
-    const uint8_t* k = blob + offs[j];
-    const uint64_t m = offs[j + 1] - offs[j];
-    if (m == 0 || offs[j + 1] < offs[j]) {  // empty pattern (device batches are not pre-validated): no rows
+    const uint8_t* k = a.blob + a.offs[j];
+    const uint64_t m = a.offs[j + 1] - a.offs[j];
+    // (empty pattern — device batches are not pre-validated — or one that occurs nowhere: no rows)
+    auto no_rows = [&]() {
         if (sub == 0) {
-            left_out[j] = 0;
-            hits_out[j] = 0;
+            a.left_out[j] = 0;
+            a.hits_out[j] = 0;
         }
-        return;
-    }
+    };
+    if (m == 0 || a.offs[j + 1] < a.offs[j]) return no_rows();
     uint64_t kw[2] = {0, 0};
     for (int q = 0; q < 16 && (uint64_t)q < m; ++q) kw[q >> 3] |= (uint64_t)k[q] << (56 - 8 * (q & 7));
-    // keyword in the key alphabet: its first min(m, nsym) symbol codes, packed like keys[]; a byte that
-    // does not occur in the text (code 0) means the keyword occurs nowhere
-    const int kc = keys ? (int)(m < (uint64_t)nsym ? m : (uint64_t)nsym) : 0;
-    uint64_t kwc = 0;
-    bool absent = false;
-    for (int q = 0; q < kc; ++q) {
-        const uint64_t c = s_code[k[q]];
-        absent |= c == 0;
-        kwc = kwc * kbase + c;
-    }
-    if (keys)
-        for (uint64_t q = kc; q < m; ++q) absent |= s_code[k[q]] == 0;
-    if (absent) {
-        if (sub == 0) {
-            left_out[j] = 0;
-            hits_out[j] = 0;
-        }
-        return;
-    }
-    // keys are numbers in base kbase: the suffixes starting with the keyword's first kc symbols are exactly
-    // those with key in [klo, klo + kpw)
-    uint64_t kpw = 1;
-    for (int q = kc; q < nsym; ++q) kpw *= kbase;
-    const uint64_t klo = kwc * kpw;
+    KeyRange kr{false, 0, 0, false};
+    if (keys) kr = key_range(s_code, k, m, nsym, kbase);
+    if (kr.absent) return no_rows();
     // three-way answer from the key of slot M alone: -1 suffix < keyword, +1 keyword < suffix,
-    // 0 = the suffix starts with the keyword's first kc symbols (decisive iff m <= nsym)
-    // (split keys: key = (keys32 << low_bits) | keylow; the 32-bit part alone decides unless it equals the
-    //  truncated range end it is compared with)
-    const uint64_t khi = klo + (kpw - 1);  // last key of the range
-    auto key_cmp = [&](int64_t M) -> int {
-        uint64_t sk;
-        if (keys64) {
-            sk = keys64[M];
-        } else {
-            const uint64_t h = keys32[M];
-            if (keylow) {
-                const uint64_t a = klo >> low_bits, b = khi >> low_bits;
-                if (h < a) return -1;
-                if (h > b) return 1;
-                if (h > a && h < b) return 0;
-                sk = (h << low_bits) | (low_bytes == 1 ? (uint64_t)static_cast<const uint8_t*>(keylow)[M]
-                                                        : (uint64_t)static_cast<const uint16_t*>(keylow)[M]);
-            } else {
-                sk = h;
-            }
-        }
-        return sk < klo ? -1 : (sk > khi ? 1 : 0);
-    };
-    auto suffix_of = [&](int64_t M, const uint8_t*& sp, uint64_t& sl) {
-        const auto e = sa[M];
-        const uint64_t d = (uint64_t)e & mask, off = (uint64_t)e >> bits;
-        const uint64_t b = doc_start[d] + off;
-        sp = text + b;
-        sl = doc_start[d + 1] - b;
-    };
+    // 0 = the suffix starts with the keyword's first min(m, nsym) symbols (decisive iff m <= nsym)
+    auto key_cmp = [&](int64_t M) -> int { return kk.cmp_range((uint64_t)M, kr.klo, kr.khi); };
+    auto suffix_of = [&](int64_t M, const uint8_t*& sp, uint64_t& sl) { sp = a.st.at(a.sa[M], sl); };
     // ---- lower bound (index.cpp:260-274), first `levels` levels from LDS
     int64_t L = 0, R = (int64_t)n - 1;
     uint32_t id = 1;
@@ -248,7 +230,7 @@ __global__ __launch_bounds__(256) void q_search_fast_kernel(typename SaOf<V>::pt
         if (le == 2 && keys) {
             const int c = key_cmp(M);
             if (c != 0) le = c > 0 ? 1 : 0;
-            else if (m <= (uint64_t)nsym) le = 1;  // keyword is a prefix of the suffix: keyword <= suffix
+            else if (kr.decisive) le = 1;  // keyword is a prefix of the suffix: keyword <= suffix
         }
         if (le == 2) {
             const uint8_t* sp;
@@ -296,7 +278,7 @@ __global__ __launch_bounds__(256) void q_search_fast_kernel(typename SaOf<V>::pt
     auto is_prefix = [&](int64_t M) -> bool {
         if (keys) {
             if (key_cmp(M) != 0) return false;
-            if (m <= (uint64_t)nsym) return true;
+            if (kr.decisive) return true;
         }
         const uint8_t* sp;
         uint64_t sl;
@@ -344,8 +326,8 @@ __global__ __launch_bounds__(256) void q_search_fast_kernel(typename SaOf<V>::pt
         right = good + 1;
     }
     if (sub == 0) {
-        left_out[j] = left;
-        hits_out[j] = right > left ? (uint64_t)(right - left) : 0ull;
+        a.left_out[j] = left;
+        a.hits_out[j] = right > left ? (uint64_t)(right - left) : 0ull;
     }
 }
 
@@ -590,49 +572,58 @@ void grow_keep(DevBuf& b, size_t need, size_t used, hipStream_t s) {
     b = std::move(nb);
 }
 
-// runs the keyword search (fast path on sorted arrays, the reference's probe sequence otherwise)
+// runs the keyword search (fast path on sorted arrays, the reference's probe sequence otherwise): ix.q_left = every keyword's
+// lower bound, ix.q_right = its hit count; ix.q_hoff is made ready for their offsets
 template <typename V>
 void launch_search(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, uint64_t npat) {
     hipStream_t s = ix.stream;
-    const auto sa = ix.sa_view<V>();
-    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
+    ix.q_left.ensure(npat * 8);
+    ix.q_right.ensure(npat * 8);
+    ix.q_hoff.ensure((npat + 1) * 8);
+    const SearchArgs<V> a{ix.sa_view<V>(), ix.size, suffix_text(ix), d_blob, d_offs, npat, ix.q_left.as<int64_t>(), ix.q_right.as<uint64_t>()};
+    const KeptKeys kk = ix.key_nsym ? keys_of(ix) : KeptKeys{};  // (no keys: the empty view, the text decides every probe)
+    auto fast = [&](auto kern, int lanes, const Pivot* piv, int levels, bool refseq) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(npat * lanes, 256)), dim3(256), 0, s, a, piv, levels, kk,
+                           (const uint16_t*)ix.d_symmap_q.as<uint16_t>(), ix.key_nsym, ix.key_base, refseq);
+    };
     int t = ix.prof.begin(s);
     if (ix.sa_sorted && ix.use_fast_search && ix.size >= 4096) {
         if (ix.pivot_levels == 0) {
             int levels = PIVOT_LEVELS;
             while (levels > 1 && (1ull << levels) > ix.size / 2) --levels;
             ix.d_pivots.alloc(((size_t)1 << levels) * sizeof(Pivot));
-            hipLaunchKernelGGL((q_pivots_kernel<V>), dim3((unsigned)ceil_div((1u << levels), 256)), dim3(256), 0, s, sa, ix.size,
-                               ix.d_text, doc_start, (int)ix.bits, ix.mask, levels, ix.d_pivots.as<Pivot>());
+            hipLaunchKernelGGL((q_pivots_kernel<V>), dim3((unsigned)ceil_div((1u << levels), 256)), dim3(256), 0, s, a.sa, a.n, a.st, levels,
+                               ix.d_pivots.as<Pivot>());
             ix.pivot_levels = levels;
         }
         // a group of 8 lanes per keyword for SMALL batches (coalesced single queries, a few thousand keywords), where the
         // chain of dependent probes is the cost: 1000 keywords 0.090 -> 0.055 ms; from ~10^4 keywords on the random loads
         // themselves are (10^5 keywords: 0.17 ms with one lane, 0.34 ms with eight).  search_lanes: 0 = by batch size
         const bool wide = ix.search_lanes == 8 || (ix.search_lanes == 0 && npat <= 4096);
-        auto kern = wide ? q_search_fast_kernel<V, 8> : q_search_fast_kernel<V, 1>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(npat * (wide ? 8 : 1), 256)), dim3(256), 0, s, sa, ix.size, ix.d_text,
-                           doc_start, (int)ix.bits, ix.mask, d_blob, d_offs, npat, (const Pivot*)ix.d_pivots.as<Pivot>(),
-                           ix.pivot_levels,
-                           ix.key_nsym && ix.d_keys.p ? (const uint64_t*)ix.d_keys.as<uint64_t>() : (const uint64_t*)nullptr,
-                           ix.key_nsym && ix.d_keys32.p ? (const uint32_t*)ix.d_keys32.as<uint32_t>() : (const uint32_t*)nullptr,
-                           ix.key_nsym && ix.d_keylow.p ? (const void*)ix.d_keylow.p : (const void*)nullptr, ix.key_low_bits,
-                           ix.key_low_bytes, (const uint16_t*)ix.d_symmap_q.as<uint16_t>(), ix.key_nsym, ix.key_base, false,
-                           ix.q_left.as<int64_t>(), ix.q_right.as<uint64_t>());
+        if (wide) fast(q_search_fast_kernel<V, 8>, 8, ix.d_pivots.as<Pivot>(), ix.pivot_levels, false);
+        else fast(q_search_fast_kernel<V, 1>, 1, ix.d_pivots.as<Pivot>(), ix.pivot_levels, false);
     } else if (!ix.sa_sorted && ix.use_fast_search && ix.key_nsym) {
-        hipLaunchKernelGGL((q_search_fast_kernel<V, 1>), dim3((unsigned)ceil_div(npat, 256)), dim3(256), 0, s, sa, ix.size, ix.d_text,
-                           doc_start, (int)ix.bits, ix.mask, d_blob, d_offs, npat, (const Pivot*)nullptr, 0,
-                           ix.d_keys.p ? (const uint64_t*)ix.d_keys.as<uint64_t>() : (const uint64_t*)nullptr,
-                           ix.d_keys32.p ? (const uint32_t*)ix.d_keys32.as<uint32_t>() : (const uint32_t*)nullptr,
-                           ix.d_keylow.p ? (const void*)ix.d_keylow.p : (const void*)nullptr, ix.key_low_bits, ix.key_low_bytes,
-                           (const uint16_t*)ix.d_symmap_q.as<uint16_t>(), ix.key_nsym, ix.key_base, true, ix.q_left.as<int64_t>(),
-                           ix.q_right.as<uint64_t>());
+        fast(q_search_fast_kernel<V, 1>, 1, nullptr, 0, true);
     } else {
-        hipLaunchKernelGGL((q_search_kernel<V>), dim3((unsigned)ceil_div(npat, 256)), dim3(256), 0, s, sa, ix.size, ix.d_text,
-                           doc_start, (int)ix.bits, ix.mask, d_blob, d_offs, npat, ix.q_left.as<int64_t>(),
-                           ix.q_right.as<uint64_t>());
+        hipLaunchKernelGGL((q_search_kernel<V>), dim3((unsigned)ceil_div(npat, 256)), dim3(256), 0, s, a);
     }
     ix.prof.end(t, "q_search", npat * 2 * (uint64_t)bit_width64(ix.size) * 128, s);
+}
+
+// The prelude of every batched query: search, then the hit counts scanned into offsets (ix.q_hoff[npat + 1]).  The scan is a
+// template on what it adds up: the plain total (HitsIn / OpAdd / HitsOut), or for query_typed the total and the longest hit list
+// (HitsIn2 / OpSumMax / HitsOut2).  One round trip: the totals come back to the host.
+template <typename T, typename In, typename Op, typename Out>
+T offset_hits(Index& ix, uint64_t npat) {
+    const In in{ix.q_right.as<uint64_t>()};
+    const T tot = scan_totals<T>(ix.stream, ix.scan_partials, in, npat, Op{}, T{});
+    scan_apply<T>(ix.stream, ix.scan_partials, in, npat, Op{}, T{}, Out{ix.q_hoff.as<uint64_t>(), npat});
+    return tot;
+}
+template <typename V>
+uint64_t search_and_offset_hits(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, uint64_t npat) {
+    launch_search<V>(ix, d_blob, d_offs, npat);
+    return offset_hits<uint64_t, HitsIn, OpAdd, HitsOut>(ix, npat);
 }
 
 // ---- OR over the keywords of one key (interface.cpp:78-113): per-document totals by atomics ------
@@ -829,143 +820,127 @@ struct DocRowOut {  // row r (document) starts at span k
     }
 };
 
-template <typename V>
-DeviceCsr query_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, uint64_t npat, bool with_offsets) {
+// ---- the row builders of a batch (query_typed below chooses) -----------------------------------------------------------
+// nothing to look up or nothing found: npat empty rows
+void empty_rows(Index& ix, uint64_t npat) {
     hipStream_t s = ix.stream;
-    DeviceCsr out;
-    out.npat = npat;
-    ix.q_rowptr.ensure((npat + 1) * 8);
-    ix.qstats.batches++;
-    if (npat == 0 || ix.size == 0 || ix.width == 0) {
-        ix.qstats.empty_batches++;
-        CDB_HIP(hipMemsetAsync(ix.q_rowptr.p, 0, (npat + 1) * 8, s));
-        ix.q_ids.ensure(16);
-        ix.q_counts.ensure(16);
-        CDB_HIP(hipStreamSynchronize(s));
-        return out;
-    }
-    const auto sa = ix.sa_view<V>();
-    ix.q_left.ensure(npat * 8);
-    ix.q_right.ensure(npat * 8);  // hit counts
-    ix.q_hoff.ensure((npat + 1) * 8);
-    int t = 0;
-    launch_search<V>(ix, d_blob, d_offs, npat);
+    ix.qstats.empty_batches++;
+    CDB_HIP(hipMemsetAsync(ix.q_rowptr.p, 0, (npat + 1) * 8, s));
+    ix.q_ids.ensure(16);
+    ix.q_counts.ensure(16);
+    CDB_HIP(hipStreamSynchronize(s));
+}
 
-    HitsIn2 hin{ix.q_right.as<uint64_t>()};
-    // Speculative wavefront rows: when the previous batch of this index went down the wavefront path, buffers
-    // sized from it (x 1.5) let this batch run search -> scan -> rows -> scan -> emit without the host learning
-    // the hit totals in between; they come back together with the row count in ONE round trip.  Anything
-    // that does not fit (a hit list over 64, more hits than the buffers hold) raises a flag and the batch is
-    // redone below with the totals known.
-    if (!with_offsets && ix.use_wave_rows && ix.ndocs < 0xFFFFFFFFull && ix.q_spec_cap > 0) {
-        const uint64_t cap = ix.q_spec_cap;
-        ix.qstats.spec_batches++;
-        scan_totals_device<U2>(s, ix.scan_partials, hin, npat, OpSumMax{}, U2{0, 0});
-        const uint64_t nb1 = ceil_div(npat, SC_TILE);
-        ix.q_spec.ensure(4 * sizeof(uint64_t));  // {H, maxh, spill flag, nrows}
-        CDB_HIP(hipMemcpyAsync(ix.q_spec.p, ix.scan_partials.as<U2>() + nb1, sizeof(U2), hipMemcpyDeviceToDevice, s));
-        CDB_HIP(hipMemsetAsync(ix.q_spec.as<uint64_t>() + 2, 0, sizeof(uint64_t), s));
-        scan_apply<U2>(s, ix.scan_partials, hin, npat, OpSumMax{}, U2{0, 0}, HitsOut2{ix.q_hoff.as<uint64_t>(), npat});
-        ix.q_keys0.ensure(cap * 4);
-        ix.q_keys1.ensure(cap * 4);
-        ix.q_flags.ensure(npat * 8);
-        ix.q_ids.ensure(std::max<uint64_t>(cap, 2) * 8);
-        ix.q_counts.ensure(std::max<uint64_t>(cap, 2) * 8);
-        t = ix.prof.begin(s);
-        hipLaunchKernelGGL((q_wave_rows_kernel<V>), dim3((unsigned)ceil_div(npat, 4)), dim3(256), 0, s, sa, ix.mask,
-                           (const int64_t*)ix.q_left.as<int64_t>(), (const uint64_t*)ix.q_right.as<uint64_t>(),
-                           (const uint64_t*)ix.q_hoff.as<uint64_t>(), npat, ix.q_keys0.as<uint32_t>(), ix.q_keys1.as<uint32_t>(),
-                           ix.q_flags.as<uint64_t>(), cap, ix.q_spec.as<unsigned long long>() + 2);
-        ix.prof.end(t, "q_wave_rows", cap * (sizeof(typename SaOf<V>::val) + 8), s);
-        NrowsIn nin{ix.q_flags.as<uint64_t>()};
-        scan_totals_device<uint64_t>(s, ix.scan_partials, nin, npat, OpAdd{}, (uint64_t)0);
-        scan_apply<uint64_t>(s, ix.scan_partials, nin, npat, OpAdd{}, (uint64_t)0, HitsOut{ix.q_rowptr.as<uint64_t>(), npat});
-        hipLaunchKernelGGL(q_wave_emit_kernel, dim3((unsigned)ceil_div(npat, 4)), dim3(256), 0, s,
-                           (const uint32_t*)ix.q_keys0.as<uint32_t>(), (const uint32_t*)ix.q_keys1.as<uint32_t>(),
-                           (const uint64_t*)ix.q_hoff.as<uint64_t>(), (const uint64_t*)ix.q_rowptr.as<uint64_t>(), npat,
-                           (const int64_t*)ix.d_ids.as<int64_t>(), ix.q_ids.as<int64_t>(), ix.q_counts.as<int64_t>());
-        CDB_HIP(hipMemcpyAsync(ix.q_spec.as<uint64_t>() + 3, ix.q_rowptr.as<uint64_t>() + npat, 8, hipMemcpyDeviceToDevice, s));
-        uint64_t h4[4] = {0, 0, 1, 0};
-        CDB_HIP(hipMemcpyAsync(h4, ix.q_spec.p, sizeof(h4), hipMemcpyDeviceToHost, s));
-        CDB_HIP(hipGetLastError());
-        CDB_HIP(hipStreamSynchronize(s));
-        if (h4[2] == 0) {
-            out.nhits = h4[0];
-            out.nrows = h4[3];
-            ix.q_spec_cap = std::max<uint64_t>(h4[0] + h4[0] / 2, 4096);
-            return out;
-        }
-        ix.q_spec_cap = 0;  // this batch is not of that kind: the ordinary path below decides again
-        ix.qstats.spec_spills++;
-    }
-    const U2 tot = scan_totals<U2>(s, ix.scan_partials, hin, npat, OpSumMax{}, U2{0, 0});
+// Enqueues the wavefront row builder behind the hit offsets: rows per pattern, their scan into ix.q_rowptr, rows to their CSR
+// place.  cap = the hits the buffers are sized for — the batch's total when the host knows it, else (speculation) a guess, and
+// `spill` the word the kernel flags when a hit list does not fit a wavefront or the buffers.  rows <= hits, so the result arrays
+// are sized by cap and the caller fetches the number of rows (q_rowptr[npat]) together with its final synchronisation instead
+// of paying a round trip of its own.
+template <typename V>
+void enqueue_wave_rows(Index& ix, uint64_t npat, uint64_t cap, unsigned long long* spill) {
+    hipStream_t s = ix.stream;
+    ix.q_keys0.ensure(cap * 4);   // row_doc
+    ix.q_keys1.ensure(cap * 4);   // row_cnt
+    ix.q_flags.ensure(npat * 8);  // rows per pattern
+    ix.q_ids.ensure(std::max<uint64_t>(cap, 2) * 8);
+    ix.q_counts.ensure(std::max<uint64_t>(cap, 2) * 8);
+    const int t = ix.prof.begin(s);
+    hipLaunchKernelGGL((q_wave_rows_kernel<V>), dim3((unsigned)ceil_div(npat, 4)), dim3(256), 0, s, ix.sa_view<V>(), ix.mask,
+                       (const int64_t*)ix.q_left.as<int64_t>(), (const uint64_t*)ix.q_right.as<uint64_t>(),
+                       (const uint64_t*)ix.q_hoff.as<uint64_t>(), npat, ix.q_keys0.as<uint32_t>(), ix.q_keys1.as<uint32_t>(),
+                       ix.q_flags.as<uint64_t>(), cap, spill);
+    ix.prof.end(t, "q_wave_rows", cap * (sizeof(typename SaOf<V>::val) + 8), s);
+    NrowsIn nin{ix.q_flags.as<uint64_t>()};
+    scan_totals_device<uint64_t>(s, ix.scan_partials, nin, npat, OpAdd{}, (uint64_t)0);
+    scan_apply<uint64_t>(s, ix.scan_partials, nin, npat, OpAdd{}, (uint64_t)0, HitsOut{ix.q_rowptr.as<uint64_t>(), npat});
+    hipLaunchKernelGGL(q_wave_emit_kernel, dim3((unsigned)ceil_div(npat, 4)), dim3(256), 0, s,
+                       (const uint32_t*)ix.q_keys0.as<uint32_t>(), (const uint32_t*)ix.q_keys1.as<uint32_t>(),
+                       (const uint64_t*)ix.q_hoff.as<uint64_t>(), (const uint64_t*)ix.q_rowptr.as<uint64_t>(), npat,
+                       (const int64_t*)ix.d_ids.as<int64_t>(), ix.q_ids.as<int64_t>(), ix.q_counts.as<int64_t>());
+}
+
+// Speculative wavefront rows: when the previous batch of this index went down the wavefront path, buffers sized from it (x 1.5)
+// let this batch run search -> scan -> rows -> scan -> emit without the host learning the hit totals in between; they come back
+// together with the row count in ONE round trip.  Anything that does not fit (a hit list over 64, more hits than the buffers
+// hold) raises a flag: false, and the caller redoes the batch with the totals known.
+template <typename V>
+bool wave_rows_speculative(Index& ix, uint64_t npat, DeviceCsr& out) {
+    hipStream_t s = ix.stream;
+    const uint64_t cap = ix.q_spec_cap;
+    ix.qstats.spec_batches++;
+    const HitsIn2 hin{ix.q_right.as<uint64_t>()};
+    scan_totals_device<U2>(s, ix.scan_partials, hin, npat, OpSumMax{}, U2{0, 0});
+    const uint64_t nb1 = ceil_div(npat, SC_TILE);
+    ix.q_spec.ensure(4 * sizeof(uint64_t));  // {H, maxh, spill flag, nrows}
+    CDB_HIP(hipMemcpyAsync(ix.q_spec.p, ix.scan_partials.as<U2>() + nb1, sizeof(U2), hipMemcpyDeviceToDevice, s));
+    CDB_HIP(hipMemsetAsync(ix.q_spec.as<uint64_t>() + 2, 0, sizeof(uint64_t), s));
     scan_apply<U2>(s, ix.scan_partials, hin, npat, OpSumMax{}, U2{0, 0}, HitsOut2{ix.q_hoff.as<uint64_t>(), npat});
-    const uint64_t H = tot.a, maxh = tot.b;
-    out.nhits = H;
-    if (H == 0) {
-        ix.qstats.empty_batches++;
-        CDB_HIP(hipMemsetAsync(ix.q_rowptr.p, 0, (npat + 1) * 8, s));
-        ix.q_ids.ensure(16);
-        ix.q_counts.ensure(16);
-        CDB_HIP(hipStreamSynchronize(s));
-        return out;
+    enqueue_wave_rows<V>(ix, npat, cap, ix.q_spec.as<unsigned long long>() + 2);
+    CDB_HIP(hipMemcpyAsync(ix.q_spec.as<uint64_t>() + 3, ix.q_rowptr.as<uint64_t>() + npat, 8, hipMemcpyDeviceToDevice, s));
+    uint64_t h4[4] = {0, 0, 1, 0};
+    CDB_HIP(hipMemcpyAsync(h4, ix.q_spec.p, sizeof(h4), hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipGetLastError());
+    CDB_HIP(hipStreamSynchronize(s));
+    if (h4[2] != 0) {
+        ix.q_spec_cap = 0;  // this batch is not of that kind: the ordinary path decides again
+        ix.qstats.spec_spills++;
+        return false;
     }
-    if (!with_offsets && maxh <= 64 && ix.use_wave_rows && ix.ndocs < 0xFFFFFFFFull && H <= (1ull << 28)) {
-        // every pattern's hit list fits one wavefront: sort + run-length encode per pattern in registers
-        ix.qstats.wave_batches++;
-        ix.q_keys0.ensure(H * 4);   // row_doc
-        ix.q_keys1.ensure(H * 4);   // row_cnt
-        ix.q_flags.ensure(npat * 8);  // rows per pattern
-        t = ix.prof.begin(s);
-        hipLaunchKernelGGL((q_wave_rows_kernel<V>), dim3((unsigned)ceil_div(npat, 4)), dim3(256), 0, s, sa, ix.mask,
-                           (const int64_t*)ix.q_left.as<int64_t>(), (const uint64_t*)ix.q_right.as<uint64_t>(),
-                           (const uint64_t*)ix.q_hoff.as<uint64_t>(), npat, ix.q_keys0.as<uint32_t>(), ix.q_keys1.as<uint32_t>(),
-                           ix.q_flags.as<uint64_t>(), H, (unsigned long long*)nullptr);
-        ix.prof.end(t, "q_wave_rows", H * (sizeof(typename SaOf<V>::val) + 8), s);
-        NrowsIn nin{ix.q_flags.as<uint64_t>()};
-        // rows <= hits, so the result arrays are sized by H and the number of rows is fetched together with
-        // the final synchronisation instead of costing a round trip of its own
-        ix.q_ids.ensure(std::max<uint64_t>(H, 2) * 8);
-        ix.q_counts.ensure(std::max<uint64_t>(H, 2) * 8);
-        scan_totals_device<uint64_t>(s, ix.scan_partials, nin, npat, OpAdd{}, (uint64_t)0);
-        scan_apply<uint64_t>(s, ix.scan_partials, nin, npat, OpAdd{}, (uint64_t)0, HitsOut{ix.q_rowptr.as<uint64_t>(), npat});
-        hipLaunchKernelGGL(q_wave_emit_kernel, dim3((unsigned)ceil_div(npat, 4)), dim3(256), 0, s,
-                           (const uint32_t*)ix.q_keys0.as<uint32_t>(), (const uint32_t*)ix.q_keys1.as<uint32_t>(),
-                           (const uint64_t*)ix.q_hoff.as<uint64_t>(), (const uint64_t*)ix.q_rowptr.as<uint64_t>(), npat,
-                           (const int64_t*)ix.d_ids.as<int64_t>(), ix.q_ids.as<int64_t>(), ix.q_counts.as<int64_t>());
-        uint64_t nrows = 0;
-        CDB_HIP(hipMemcpyAsync(&nrows, ix.q_rowptr.as<uint64_t>() + npat, 8, hipMemcpyDeviceToHost, s));
-        CDB_HIP(hipGetLastError());
-        CDB_HIP(hipStreamSynchronize(s));
-        out.nrows = nrows;
-        ix.q_spec_cap = std::max<uint64_t>(H + H / 2, 4096);  // the next batch may run speculatively
-        return out;
+    out.nhits = h4[0];
+    out.nrows = h4[3];
+    ix.q_spec_cap = std::max<uint64_t>(h4[0] + h4[0] / 2, 4096);
+    return true;
+}
+
+// every pattern's hit list fits one wavefront (the host knows the totals): sort + run-length encode per pattern in registers
+template <typename V>
+uint64_t wave_rows(Index& ix, uint64_t npat, uint64_t H) {
+    hipStream_t s = ix.stream;
+    ix.qstats.wave_batches++;
+    enqueue_wave_rows<V>(ix, npat, H, nullptr);
+    uint64_t nrows = 0;
+    CDB_HIP(hipMemcpyAsync(&nrows, ix.q_rowptr.as<uint64_t>() + npat, 8, hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipGetLastError());
+    CDB_HIP(hipStreamSynchronize(s));
+    ix.q_spec_cap = std::max<uint64_t>(H + H / 2, 4096);  // the next batch may run speculatively
+    return nrows;
+}
+
+// Chunks of patterns whose hit lists fit the scratch budget (16 B of sort scratch per hit); almost always one chunk.  A short
+// pattern over a big corpus can match a large share of the text, and a whole batch of them can exceed any buffer — they are
+// then resolved chunk by chunk.  Chunk c = patterns [cut[c], cut[c + 1]); a lone pattern is never cut.
+std::vector<uint64_t> cut_chunks(Index& ix, uint64_t npat, uint64_t H) {
+    std::vector<uint64_t> cut{0, npat};
+    if (H <= ix.query_hit_budget) return cut;
+    hipStream_t s = ix.stream;
+    std::vector<uint64_t> hoff(npat + 1);
+    CDB_HIP(hipMemcpyAsync(hoff.data(), ix.q_hoff.p, (npat + 1) * 8, hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipStreamSynchronize(s));
+    cut.assign(1, 0);
+    uint64_t start = 0;
+    for (uint64_t j = 1; j <= npat; ++j) {
+        if (hoff[j] - hoff[start] > ix.query_hit_budget && j - 1 > start) {
+            cut.push_back(j - 1);
+            start = j - 1;
+        }
     }
-    ix.q_spec_cap = 0;
+    cut.push_back(npat);
+    return cut;
+}
+
+// the general row builder: (pattern ∘ doc) keys of every hit, one stable radix sort per chunk, rows = runs of equal keys
+template <typename V>
+uint64_t sort_rows(Index& ix, uint64_t npat, uint64_t H, bool with_offsets) {
+    hipStream_t s = ix.stream;
+    const auto sa = ix.sa_view<V>();
     const int dbits = (int)ix.bits;
     const int obits = with_offsets ? ix.off_bits : 0;  // offset field of the sort key (offset emission)
     if (with_offsets) ix.q_hitoff.ensure(H * 8);
-    // Chunks of patterns whose hit lists fit the scratch budget (16 B of sort scratch per hit); almost
-    // always one chunk.  A short pattern over a big corpus can match a large share of the text, and a
-    // whole batch of them can exceed any buffer — they are then resolved chunk by chunk.
-    std::vector<uint64_t> cut{0, npat};
-    if (H > ix.query_hit_budget) {
-        std::vector<uint64_t> hoff(npat + 1);
-        CDB_HIP(hipMemcpyAsync(hoff.data(), ix.q_hoff.p, (npat + 1) * 8, hipMemcpyDeviceToHost, s));
-        CDB_HIP(hipStreamSynchronize(s));
-        cut.assign(1, 0);
-        uint64_t start = 0;
-        for (uint64_t j = 1; j <= npat; ++j) {
-            if (hoff[j] - hoff[start] > ix.query_hit_budget && j - 1 > start) {
-                cut.push_back(j - 1);
-                start = j - 1;
-            }
-        }
-        cut.push_back(npat);
-    }
+    const std::vector<uint64_t> cut = cut_chunks(ix, npat, H);
     ix.qstats.sort_batches++;
     ix.qstats.sort_chunks += cut.size() - 1;
     uint64_t rows_total = 0, hits_done = 0;
+    int t = 0;
     for (size_t c = 0; c + 1 < cut.size(); ++c) {
         const uint64_t j0 = cut[c], j1 = cut[c + 1];
         uint64_t Hc = H;
@@ -1020,7 +995,6 @@ DeviceCsr query_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, 
         rows_total += nrows;
         hits_done += Hc;
     }
-    out.nrows = rows_total;
     if (with_offsets) {
         ix.q_hitptr.ensure((rows_total + 1) * 8);
         CDB_HIP(hipMemcpyAsync(ix.q_hitptr.as<uint64_t>() + rows_total, &hits_done, 8, hipMemcpyHostToDevice, s));
@@ -1029,6 +1003,34 @@ DeviceCsr query_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, 
     CDB_HIP(hipGetLastError());
     radix_check_error(s, ix.rws);
     CDB_HIP(hipStreamSynchronize(s));
+    return rows_total;
+}
+
+// Which row builder answers a batch: tests/test_gpu_query_paths.py restates this rule (Model) and walks it.
+template <typename V>
+DeviceCsr query_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_offs, uint64_t npat, bool with_offsets) {
+    DeviceCsr out;
+    out.npat = npat;
+    ix.q_rowptr.ensure((npat + 1) * 8);
+    ix.qstats.batches++;
+    if (npat == 0 || ix.size == 0 || ix.width == 0) {
+        empty_rows(ix, npat);
+        return out;
+    }
+    launch_search<V>(ix, d_blob, d_offs, npat);
+    const bool wave_ok = !with_offsets && ix.use_wave_rows && ix.ndocs < 0xFFFFFFFFull;
+    if (wave_ok && ix.q_spec_cap > 0 && wave_rows_speculative<V>(ix, npat, out)) return out;
+    const U2 tot = offset_hits<U2, HitsIn2, OpSumMax, HitsOut2>(ix, npat);
+    const uint64_t H = tot.a, maxh = tot.b;
+    out.nhits = H;
+    if (H == 0) {
+        empty_rows(ix, npat);
+    } else if (wave_ok && maxh <= 64 && H <= (1ull << 28)) {
+        out.nrows = wave_rows<V>(ix, npat, H);
+    } else {
+        ix.q_spec_cap = 0;
+        out.nrows = sort_rows<V>(ix, npat, H, with_offsets);
+    }
     return out;
 }
 
@@ -1041,13 +1043,7 @@ DeviceCsr query_or_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d_off
     ix.q_counts.ensure(16);
     if (npat == 0 || ix.size == 0 || ix.width == 0) return out;
     const auto sa = ix.sa_view<V>();
-    ix.q_left.ensure(npat * 8);
-    ix.q_right.ensure(npat * 8);
-    ix.q_hoff.ensure((npat + 1) * 8);
-    launch_search<V>(ix, d_blob, d_offs, npat);
-    HitsIn hin{ix.q_right.as<uint64_t>()};
-    const uint64_t H = scan_totals<uint64_t>(s, ix.scan_partials, hin, npat, OpAdd{}, (uint64_t)0);
-    scan_apply<uint64_t>(s, ix.scan_partials, hin, npat, OpAdd{}, (uint64_t)0, HitsOut{ix.q_hoff.as<uint64_t>(), npat});
+    const uint64_t H = search_and_offset_hits<V>(ix, d_blob, d_offs, npat);
     out.nhits = H;
     if (H == 0) {
         CDB_HIP(hipStreamSynchronize(s));
@@ -1103,13 +1099,7 @@ SpanResult query_spans_typed(Index& ix, const uint8_t* d_blob, const uint64_t* d
         CDB_HIP(hipMemcpyAsync(&H, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
         CDB_HIP(hipStreamSynchronize(s));
     } else {
-        ix.q_left.ensure(npat * 8);
-        ix.q_right.ensure(npat * 8);
-        ix.q_hoff.ensure((npat + 1) * 8);
-        launch_search<V>(ix, d_blob, d_offs, npat);
-        HitsIn hin{ix.q_right.as<uint64_t>()};
-        H = scan_totals<uint64_t>(s, ix.scan_partials, hin, npat, OpAdd{}, (uint64_t)0);
-        scan_apply<uint64_t>(s, ix.scan_partials, hin, npat, OpAdd{}, (uint64_t)0, HitsOut{ix.q_hoff.as<uint64_t>(), npat});
+        H = search_and_offset_hits<V>(ix, d_blob, d_offs, npat);
     }
     out.nhits = H;
     if (H == 0) {
@@ -1208,26 +1198,28 @@ __device__ __forceinline__ void q_single_answer(typename SaOf<V>::ptr sa, uint64
     __shared__ int64_t s_rid[SINGLE_MAX_HITS];    // rows are assembled in LDS and leave for the host-mapped block
     __shared__ uint32_t s_rcnt[SINGLE_MAX_HITS];  // with consecutive lanes on consecutive slots
     __shared__ uint32_t s_wcnt[4];
+    const SuffixText st{text, doc_start, bits, mask};
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (wave == 0) {  // ---- the search is the first wavefront's business
     // three-way compare of the keyword with the suffix at slot M: <0 keyword smaller, 0 keyword is a prefix of
     // the suffix or equal on the common part
     auto probe = [&](int64_t M, bool& le, bool& pref) {
         if (sk.nsym) {  // the kept sort key of slot M decides most probes with ONE load (see q_search_fast_kernel)
+            // (KeptKeys::cmp_range's compare written out: the shared function gave these two kernels another instruction
+            //  stream, and their latency then lay above the parent's spread without a cause found in it)
+            const KeptKeys& kk = sk.keys;
             uint64_t key;
             bool known = true;
-            if (sk.keys64) {
-                key = sk.keys64[M];
+            if (kk.k64) {
+                key = kk.k64[M];
             } else {
-                const uint64_t hpart = sk.keys32[M];
+                const uint64_t hpart = kk.k32[M];
                 // (the low digits are fetched beside the high part, not after it: one round trip instead of two for the
                 //  lanes that need them — the wavefront waits for its slowest lane)
                 uint64_t lowv = 0;
-                if (sk.keylow)
-                    lowv = sk.low_bytes == 1 ? (uint64_t)static_cast<const uint8_t*>(sk.keylow)[M]
-                                             : (uint64_t)static_cast<const uint16_t*>(sk.keylow)[M];
-                if (sk.keylow) {
-                    const uint64_t a = sk.klo >> sk.low_bits, b2 = sk.khi >> sk.low_bits;
+                if (kk.low) lowv = kk.low_bytes == 1 ? (uint64_t)kk.low[M] : (uint64_t)reinterpret_cast<const uint16_t*>(kk.low)[M];
+                if (kk.low) {
+                    const uint64_t a = sk.klo >> kk.low_bits, b2 = sk.khi >> kk.low_bits;
                     if (hpart < a || hpart > b2 || (hpart > a && hpart < b2)) {
                         key = hpart < a ? 0 : (hpart > b2 ? ~0ull : sk.klo);  // below / above / inside the range
                         known = false;
@@ -1235,7 +1227,7 @@ __device__ __forceinline__ void q_single_answer(typename SaOf<V>::ptr sa, uint64
                         if (hpart > b2) { le = true; pref = false; return; }
                         if (sk.decisive) { le = true; pref = true; return; }
                     } else {
-                        key = (hpart << sk.low_bits) | lowv;
+                        key = (hpart << kk.low_bits) | lowv;
                     }
                 } else {
                     key = hpart;
@@ -1248,10 +1240,9 @@ __device__ __forceinline__ void q_single_answer(typename SaOf<V>::ptr sa, uint64
             }
             // the suffix starts with the keyword's first symbols and the keyword is longer than the key: the text decides
         }
-        const auto e = sa[M];
-        const uint64_t d = (uint64_t)e & mask, off = (uint64_t)e >> bits;
-        const uint64_t b = doc_start[d] + off, sl = doc_start[d + 1] - b;
-        const int c = cmp_common(k, m, text + b, sl);
+        uint64_t sl;
+        const uint8_t* sp = st.at(sa[M], sl);
+        const int c = cmp_common(k, m, sp, sl);
         le = c < 0 || (c == 0 && m <= sl);
         pref = c == 0 && sl >= m;
     };
@@ -1384,7 +1375,9 @@ __device__ __forceinline__ void q_single_answer(typename SaOf<V>::ptr sa, uint64
         if (wave == 0) {
         uint32_t v = 0xFFFFFFFFu;
         if ((uint32_t)lane < h)  // (doc indices fit 32 bits: index.cpp:199)
-            v = s_inwin ? (uint32_t)(s_win[lane] & mask) : (uint32_t)((uint64_t)sa[(uint64_t)left + lane] & mask);
+            v = s_inwin ? (uint32_t)(s_win[lane] & st.mask) : (uint32_t)((uint64_t)sa[(uint64_t)left + lane] & st.mask);
+        // (the network and the ballot encoding of q_wave_rows_kernel; a function shared by the two gave this kernel another
+        //  instruction stream, like the key compare above)
 #pragma unroll
         for (int kk = 2; kk <= 64; kk <<= 1) {
 #pragma unroll
@@ -1417,7 +1410,7 @@ __device__ __forceinline__ void q_single_answer(typename SaOf<V>::ptr sa, uint64
     // counted per thread chunk, rows written in order
     uint32_t cap = 128;
     while (cap < h) cap <<= 1;
-    for (uint32_t i = tid; i < cap; i += 256) s_doc[i] = i < h ? (uint32_t)((uint64_t)sa[(uint64_t)left + i] & mask) : 0xFFFFFFFFu;
+    for (uint32_t i = tid; i < cap; i += 256) s_doc[i] = i < h ? (uint32_t)((uint64_t)sa[(uint64_t)left + i] & st.mask) : 0xFFFFFFFFu;
     __syncthreads();
     for (uint32_t kk = 2; kk <= cap; kk <<= 1) {
         for (uint32_t q = kk >> 1; q > 0; q >>= 1) {
@@ -1569,16 +1562,20 @@ __global__ __launch_bounds__(256) void q_resident_kernel(typename SaOf<V>::ptr s
 
 // true = answered (rows in freshly malloc'd *ids_out / *counts_out); false = take the batched path
 namespace {
-void single_empty_rows(Index& ix, int64_t** ids_out, int64_t** counts_out, size_t* nrows) {
-    *nrows = 0;
-    *ids_out = (int64_t*)std::malloc(8);
-    *counts_out = (int64_t*)std::malloc(8);
+// the (ids, counts) blocks a lone keyword's n rows go back in (released by the caller through cdb_free); both or neither
+void malloc_rows(uint64_t n, int64_t** ids_out, int64_t** counts_out) {
+    *ids_out = (int64_t*)std::malloc(std::max<uint64_t>(n, 1) * 8);
+    *counts_out = (int64_t*)std::malloc(std::max<uint64_t>(n, 1) * 8);
     if (!*ids_out || !*counts_out) {
         std::free(*ids_out);
         std::free(*counts_out);
         *ids_out = *counts_out = nullptr;
         throw std::bad_alloc();
     }
+}
+void single_empty_rows(Index& ix, int64_t** ids_out, int64_t** counts_out, size_t* nrows) {
+    *nrows = 0;
+    malloc_rows(0, ids_out, counts_out);
     ix.qstats.nhits = ix.qstats.nrows = 0;
 }
 }  // namespace
@@ -1599,8 +1596,8 @@ void query_resident_ensure(Index& ix, const SingleKeys& sk) {
     sa_dispatch(ix, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL((q_resident_kernel<T>), dim3(1), dim3(256), 0, ix.res_stream, ix.sa_view<T>(), ix.size, ix.d_text,
-                           (const uint64_t*)ix.d_doc_start.as<uint64_t>(), (int)ix.bits, ix.mask, (const int64_t*)ix.d_ids.as<int64_t>(),
-                           static_cast<ResidentBox*>(ix.d_res), out, ix.sa_sorted, base, seq0);
+                           (const uint64_t*)ix.d_doc_start.as<uint64_t>(), (int)ix.bits, ix.mask,
+                           (const int64_t*)ix.d_ids.as<int64_t>(), static_cast<ResidentBox*>(ix.d_res), out, ix.sa_sorted, base, seq0);
     });
     CDB_HIP(hipGetLastError());
     ix.res_running = true;
@@ -1616,7 +1613,7 @@ void query_resident_stop(Index& ix) {
 }
 
 // Host-side key directory (index_impl.h: h_keydir): one bisection per cell over the kept keys, once per index.
-__global__ __launch_bounds__(256) void q_keydir_kernel(SingleKeys sk, uint64_t n, int shift, uint32_t cells, uint32_t* __restrict__ dir) {
+__global__ __launch_bounds__(256) void q_keydir_kernel(KeptKeys keys, uint64_t n, int shift, uint32_t cells, uint32_t* __restrict__ dir) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i > cells) return;
     if (i == cells) {
@@ -1627,16 +1624,7 @@ __global__ __launch_bounds__(256) void q_keydir_kernel(SingleKeys sk, uint64_t n
     uint64_t lo = 0, hi = n;  // first slot in [0, n] whose key is >= T
     while (lo < hi) {
         const uint64_t M = lo + (hi - lo) / 2;
-        uint64_t key;
-        if (sk.keys64) {
-            key = sk.keys64[M];
-        } else {
-            key = sk.keys32[M];
-            if (sk.keylow)
-                key = (key << sk.low_bits) | (sk.low_bytes == 1 ? (uint64_t)static_cast<const uint8_t*>(sk.keylow)[M]
-                                                                : (uint64_t)static_cast<const uint16_t*>(sk.keylow)[M]);
-        }
-        if (key >= T) hi = M; else lo = M + 1;
+        if (keys.at(M) >= T) hi = M; else lo = M + 1;
     }
     dir[i] = (uint32_t)lo;
 }
@@ -1660,7 +1648,7 @@ void query_keydir_ensure(Index& ix, const SingleKeys& sk) {
     DevBuf d_dir;
     d_dir.alloc(((size_t)cells + 1) * sizeof(uint32_t));
     hipStream_t s = ix.stream;
-    hipLaunchKernelGGL(q_keydir_kernel, dim3((unsigned)ceil_div((uint64_t)cells + 1, 256)), dim3(256), 0, s, sk, n, kb - bits, cells,
+    hipLaunchKernelGGL(q_keydir_kernel, dim3((unsigned)ceil_div((uint64_t)cells + 1, 256)), dim3(256), 0, s, sk.keys, n, kb - bits, cells,
                        d_dir.as<uint32_t>());
     std::vector<uint32_t> dir((size_t)cells + 1);
     CDB_HIP(hipMemcpyAsync(dir.data(), d_dir.p, dir.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1687,25 +1675,13 @@ SingleLaunch query_single_launch(Index& ix, const char* kw, size_t len) {
     SingleOut* out = static_cast<SingleOut*>(ix.h_single);
     SingleKeys sk;
     if (ix.sa_sorted && ix.use_fast_search && ix.key_nsym && (ix.d_keys.p || ix.d_keys32.p)) {
-        const int kc = (int)std::min<size_t>(len, (size_t)ix.key_nsym);
-        uint64_t kwc = 0, kpw = 1;
-        bool absent = false;
-        for (size_t q = 0; q < len; ++q) {
-            const uint64_t c = ix.h_symmap_q[(uint8_t)kw[q]];
-            absent |= c == 0;
-            if ((int)q < kc) kwc = kwc * ix.key_base + c;
-        }
-        if (absent) return SingleLaunch::Absent;  // a byte the text never holds: the keyword occurs nowhere
-        for (int q = kc; q < ix.key_nsym; ++q) kpw *= ix.key_base;
-        sk.keys64 = ix.d_keys.p ? ix.d_keys.as<uint64_t>() : nullptr;
-        sk.keys32 = ix.d_keys32.p ? ix.d_keys32.as<uint32_t>() : nullptr;
-        sk.keylow = ix.d_keylow.p;
-        sk.low_bits = ix.key_low_bits;
-        sk.low_bytes = ix.key_low_bytes;
+        const KeyRange kr = key_range(ix.h_symmap_q, reinterpret_cast<const uint8_t*>(kw), len, ix.key_nsym, ix.key_base);
+        if (kr.absent) return SingleLaunch::Absent;  // a byte the text never holds: the keyword occurs nowhere
+        sk.keys = keys_of(ix);
         sk.nsym = ix.key_nsym;
-        sk.decisive = len <= (size_t)ix.key_nsym;
-        sk.klo = kwc * kpw;
-        sk.khi = sk.klo + (kpw - 1);
+        sk.decisive = kr.decisive;
+        sk.klo = kr.klo;
+        sk.khi = kr.khi;
         query_keydir_ensure(ix, sk);
         if (!ix.h_keydir.empty()) {
             const uint64_t cells = 1ull << ix.keydir_bits;
@@ -1761,8 +1737,8 @@ SingleLaunch query_single_launch(Index& ix, const char* kw, size_t len) {
     sa_dispatch(ix, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL((q_single_kernel<T>), dim3(1), dim3(256), 0, s, ix.sa_view<T>(), ix.size, ix.d_text,
-                           (const uint64_t*)ix.d_doc_start.as<uint64_t>(), (int)ix.bits, ix.mask, (const int64_t*)ix.d_ids.as<int64_t>(), k,
-                           static_cast<SingleOut*>(ix.d_single), ix.sa_sorted, sk);
+                           (const uint64_t*)ix.d_doc_start.as<uint64_t>(), (int)ix.bits, ix.mask,
+                           (const int64_t*)ix.d_ids.as<int64_t>(), k, static_cast<SingleOut*>(ix.d_single), ix.sa_sorted, sk);
     });
     CDB_HIP(hipGetLastError());
     return SingleLaunch::Launched;
@@ -1811,14 +1787,7 @@ bool query_single_collect(Index& ix, int64_t** ids_out, int64_t** counts_out, si
         return false;
     }
     *nrows = (size_t)out->nrows;
-    *ids_out = (int64_t*)std::malloc(std::max<uint64_t>(out->nrows, 1) * 8);  // (released by the caller through cdb_free)
-    *counts_out = (int64_t*)std::malloc(std::max<uint64_t>(out->nrows, 1) * 8);
-    if (!*ids_out || !*counts_out) {
-        std::free(*ids_out);
-        std::free(*counts_out);
-        *ids_out = *counts_out = nullptr;
-        throw std::bad_alloc();
-    }
+    malloc_rows(out->nrows, ids_out, counts_out);
     std::memcpy(*ids_out, out->ids, out->nrows * 8);
     std::memcpy(*counts_out, out->counts, out->nrows * 8);
     ix.qstats.nhits = out->hits;

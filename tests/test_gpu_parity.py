@@ -47,6 +47,26 @@ def _csr_rows(rp, ids, cnt, j):
     return list(zip(ids[a:b].tolist(), cnt[a:b].tolist()))
 
 
+def _device_batch(g, blob, offs):
+    # the batch with its patterns resident on the device; rows fetched back in query_batch's form
+    import torch
+    d_blob = torch.from_numpy(np.concatenate([blob, np.zeros(16, dtype=np.uint8)])).cuda()
+    d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
+    torch.cuda.synchronize()
+    npat = len(offs) - 1
+    r = g.query_batch_device(d_blob.data_ptr(), d_offs.data_ptr(), npat, len(blob))
+
+    def dev(ptr, cnt):
+        if cnt == 0:
+            return np.empty(0, dtype=np.int64)
+
+        class A:
+            __cuda_array_interface__ = {"shape": (int(cnt),), "typestr": "<i8", "data": (int(ptr), False), "version": 2}
+        return torch.as_tensor(A(), device="cuda").cpu().numpy().copy()
+    nrows = int(r.nrows)
+    return dev(r.d_row_ptr, npat + 1).astype(np.uint64), dev(r.d_ids, nrows), dev(r.d_counts, nrows), int(r.nhits)
+
+
 def _check_parity(G, blob, ds, ids=None, patterns=None, **opts):
     nd = len(ds) - 1
     if ids is None:
@@ -1057,24 +1077,43 @@ def test_key_directory_over_every_kept_key_layout(G):
     # the host-side key directory of the lone-keyword path is built from the kept search keys in whatever layout the build
     # left them: u32, u32 + low byte (LSD split sort and the MSD-first sort's last pass), u32 + two low bytes, u64.  Same rows
     # as the oracle for keywords that hit, miss, are prefixes of each other, or exceed the key width; resident workgroup too.
-    cases = [(W.ascii_corpus(600, 300, seed=21, lo=0x61, hi=0x66), dict()),                                   # 6 symbols: u32 keys
+    cases = [(W.ascii_corpus(600, 300, seed=21, lo=0x61, hi=0x66), dict()),                                   # 6 symbols, whatever layout the defaults choose
+             (W.ascii_corpus(600, 300, seed=21, lo=0x61, hi=0x66), dict(key_coding=2, key_symbols=10)),      # ... and 7^11 < 2^31: u32 keys
              (W.ascii_corpus(700, 256, seed=22), dict(key_coding=2, key_symbols=6, sort_variant=31)),         # MSD-first: u32 + low byte
              (W.ascii_corpus(700, 256, seed=23), dict(key_coding=2, key_symbols=6, sort_variant=31, msd_first=0)),  # LSD split
              (W.ascii_corpus(500, 400, seed=24, lo=0x20, hi=0xE7), dict(key_coding=2, key_symbols=6, reference_compat=0)),  # 200 symbols: two low bytes
              (W.ascii_corpus(500, 400, seed=25, lo=0x00, hi=0xFF), dict(reference_compat=0))]                 # all byte values: u64 keys
+    # The same patterns also go through the batched search as ONE batch, with eight lanes and with one lane per keyword, from the
+    # host and (eight lanes) with the patterns resident on the device: the split forms decide its probes too.
+    layouts = set()
     for (blob, ds), opts in cases:
         ids = np.arange(len(ds) - 1, dtype=np.int64) * 5 + 2
         o = _oracle(blob, ds, ids) if opts.get("reference_compat", 1) else None
         g = _gpu(G, blob, ds, ids, **opts)
         gr = _gpu(G, blob, ds, ids, resident_query=1, **opts)
         gn = _gpu(G, blob, ds, ids, key_directory=0, **opts)
+        layouts.add(int(g.stat("key_layout")))
         pb, po = W.sample_patterns(blob, ds, 250, 1, 12, seed=6, miss_frac=0.15, miss_byte=int(blob[0]))
+        lone = []
         for j in range(250):
             kw = bytes(pb[int(po[j]):int(po[j + 1])])
             want = o.query(kw) if o is not None else gn.query(kw)
             assert g.query(kw) == want, (opts, kw)
             assert gr.query(kw) == want, (opts, kw)
+            lone.append(want)
         assert g.stat("key_directory_cells") >= 256 and gn.stat("key_directory_cells") == 0, opts
+        if o is not None:
+            want_rows = o.query_batch(pb, po)
+        else:   # no oracle for this case: the rows of the key_directory = 0 handle's lone answers, pattern after pattern
+            want_rows = (np.cumsum([0] + [len(r) for r in lone]).astype(np.uint64),
+                         np.array([i for r in lone for i, _ in r], dtype=np.int64),
+                         np.array([c for r in lone for _, c in r], dtype=np.int64), sum(c for r in lone for _, c in r))
+        for lanes in (8, 1):
+            g.set_option("search_lanes", lanes)
+            gots = [g.query_batch(pb, po)] + ([_device_batch(g, pb, po)] if lanes == 8 else [])
+            for got in gots:
+                assert got[3] == want_rows[3] and all(np.array_equal(a, b) for a, b in zip(got[:3], want_rows[:3])), (opts, lanes)
+    assert layouts >= {0, 1, 2, 3}, layouts   # u64, u32, u32 + low byte, u32 + two low bytes: every form the comments claim
 
 
 @pytest.mark.parametrize("variant", [31, 33])
