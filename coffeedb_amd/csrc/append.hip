@@ -334,7 +334,7 @@ void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int
                            (const uint64_t*)p.d_start.as<uint64_t>() + D, p.ndocs + 1, n, in.d_doc_start.as<uint64_t>());
         CDB_HIP(hipGetLastError());
         build_suffix_array(in);  // (synchronises; a failure here is a failure before the commit)
-        if (!in.sa_sorted) throw Error("append: the new documents' array is not sorted (internal)");
+        if (!in.sa_sorted) throw InternalError("append: the new documents' array is not sorted (internal)");
         const unsigned blocks = (unsigned)ceil_div(m, 256);
         int t = ix.prof.begin(s);
         sa_dispatch(in, [&](auto tag) {
@@ -354,7 +354,7 @@ void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int
     const uint16_t* symmap = with_keys ? (const uint16_t*)ix.d_symmap_q.as<uint16_t>() : (const uint16_t*)nullptr;
     if (m) {
         const uint64_t nsamples = (m - 1) / AP_SAMPLE + 2;
-        if (ceil_div(m, 256) >= (1ull << 31)) throw Error("append: too many new suffixes for one launch (internal)");
+        if (ceil_div(m, 256) >= (1ull << 31)) throw InternalError("append: too many new suffixes for one launch (internal)");
         const int kf = !with_keys ? 0 : kin.k64 ? 1 : !kin.low_bits ? 2 : kin.low_bytes == 2 ? 4 : 3;
         for (int phase = 0; phase < 2; ++phase) {
             const unsigned blocks = (unsigned)ceil_div(phase == 0 ? nsamples : m, 256);
@@ -390,7 +390,7 @@ void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int
     }
     const uint64_t ntiles = ceil_div(N, ST_TILE);
     if (tile_bases(ix, "append", SlotIsNew{flag.as<uint8_t>()}, N, tile_base, "ap_count", N + ntiles * 8) != m)
-        throw Error("append: new entries and new bytes differ (internal)");
+        throw InternalError("append: new entries and new bytes differ (internal)");
     const KeptKeys kout = with_keys ? p.arr.alloc_keys_like(ix, N) : KeptKeys{};
     const int old_bytes = ix.sa_packed ? 5 : ix.width;
     const int t = ix.prof.begin(s);

@@ -17,35 +17,17 @@ using namespace cdb;
 
 namespace {
 
-double wall_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
+static_assert((int)Status::Invalid == CDB_E_INVALID && (int)Status::Device == CDB_E_DEVICE && (int)Status::Internal == CDB_E_INTERNAL,
+              "errors.h: Status restates the CDB_E_* codes");
 
-// queries run concurrently on one handle (database.cpp:388), so the last-error string has its own lock
-void set_error(Index& ix, const char* msg) {
+void set_error(Index& ix, const std::string& msg) {
     std::lock_guard<std::mutex> g(ix.err_mu);
     ix.err = msg;
 }
 
 template <typename F>
 int guarded(cdb_index* h, F&& f) {
-    ForegroundCall fg;  // (the order proof of any handle yields to calls in flight: common.h)
-    try {
-        f();
-        return CDB_OK;
-    } catch (const Error& e) {
-        set_error(h->ix, e.what());
-        const bool dev = std::strncmp(e.what(), "HIP error", 9) == 0;
-        const bool internal = std::strstr(e.what(), "internal") != nullptr;
-        return dev ? CDB_E_DEVICE : (internal ? CDB_E_INTERNAL : CDB_E_INVALID);
-    } catch (const std::bad_alloc&) {
-        set_error(h->ix, "out of host memory");
-        return CDB_E_DEVICE;
-    } catch (const std::exception& e) {
-        set_error(h->ix, e.what());
-        return CDB_E_INTERNAL;
-    }
+    return guarded_ix(h->ix, std::forward<F>(f));
 }
 
 // bits / mask / size / width exactly as string_index::build does (reference src/index.cpp:182-208).  Computed
@@ -135,7 +117,7 @@ void upload_chunked(void* dst, size_t bytes, hipStream_t s, int device, hipStrea
     const size_t nchunks = (bytes + CHUNK - 1) / CHUNK;
     if (T > 1) upload_fork(s, s2);
     else s2 = nullptr;
-    std::string failure;
+    std::exception_ptr failure;  // the first one
     std::mutex fmu;
     std::vector<std::thread> th;
     auto work = [&](int t) {
@@ -145,7 +127,7 @@ void upload_chunked(void* dst, size_t bytes, hipStream_t s, int device, hipStrea
             CDB_HIP(hipSetDevice(device));
             for (int k = 0; k < UPLOAD_BLOCKS; ++k) {
                 pin[k] = HostPool::get().alloc(CHUNK);
-                if (!pin[k]) throw Error("HIP error: no pinned staging memory");
+                if (!pin[k]) throw DeviceError("HIP error: no pinned staging memory");
                 CDB_HIP(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
             }
             int k = 0;
@@ -161,11 +143,11 @@ void upload_chunked(void* dst, size_t bytes, hipStream_t s, int device, hipStrea
             }
             for (int q = 0; q < UPLOAD_BLOCKS; ++q)
                 if (used[q]) CDB_HIP(hipEventSynchronize(ev[q]));
-        } catch (const std::exception& e) {
+        } catch (...) {
             (void)hipStreamSynchronize(s);  // a DMA out of the pinned blocks may still be in flight: it ends before they go back
             if (s2) (void)hipStreamSynchronize(s2);
             std::lock_guard<std::mutex> g(fmu);
-            if (failure.empty()) failure = e.what();
+            if (!failure) failure = std::current_exception();
         }
         for (int q = 0; q < UPLOAD_BLOCKS; ++q) {
             if (ev[q]) (void)hipEventDestroy(ev[q]);
@@ -178,7 +160,7 @@ void upload_chunked(void* dst, size_t bytes, hipStream_t s, int device, hipStrea
         for (int t = 0; t < T; ++t) th.emplace_back(work, t);
         for (auto& x : th) x.join();
     }
-    if (!failure.empty()) throw Error(failure);
+    if (failure) std::rethrow_exception(failure);
 }
 void upload_pageable(void* dst, const char* src, size_t bytes, hipStream_t s, int device, hipStream_t s2 = nullptr) {
     if (bytes < 4 * UPLOAD_CHUNK) {
@@ -477,15 +459,7 @@ extern "C" {
 int cdb_create(cdb_index** out, int device) {
     if (!out) return CDB_E_INVALID;
     *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return CDB_E_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return CDB_E_DEVICE;
-    }
-    if (device >= count) return CDB_E_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return CDB_E_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return CDB_E_DEVICE;  // kernels exist for gfx950 only
+    if (!usable_device(device)) return CDB_E_DEVICE;
     cdb_index* h = new (std::nothrow) cdb_index();
     if (!h) return CDB_E_DEVICE;
     h->ix.device = device;
@@ -524,14 +498,8 @@ void cdb_destroy(cdb_index* h) {
 }
 
 const char* cdb_last_error(const cdb_index* h) {
-    if (!h) return "null handle";
-    // a per-thread copy: another thread's failing call cannot pull the string away under the reader
     static thread_local std::string copy;
-    {
-        std::lock_guard<std::mutex> g(h->ix.err_mu);
-        copy = h->ix.err;
-    }
-    return copy.c_str();
+    return h ? last_error_copy(h->ix.err_mu, h->ix.err, copy) : "null handle";
 }
 
 int cdb_add(cdb_index* h, int64_t id, const char* value, size_t len) {
@@ -1003,7 +971,7 @@ void build_view_locked(Index& ix, const int64_t* ids, const char* blob, const ui
         size_t fre = 0, tot = 0;
         if (hipMemGetInfo(&fre, &tot) == hipSuccess) {
             if ((double)n_claimed + (double)TEXT_PAD > (double)fre + (double)cdb_cached_memory_bytes())
-                throw Error("HIP error: the column does not fit the device memory that is free");
+                throw DeviceError("HIP error: the column does not fit the device memory that is free");
         } else {
             (void)hipGetLastError();
         }
@@ -1011,14 +979,14 @@ void build_view_locked(Index& ix, const int64_t* ids, const char* blob, const ui
     replace_column(ix, [&](NewColumn& col) {
         alloc_padded_text(ix, col.text, n_claimed);
         col.upload_t0 = wall_ms();
-        std::string uerr;
+        std::exception_ptr uerr;
         hipStream_t s2 = upload_stream(ix);
         std::thread up([&] {
             try {
                 CDB_HIP(hipSetDevice(ix.device));
                 if (n_claimed) upload_pageable(col.text.p, blob + first, n_claimed, ix.stream, ix.device, s2);
-            } catch (const std::exception& e) {
-                uerr = e.what();
+            } catch (...) {
+                uerr = std::current_exception();
             }
         });
         struct Joiner {
@@ -1028,7 +996,7 @@ void build_view_locked(Index& ix, const int64_t* ids, const char* blob, const ui
         rebase_tables(doc_start, ids, ndocs, first, col);
         col.L = layout_of(col.doc_start, ndocs);  // (throws the reference's capacity errors: nothing changed yet)
         up.join();
-        if (!uerr.empty()) throw Error(uerr);
+        if (uerr) std::rethrow_exception(uerr);
         // (tried: the 16 MB of document tables on a helper thread beside the text — the runtime's pageable staging then competes
         //  with the chunk copies: 21.4 instead of 20.1 ms)
         upload_tables(ix, col.doc_start, col.ids, ndocs, col.d_start, col.d_ids);
@@ -1632,14 +1600,15 @@ int cdb_query(cdb_index* h, const char* keyword, size_t len, int64_t** ids, int6
                 for (void* p : taken) batch.push_back(static_cast<PendingQuery*>(p));
                 run_coalesced(h, batch);
             } catch (...) {  // (host allocation failure while assembling the batch)
+                const Failure fail = classify_current_exception();
                 for (void* p : taken) {
                     PendingQuery* q = static_cast<PendingQuery*>(p);
                     std::free(q->ids);
                     std::free(q->counts);
                     q->ids = q->counts = nullptr;
-                    q->rc = CDB_E_DEVICE;
+                    q->rc = fail.code;
                 }
-                set_error(ix, "out of host memory");
+                set_error(ix, fail.message);
             }
             lk.lock();
             for (void* p : taken) static_cast<PendingQuery*>(p)->done = true;
@@ -1802,7 +1771,7 @@ int cdb_set_option(cdb_index* h, const char* name, int64_t value) {
     else if (!std::strcmp(name, "wave_rows")) ix.use_wave_rows = value != 0;
     else if (!std::strcmp(name, "keep_keys")) ix.keep_keys = value != 0;
     else {
-        set_error(ix, (std::string("unknown option: ") + name).c_str());
+        set_error(ix, std::string("unknown option: ") + name);
         return CDB_E_INVALID;
     }
     return CDB_OK;

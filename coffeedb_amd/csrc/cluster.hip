@@ -15,7 +15,6 @@
 // re-ordered by std::string::operator< on the host when the array is not in plain unsigned order; an (id, document) table when
 // the ids do not ascend.  Per call: id -> document -> class, sort of (class, id rank), run lengths.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <numeric>
 #include <string_view>
@@ -36,11 +35,6 @@ constexpr uint64_t SIGN = 1ull << 63;
 // bisection's locality): provisional for other shapes — more distinct values lengthen the dense pass over the runs, shuffled rows
 // slow both lookups; not measured.
 constexpr uint64_t DENSE_NUM = 1, DENSE_DEN = 4;
-
-double wall_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
     for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
@@ -607,7 +601,7 @@ void cluster_prepare(Index& ix) {
         ix.prof.end(t, "clu_compact_write", entry_bytes + nne * 4, s);
     });
     CDB_HIP(hipGetLastError());
-    if (nne > ndocs) throw Error("cdb_cluster: more offset-0 entries than documents (internal)");
+    if (nne > ndocs) throw InternalError("cdb_cluster: more offset-0 entries than documents (internal)");
     const uint32_t first = nne < ndocs ? 1 : 0;  // empty documents have no suffix: they are class 0
     // 2. neighbours compared against the text, heads scanned into class numbers
     uint64_t nclasses = first;

@@ -12,7 +12,6 @@
 // and duplicate-free by construction).  A column key of an AND that is broader than the other keys is never materialised: the
 // merged rows of the other keys are probed against it (id -> rank by binary search over id_sorted -> vpos -> windows).
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -31,11 +30,6 @@ constexpr uint64_t MAX_ROWS = 0xFFFFFFFFull;  // vpos and the carried ranks are 
 // timestamp ids, both paths forced at 19 selectivities from 0.2 % to 95 %: sparse still wins at 60 % (1.75 vs
 // 1.78 ms), dense wins from 65 % on (1.81 vs 1.84 ms; 2.28 vs 2.59 ms at 95 %) — the crossover lies between, 5/8 is its middle.
 constexpr uint64_t DENSE_NUM = 5, DENSE_DEN = 8;
-
-double wall_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 // ---- keys --------------------------------------------------------------------------------------------------------------
 // int64: v ^ 2^63; double: sign-flip order with -0.0 folded onto +0.0 (the two zeros compare equal in the reference's pairs and
@@ -428,7 +422,7 @@ Windows column_windows(cdb_column* c, const std::vector<std::string>& ranges) {
             } catch (const Error&) {
                 throw;
             } catch (const std::runtime_error& e) {
-                throw Error(e.what());  // "Invalid range: ..." / "Invalid value: ..." verbatim
+                throw Error(e.what());  // "Invalid range: ..." / "Invalid value: ..." verbatim: the caller's mistake, whatever its words
             }
         }
         const uint64_t nb = 2 * nr;
@@ -575,15 +569,7 @@ int cdb_column_create(cdb_column** out, int device, int kind) {
     if (!out) return CDB_E_INVALID;
     *out = nullptr;
     if (kind < 0 || kind > 2) return CDB_E_INVALID;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return CDB_E_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return CDB_E_DEVICE;
-    }
-    if (device >= count) return CDB_E_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return CDB_E_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return CDB_E_DEVICE;  // kernels exist for gfx950 only
+    if (!usable_device(device)) return CDB_E_DEVICE;
     cdb_column* c = new (std::nothrow) cdb_column();
     if (!c) return CDB_E_DEVICE;
     c->kind = kind;
@@ -610,13 +596,8 @@ void cdb_column_destroy(cdb_column* c) {
 }
 
 const char* cdb_column_last_error(const cdb_column* c) {
-    if (!c) return "null column";
     static thread_local std::string copy;
-    {
-        std::lock_guard<std::mutex> g(c->ws.err_mu);
-        copy = c->ws.err;
-    }
-    return copy.c_str();
+    return c ? last_error_copy(c->ws.err_mu, c->ws.err, copy) : "null column";
 }
 
 int cdb_column_add_bulk(cdb_column* c, const int64_t* ids, const void* values, uint64_t n) {

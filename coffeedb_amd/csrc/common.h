@@ -4,21 +4,20 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "errors.h"
+
 namespace cdb {
 
-struct Error : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
 // the bucket-wise build chose a key form that exists in the sweep kernels only (variable-length keys, partial symbol) and then had
 // to take another records form: build_suffix_array redoes the build with plain dense keys (counted: stat "dense_key_retries")
 struct RetryWithDenseKeys : Error {
@@ -29,9 +28,22 @@ struct RetryWithDenseKeys : Error {
     do {                                                                                         \
         hipError_t e_ = (expr);                                                                  \
         if (e_ != hipSuccess)                                                                    \
-            throw ::cdb::Error(std::string("HIP error in " #expr ": ") + hipGetErrorString(e_)); \
+            throw ::cdb::DeviceError(std::string("HIP error in " #expr ": ") + hipGetErrorString(e_)); \
     } while (0)
 
+inline double wall_ms() {  // host wall clock
+    using namespace std::chrono;
+    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+// `device` (negative: the calling thread's current one, written back) exists and is a gfx950: kernels exist for gfx950 only
+inline bool usable_device(int& device) {
+    int count = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return false;
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return false;
+    if (device >= count || hipGetDeviceProperties(&prop, device) != hipSuccess) return false;
+    return std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
+}
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 inline int bit_width64(uint64_t x) { return x == 0 ? 0 : 64 - __builtin_clzll(x); }
 // workgroups of 256 threads for a grid-stride loop over n items
@@ -48,7 +60,7 @@ __device__ __forceinline__ uint64_t load_be8(const uint8_t* p) {
 // may still touch it is tagged (stream, event) and handed to ANOTHER stream only once the event has completed;
 // the same stream may take it back at once (stream order).
 inline thread_local hipStream_t tls_stream = nullptr;
-// Library calls in flight (every C-ABI entry that does device work counts itself in: capi.hip guarded(), shards.hip guarded_on()).
+// Library calls in flight (every C-ABI entry that does device work counts itself in: index_impl.h guarded_call()).
 // The order proof behind a build (verify.hip) launches its slices in the gaps: a batched search is bound by the memory system's
 // random-sector rate, and a sweep that reads a random text sector per suffix beside it cost the query 5 x its time (8 GiB Zipf:
 // 18 -> 100 ms per million patterns).
@@ -156,7 +168,7 @@ public:
         }
         if (e != hipSuccess) {
             (void)hipGetLastError();  // (callers may catch this and carry on: leave no sticky error behind)
-            throw Error(std::string("HIP error in hipMalloc: ") + hipGetErrorString(e));
+            throw DeviceError(std::string("HIP error in hipMalloc: ") + hipGetErrorString(e));
         }
         actual = need;
         {

@@ -650,29 +650,33 @@ __host__ __device__ __forceinline__ uint64_t column_key_raw(int kind, uint64_t k
     if (kind == 2) return (key & S) ? (key ^ S) : ~key;
     return key;
 }
-// body of a C-ABI entry point that reports through an Index (columns, clusters): exceptions -> CDB_E_* + last-error text
+// The body of every C-ABI entry point that can fail: the call counts itself in (common.h: ForegroundCall), and an exception
+// becomes its CDB_E_* code (errors.h) plus the object's last-error text.  Calls run concurrently on one object (database.cpp:388),
+// so the text has its own lock.
 template <typename F>
-int guarded_ix(Index& ix, F&& f) {
+int guarded_call(std::mutex& err_mu, std::string& err, F&& f) {
     ForegroundCall fg;
-    auto set_err = [&ix](const char* msg) {
-        std::lock_guard<std::mutex> g(ix.err_mu);
-        ix.err = msg;
-    };
     try {
         f();
         return CDB_OK;
-    } catch (const Error& e) {
-        set_err(e.what());
-        const bool dev = std::strncmp(e.what(), "HIP error", 9) == 0;
-        const bool internal = std::strstr(e.what(), "internal") != nullptr;
-        return dev ? CDB_E_DEVICE : (internal ? CDB_E_INTERNAL : CDB_E_INVALID);
-    } catch (const std::bad_alloc&) {
-        set_err("out of host memory");
-        return CDB_E_DEVICE;
-    } catch (const std::exception& e) {
-        set_err(e.what());
-        return CDB_E_INTERNAL;
+    } catch (...) {
+        Failure fail = classify_current_exception();
+        std::lock_guard<std::mutex> g(err_mu);
+        err = std::move(fail.message);
+        return fail.code;
     }
+}
+// ... for an object that reports through an Index (string indexes, columns, clusters)
+template <typename F>
+int guarded_ix(Index& ix, F&& f) {
+    return guarded_call(ix.err_mu, ix.err, std::forward<F>(f));
+}
+// What a *_last_error accessor returns: the text copied under its lock into the accessor's own per-thread string, so that
+// another thread's failing call cannot pull it away under the reader.
+inline const char* last_error_copy(std::mutex& err_mu, const std::string& err, std::string& copy) {
+    std::lock_guard<std::mutex> g(err_mu);
+    copy = err;
+    return copy.c_str();
 }
 int query_and_with_lead(cdb_index* lead, const cdb_key_query* keys, int nkeys, int ranked, int64_t corr_lo, int64_t corr_hi,
                         uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows);

@@ -1767,7 +1767,7 @@ bool query_single_collect(Index& ix, int64_t** ids_out, int64_t** counts_out, si
             }
             __builtin_ia32_pause();
         }
-        if (v == ~0ull) throw Error("HIP error: the resident query kernel did not answer");
+        if (v == ~0ull) throw DeviceError("HIP error: the resident query kernel did not answer");
         ix.res_answers++;
     } else {
         ix.launched_answers++;
@@ -1781,7 +1781,7 @@ bool query_single_collect(Index& ix, int64_t** ids_out, int64_t** counts_out, si
         if (v == ~0ull) CDB_HIP(hipStreamSynchronize(s));
     }
     if (out->nrows >= ~0ull - 1) {
-        if (out->nrows == ~0ull) throw Error("HIP error: the single-keyword kernel did not answer");
+        if (out->nrows == ~0ull) throw DeviceError("HIP error: the single-keyword kernel did not answer");
         if (getenv("CDB_DEBUG_SINGLE")) std::fprintf(stderr, "[single] handed over: hits=%llu\n", (unsigned long long)out->hits);
         if (!ix.resident_query) CDB_HIP(hipStreamSynchronize(s));
         return false;

@@ -1495,7 +1495,7 @@ int radix_sort_cfg(hipStream_t s, RadixWorkspace& ws, Profiler& prof, K* k0, K* 
     int lead = 0;
     if constexpr (GEN && HAS_W) lead = gen->low_bits / dbits;
     else if constexpr (HAS_W) lead = lead_in;
-    if (HAS_W && !GEN && !h_hist_in && !d_hist_in) throw Error("radix_sort: split records need caller-supplied histograms (internal)");
+    if (HAS_W && !GEN && !h_hist_in && !d_hist_in) throw InternalError("radix_sort: split records need caller-supplied histograms (internal)");
     const int LEAD = lead;
     if (n == 0 || end_bit < begin_bit || (!LEAD && end_bit == begin_bit)) return 0;
     const int nbits = end_bit - begin_bit;
@@ -1521,7 +1521,7 @@ int radix_sort_cfg(hipStream_t s, RadixWorkspace& ws, Profiler& prof, K* k0, K* 
         hipLaunchKernelGGL(rs_digit_start_kernel, dim3(npass), dim3(256), 0, s, d_hist, d_start);
         CDB_HIP(hipStreamSynchronize(s));  // h_hist is pageable host memory
     } else {
-        if (GEN) throw Error("radix_sort: a generated first pass needs caller-supplied histograms (internal)");
+        if (GEN) throw InternalError("radix_sort: a generated first pass needs caller-supplied histograms (internal)");
         CDB_HIP(hipMemsetAsync(d_hist, 0, RS_MAX_PASSES * 256 * sizeof(uint64_t), s));
         const int grid = (int)std::min<uint64_t>(ceil_div(n, 256 * 16), 256 * 8);
         int t = prof.begin(s);
@@ -1672,7 +1672,7 @@ int radix_sort(hipStream_t s, RadixWorkspace& ws, Profiler& prof, K* k0, K* k1, 
                                                                  stats, dbits, h_hist_in, gen);                       \
     CDB_RS(__VA_ARGS__)
         if (gen && !rs_variant_has_gen(variant))
-            throw Error("radix_sort: this kernel configuration has no generated first pass (internal)");
+            throw InternalError("radix_sort: this kernel configuration has no generated first pass (internal)");
         switch (variant) {
             // production configurations: IPT, REUSE, EARLYV, NT, NONTEMP, MINW, ABL, LB
             default:
@@ -1703,7 +1703,7 @@ inline void radix_check_error(hipStream_t s, RadixWorkspace& ws) {
     CDB_HIP(hipStreamSynchronize(s));
     if (e) {
         CDB_HIP(hipMemsetAsync(ws.err_ptr(), 0, sizeof(uint32_t), s));
-        throw Error("radix sort look-back timed out (internal error)");
+        throw LookbackTimeout("radix sort look-back timed out (internal error)");
     }
     if (getenv("CDB_LOOKBACK_STATS")) {
         uint32_t c[3] = {0, 0, 0};
@@ -1807,10 +1807,10 @@ void radix_sort_segmented(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uin
                           W* w0, W* w1, uint64_t m, const SegInfo* d_segs, const uint32_t* d_tile_seg, uint32_t nseg, uint32_t tiles,
                           const unsigned long long* d_hist, unsigned long long* d_starts, int key_bits, int lead, SegFinalArgs fin,
                           SortStats* stats) {
-    if (!rs_atomic_rank_ok(s)) throw Error("radix_sort_segmented: needs the one-atomic ranking (internal)");
+    if (!rs_atomic_rank_ok(s)) throw InternalError("radix_sort_segmented: needs the one-atomic ranking (internal)");
     const int kpass = (int)ceil_div((uint64_t)key_bits, 8);
     const int npass = kpass + lead;
-    if (npass < 1 || npass > 8 || kpass < 1) throw Error("radix_sort_segmented: unsupported pass count (internal)");
+    if (npass < 1 || npass > 8 || kpass < 1) throw InternalError("radix_sort_segmented: unsupported pass count (internal)");
     const int last_bits = key_bits - 8 * (kpass - 1);
     const uint32_t last_mask = (1u << last_bits) - 1u;
     ws.prepare((uint64_t)tiles * RS_SEG_TILE, RS_SEG_TILE, s);
@@ -2115,7 +2115,7 @@ inline void radix_sort_msd(hipStream_t s, RadixWorkspace& ws, MsdWorkspace& mw, 
                            const uint32_t* d_tile_counts = nullptr, TileBaseWorkspace* tbw = nullptr, bool sweep_form = true) {
     // gen_in says how the generated pass splits a key into (top digit, u32 rest): msd_shift = 32 (msd_m = 2^32) or the pair
     // form (msd_m = span * base^4); the last pass puts the full key together again as top * msd_m + rest
-    if (!rs_atomic_rank_ok(s)) throw Error("radix_sort_msd: needs the one-atomic ranking (internal)");
+    if (!rs_atomic_rank_ok(s)) throw InternalError("radix_sort_msd: needs the one-atomic ranking (internal)");
     constexpr int TILE = RS_SEG_TILE;
     constexpr int KPASS = 4;
     using CfgG = RsCfg<16, true, true, 1024, false, 1, 0, 4, false, true, true, 1, RS_GROUP>;
@@ -2132,7 +2132,7 @@ inline void radix_sort_msd(hipStream_t s, RadixWorkspace& ws, MsdWorkspace& mw, 
             seg_tiles += (uint32_t)ceil_div(h_top[d], (uint64_t)TILE);
             at += h_top[d];
         }
-        if (at != n) throw Error("radix_sort_msd: top-digit histogram does not add up (internal)");
+        if (at != n) throw InternalError("radix_sort_msd: top-digit histogram does not add up (internal)");
     }
     const uint32_t nseg = (uint32_t)h_segs.size();
     const uint32_t gen_tiles = (uint32_t)ceil_div(n, (uint64_t)TILE);
@@ -2286,7 +2286,7 @@ void radix_gen_records(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uint32
                        const TextGen& gen_in, const uint32_t* d_tile_seg, const SegInfo* d_segs, uint32_t nseg, uint32_t seg_tiles, int lead,
                        int npass, unsigned long long* d_hist_out, SortStats* stats,
                        const uint32_t* d_tile_counts = nullptr, const uint16_t* d_src_col = nullptr, TileBaseWorkspace* tbw = nullptr) {
-    if (!rs_atomic_rank_ok(s)) throw Error("radix_gen_records: needs the one-atomic ranking (internal)");
+    if (!rs_atomic_rank_ok(s)) throw InternalError("radix_gen_records: needs the one-atomic ranking (internal)");
     constexpr int TILE = RS_SEG_TILE;
     using CfgG = RsCfg<16, true, true, 1024, false, 1, 0, 4, false, true, true, 1, RS_GROUP>;
     using CfgP = RsCfg<16, true, true, 1024, false, 1, 0, 4, false, true>;

@@ -946,8 +946,8 @@ void radix_sweep_records(hipStream_t s, Profiler& prof, uint32_t* k, uint32_t* v
                          uint32_t g0, uint32_t g1,
                          uint64_t gstart, uint64_t gelems, const uint32_t* d_tile_seg, const SegInfo* d_segs, uint32_t nseg, uint32_t seg_tiles,
                          int lead, int npass, unsigned long long* d_hist_out, SortStats* stats) {
-    if (!gen_in.tile_base || !gen_in.tile_doc || !d_codeslot || !gen_in.slotmap) throw Error("radix_sweep_records: tile bases / documents / slots missing (internal)");
-    if (!rs_sweep_records_ok(gen_in.base, gen_in.nsym)) throw Error("radix_sweep_records: key shape (internal)");
+    if (!gen_in.tile_base || !gen_in.tile_doc || !d_codeslot || !gen_in.slotmap) throw InternalError("radix_sweep_records: tile bases / documents / slots missing (internal)");
+    if (!rs_sweep_records_ok(gen_in.base, gen_in.nsym)) throw InternalError("radix_sweep_records: key shape (internal)");
     const uint32_t tiles8 = (uint32_t)ceil_div(n, (uint64_t)RS_SWEEP_TILE);
     const uint32_t grid = (uint32_t)(ceil_div(tiles8, 8u * RS_GROUP) * 8u * RS_GROUP);
     CDB_HIP(hipMemsetAsync(d_hist_out, 0, (size_t)nseg * 8 * 256 * sizeof(uint64_t), s));
@@ -969,8 +969,8 @@ void radix_sweep_records_vl(hipStream_t s, Profiler& prof, uint32_t* k, uint32_t
                             const VlTables& vl, uint32_t g0, uint32_t g1, uint64_t gstart, uint64_t gelems, const uint32_t* d_tile_seg,
                             const SegInfo* d_segs, uint32_t nseg, uint32_t seg_tiles, int lead, int npass, unsigned long long* d_hist_out,
                             SortStats* stats) {
-    if (!gen_in.tile_base || !gen_in.tile_doc || !d_codeslot || !vl.sym || !vl.dec) throw Error("radix_sweep_records_vl: tables missing (internal)");
-    if (vl.key_bits < 16 || vl.key_bits > 56) throw Error("radix_sweep_records_vl: key width (internal)");
+    if (!gen_in.tile_base || !gen_in.tile_doc || !d_codeslot || !vl.sym || !vl.dec) throw InternalError("radix_sweep_records_vl: tables missing (internal)");
+    if (vl.key_bits < 16 || vl.key_bits > 56) throw InternalError("radix_sweep_records_vl: key width (internal)");
     const uint32_t tiles8 = (uint32_t)ceil_div(n, (uint64_t)RS_SWEEP_TILE);
     const uint32_t grid = (uint32_t)(ceil_div(tiles8, 8u * RS_GROUP) * 8u * RS_GROUP);
     CDB_HIP(hipMemsetAsync(d_hist_out, 0, (size_t)nseg * 8 * 256 * sizeof(uint64_t), s));

@@ -253,7 +253,7 @@ void remove_compact(Index& ix, RemovePlan& p, int new_bits, int new_width, bool 
     DevBuf tile_base;
     const EntryKept kept{ix.d_sa.as<uint32_t>(), (!ix.sa_packed && ix.width == 8) ? 2 : 1, (uint32_t)ix.mask, p.drop.as<uint8_t>()};
     if (tile_bases(ix, "remove", kept, n, tile_base, "rm_count", n * (4 + 1) + ntiles * 8) != m)
-        throw Error("remove: kept entries and kept bytes differ (internal)");
+        throw InternalError("remove: kept entries and kept bytes differ (internal)");
     const int old_bytes = ix.sa_packed ? 5 : ix.width;
     const int t = ix.prof.begin(s);
     sa_dispatch(ix, [&](auto src_tag) {

@@ -16,7 +16,6 @@
 //   5. per row: span_ptr by bisection over the spans' page positions, text_ptr from it; per span: offsets inside the document.
 // No sort, no atomic per occurrence, no loop along a document: one very long document spreads over as many workgroups as it has tiles.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 
 #include "../../include/coffeedb_gpu.h"
@@ -37,11 +36,6 @@ constexpr int RN_MAX_KW = 256;
 constexpr int RN_KW_BYTES = 8192;
 constexpr uint32_t RN_NODOC = 0xFFFFFFFFu;
 constexpr uint64_t RN_MAX_DOC = 0xFFFF0000ull;  // (row ends relative to a tile are kept in 32 bits)
-
-double wall_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 
 // row i -> doc[i] (RN_NODOC: the index does not hold ids[i]) and found[i]; out[0] += rows missed, out[1] = longest document met
 __global__ __launch_bounds__(256) void rnd_lookup_kernel(const int64_t* __restrict__ ids, uint64_t nrows, const int64_t* __restrict__ id_tab,
@@ -449,7 +443,7 @@ void render_rows(Index& ix, const int64_t* ids, uint64_t nrows, const Keywords& 
         MarkIn min_{d_mark.as<uint8_t>()};
         const U2 tot = scan_totals<U2>(s, ix.scan_partials, min_, P, OpAdd{}, U2{0, 0});
         ix.prof.end(t, "rnd_mark_scan", P, s);
-        if (tot.a != tot.b) throw Error("cdb_render_rows: span begins and ends do not pair up (internal)");
+        if (tot.a != tot.b) throw InternalError("cdb_render_rows: span begins and ends do not pair up (internal)");
         nspans = tot.a;
         d_sbeg.alloc(nspans * 8);
         d_send.alloc(nspans * 8);

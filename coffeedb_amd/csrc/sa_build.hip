@@ -3327,7 +3327,7 @@ InitialSort initial_sort_bucketwise(Index& ix, Alphabet& al, const KeyPlan& kp, 
             if (fuse_rec) seg_cap = n;  // (decided with the same bound before the entries were NOT partitioned)
         }
         if (!fuse_rec && ix.debug_no_segcap) seg_cap = 0;  // (test hook: "a bucket does not fit the record memory")
-        if (fuse_rec && !seg_cap) throw Error("bucket-wise build: fused records without the segmented sort (internal)");
+        if (fuse_rec && !seg_cap) throw InternalError("bucket-wise build: fused records without the segmented sort (internal)");
         if ((rf.vl_bits || rf.part_m > 1) && !seg_cap) throw RetryWithDenseKeys(kVlRetry);
         if (rf.sweep_rec && !seg_cap) {  // (a bucket larger than the record memory: partition + gather, bucket by bucket)
             rf.sweep_rec = false;
@@ -3528,7 +3528,7 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
         st.unresolved_max = std::max(st.unresolved_max, m);
         if (m == 0) break;
         // (the per-entry kernels of a round address one thread per unresolved entry: a launch holds < 2^32 of them)
-        if (m >= (1ull << 32) - 4096) throw Error("too many unresolved suffixes for one refinement round (internal limit: 2^32)");
+        if (m >= (1ull << 32) - 4096) throw InternalError("too many unresolved suffixes for one refinement round (internal limit: 2^32)");
         const int gbits = bit_width64(G - 1);
         int nsym2 = std::min((64 - gbits) / symbits, KG_LOOK);
         if (!isa) {
@@ -3557,7 +3557,7 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
             }
         }
         const int kbits = isa ? bit_width64(n) : nsym2 * symbits;
-        if (kbits + gbits > 64) throw Error("refinement key does not fit 64 bits (internal limit)");
+        if (kbits + gbits > 64) throw InternalError("refinement key does not fit 64 bits (internal limit)");
         if (m > cap) {
             cap = m;
             U.alloc(m * sizeof(I));
@@ -3653,7 +3653,7 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
         }
         h = hnew;
         st.rounds++;
-        if (st.rounds > 80) throw Error("suffix-array refinement did not converge (internal error)");
+        if (st.rounds > 80) throw InternalError("suffix-array refinement did not converge (internal error)");
     }
     return h;
 }
@@ -3731,7 +3731,7 @@ void build_typed(Index& ix, bool big) {
         ix.drop_keys();
         return;
     }
-    if (sizeof(R) == 4 && n + D + 2 >= (1ull << 32)) throw Error("internal: 32-bit ranks selected for a corpus >= 2^32");
+    if (sizeof(R) == 4 && n + D + 2 >= (1ull << 32)) throw InternalError("internal: 32-bit ranks selected for a corpus >= 2^32");
     Alphabet al;
     count_alphabet<V>(ix, big, al);
     TopCounts tc;
@@ -3753,7 +3753,7 @@ void build_typed(Index& ix, bool big) {
         h = refine_groups<V, I, R>(ix, SaRW<V>{is.sa_buf.as<V>()}, is, al, kp, ss, rb);
     }
     if (ix.debug_fail_build) throw Error("debug: build failure requested (test hook)");
-    if (ix.debug_starve_group == 1 && !ix.rws.plain_order) throw Error("radix sort look-back timed out (test hook)");
+    if (ix.debug_starve_group == 1 && !ix.rws.plain_order) throw LookbackTimeout("radix sort look-back timed out (test hook)");
     st.final_depth = h;
     st.sort_passes = ss.passes_run;
     st.sort_passes_skipped = ss.passes_skipped;
@@ -3777,7 +3777,7 @@ void build_suffix_array(Index& ix) {
     if (!ix.debug_starve_group && rs_group_order_starved(ix.device)) ix.rws.plain_order = true;  // (learnt by an earlier handle)
     auto run = [&]() {
         const bool wide = ix.size + ix.ndocs + 2 >= (1ull << 32) || ix.force_big_path;
-        if (wide && ix.width != 8 && !ix.force_big_path) throw Error("internal: a corpus >= 2^32 bytes must have 8-byte entries");
+        if (wide && ix.width != 8 && !ix.force_big_path) throw InternalError("internal: a corpus >= 2^32 bytes must have 8-byte entries");
         if (!wide) {
             if (ix.width == 4) build_typed<uint32_t, uint32_t, uint32_t>(ix, false);
             else build_typed<uint64_t, uint32_t, uint32_t>(ix, false);
@@ -3812,11 +3812,11 @@ void build_suffix_array(Index& ix) {
     try {
         try {
             run_dense_after_vl();
-        } catch (const Error& e) {
+        } catch (const LookbackTimeout&) {
             // A pass in XCD-aware tile order needs a few dozen workgroups resident at once (radix_sort.h: RS_GROUP);
             // other kernels on the device can starve it, which ends in the (bounded) look-back timeout.  The plain
             // ticket order needs one resident workgroup: rebuild with it, and keep it for this handle.
-            if (ix.rws.plain_order || std::strstr(e.what(), "look-back timed out") == nullptr) throw;
+            if (ix.rws.plain_order) throw;
             discard(false);
             ix.rws.plain_order = true;
             if (!ix.debug_starve_group) rs_group_order_disable(ix.device);  // (the test hook leaves the device alone)
@@ -3882,7 +3882,7 @@ void build_suffix_array(Index& ix) {
             }
             if (!check()) {
                 discard(true);
-                throw Error("suffix array self-check failed: " + std::to_string(sc[0]) + " pairs out of order, " + std::to_string(sc[1]) +
+                throw InternalError("suffix array self-check failed: " + std::to_string(sc[0]) + " pairs out of order, " + std::to_string(sc[1]) +
                             " invalid entries among the sampled pairs (internal error)");
             }
         }

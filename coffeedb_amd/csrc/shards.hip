@@ -84,7 +84,7 @@ struct RcclApi {
         ncclResult_t r_ = (expr);                                                                         \
         if (r_ != ncclSuccess) {                                                                          \
             const RcclApi& a_ = RcclApi::get();                                                           \
-            throw ::cdb::Error(std::string("HIP error in " #expr " (RCCL): ") +                           \
+            throw ::cdb::DeviceError(std::string("HIP error in " #expr " (RCCL): ") +                           \
                                (a_.GetErrorString ? a_.GetErrorString(r_) : "unknown"));                  \
         }                                                                                                 \
     } while (0)
@@ -112,7 +112,7 @@ struct RcclTransport : Transport {
     ncclComm_t comm_of(int rank) const {
         for (size_t i = 0; i < local_rank.size(); ++i)
             if (local_rank[i] == rank) return comms[i];
-        throw Error("internal: rank is not local to this communicator");
+        throw InternalError("internal: rank is not local to this communicator");
     }
     void all_gather(int rank, const void* send, void* recv, size_t bytes, hipStream_t s) override {
         CDB_NCCL(RcclApi::get().AllGather(send, recv, bytes, ncclUint8, comm_of(rank), s));
@@ -250,7 +250,7 @@ struct MergeRank {
     bool own_stream = false;
     std::shared_ptr<Transport> tr;
     DevBuf cnt, all_cnt, flat_ptr, g_row_ptr, offs, st_ids, st_cnt, out_ids, out_cnt, partials;
-    std::mutex err_mu;
+    mutable std::mutex err_mu;
     std::string err;
     ~MergeRank() {
         if (own_stream && stream) {
@@ -300,7 +300,7 @@ void merge_core(MergeRank& mr, const cdb_device_result& local, cdb_device_result
     CDB_HIP(hipStreamSynchronize(s));
     for (int q = 0; q < G; ++q) cntv[q] = off[q + 1] - off[q];
     const uint64_t total = off[G];
-    if (cntv[mr.rank] != local.nrows) throw Error("internal: shard row count does not match its row_ptr");
+    if (cntv[mr.rank] != local.nrows) throw InternalError("internal: shard row count does not match its row_ptr");
     merged.nrows = total;
     merged.d_row_ptr = mr.g_row_ptr.as<uint64_t>();
     if (total == 0) return;
@@ -370,25 +370,8 @@ void merge_counts_core(MergeRank& mr, const cdb_device_result& local, cdb_shard_
 }
 
 template <typename T, typename F>
-int guarded_on(T* obj, F&& f) {
-    ForegroundCall fg;  // (order proofs yield to calls in flight: common.h)
-    try {
-        f();
-        return CDB_OK;
-    } catch (const Error& e) {
-        std::lock_guard<std::mutex> g(obj->err_mu);
-        obj->err = e.what();
-        const bool dev = std::strncmp(e.what(), "HIP error", 9) == 0;
-        return dev ? CDB_E_DEVICE : (std::strstr(e.what(), "internal") ? CDB_E_INTERNAL : CDB_E_INVALID);
-    } catch (const std::bad_alloc&) {
-        std::lock_guard<std::mutex> g(obj->err_mu);
-        obj->err = "out of host memory";
-        return CDB_E_DEVICE;
-    } catch (const std::exception& e) {
-        std::lock_guard<std::mutex> g(obj->err_mu);
-        obj->err = e.what();
-        return CDB_E_INTERNAL;
-    }
+int guarded_on(T* obj, F&& f) {  // (a merge rank or a sharded index: each has its own err / err_mu)
+    return guarded_call(obj->err_mu, obj->err, std::forward<F>(f));
 }
 
 // doc-aligned split into `parts` contiguous ranges balanced by bytes: docs [b[r], b[r+1])
@@ -506,11 +489,8 @@ int cdb_comm_create_group(cdb_comm** out, int world, const int* devices) {
 void cdb_comm_destroy(cdb_comm* c) { delete c; }
 
 const char* cdb_comm_last_error(const cdb_comm* c) {
-    if (!c) return "null handle";
     static thread_local std::string copy;
-    std::lock_guard<std::mutex> g(const_cast<cdb_comm*>(c)->mr.err_mu);
-    copy = c->mr.err;
-    return copy.c_str();
+    return c ? last_error_copy(c->mr.err_mu, c->mr.err, copy) : "null handle";
 }
 
 int cdb_comm_merge(cdb_comm* c, const cdb_device_result* local, cdb_device_result* merged) {
@@ -590,7 +570,7 @@ struct cdb_shards {
     std::mutex opt_mu;
     StateLock state;
     std::mutex staging_mu;                   // add* / build read and write the staged column
-    std::mutex err_mu;
+    mutable std::mutex err_mu;
     std::string err;
 };
 
@@ -605,24 +585,23 @@ void parallel_shards(int n, F&& f) {
     }
     std::vector<std::thread> th;
     std::mutex emu;
-    std::string first;
-    bool failed = false;
+    std::exception_ptr first;
     for (int i = 0; i < n; ++i)
         th.emplace_back([&, i] {
             try {
                 f(i);
-            } catch (const std::exception& e) {
+            } catch (...) {
                 std::lock_guard<std::mutex> g(emu);
-                if (!failed) first = e.what();
-                failed = true;
+                if (!first) first = std::current_exception();
             }
         });
     for (auto& t : th) t.join();
-    if (failed) throw Error(first);
+    if (first) std::rethrow_exception(first);
 }
 
+// a shard's failure becomes this call's: same code, same text
 void check_handle(cdb_index* p, int rc) {
-    if (rc != CDB_OK) throw Error(cdb_last_error(p));
+    if (rc != CDB_OK) throw Error((Status)rc, cdb_last_error(p));
 }
 void check_shard(cdb_shards* h, int i, int rc) { check_handle(h->shard[i], rc); }
 
@@ -670,7 +649,7 @@ std::vector<cdb_index*> fresh_handles(cdb_shards* h, size_t* options_seen = null
     try {
         for (size_t i = 0; i < h->devices.size(); ++i) {
             cdb_index* p = nullptr;
-            if (cdb_create(&p, h->devices[i]) != CDB_OK) throw Error("HIP error: cannot create a shard handle");
+            if (cdb_create(&p, h->devices[i]) != CDB_OK) throw DeviceError("HIP error: cannot create a shard handle");
             fresh.push_back(p);
             for (auto& kv : options) (void)cdb_set_option(p, kv.first.c_str(), kv.second);
         }
@@ -784,11 +763,8 @@ void cdb_shards_destroy(cdb_shards* h) {
 }
 
 const char* cdb_shards_last_error(const cdb_shards* h) {
-    if (!h) return "null handle";
     static thread_local std::string copy;
-    std::lock_guard<std::mutex> g(const_cast<cdb_shards*>(h)->err_mu);
-    copy = h->err;
-    return copy.c_str();
+    return h ? last_error_copy(h->err_mu, h->err, copy) : "null handle";
 }
 
 int cdb_shards_add(cdb_shards* h, int64_t id, const char* value, size_t len) {

@@ -47,7 +47,7 @@ template <typename Pred>
 uint64_t tile_bases(Index& ix, const char* op, Pred flagged, uint64_t n, DevBuf& tile_base, const char* label, uint64_t bytes) {
     hipStream_t s = ix.stream;
     const uint64_t ntiles = ceil_div(n, ST_TILE);
-    if (ntiles >= (1ull << 31)) throw Error(std::string(op) + ": the array has too many tiles for one launch (internal)");
+    if (ntiles >= (1ull << 31)) throw InternalError(std::string(op) + ": the array has too many tiles for one launch (internal)");
     DevBuf tile_count;
     tile_count.alloc(ntiles * 8);
     tile_base.alloc(ntiles * 8);

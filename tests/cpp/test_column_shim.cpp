@@ -63,6 +63,9 @@ static void numeric_on_gpu() {
     threw = false;
     try { bi.query("maybe"); } catch (const std::runtime_error& e) { threw = std::string(e.what()) == "Invalid query: \"maybe\""; }
     CHECK(threw);
+    threw = false;  // the caller's words do not decide the error's class: the reference's wording, no "GPU column: " in front
+    try { bi.query("internal"); } catch (const std::runtime_error& e) { threw = std::string(e.what()) == "Invalid query: \"internal\""; }
+    CHECK(threw);
     CHECK(string_index::number == 3 && double_index::number == 2 && integer_index::number == 1 && bool_index::number == 0);
 }
 

@@ -218,6 +218,34 @@ def test_bool_insertion_order_and_messages():
     col.close()
 
 
+# ---- the status of a range error is the caller's mistake, whatever words the caller sent ------------------------------------
+def _query_status(col, range_):
+    """(code, last-error text) of cdb_column_query, below the binding (which keeps only the text)."""
+    import ctypes as C
+    r = range_.encode()
+    ids, n = C.POINTER(C.c_int64)(), C.c_size_t(0)
+    rc = col._lib.cdb_column_query(col._h, r, len(r), C.byref(ids), C.byref(n))
+    return rc, col._lib.cdb_column_last_error(col._h).decode()
+
+
+def test_echoed_range_text_does_not_steer_the_status_code():
+    CDB_E_INVALID = 1
+    ids = np.arange(4, dtype=np.int64)
+    b = capi.GpuColumn("bool", device=0)
+    b.add_bulk(ids, [0, 1, 0, 1])
+    b.build()
+    assert _query_status(b, "internal") == (CDB_E_INVALID, 'Invalid query: "internal"')
+    b.close()
+    c = capi.GpuColumn("int64", device=0)
+    c.add_bulk(ids, [1, 2, 3, 4])
+    c.build()
+    assert _query_status(c, "[internal,5]") == (CDB_E_INVALID, "Invalid value: internal")
+    assert _query_status(c, "HIP error [1,2]") == (CDB_E_INVALID, "Invalid range: HIP error [1,2]")
+    assert _query_status(c, "[HIP error,2]") == (CDB_E_INVALID, "Invalid value: hip error")   # (utility.h:51 lowers the value)
+    assert c.query("[2,3]") == [(1, 0), (2, 0)]
+    c.close()
+
+
 # ---- query_any: both materialising paths ---------------------------------------------------------------------------------
 def test_query_any_sparse_and_dense_paths():
     rng = np.random.default_rng(21)

@@ -167,6 +167,26 @@ def test_sharded_and_persistence_raw_ingest(tmp_path):
         x.close()
 
 
+def test_a_shard_threads_error_keeps_its_code_and_text(tmp_path):
+    # two shards on one device; shard 1's file is gone, so cdb_load fails inside that shard's thread with a caller error, which
+    # parallel_shards + check_handle hand to cdb_shards_load: the code and the text are the shard's own
+    from coffeedb_amd import capi
+    blob, ds = W.ragged_corpus(40, 30, seed=3, lo=0x61, hi=0x64, empty_every=0)
+    sh = capi.GpuShards([0, 0])
+    sh.set_option("use_all_devices", 1)
+    sh.add_bulk(np.arange(40, dtype=np.int64), blob, ds)
+    sh.build()
+    path = str(tmp_path / "col.cdbs")
+    sh.save(path)
+    (tmp_path / "col.cdbs.1").unlink()
+    sl = capi.GpuShards([0, 0])
+    rc = sl._lib.cdb_shards_load(sl._h, path.encode())
+    assert (rc, sl._lib.cdb_shards_last_error(sl._h).decode()) == (1, f"Cannot open file: {path}.1")   # CDB_E_INVALID
+    assert sl.count == 0
+    for x in (sl, sh):
+        x.close()
+
+
 def test_sharded_queries_run_while_a_rebuild_takes_over():
     # database.cpp:276-280: the old index keeps answering (shared lock) while build() prepares the new one, which then
     # takes over under the exclusive lock.  Four query threads hammer the handle while it is rebuilt three times.
