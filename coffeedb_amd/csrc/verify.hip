@@ -174,6 +174,9 @@ struct RefOrderCtx {
 
 // is the bucket of the l-prefix that entries i - 1 and i share a radix node of the reference (more than `chuck` suffixes)?  pa =
 // suffix of entry i - 1 (>= l bytes).  Counted outwards from the pair, capped at chuck + 1.
+// (Exact where the entries that share the prefix are contiguous, as in an undamaged array.  On a damaged one the gallop can step over
+//  a foreign entry inside the bucket and count it: the result is an UPPER BOUND of the contiguous run around the pair.  "Not a node"
+//  is therefore final; "a node" is confirmed entry by entry, block_bucket_is_node below.)
 template <typename V>
 __device__ __forceinline__ bool ref_bucket_is_node(const RefOrderCtx<V>& c, uint64_t i, const uint8_t* pa, uint64_t l, uint64_t chuck) {
     uint64_t cnt = 2;
@@ -211,6 +214,95 @@ __device__ __forceinline__ bool ref_bucket_is_node(const RefOrderCtx<V>& c, uint
         cnt += good;
     }
     return cnt > chuck;
+}
+
+// number of consecutive entries at distances 1, 2, ... <= top from entry `from` (forwards or backwards) that have at least l bytes and
+// share q[0, l).  Called by a whole workgroup of 256 threads with the same arguments: 2048 entries per step, the loads of a step
+// issued side by side.  s_fail: one LDS word of the caller.
+template <typename V>
+__device__ __forceinline__ uint64_t block_shared_run(const RefOrderCtx<V>& c, uint64_t from, bool fwd, uint64_t top, const uint8_t* q, uint64_t l,
+                                                     unsigned long long* s_fail) {
+    constexpr int U = 8;
+    for (uint64_t base = 0; base < top; base += 256 * U) {
+        bool in[U];
+        uint64_t ent[U], s0[U], s1[U];
+        unsigned long long fail = ~0ull;  // the nearest distance of this thread's that does not share
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t d = base + 256 * u + threadIdx.x + 1;
+            in[u] = d <= top;
+            ent[u] = in[u] ? (uint64_t)c.sa[fwd ? from + d : from - d] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t dd = ent[u] & c.mask;
+            in[u] = in[u] && dd < c.ndocs;  // (an entry that names no document is an empty suffix: RefOrderCtx::suffix)
+            s0[u] = in[u] ? c.doc_start[dd] : 0;
+            s1[u] = in[u] ? c.doc_start[dd + 1] : 0;
+        }
+        bool ok[U];
+        const uint8_t* p[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t o = ent[u] >> c.bits, dl = s1[u] - s0[u];
+            ok[u] = in[u] && o < dl && dl - o >= l;
+            p[u] = c.text + s0[u] + o;
+        }
+        for (uint64_t k = 0; k < l; ++k) {  // byte k of every suffix of the step at once
+            uint8_t b[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) b[u] = ok[u] ? p[u][k] : q[k];
+#pragma unroll
+            for (int u = 0; u < U; ++u) ok[u] = ok[u] && b[u] == q[k];
+        }
+#pragma unroll
+        for (int u = U - 1; u >= 0; --u)
+            if (!ok[u]) fail = base + 256 * u + threadIdx.x + 1;  // (u descends: the nearest one stays)
+        __syncthreads();
+        if (threadIdx.x == 0) *s_fail = ~0ull;
+        __syncthreads();
+        if (fail != ~0ull) atomicMin(s_fail, fail);
+        __syncthreads();
+        const unsigned long long f = *s_fail;
+        if (f != ~0ull) return f - 1;  // (distances behind `top` do not share: never more than top)
+    }
+    return top;
+}
+
+// ref_bucket_is_node for the threads of a workgroup that `ask`, exact on any array.  EVERY thread of the workgroup (256) must arrive.
+// The gallop answers first; where it says "node" for a prefix of l > 0 bytes (one pair per radix node of an undamaged array: the
+// boundary between its children >= 0x80 and < 0x80) the workgroup counts the contiguous run around that pair together, up to
+// chuck + 1 entries.
+template <typename V>
+__device__ __forceinline__ bool block_bucket_is_node(const RefOrderCtx<V>& c, bool ask, uint64_t i, const uint8_t* pa, uint64_t l, uint64_t chuck) {
+    __shared__ unsigned long long s_i[256], s_l[256], s_q[256], s_fail;
+    __shared__ int s_n;
+    bool node = false;
+    if (ask) node = l == 0 ? c.n > chuck : ref_bucket_is_node(c, i, pa, l, chuck);  // (every entry shares the empty prefix)
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    int slot = -1;
+    if (ask && node && l > 0) {
+        slot = atomicAdd(&s_n, 1);
+        s_i[slot] = i;
+        s_l[slot] = l;
+        s_q[slot] = (unsigned long long)reinterpret_cast<uintptr_t>(pa);
+    }
+    __syncthreads();
+    const int asked = s_n;
+    for (int k = 0; k < asked; ++k) {
+        const uint64_t vi = s_i[k], vl = s_l[k];
+        const uint8_t* vq = reinterpret_cast<const uint8_t*>((uintptr_t)s_q[k]);
+        uint64_t cnt = 2;
+        cnt += block_shared_run(c, vi - 1, false, (vi - 1 < chuck - 1 ? vi - 1 : chuck - 1), vq, vl, &s_fail);
+        if (cnt <= chuck) {
+            const uint64_t room = chuck + 1 - cnt, lim_f = c.n - 1 - vi;
+            cnt += block_shared_run(c, vi, true, lim_f < room ? lim_f : room, vq, vl, &s_fail);
+        }
+        if (slot == k) node = cnt > chuck;
+    }
+    __syncthreads();  // (s_n and the slots are free for the next call)
+    return node;
 }
 
 // The FULL sweep (self_check = 2) by the same rules, laid out for throughput: every lane fetches ONE suffix — its entry, the
@@ -258,7 +350,7 @@ __device__ __forceinline__ SfxHead sfx_head(typename SaOf<V>::ptr sa, uint64_t i
     h.w1 = b;
     return h;
 }
-template <typename V>
+template <typename V, bool BUCKETS>  // BUCKETS: chuck > 0 (the code that counts buckets costs registers the plain sweep does not pay)
 __global__ __launch_bounds__(256) void sa_full_check_kernel(typename SaOf<V>::ptr sa, uint64_t n, const uint8_t* __restrict__ text,
                                                             const uint64_t* __restrict__ doc_start, uint64_t ndocs, int bits,
                                                             uint64_t mask, bool plain, unsigned long long* __restrict__ out,
@@ -285,10 +377,11 @@ __global__ __launch_bounds__(256) void sa_full_check_kernel(typename SaOf<V>::pt
         a.pos = __shfl_up(b.pos, 1);
         a.ok = __shfl_up(b.ok, 1);
         if (lane == 0 && valid && i > 0) a = sfx_head<V>(sa, i - 1, n, text, doc_start, ndocs, bits, mask);
-        if (!valid || i == 0 || !a.ok || !b.ok) continue;
         const uint64_t len = a.len < b.len ? a.len : b.len;
-        bool bad = false;
-        if (a.w0 != b.w0 || a.w1 != b.w1) {
+        bool bad = false, ask = false, high_first = false;  // ask: a mixed pair whose bucket size decides (judged below, by the workgroup)
+        uint64_t ask_l = 0;
+        if (!valid || i == 0 || !a.ok || !b.ok) {
+        } else if (a.w0 != b.w0 || a.w1 != b.w1) {
             // first differing byte (inside min(len, 16) bytes unless one suffix ends first: its padding is 0 there)
             const uint64_t x = a.w0 != b.w0 ? a.w0 : a.w1, y = a.w0 != b.w0 ? b.w0 : b.w1;
             const uint32_t byte = (uint32_t)__builtin_clzll(x ^ y) >> 3;
@@ -300,10 +393,9 @@ __global__ __launch_bounds__(256) void sa_full_check_kernel(typename SaOf<V>::pt
                 bad = ca > cb && (plain || ((ca ^ cb) & 0x80u) == 0);
                 if (!plain && ((ca ^ cb) & 0x80u)) {
                     nskip += 1;
-                    if (chuck) {
-                        const RefOrderCtx<V> c{sa, n, text, doc_start, bits, mask, ndocs};
-                        bad = (ca >= 0x80u) != ref_bucket_is_node(c, i, text + a.pos, l, chuck);
-                    }
+                    ask = BUCKETS;
+                    high_first = ca >= 0x80u;
+                    ask_l = l;
                 }
             }
         } else if (len <= 16) {  // equal through the end of the shorter one
@@ -319,12 +411,16 @@ __global__ __launch_bounds__(256) void sa_full_check_kernel(typename SaOf<V>::pt
                 bad = pa[l] > pb[l] && (plain || ((pa[l] ^ pb[l]) & 0x80u) == 0);
                 if (!plain && ((pa[l] ^ pb[l]) & 0x80u)) {
                     nskip += 1;
-                    if (chuck) {
-                        const RefOrderCtx<V> c{sa, n, text, doc_start, bits, mask, ndocs};
-                        bad = (pa[l] >= 0x80u) != ref_bucket_is_node(c, i, pa, l, chuck);
-                    }
+                    ask = BUCKETS;
+                    high_first = pa[l] >= 0x80u;
+                    ask_l = l;
                 }
             }
+        }
+        if constexpr (BUCKETS) {  // (the same for every thread: the whole workgroup arrives)
+            const RefOrderCtx<V> c{sa, n, text, doc_start, bits, mask, ndocs};
+            const bool node = block_bucket_is_node(c, ask, i, text + a.pos, ask_l, chuck);
+            if (ask) bad = high_first != node;
         }
         if (bad) nbad += 1;
     }
@@ -340,31 +436,39 @@ __global__ __launch_bounds__(256) void sa_verify_reference_kernel(RefOrderCtx<V>
     unsigned long long bad = 0, mixed = 0, big = 0, tie = 0;
     const uint64_t stride = (uint64_t)gridDim.x * 256;
     if (end > c.n) end = c.n;
-    for (uint64_t i = first + (uint64_t)blockIdx.x * 256 + threadIdx.x; i < end; i += stride) {
-        if (i == 0) continue;
-        const uint8_t *pa, *pb;
-        uint64_t la, lb;
-        c.suffix(i - 1, pa, la);
-        c.suffix(i, pb, lb);
-        const uint64_t lim = la < lb ? la : lb;
+    for (uint64_t base = first + (uint64_t)blockIdx.x * 256; base < end; base += stride) {  // (uniform trip count: block_bucket_is_node)
+        const uint64_t i = base + threadIdx.x;
+        bool ask = false, high_first = false;
+        const uint8_t* pa = c.text;
         uint64_t l = 0;
-        while (l < lim && pa[l] == pb[l]) ++l;
-        if (l == la && l == lb) {  // equal suffixes
-            if (((uint64_t)c.sa[i - 1] & c.mask) >= ((uint64_t)c.sa[i] & c.mask)) tie += 1;
-            continue;
+        if (i < end && i != 0) {
+            const uint8_t* pb;
+            uint64_t la, lb;
+            c.suffix(i - 1, pa, la);
+            c.suffix(i, pb, lb);
+            const uint64_t lim = la < lb ? la : lb;
+            while (l < lim && pa[l] == pb[l]) ++l;
+            if (l == la && l == lb) {  // equal suffixes
+                if (((uint64_t)c.sa[i - 1] & c.mask) >= ((uint64_t)c.sa[i] & c.mask)) tie += 1;
+            } else if (l == la) {       // the shorter one first: right in both orders
+            } else if (l == lb) {
+                bad += 1;
+            } else {
+                const uint8_t x = pa[l], y = pb[l];
+                if ((x >= 0x80) == (y >= 0x80)) {
+                    if (x > y) bad += 1;
+                } else {
+                    mixed += 1;
+                    ask = true;
+                    high_first = x >= 0x80;
+                }
+            }
         }
-        if (l == la) continue;          // the shorter one first: right in both orders
-        if (l == lb) { bad += 1; continue; }
-        const uint8_t x = pa[l], y = pb[l];
-        if ((x >= 0x80) == (y >= 0x80)) {
-            if (x > y) bad += 1;
-            continue;
+        const bool node = block_bucket_is_node(c, ask, i, pa, l, chuck);  // a radix node of the reference: signed child order
+        if (ask) {
+            if (node) big += 1;
+            if (high_first != node) bad += 1;
         }
-        mixed += 1;
-        const bool node = ref_bucket_is_node(c, i, pa, l, chuck);  // a radix node of the reference: signed child order
-        if (node) big += 1;
-        const bool high_first = x >= 0x80;
-        if (high_first != node) bad += 1;
     }
     if (bad) atomicAdd(&out[0], bad);
     if (mixed) atomicAdd(&out[1], mixed);
@@ -426,7 +530,7 @@ void spot_check_suffix_array(Index& ix, uint32_t samples, uint64_t out[2]) {
         sa_dispatch(ix, [&](auto tag) {
             using T = decltype(tag);
             const unsigned g2 = (unsigned)std::min<uint64_t>(ceil_div(ix.size, 256), 1u << 16);
-            hipLaunchKernelGGL((sa_full_check_kernel<T>), dim3(g2), dim3(256), 0, s, ix.sa_view<T>(), ix.size, ix.d_text,
+            hipLaunchKernelGGL((ix.sa_sorted ? sa_full_check_kernel<T, false> : sa_full_check_kernel<T, true>), dim3(g2), dim3(256), 0, s, ix.sa_view<T>(), ix.size, ix.d_text,
                                (const uint64_t*)ix.d_doc_start.as<uint64_t>(), ix.ndocs, (int)ix.bits, ix.mask, ix.sa_sorted,
                                d_out.as<unsigned long long>(), (uint64_t)0, ix.size, (unsigned long long*)nullptr,
                                // (every pair means every pair: the bucket-size-dependent ones of a reference-compat order too)
@@ -473,7 +577,7 @@ bool proof_sweep(Index& ix, uint64_t found[3]) {
         sa_dispatch(ix, [&](auto tag) {
             using T = decltype(tag);
             const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(end - first, 256), 1u << 14);
-            hipLaunchKernelGGL((sa_full_check_kernel<T>), dim3(grid), dim3(256), 0, pf.stream, ix.sa_view<T>(), ix.size, ix.d_text,
+            hipLaunchKernelGGL((ix.sa_sorted ? sa_full_check_kernel<T, false> : sa_full_check_kernel<T, true>), dim3(grid), dim3(256), 0, pf.stream, ix.sa_view<T>(), ix.size, ix.d_text,
                                (const uint64_t*)ix.d_doc_start.as<uint64_t>(), ix.ndocs, (int)ix.bits, ix.mask, ix.sa_sorted,
                                static_cast<unsigned long long*>(pf.d_out), first, end, static_cast<unsigned long long*>(pf.d_out) + 2,
                                ix.sa_sorted ? (uint64_t)0 : std::max<uint64_t>(4096, ix.size / 256) /* index.cpp:218 */);

@@ -799,16 +799,17 @@ def test_full_self_check_finds_what_a_sample_can_miss(G, tmp_path):
     ds = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
     blob = W.random_bytes(int(ds[-1]), 4, 0x61, 0x68)
     lens8 = lens.copy()
-    lens8[77] = 70000                                           # (8-byte entries)
+    lens8[77] = 140000                                          # (15 document bits + 18 offset bits = 33: 8-byte entries)
     ds8 = np.concatenate([[0], np.cumsum(lens8)]).astype(np.uint64)
     blob8 = W.random_bytes(int(ds8[-1]), 5, 0x61, 0x68)
-    for (b_, d_), opts in (((blob, ds), {}), ((blob8, ds8), {}), ((blob8, ds8), {"pack_sa": 0})):
+    for (b_, d_), opts, width, packed in (((blob, ds), {}, 4, 0), ((blob8, ds8), {}, 8, 1), ((blob8, ds8), {"pack_sa": 0}, 8, 0)):
         nd = len(d_) - 1
         g = G()
         for k, v in opts.items():
             g.set_option(k, v)
         g.add_bulk(np.arange(nd, dtype=np.int64), b_, d_)
         g.build()
+        assert g.sa_width == width and g.stat("sa_packed") == packed
         assert g.self_check(full=True) == (0, 0) and g.self_check() == (0, 0)
         path = str(tmp_path / "sc.cdb")
         g.save(path)
@@ -841,6 +842,7 @@ def test_full_self_check_finds_what_a_sample_can_miss(G, tmp_path):
             except RuntimeError:
                 assert name == "no such document"                # (cdb_load refuses entries that name nothing)
                 continue
+            assert h.sa_width == width and h.stat("sa_packed") == packed
             wrong, invalid = h.self_check(full=True)
             assert wrong + invalid >= 1, (name, opts)
 
