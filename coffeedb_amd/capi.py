@@ -34,6 +34,7 @@ EXPORTS = [
     "cdb_render_rows", "cdb_shards_render_rows", "cdb_rendered_free",
     "cdb_remove", "cdb_column_remove",
     "cdb_append", "cdb_debug_verify_keys",
+    "cdb_debug_sort_ws_create", "cdb_debug_sort_ws_destroy", "cdb_debug_radix_sort_ex", "cdb_debug_radix_sort_split",
 ]
 
 
@@ -1075,6 +1076,82 @@ def debug_radix_sort(d_keys_ptr, d_vals_ptr, n, val_bytes, key_bits, variant=0, 
     if rc != 0:
         raise RuntimeError(f"cdb_debug_radix_sort failed ({rc})")
     return ms.value, passes.value
+
+
+SORT_DEVICE_HIST, SORT_SPARE_VALUES, SORT_POISON, SORT_GROUPED, SORT_PROFILE = 1, 2, 4, 8, 16
+
+
+class CdbDebugSortResult(C.Structure):
+    _fields_ = [("passes_run", C.c_int), ("passes_skipped", C.c_int), ("key_result", C.c_int), ("value_result", C.c_int),
+                ("fell_back", C.c_int), ("epoch", C.c_uint32), ("onesweep_ms", C.c_double)]
+
+
+class SortError(RuntimeError):
+    """A sort hook failed; `status` is the CDB_E_* code of the error thrown inside the library."""
+
+    def __init__(self, what, status):
+        super().__init__(f"{what} failed ({status})")
+        self.status = status
+
+
+class DebugSortWorkspace:
+    """A RadixWorkspace and its stream that outlive one sort (cdb_debug_sort_ws_*): pass it as `ws` to the sort hooks."""
+
+    def __init__(self, device=-1):
+        lib = load_library()
+        lib.cdb_debug_sort_ws_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        lib.cdb_debug_sort_ws_destroy.argtypes = [C.c_void_p]
+        lib.cdb_debug_sort_ws_destroy.restype = None
+        self._h = C.c_void_p()
+        rc = lib.cdb_debug_sort_ws_create(device, C.byref(self._h))
+        if rc != 0:
+            raise SortError("cdb_debug_sort_ws_create", rc)
+
+    def close(self):
+        if self._h:
+            load_library().cdb_debug_sort_ws_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _sort_result(r):
+    return {name: getattr(r, name) for name, _ in CdbDebugSortResult._fields_}
+
+
+def debug_radix_sort_ex(d_keys_ptr, d_vals_ptr, n, key_bytes, val_bytes, begin_bit, end_bit, dbits=8, variant=0, flags=0, ws=None,
+                        device=-1):
+    """radix_sort<K, V> as the library calls it, in place on device memory; returns the hook's result record as a dict.
+    Raises SortError with the status of the error thrown."""
+    lib = load_library()
+    lib.cdb_debug_radix_sort_ex.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_uint, C.POINTER(CdbDebugSortResult)]
+    r = CdbDebugSortResult()
+    rc = lib.cdb_debug_radix_sort_ex(device, ws._h if ws is not None else None, C.c_void_p(d_keys_ptr),
+                                     C.c_void_p(d_vals_ptr) if d_vals_ptr else None, n, key_bytes, val_bytes, begin_bit, end_bit,
+                                     dbits, variant, flags, C.byref(r))
+    if rc != 0:
+        raise SortError("cdb_debug_radix_sort_ex", rc)
+    return _sort_result(r)
+
+
+def debug_radix_sort_split(d_keys_ptr, d_vals_ptr, d_aux_ptr, n, val_bytes, aux_bytes, hi_bits, lead_digits, variant=0, flags=0,
+                           ws=None, device=-1):
+    """radix_sort_split over materialised (u32 key, value, auxiliary word) records, in place on device memory."""
+    lib = load_library()
+    lib.cdb_debug_radix_sort_split.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(CdbDebugSortResult)]
+    r = CdbDebugSortResult()
+    rc = lib.cdb_debug_radix_sort_split(device, ws._h if ws is not None else None, C.c_void_p(d_keys_ptr), C.c_void_p(d_vals_ptr),
+                                        C.c_void_p(d_aux_ptr), n, val_bytes, aux_bytes, hi_bits, lead_digits, variant, flags,
+                                        C.byref(r))
+    if rc != 0:
+        raise SortError("cdb_debug_radix_sort_split", rc)
+    return _sort_result(r)
 
 
 def layout_rule(ndocs, longest):

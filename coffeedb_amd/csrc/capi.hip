@@ -1898,56 +1898,6 @@ int cdb_debug_verify_keys(cdb_index* h, uint64_t out[2]) {
     });
 }
 
-int cdb_debug_radix_sort(int device, void* d_keys, void* d_vals, uint64_t n, int val_bytes, int key_bits,
-                         int variant, double* onesweep_ms, int* passes) {
-    if (!d_keys || (val_bytes != 0 && val_bytes != 4 && val_bytes != 8) || key_bits < 1 || key_bits > 64)
-        return CDB_E_INVALID;
-    try {
-        if (device >= 0) CDB_HIP(hipSetDevice(device));
-        hipStream_t s;
-        CDB_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        {
-            StreamScope sscope(s);
-            RadixWorkspace ws;
-            Profiler prof;
-            prof.enabled = true;
-            DevBuf k1, v1;
-            k1.alloc(n * 8);
-            if (val_bytes) v1.alloc(n * val_bytes);
-            SortStats st;
-            int sel = 0;
-            uint64_t* k0 = static_cast<uint64_t*>(d_keys);
-            if (val_bytes == 4)
-                sel = radix_sort<uint64_t, uint32_t>(s, ws, prof, k0, k1.as<uint64_t>(), static_cast<uint32_t*>(d_vals),
-                                                     v1.as<uint32_t>(), n, 0, key_bits, &st, variant);
-            else if (val_bytes == 8)
-                sel = radix_sort<uint64_t, uint64_t>(s, ws, prof, k0, k1.as<uint64_t>(), static_cast<uint64_t*>(d_vals),
-                                                     v1.as<uint64_t>(), n, 0, key_bits, &st, variant);
-            else
-                sel = radix_sort<uint64_t, NoVal>(s, ws, prof, k0, k1.as<uint64_t>(), (NoVal*)nullptr, (NoVal*)nullptr, n,
-                                                  0, key_bits, &st, variant);
-            if (sel == 1) {
-                CDB_HIP(hipMemcpyAsync(d_keys, k1.p, n * 8, hipMemcpyDeviceToDevice, s));
-                if (val_bytes) CDB_HIP(hipMemcpyAsync(d_vals, v1.p, n * val_bytes, hipMemcpyDeviceToDevice, s));
-            }
-            radix_check_error(s, ws);
-            CDB_HIP(hipStreamSynchronize(s));
-            prof.resolve();
-            double ms = 0;
-            for (auto& kv : prof.recs)
-                if (kv.first.rfind("rs_onesweep", 0) == 0) ms += kv.second.ms;  // every tile size
-            if (onesweep_ms) *onesweep_ms = ms;
-            if (passes) *passes = st.passes_run;
-        }
-        DevPool::get().retire_stream(s);
-        (void)hipStreamDestroy(s);
-        return CDB_OK;
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "cdb_debug_radix_sort: %s\n", e.what());
-        return CDB_E_DEVICE;
-    }
-}
-
 int cdb_debug_query_latency(cdb_index* h, const char* blob, const uint64_t* offsets, size_t nkw, int reps, double* us_out) {
     if (!h || !blob || !offsets || !us_out || reps < 1) return CDB_E_INVALID;
     std::vector<double> t((size_t)reps);

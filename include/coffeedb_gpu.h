@@ -621,6 +621,40 @@ int cdb_proof_wait(cdb_index* h, double timeout_ms);
 int cdb_debug_radix_sort(int device, void* d_keys, void* d_vals, uint64_t n, int val_bytes, int key_bits,
                          int variant, double* onesweep_ms, int* passes);
 
+/* Test hooks that call the radix-sort primitive the way the library itself does (tests/test_gpu_sort_edges.py; debug_sort.hip).
+ * Not part of the stable ABI.  flags: */
+#define CDB_DEBUG_SORT_DEVICE_HIST 1u  /* digit histograms counted on the device and handed over there: no pass is skipped */
+#define CDB_DEBUG_SORT_SPARE_VALUES 2u /* a third value buffer (RadixWorkspace::value_spare) */
+#define CDB_DEBUG_SORT_POISON 4u       /* the sort finds the look-back error flag already up (RadixWorkspace::debug_poison) */
+#define CDB_DEBUG_SORT_GROUPED 8u      /* XCD-aware tile order allowed (allow_group); after a look-back timeout the hook restores
+                                        * the input, sorts once more in plain ticket order and reports fell_back = 1 */
+#define CDB_DEBUG_SORT_PROFILE 16u     /* time the onesweep launches with HIP events (onesweep_ms) */
+typedef struct cdb_debug_sort_result {
+    int passes_run, passes_skipped;
+    int key_result;     /* the sort's return value: the buffer (0 / 1) the keys (and auxiliary words) ended in */
+    int value_result;   /* RadixWorkspace::value_result: the buffer the values ended in */
+    int fell_back;
+    uint32_t epoch;     /* the workspace's epoch after the sort */
+    double onesweep_ms;
+} cdb_debug_sort_result;
+/* A workspace that outlives one sort, with the stream it sorts on: a sequence of hook calls on one handle sees what a library
+ * handle's workspace sees (epoch wrap, status array growth, stale status words of other tile sizes and key types). */
+typedef struct cdb_debug_sort_ws cdb_debug_sort_ws;
+int cdb_debug_sort_ws_create(int device, cdb_debug_sort_ws** out);
+void cdb_debug_sort_ws_destroy(cdb_debug_sort_ws* ws);
+/* radix_sort<K, V>: stable sort of n keys of key_bytes (4 / 8) with values of val_bytes (0 / 4 / 8) in DEVICE memory by key bits
+ * [begin_bit, end_bit) in digits of dbits (1..8) bits; the other key bits travel along.  variant: 0, 1, 21, 26, 31, 33, 36, 32, and for
+ * 8-byte keys 4 and 41.  ws = NULL: a fresh workspace for this call.  The result is always left in d_keys / d_vals, whatever buffer
+ * the sort ended in; after an error they hold what buffers 0 held when the sort gave up.  Returns the status of the error thrown. */
+int cdb_debug_radix_sort_ex(int device, cdb_debug_sort_ws* ws, void* d_keys, void* d_vals, uint64_t n, int key_bytes, int val_bytes,
+                            int begin_bit, int end_bit, int dbits, int variant, unsigned flags, cdb_debug_sort_result* out);
+/* radix_sort_split over materialised records (no generated pass): 4-byte keys sorted by their low hi_bits bits below which the
+ * lead_digits lowest bytes of the auxiliary word (aux_bytes 1 / 2 / 4) sort first; values of 4 bytes (any aux_bytes) or 8 bytes
+ * (aux_bytes 1 / 2).  The histograms the sort requires are counted by the hook: on the host from a copy, or with
+ * CDB_DEBUG_SORT_DEVICE_HIST by a kernel. */
+int cdb_debug_radix_sort_split(int device, cdb_debug_sort_ws* ws, void* d_keys, void* d_vals, void* d_aux, uint64_t n, int val_bytes,
+                               int aux_bytes, int hi_bits, int lead_digits, int variant, unsigned flags, cdb_debug_sort_result* out);
+
 /* Measurement hook: wall time of `reps` back-to-back cdb_query calls for each of `nkw` keywords (blob + offsets like
  * cdb_query_batch), taken inside the library with a steady clock — what a C++ caller such as database.cpp:392 sees,
  * without a language binding in between.  us_out[nkw] receives the MEDIAN microseconds per call of every keyword;
