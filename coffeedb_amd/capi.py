@@ -35,6 +35,9 @@ EXPORTS = [
     "cdb_remove", "cdb_column_remove",
     "cdb_append", "cdb_debug_verify_keys",
     "cdb_debug_sort_ws_create", "cdb_debug_sort_ws_destroy", "cdb_debug_radix_sort_ex", "cdb_debug_radix_sort_split",
+    "cdb_filter", "cdb_rowset_free", "cdb_rowset_last_error", "cdb_rowset_size", "cdb_rowset_rows", "cdb_rowset_page", "cdb_rowset_cluster",
+    "cdb_rowset_cluster_column", "cdb_rowset_get_stat", "cdb_debug_rowset_from_rows", "cdb_debug_rowset_set_option",
+    "cdb_debug_rowset_profile_dump",
 ]
 
 
@@ -249,6 +252,22 @@ def load_library():
     lib.cdb_column_remove.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     lib.cdb_append.argtypes = [vp, vp, vp, vp, u64, C.POINTER(u64)]
     lib.cdb_debug_verify_keys.argtypes = [vp, C.POINTER(u64)]
+    rows_out = [C.POINTER(C.POINTER(i64)), C.POINTER(C.POINTER(i64)), C.POINTER(C.c_size_t)]
+    lib.cdb_filter.argtypes = [C.POINTER(CdbKeyQuery), C.c_int, C.POINTER(CdbColumnKey), C.c_int, C.c_int, i64, i64, C.POINTER(vp)]
+    lib.cdb_rowset_free.argtypes = [vp]
+    lib.cdb_rowset_free.restype = None
+    lib.cdb_rowset_last_error.argtypes = [vp]
+    lib.cdb_rowset_last_error.restype = cp
+    lib.cdb_rowset_size.argtypes = [vp]
+    lib.cdb_rowset_size.restype = u64
+    lib.cdb_rowset_rows.argtypes = [vp] + rows_out
+    lib.cdb_rowset_page.argtypes = [vp, u64, u64] + rows_out
+    lib.cdb_rowset_cluster.argtypes = [vp, vp, C.c_int, C.POINTER(CdbClusters)]
+    lib.cdb_rowset_cluster_column.argtypes = [vp, vp, C.POINTER(CdbClusters)]
+    lib.cdb_rowset_get_stat.argtypes = [vp, cp, C.POINTER(C.c_double)]
+    lib.cdb_debug_rowset_from_rows.argtypes = [C.c_int, vp, vp, u64, C.POINTER(vp)]
+    lib.cdb_debug_rowset_set_option.argtypes = [vp, cp, i64]
+    lib.cdb_debug_rowset_profile_dump.argtypes = [vp, C.c_char_p, C.c_size_t]
     _LIB = lib
     return lib
 
@@ -967,9 +986,9 @@ def memory_reset_peak():
     load_library().cdb_memory_reset_peak()
 
 
-def _query_and_columns(keys, ranked, lo, hi, limit):
-    """cdb_query_and_columns: the keys of query_and() with (GpuColumn, [ranges]) among them."""
-    lib = load_library()
+def _pack_column_keys(keys):
+    """The keys of query_and() as the arrays cdb_query_and_columns / cdb_filter take: (cdb_key_query array or None, its length,
+    cdb_column_key array, its length, the handle that carries an error, the buffers to keep alive during the call)."""
     plain = [(ix, data) for ix, data in keys if not isinstance(ix, GpuColumn)]
     colk = [(ix, data) for ix, data in keys if isinstance(ix, GpuColumn)]
     arr = (CdbKeyQuery * max(len(plain), 1))()
@@ -1004,13 +1023,28 @@ def _query_and_columns(keys, ranked, lo, hi, limit):
         carr[j].blob = blob.ctypes.data if len(blob) else None
         carr[j].offsets = offs.ctypes.data
         carr[j].nranges = len(ranges)
+    if lead is None and colk:
+        lead = colk[0][0]
+    return (arr if plain else None), len(plain), carr, len(colk), lead, keep
+
+
+def _raise_lead_error(lib, lead, what):
+    if isinstance(lead, GpuColumn):
+        raise RuntimeError(lib.cdb_column_last_error(lead._h).decode(errors="replace"))
+    if lead is not None:
+        raise RuntimeError(lib.cdb_last_error(lead._h).decode(errors="replace"))
+    raise RuntimeError(f"{what}: no string key and no column")
+
+
+def _query_and_columns(keys, ranked, lo, hi, limit):
+    """cdb_query_and_columns: the keys of query_and() with (GpuColumn, [ranges]) among them."""
+    lib = load_library()
+    arr, nk, carr, nc, lead, keep = _pack_column_keys(keys)
     ids, cnt, n = C.POINTER(C.c_int64)(), C.POINTER(C.c_int64)(), C.c_size_t(0)
-    rc_ = lib.cdb_query_and_columns(arr if plain else None, len(plain), carr, len(colk), 1 if ranked else 0, int(lo), int(hi), int(limit),
+    rc_ = lib.cdb_query_and_columns(arr, nk, carr, nc, 1 if ranked else 0, int(lo), int(hi), int(limit),
                                     C.byref(ids), C.byref(cnt), C.byref(n))
     if rc_ != 0:
-        if lead is not None:
-            raise RuntimeError(lib.cdb_last_error(lead._h).decode(errors="replace"))
-        raise RuntimeError(lib.cdb_column_last_error(colk[0][0]._h).decode(errors="replace"))
+        _raise_lead_error(lib, lead, "cdb_query_and_columns")
     out = [(ids[i], cnt[i]) for i in range(n.value)]
     lib.cdb_free(ids)
     lib.cdb_free(cnt)
@@ -1065,6 +1099,129 @@ def query_and(keys, ranked=False, lo=1, hi=(1 << 62), limit=0):
     lib.cdb_free(ids)
     lib.cdb_free(cnt)
     return out
+
+
+class GpuRowSet:
+    """A filtered row set that stays on the device (cdb_rowset_*): made by filter_rows() or debug_rowset_from_rows().  `size` is the
+    `count` operation; rows() all rows ascending by id; page(first, last) rows [first, last) of the ranking (descending count as
+    signed int64, ties ascending id); cluster(field) groups the rows by a GpuStringIndex or GpuColumn without uploading them.
+    rows() and page() return (ids, counts) as numpy int64 arrays."""
+
+    def __init__(self, handle):
+        self._lib = load_library()
+        self._h = handle
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.cdb_rowset_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(self._lib.cdb_rowset_last_error(self._h).decode(errors="replace"))
+
+    @property
+    def size(self):
+        return int(self._lib.cdb_rowset_size(self._h))
+
+    def __len__(self):
+        return self.size
+
+    def _rows(self, fn, *args):
+        ids, cnt, n = C.POINTER(C.c_int64)(), C.POINTER(C.c_int64)(), C.c_size_t(0)
+        self._check(fn(self._h, *args, C.byref(ids), C.byref(cnt), C.byref(n)))
+        try:
+            return _array(ids, n.value, np.int64), _array(cnt, n.value, np.int64)
+        finally:
+            self._lib.cdb_free(ids)
+            self._lib.cdb_free(cnt)
+
+    def rows(self):
+        return self._rows(self._lib.cdb_rowset_rows)
+
+    def page(self, first, last):
+        return self._rows(self._lib.cdb_rowset_page, int(first), int(last))
+
+    def cluster(self, field, with_values=True):
+        """GpuStringIndex.cluster / GpuColumn.cluster of this set's ids, with their return values."""
+        r = CdbClusters()
+        if isinstance(field, GpuColumn):
+            self._check(self._lib.cdb_rowset_cluster_column(self._h, field._h, C.byref(r)))
+        elif isinstance(field, GpuStringIndex):
+            self._check(self._lib.cdb_rowset_cluster(self._h, field._h, 1 if with_values else 0, C.byref(r)))
+        else:
+            raise TypeError(f"GpuRowSet.cluster: {type(field).__name__} is neither a GpuStringIndex nor a GpuColumn")
+        try:
+            ng = int(r.ngroups)
+            counts, reps = _array(r.counts, ng, np.int64), _array(r.rep_ids, ng, np.int64)
+            if isinstance(field, GpuColumn):
+                raw = _array(r.values, ng, np.uint64)
+                values = raw.astype(np.bool_) if field.kind == 0 else raw.view(np.int64 if field.kind == 1 else np.float64)
+                return values, counts, reps, int(r.missing)
+            values = None
+            if with_values:
+                ptr = _array(r.value_ptr, ng + 1, np.uint64)
+                blob = C.string_at(r.value_blob, int(ptr[ng])) if ng else b""
+                values = [blob[int(ptr[g]):int(ptr[g + 1])] for g in range(ng)]
+            return values, counts, reps, int(r.missing)
+        finally:
+            self._lib.cdb_clusters_free(C.byref(r))
+
+    def stat(self, name):
+        v = C.c_double(0)
+        if self._lib.cdb_rowset_get_stat(self._h, name.encode(), C.byref(v)) != 0:
+            raise KeyError(name)
+        return v.value
+
+    def set_option(self, name, value):
+        """Test / measurement hook (cdb_debug_rowset_set_option): "debug_page_path" (0 automatic, 1 select, 2 sort), "profile"."""
+        if self._lib.cdb_debug_rowset_set_option(self._h, name.encode(), int(value)) != 0:
+            raise ValueError(f"GpuRowSet.set_option: {name} = {value}")
+
+    def profile(self):
+        buf = C.create_string_buffer(1 << 16)
+        self._lib.cdb_debug_rowset_profile_dump(self._h, buf, len(buf))
+        out = {}
+        for line in buf.value.decode().splitlines():
+            name, ms, launches, nbytes = line.split()
+            out[name] = {"ms": float(ms), "launches": int(launches), "bytes": int(nbytes)}
+        return out
+
+
+def filter_rows(keys, corr=None):
+    """cdb_filter: the keys of query_and() (GpuStringIndex, GpuColumn and host-row keys; resolve a GpuShards key with its query_or
+    first) merged on the device into a GpuRowSet.  corr = (lo, hi) keeps rows with lo <= count < hi."""
+    lib = load_library()
+    arr, nk, carr, nc, lead, keep = _pack_column_keys(keys)
+    lo, hi = (0, 0) if corr is None else corr
+    h = C.c_void_p()
+    rc_ = lib.cdb_filter(arr, nk, carr if nc else None, nc, 0 if corr is None else 1, int(lo), int(hi), C.byref(h))
+    if rc_ != 0:
+        _raise_lead_error(lib, lead, "cdb_filter")
+    return GpuRowSet(h)
+
+
+def debug_rowset_from_rows(ids, counts, device=-1):
+    """Test hook (cdb_debug_rowset_from_rows): a GpuRowSet over the given rows, ids ascending."""
+    lib = load_library()
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    if len(ids) != len(counts):
+        raise ValueError("debug_rowset_from_rows: ids and counts differ in length")
+    h = C.c_void_p()
+    rc_ = lib.cdb_debug_rowset_from_rows(device, _ptr(ids) if len(ids) else None, _ptr(counts) if len(counts) else None, len(ids), C.byref(h))
+    if rc_ != 0:
+        raise RuntimeError(f"cdb_debug_rowset_from_rows failed (code {rc_})" + (": no usable gfx950 device" if rc_ == 2 else ""))
+    return GpuRowSet(h)
 
 
 def debug_radix_sort(d_keys_ptr, d_vals_ptr, n, val_bytes, key_bits, variant=0, device=-1):

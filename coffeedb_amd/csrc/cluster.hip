@@ -379,9 +379,17 @@ struct Result {
     }
 };
 
-void upload_ids(hipStream_t s, DevBuf& d, const int64_t* ids, uint64_t nrows) {
+// the rows' ids: a host array, or an array that already lies on the field's GPU (a row set's: rowset.hip)
+struct RowIds {
+    const int64_t* host = nullptr;
+    const int64_t* device = nullptr;
+};
+// ... where the kernels read them: uploaded into d, or the caller's device array as it is
+const int64_t* resident_ids(hipStream_t s, DevBuf& d, RowIds ids, uint64_t nrows) {
+    if (ids.device) return ids.device;
     d.alloc(nrows * 8);
-    CDB_HIP(hipMemcpyAsync(d.p, ids, nrows * 8, hipMemcpyHostToDevice, s));
+    CDB_HIP(hipMemcpyAsync(d.p, ids.host, nrows * 8, hipMemcpyHostToDevice, s));
+    return d.as<int64_t>();
 }
 
 // ---- columns: host side ------------------------------------------------------------------------------------------------------------
@@ -404,7 +412,7 @@ void column_run_starts(cdb_column* c) {
     c->clu_generation = c->generation;
 }
 
-void column_cluster(cdb_column* c, const int64_t* ids, uint64_t nrows, Result& res) {
+void column_cluster(cdb_column* c, RowIds ids, uint64_t nrows, Result& res) {
     Index& ws = c->ws;
     hipStream_t s = ws.stream;
     const double t0 = wall_ms();
@@ -418,11 +426,10 @@ void column_cluster(cdb_column* c, const int64_t* ids, uint64_t nrows, Result& r
         return;
     }
     DevBuf d_ids, d_out;
-    upload_ids(s, d_ids, ids, nrows);
+    const int64_t* idp = resident_ids(s, d_ids, ids, nrows);
     d_out.alloc(64);
     const uint64_t init[5] = {0, 0, 0, ~0ull, ~0ull};
     CDB_HIP(hipMemcpyAsync(d_out.p, init, sizeof(init), hipMemcpyHostToDevice, s));
-    const int64_t* idp = d_ids.as<int64_t>();
     const int64_t* id_sorted = c->id_sorted.as<int64_t>();
     const uint32_t* vpos = c->vpos.as<uint32_t>();
     const uint64_t* keys_v = c->keys_v.as<uint64_t>();
@@ -677,7 +684,7 @@ void cluster_prepare(Index& ix) {
     ct.valid = true;
 }
 
-void index_cluster(Index& ix, const int64_t* ids, uint64_t nrows, bool with_values, Result& res) {
+void index_cluster(Index& ix, RowIds ids, uint64_t nrows, bool with_values, Result& res) {
     hipStream_t s = ix.stream;
     auto empty = [&] {
         res.r.missing = nrows;
@@ -706,13 +713,13 @@ void index_cluster(Index& ix, const int64_t* ids, uint64_t nrows, bool with_valu
     const int64_t* id_tab = ix.idt.ids_ascend ? ix.d_ids.as<int64_t>() : ix.idt.id_sorted.as<int64_t>();
     const uint32_t* id_doc = ix.idt.ids_ascend ? nullptr : ix.idt.id_doc.as<uint32_t>();
     DevBuf d_ids, d_out, k0, k1, start, d_counts, d_rep, d_repdoc;
-    upload_ids(s, d_ids, ids, nrows);
+    const int64_t* idp = resident_ids(s, d_ids, ids, nrows);
     d_out.alloc(16);
     CDB_HIP(hipMemsetAsync(d_out.p, 0, 16, s));
     k0.alloc(nrows * 8);
     k1.alloc(nrows * 8);
     int t = ix.prof.begin(s);
-    hipLaunchKernelGGL(clu_str_lookup_kernel, dim3(grid_for(nrows)), dim3(256), 0, s, (const int64_t*)d_ids.as<int64_t>(), nrows, id_tab, id_doc, ndocs,
+    hipLaunchKernelGGL(clu_str_lookup_kernel, dim3(grid_for(nrows)), dim3(256), 0, s, idp, nrows, id_tab, id_doc, ndocs,
                        (const uint32_t*)ct.class_of_doc.as<uint32_t>(), nclasses, rbits, k0.as<uint64_t>(), d_out.as<unsigned long long>());
     ix.prof.end(t, "clu_str_lookup", nrows * (8 + 8 * (uint64_t)bit_width64(ndocs) + 12), s);
     CDB_HIP(hipGetLastError());
@@ -766,32 +773,42 @@ void index_cluster(Index& ix, const int64_t* ids, uint64_t nrows, bool with_valu
     ix.clu.last_ms = wall_ms() - t0;
 }
 
+void run_column_cluster(cdb_column* c, RowIds ids, uint64_t nrows, cdb_clusters* out) {
+    std::lock_guard<std::mutex> g(c->ws.mu);
+    IndexScope scope(c->ws);
+    Result res(c->ws.stream);
+    column_cluster(c, ids, nrows, res);
+    res.hand_over(out);
+}
+void run_index_cluster(Index& ix, RowIds ids, uint64_t nrows, bool with_values, cdb_clusters* out) {
+    std::lock_guard<std::mutex> g(ix.mu);
+    IndexScope scope(ix);
+    Result res(ix.stream);
+    index_cluster(ix, ids, nrows, with_values, res);
+    res.hand_over(out);
+}
+
 }  // namespace
+
+void cdb::cluster_index_device_rows(cdb_index* h, const int64_t* d_ids, uint64_t nrows, bool with_values, cdb_clusters* out) {
+    run_index_cluster(h->ix, RowIds{nullptr, d_ids}, nrows, with_values, out);
+}
+void cdb::cluster_column_device_rows(cdb_column* c, const int64_t* d_ids, uint64_t nrows, cdb_clusters* out) {
+    run_column_cluster(c, RowIds{nullptr, d_ids}, nrows, out);
+}
 
 extern "C" {
 
 int cdb_column_cluster(cdb_column* c, const int64_t* ids, uint64_t nrows, cdb_clusters* out) {
     if (!c || !out || (nrows && !ids)) return CDB_E_INVALID;
     *out = cdb_clusters{};
-    return guarded_ix(c->ws, [&] {
-        std::lock_guard<std::mutex> g(c->ws.mu);
-        IndexScope scope(c->ws);
-        Result res(c->ws.stream);
-        column_cluster(c, ids, nrows, res);
-        res.hand_over(out);
-    });
+    return guarded_ix(c->ws, [&] { run_column_cluster(c, RowIds{ids, nullptr}, nrows, out); });
 }
 
 int cdb_cluster(cdb_index* h, const int64_t* ids, uint64_t nrows, int with_values, cdb_clusters* out) {
     if (!h || !out || (nrows && !ids)) return CDB_E_INVALID;
     *out = cdb_clusters{};
-    return guarded_ix(h->ix, [&] {
-        std::lock_guard<std::mutex> g(h->ix.mu);
-        IndexScope scope(h->ix);
-        Result res(h->ix.stream);
-        index_cluster(h->ix, ids, nrows, with_values != 0, res);
-        res.hand_over(out);
-    });
+    return guarded_ix(h->ix, [&] { run_index_cluster(h->ix, RowIds{ids, nullptr}, nrows, with_values != 0, out); });
 }
 
 void cdb_clusters_free(cdb_clusters* r) {

@@ -716,172 +716,194 @@ int cdb_column_query_any(cdb_column* c, const char* blob, const uint64_t* offset
     });
 }
 
-int cdb_query_and_columns(const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols, int ranked, int64_t corr_lo,
-                          int64_t corr_hi, uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows) {
-    if (nkeys < 0 || ncols < 0 || nkeys + ncols < 1 || (nkeys && !keys) || (ncols && !cols) || !ids || !counts || !nrows) return CDB_E_INVALID;
-    *ids = nullptr;
-    *counts = nullptr;
-    *nrows = 0;
+}  // extern "C"
+
+// ---- the AND of cdb_query_and_columns and cdb_filter (rowset.hip), up to "rows in ix.q_ids / q_counts" ---------------------------
+// The handle that runs the merge and carries the error: the first string key (as in cdb_query_and); without one, the first
+// column.  nullptr: the keys are not a valid query (CDB_E_INVALID).
+Index* cdb::filter_lead(const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols) {
+    if (nkeys < 0 || ncols < 0 || nkeys + ncols < 1 || (nkeys && !keys) || (ncols && !cols)) return nullptr;
     for (int j = 0; j < ncols; ++j)
-        if (!cols[j].column) return CDB_E_INVALID;
-    // the first string key runs the merge and carries the error (as in cdb_query_and); without one, the first column
+        if (!cols[j].column) return nullptr;
     Index* lead = nullptr;
     for (int k = 0; k < nkeys && !lead; ++k)
         if (keys[k].index) lead = &keys[k].index->ix;
     if (!lead) {
-        if (ncols == 0) return CDB_E_INVALID;  // host rows only: that is cdb_query_and's domain (it needs a string key too)
+        if (ncols == 0) return nullptr;  // host rows only: that is cdb_query_and's domain (it needs a string key too)
         lead = &cols[0].column->ws;
     }
-    Index& ix = *lead;
-    return guarded_ix(ix, [&] {
-        for (int k = 0; k < nkeys; ++k) {
-            const cdb_key_query& q = keys[k];
-            if (q.index) {
-                if (q.index->ix.device != ix.device) throw Error("cdb_query_and_columns: all keys must live on one GPU");
-                if (q.nkw == 0) throw Error("The constraint list cannot be empty");  // interface.cpp:75-77
-                if (!q.offsets) throw Error("cdb_query_and_columns: keyword offsets missing");
-                for (uint64_t j = 0; j < q.nkw; ++j)
-                    if (q.offsets[j + 1] <= q.offsets[j]) throw Error("Empty keywords are not allowed");
-            } else if (q.nrows && (!q.ids || !q.counts)) {
-                throw Error("cdb_query_and_columns: row list missing");
+    return lead;
+}
+
+// Validates the keys, locks every handle and column involved, resolves the keys and merges them on the lead's stream; `consume`
+// runs while the locks are held, with the rows in ix.q_ids / q_counts (ascending id, or filtered and ranked when `ranked`).
+void cdb::filter_rows_on_lead(Index& ix, const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols, bool ranked,
+                              int64_t corr_lo, int64_t corr_hi, uint64_t limit, const std::function<void(hipStream_t, DeviceCsr)>& consume) {
+    for (int k = 0; k < nkeys; ++k) {
+        const cdb_key_query& q = keys[k];
+        if (q.index) {
+            if (q.index->ix.device != ix.device) throw Error("cdb_query_and_columns: all keys must live on one GPU");
+            if (q.nkw == 0) throw Error("The constraint list cannot be empty");  // interface.cpp:75-77
+            if (!q.offsets) throw Error("cdb_query_and_columns: keyword offsets missing");
+            for (uint64_t j = 0; j < q.nkw; ++j)
+                if (q.offsets[j + 1] <= q.offsets[j]) throw Error("Empty keywords are not allowed");
+        } else if (q.nrows && (!q.ids || !q.counts)) {
+            throw Error("cdb_query_and_columns: row list missing");
+        }
+    }
+    for (int j = 0; j < ncols; ++j) {
+        if (cols[j].column->ws.device != ix.device) throw Error("cdb_query_and_columns: all keys must live on one GPU");
+        if (cols[j].nranges == 0) throw Error("The constraint list cannot be empty");
+        if (!cols[j].offsets) throw Error("cdb_query_and_columns: range offsets missing");
+    }
+    // every handle and column involved stays locked until the merge has read its rows (address order: no lock inversion)
+    std::vector<std::mutex*> mus;
+    for (int k = 0; k < nkeys; ++k)
+        if (keys[k].index) mus.push_back(&keys[k].index->ix.mu);
+    for (int j = 0; j < ncols; ++j) mus.push_back(&cols[j].column->ws.mu);
+    std::sort(mus.begin(), mus.end());
+    mus.erase(std::unique(mus.begin(), mus.end()), mus.end());
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (std::mutex* m : mus) locks.emplace_back(*m);
+
+    // windows of every column key (the reference's range errors surface here)
+    std::vector<Windows> wins(ncols);
+    for (int j = 0; j < ncols; ++j) {
+        cdb_column* c = cols[j].column;
+        ColumnScope cs(c);
+        wins[j] = column_windows(c, ranges_of(cols[j].blob, cols[j].offsets, cols[j].nranges));
+        c->last_k = wins[j].k;
+    }
+    CDB_HIP(hipSetDevice(ix.device));
+    StreamScope lead_scope(ix.stream);
+    hipStream_t s = ix.stream;
+    std::vector<DeviceRows> lists;
+    std::vector<DevBuf> held;
+    uint64_t m_other = UINT64_MAX;
+    for (int k = 0; k < nkeys; ++k) {  // string keys and host rows exactly as cdb_query_and resolves them
+        const cdb_key_query& q = keys[k];
+        DevBuf di, dc;
+        uint64_t n = 0;
+        if (q.index) {
+            Index& kx = q.index->ix;
+            StreamScope kss(kx.stream);
+            const uint64_t base = q.offsets[0], nbytes = q.offsets[q.nkw] - base;
+            kx.q_pat.ensure(nbytes + 16);
+            kx.q_offs.ensure((q.nkw + 1) * 8);
+            std::vector<uint64_t> rel(q.nkw + 1);
+            for (uint64_t j = 0; j <= q.nkw; ++j) rel[j] = q.offsets[j] - base;
+            CDB_HIP(hipMemcpyAsync(kx.q_pat.p, q.blob + base, nbytes, hipMemcpyHostToDevice, kx.stream));
+            CDB_HIP(hipMemcpyAsync(kx.q_offs.p, rel.data(), (q.nkw + 1) * 8, hipMemcpyHostToDevice, kx.stream));
+            const DeviceCsr r = query_or_on_device(kx, kx.q_pat.as<uint8_t>(), kx.q_offs.as<uint64_t>(), q.nkw);  // (synchronises)
+            n = r.nrows;
+            di.alloc(std::max<uint64_t>(n, 1) * 8);
+            dc.alloc(std::max<uint64_t>(n, 1) * 8);
+            if (n) {
+                CDB_HIP(hipMemcpyAsync(di.p, kx.q_ids.p, n * 8, hipMemcpyDeviceToDevice, s));
+                CDB_HIP(hipMemcpyAsync(dc.p, kx.q_counts.p, n * 8, hipMemcpyDeviceToDevice, s));
+            }
+        } else {
+            n = q.nrows;
+            di.alloc(std::max<uint64_t>(n, 1) * 8);
+            dc.alloc(std::max<uint64_t>(n, 1) * 8);
+            if (n) {
+                CDB_HIP(hipMemcpyAsync(di.p, q.ids, n * 8, hipMemcpyHostToDevice, s));
+                CDB_HIP(hipMemcpyAsync(dc.p, q.counts, n * 8, hipMemcpyHostToDevice, s));
             }
         }
-        for (int j = 0; j < ncols; ++j) {
-            if (cols[j].column->ws.device != ix.device) throw Error("cdb_query_and_columns: all keys must live on one GPU");
-            if (cols[j].nranges == 0) throw Error("The constraint list cannot be empty");
-            if (!cols[j].offsets) throw Error("cdb_query_and_columns: range offsets missing");
-        }
-        // every handle and column involved stays locked until the merge has read its rows (address order: no lock inversion)
-        std::vector<std::mutex*> mus;
-        for (int k = 0; k < nkeys; ++k)
-            if (keys[k].index) mus.push_back(&keys[k].index->ix.mu);
-        for (int j = 0; j < ncols; ++j) mus.push_back(&cols[j].column->ws.mu);
-        std::sort(mus.begin(), mus.end());
-        mus.erase(std::unique(mus.begin(), mus.end()), mus.end());
-        std::vector<std::unique_lock<std::mutex>> locks;
-        for (std::mutex* m : mus) locks.emplace_back(*m);
-
-        // windows of every column key (the reference's range errors surface here)
-        std::vector<Windows> wins(ncols);
-        for (int j = 0; j < ncols; ++j) {
-            cdb_column* c = cols[j].column;
-            ColumnScope cs(c);
-            wins[j] = column_windows(c, ranges_of(cols[j].blob, cols[j].offsets, cols[j].nranges));
-            c->last_k = wins[j].k;
-        }
-        CDB_HIP(hipSetDevice(ix.device));
-        StreamScope lead_scope(ix.stream);
-        hipStream_t s = ix.stream;
-        std::vector<DeviceRows> lists;
-        std::vector<DevBuf> held;
-        uint64_t m_other = UINT64_MAX;
-        for (int k = 0; k < nkeys; ++k) {  // string keys and host rows exactly as cdb_query_and resolves them
-            const cdb_key_query& q = keys[k];
+        m_other = std::min(m_other, n);
+        lists.push_back(DeviceRows{di.as<int64_t>(), dc.as<int64_t>(), n});
+        held.push_back(std::move(di));
+        held.push_back(std::move(dc));
+    }
+    CDB_HIP(hipStreamSynchronize(s));  // (host rows are pageable)
+    // a column key no broader than the smallest other list is materialised and merged; a broader one filters the merge.  Among
+    // the column keys only the narrowest can be the smallest list: it is materialised when no other key is smaller, the rest probe
+    uint64_t k_min = UINT64_MAX;
+    for (int j = 0; j < ncols; ++j) k_min = std::min(k_min, wins[j].k);
+    std::vector<int> probes;
+    for (int j = 0; j < ncols; ++j) {
+        cdb_column* c = cols[j].column;
+        if (wins[j].k == k_min && wins[j].k <= m_other) {
             DevBuf di, dc;
             uint64_t n = 0;
-            if (q.index) {
-                Index& kx = q.index->ix;
-                StreamScope kss(kx.stream);
-                const uint64_t base = q.offsets[0], nbytes = q.offsets[q.nkw] - base;
-                kx.q_pat.ensure(nbytes + 16);
-                kx.q_offs.ensure((q.nkw + 1) * 8);
-                std::vector<uint64_t> rel(q.nkw + 1);
-                for (uint64_t j = 0; j <= q.nkw; ++j) rel[j] = q.offsets[j] - base;
-                CDB_HIP(hipMemcpyAsync(kx.q_pat.p, q.blob + base, nbytes, hipMemcpyHostToDevice, kx.stream));
-                CDB_HIP(hipMemcpyAsync(kx.q_offs.p, rel.data(), (q.nkw + 1) * 8, hipMemcpyHostToDevice, kx.stream));
-                const DeviceCsr r = query_or_on_device(kx, kx.q_pat.as<uint8_t>(), kx.q_offs.as<uint64_t>(), q.nkw);  // (synchronises)
-                n = r.nrows;
-                di.alloc(std::max<uint64_t>(n, 1) * 8);
-                dc.alloc(std::max<uint64_t>(n, 1) * 8);
-                if (n) {
-                    CDB_HIP(hipMemcpyAsync(di.p, kx.q_ids.p, n * 8, hipMemcpyDeviceToDevice, s));
-                    CDB_HIP(hipMemcpyAsync(dc.p, kx.q_counts.p, n * 8, hipMemcpyDeviceToDevice, s));
-                }
-            } else {
-                n = q.nrows;
-                di.alloc(std::max<uint64_t>(n, 1) * 8);
-                dc.alloc(std::max<uint64_t>(n, 1) * 8);
-                if (n) {
-                    CDB_HIP(hipMemcpyAsync(di.p, q.ids, n * 8, hipMemcpyHostToDevice, s));
-                    CDB_HIP(hipMemcpyAsync(dc.p, q.counts, n * 8, hipMemcpyHostToDevice, s));
-                }
+            {
+                ColumnScope cs(c);
+                n = column_union(c, wins[j], di);
+                ++c->materialised_keys;
             }
-            m_other = std::min(m_other, n);
+            dc.alloc(std::max<uint64_t>(n, 1) * 8);
+            CDB_HIP(hipMemsetAsync(dc.p, 0, std::max<uint64_t>(n, 1) * 8, s));
             lists.push_back(DeviceRows{di.as<int64_t>(), dc.as<int64_t>(), n});
             held.push_back(std::move(di));
             held.push_back(std::move(dc));
+        } else {
+            probes.push_back(j);
         }
-        CDB_HIP(hipStreamSynchronize(s));  // (host rows are pageable)
-        // a column key no broader than the smallest other list is materialised and merged; a broader one filters the merge.  Among
-        // the column keys only the narrowest can be the smallest list: it is materialised when no other key is smaller, the rest probe
-        uint64_t k_min = UINT64_MAX;
-        for (int j = 0; j < ncols; ++j) k_min = std::min(k_min, wins[j].k);
-        std::vector<int> probes;
-        for (int j = 0; j < ncols; ++j) {
+    }
+    DeviceCsr r = and_merge_on_device(ix, lists, ranked && probes.empty(), corr_lo, corr_hi, limit);
+    if (!probes.empty()) {
+        for (int j : probes) {
             cdb_column* c = cols[j].column;
-            if (wins[j].k == k_min && wins[j].k <= m_other) {
-                DevBuf di, dc;
-                uint64_t n = 0;
-                {
-                    ColumnScope cs(c);
-                    n = column_union(c, wins[j], di);
-                    ++c->materialised_keys;
+            ++c->probe_filters;
+            if (r.nrows == 0) continue;
+            DevBuf dw, oi, oc;
+            upload_windows(s, wins[j], dw);
+            const uint32_t nw = (uint32_t)wins[j].lo.size();
+            ProbeIn in{ix.q_ids.as<int64_t>(), c->id_sorted.as<int64_t>(), c->n, c->vpos.as<uint32_t>(), dw.as<uint64_t>(),
+                       dw.as<uint64_t>() + nw, nw};
+            const int t = ix.prof.begin(s);
+            const uint64_t m = scan_totals<uint64_t>(s, ix.scan_partials, in, r.nrows, OpAdd{}, (uint64_t)0);
+            oi.alloc(std::max<uint64_t>(m, 1) * 8);
+            oc.alloc(std::max<uint64_t>(m, 1) * 8);
+            scan_apply<uint64_t>(s, ix.scan_partials, in, r.nrows, OpAdd{}, (uint64_t)0,
+                                 ProbeOut{ix.q_ids.as<int64_t>(), ix.q_counts.as<int64_t>(), oi.as<int64_t>(), oc.as<int64_t>()});
+            ix.prof.end(t, "col_probe", r.nrows * (16 + 2 * (uint64_t)bit_width64(c->n) * 8 + 8) + m * 16, s);
+            if (m) {
+                CDB_HIP(hipMemcpyAsync(ix.q_ids.p, oi.p, m * 8, hipMemcpyDeviceToDevice, s));
+                CDB_HIP(hipMemcpyAsync(ix.q_counts.p, oc.p, m * 8, hipMemcpyDeviceToDevice, s));
+            }
+            CDB_HIP(hipGetLastError());
+            CDB_HIP(hipStreamSynchronize(s));
+            r.nrows = m;
+        }
+        if (ranked) r = rank_rows_on_device(ix, r, corr_lo, corr_hi, limit);
+        else ix.prof.resolve();
+    }
+    consume(s, r);
+}
+
+extern "C" {
+
+int cdb_query_and_columns(const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols, int ranked, int64_t corr_lo,
+                          int64_t corr_hi, uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows) {
+    if (!ids || !counts || !nrows) return CDB_E_INVALID;
+    *ids = nullptr;
+    *counts = nullptr;
+    *nrows = 0;
+    Index* lead = filter_lead(keys, nkeys, cols, ncols);
+    if (!lead) return CDB_E_INVALID;
+    Index& ix = *lead;
+    return guarded_ix(ix, [&] {
+        filter_rows_on_lead(ix, keys, nkeys, cols, ncols, ranked != 0, corr_lo, corr_hi, limit, [&](hipStream_t s, DeviceCsr r) {
+            int64_t* hi = (int64_t*)host_alloc(r.nrows * 8);
+            int64_t* hc = nullptr;
+            try {
+                hc = (int64_t*)host_alloc(r.nrows * 8);
+                if (r.nrows) {
+                    CDB_HIP(hipMemcpyAsync(hi, ix.q_ids.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
+                    CDB_HIP(hipMemcpyAsync(hc, ix.q_counts.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
+                    CDB_HIP(hipStreamSynchronize(s));
                 }
-                dc.alloc(std::max<uint64_t>(n, 1) * 8);
-                CDB_HIP(hipMemsetAsync(dc.p, 0, std::max<uint64_t>(n, 1) * 8, s));
-                lists.push_back(DeviceRows{di.as<int64_t>(), dc.as<int64_t>(), n});
-                held.push_back(std::move(di));
-                held.push_back(std::move(dc));
-            } else {
-                probes.push_back(j);
+            } catch (...) {
+                host_free(hi);
+                host_free(hc);
+                throw;
             }
-        }
-        DeviceCsr r = and_merge_on_device(ix, lists, ranked != 0 && probes.empty(), corr_lo, corr_hi, limit);
-        if (!probes.empty()) {
-            for (int j : probes) {
-                cdb_column* c = cols[j].column;
-                ++c->probe_filters;
-                if (r.nrows == 0) continue;
-                DevBuf dw, oi, oc;
-                upload_windows(s, wins[j], dw);
-                const uint32_t nw = (uint32_t)wins[j].lo.size();
-                ProbeIn in{ix.q_ids.as<int64_t>(), c->id_sorted.as<int64_t>(), c->n, c->vpos.as<uint32_t>(), dw.as<uint64_t>(),
-                           dw.as<uint64_t>() + nw, nw};
-                const int t = ix.prof.begin(s);
-                const uint64_t m = scan_totals<uint64_t>(s, ix.scan_partials, in, r.nrows, OpAdd{}, (uint64_t)0);
-                oi.alloc(std::max<uint64_t>(m, 1) * 8);
-                oc.alloc(std::max<uint64_t>(m, 1) * 8);
-                scan_apply<uint64_t>(s, ix.scan_partials, in, r.nrows, OpAdd{}, (uint64_t)0,
-                                     ProbeOut{ix.q_ids.as<int64_t>(), ix.q_counts.as<int64_t>(), oi.as<int64_t>(), oc.as<int64_t>()});
-                ix.prof.end(t, "col_probe", r.nrows * (16 + 2 * (uint64_t)bit_width64(c->n) * 8 + 8) + m * 16, s);
-                if (m) {
-                    CDB_HIP(hipMemcpyAsync(ix.q_ids.p, oi.p, m * 8, hipMemcpyDeviceToDevice, s));
-                    CDB_HIP(hipMemcpyAsync(ix.q_counts.p, oc.p, m * 8, hipMemcpyDeviceToDevice, s));
-                }
-                CDB_HIP(hipGetLastError());
-                CDB_HIP(hipStreamSynchronize(s));
-                r.nrows = m;
-            }
-            if (ranked) r = rank_rows_on_device(ix, r, corr_lo, corr_hi, limit);
-            else ix.prof.resolve();
-        }
-        int64_t* hi = (int64_t*)host_alloc(r.nrows * 8);
-        int64_t* hc = nullptr;
-        try {
-            hc = (int64_t*)host_alloc(r.nrows * 8);
-            if (r.nrows) {
-                CDB_HIP(hipMemcpyAsync(hi, ix.q_ids.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-                CDB_HIP(hipMemcpyAsync(hc, ix.q_counts.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-                CDB_HIP(hipStreamSynchronize(s));
-            }
-        } catch (...) {
-            host_free(hi);
-            host_free(hc);
-            throw;
-        }
-        *ids = hi;
-        *counts = hc;
-        *nrows = (size_t)r.nrows;
+            *ids = hi;
+            *counts = hc;
+            *nrows = (size_t)r.nrows;
+        });
     });
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <atomic>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -678,6 +679,16 @@ inline const char* last_error_copy(std::mutex& err_mu, const std::string& err, s
     copy = err;
     return copy.c_str();
 }
+// columns.hip — the body cdb_query_and_columns and cdb_filter (rowset.hip) share: filter_lead names the handle that runs the merge
+// and carries the error (nullptr: CDB_E_INVALID); filter_rows_on_lead validates, locks, resolves and merges the keys and calls
+// `consume` under those locks with the rows in ix.q_ids / q_counts on ix.stream
+Index* filter_lead(const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols);
+void filter_rows_on_lead(Index& ix, const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols, bool ranked,
+                         int64_t corr_lo, int64_t corr_hi, uint64_t limit, const std::function<void(hipStream_t, DeviceCsr)>& consume);
+// cluster.hip — cdb_cluster / cdb_column_cluster over ids that already lie in device memory on the field's GPU (complete when the
+// call is made; the caller keeps them unchanged during it).  They take the field's lock and throw.
+void cluster_index_device_rows(cdb_index* h, const int64_t* d_ids, uint64_t nrows, bool with_values, cdb_clusters* out);
+void cluster_column_device_rows(cdb_column* c, const int64_t* d_ids, uint64_t nrows, cdb_clusters* out);
 int query_and_with_lead(cdb_index* lead, const cdb_key_query* keys, int nkeys, int ranked, int64_t corr_lo, int64_t corr_hi,
                         uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows);
 }

@@ -269,6 +269,49 @@ int cdb_column_cluster(cdb_column* c, const int64_t* ids, uint64_t nrows, cdb_cl
 int cdb_cluster(cdb_index* h, const int64_t* ids, uint64_t nrows, int with_values, cdb_clusters* out);
 void cdb_clusters_free(cdb_clusters* r);
 
+/* ---- row sets (rowset.hip) -----------------------------------------------------------------------------
+ * The reference's read operations — `count`, `query` with `span`, `cluster`, and the row list `remove` takes — all start with the same
+ * filter() (interface.cpp:46-148) and then use a sliver of its result.  A row set is that result left in device memory: filter once,
+ * then count, page and cluster without the rows crossing PCIe in between.
+ *
+ * cdb_filter is filter() up to interface.cpp:143: keys / cols exactly as cdb_query_and_columns takes and validates them (same errors,
+ * same messages, reported on the same handle / column: the first string key's, or without one the first column's); has_corr != 0
+ * keeps rows with corr_lo <= count < corr_hi (signed).  The rows — ascending object id, each id once, counts summed — stay in device
+ * memory owned by the row set, which holds copies of its own: it survives later queries on the handles that produced it, their
+ * rebuild and their destruction, and holds none of their locks once cdb_filter has returned.  Sharded keys go in as host rows
+ * resolved with cdb_shards_query_or.  Calls on one row set serialise on its lock; the cluster calls take the row set's lock and then
+ * the field's, and wait out a rebuild as cdb_cluster does.  Release result arrays with cdb_free / cdb_clusters_free.
+ *
+ * ORDER OF A PAGE: descending count compared as SIGNED int64 (the reference's comparator, interface.cpp:144-146), ties ascending id.
+ * cdb_query_ranked / cdb_query_and(_columns) with ranked = 1 order counts as unsigned, so a negative count (possible only in host
+ * rows) ranks first there and last here; the two agree on every non-negative count. */
+typedef struct cdb_rowset cdb_rowset;
+int cdb_filter(const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols, int has_corr, int64_t corr_lo,
+               int64_t corr_hi, cdb_rowset** out);
+void cdb_rowset_free(cdb_rowset* rs);
+const char* cdb_rowset_last_error(const cdb_rowset* rs);
+uint64_t cdb_rowset_size(const cdb_rowset* rs);  /* the `count` operation: no download */
+/* all rows, ascending id (what `remove` needs; what cdb_query_and_columns(ranked = 0) returns, after the corr filter) */
+int cdb_rowset_rows(cdb_rowset* rs, int64_t** ids, int64_t** counts, size_t* nrows);
+/* rows [first, last) of the ranking (interface.cpp:144-146, then `span`, :228-241).  last > size is clamped; first >= min(last, size)
+ * gives zero rows.  From 2^22 rows on only the rows up to the end of the page are sorted: a radix select over the counts finds them.
+ * Smaller sets key and sort all their rows, which measured faster there. */
+int cdb_rowset_page(cdb_rowset* rs, uint64_t first, uint64_t last, int64_t** ids, int64_t** counts, size_t* nrows);
+/* cluster (database.cpp:442-460) of the row set's ids by a string index / a column on the same GPU (another device: CDB_E_INVALID);
+ * result rules of cdb_cluster / cdb_column_cluster; nothing is uploaded.  Errors are reported on the row set. */
+int cdb_rowset_cluster(cdb_rowset* rs, cdb_index* field, int with_values, cdb_clusters* out);
+int cdb_rowset_cluster_column(cdb_rowset* rs, cdb_column* field, cdb_clusters* out);
+/* "rows", "page_selects", "page_sorts" (pages answered by either path; a page without rows runs neither), "select_passes" (key
+ * bytes the last select visited), "page_ms", "clusters", "cluster_ms" */
+int cdb_rowset_get_stat(const cdb_rowset* rs, const char* name, double* value);
+/* Test and measurement hooks — NOT part of the stable ABI: a row set over the caller's rows (ids ascending, taken as given);
+ * options "debug_page_path" (0 automatic: select from 2^22 rows on; 1 select wherever the page ends before the last row; 2 always sort) and "profile" (the
+ * page's kernels timed as pg_*, read as "name ms launches bytes" lines). */
+int cdb_debug_rowset_from_rows(int device, const int64_t* ids, const int64_t* counts, uint64_t n, cdb_rowset** out);
+int cdb_debug_rowset_set_option(cdb_rowset* rs, const char* name, int64_t value);
+/* CDB_E_INVALID when the table does not fit cap bytes (buf then holds its NUL-terminated head) */
+int cdb_debug_rowset_profile_dump(cdb_rowset* rs, char* buf, size_t cap);
+
 /* Highlight spans — replaces the per-document re-scan of ac_automaton::render (database.cpp:58-76) that
  * select() runs for every returned object (database.cpp:394-441): for the keyword list of ONE string
  * key, every matching document's merged highlight spans [begin, end] (byte offsets, end inclusive), with
