@@ -38,8 +38,6 @@ int guarded_hook(const char* who, F&& f) {
     return rc;
 }
 
-bool production_variant(int v) { return v == 0 || v == 1 || v == 21 || v == 26 || v == 31 || v == 33 || v == 36 || v == 32; }
-
 // the stream + workspace of one hook call: the handle's, or a fresh pair that lives for the call
 struct CallScope {
     cdb_debug_sort_ws* h;
@@ -288,7 +286,7 @@ int cdb_debug_radix_sort_ex(int device, cdb_debug_sort_ws* ws, void* d_keys, voi
         begin_bit < 0 || end_bit <= begin_bit || end_bit > 8 * key_bytes || dbits < 1 || dbits > 8)
         return CDB_E_INVALID;
     // 4 and 41 (kept for A/B measurements) exist for 64-bit keys only, as in production
-    if (!(production_variant(variant) || (key_bytes == 8 && (variant == 4 || variant == 41)))) return CDB_E_INVALID;
+    if (!(rs_variant_production(variant) || (key_bytes == 8 && (variant == RS_VARIANT_FIRST || variant == RS_VARIANT_DMA)))) return CDB_E_INVALID;
     // radix_sort() passes d_hist_in on to its pair configurations only: for a key-only sort the flag would silently do nothing
     if ((flags & CDB_DEBUG_SORT_DEVICE_HIST) && val_bytes == 0) return CDB_E_INVALID;
     if (n == 0) return CDB_OK;
@@ -341,7 +339,7 @@ int cdb_debug_radix_sort_split(int device, cdb_debug_sort_ws* ws, void* d_keys, 
     const bool pair_ok = (val_bytes == 4 && (aux_bytes == 1 || aux_bytes == 2 || aux_bytes == 4)) ||
                          (val_bytes == 8 && (aux_bytes == 1 || aux_bytes == 2));
     if (!d_keys || !d_vals || !d_aux || !pair_ok || hi_bits < 1 || hi_bits > 32 || lead_digits < 0 || lead_digits > aux_bytes ||
-        !production_variant(variant))
+        !rs_variant_production(variant))
         return CDB_E_INVALID;
     if (n == 0) return CDB_OK;
     return guarded_hook("cdb_debug_radix_sort_split", [&] {
@@ -371,7 +369,7 @@ int cdb_debug_radix_sort(int device, void* d_keys, void* d_vals, uint64_t n, int
                          double* onesweep_ms, int* passes) {
     if (key_bits < 1 || key_bits > 64) return CDB_E_INVALID;
     cdb_debug_sort_result r = {};
-    if (variant != 4 && variant != 41 && !production_variant(variant)) variant = 21;  // (radix_sort's default case, as before)
+    if (variant != RS_VARIANT_FIRST && variant != RS_VARIANT_DMA && !rs_variant_production(variant)) variant = RS_VARIANT_BIG_BALLOT;  // (rs_dispatch_variant's default)
     const int rc = cdb_debug_radix_sort_ex(device, nullptr, d_keys, val_bytes ? d_vals : nullptr, n, 8, val_bytes, 0, key_bits, 8, variant,
                                            CDB_DEBUG_SORT_PROFILE, &r);
     if (onesweep_ms) *onesweep_ms = r.onesweep_ms;

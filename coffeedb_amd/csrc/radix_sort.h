@@ -41,15 +41,10 @@ constexpr uint32_t RS_SPIN_LIMIT_PLAIN = 1u << 22;
 // Tiles are reserved for workgroups that have not started yet, so up to 7 * RS_GROUP resident workgroups can wait for
 // one that is still to be dispatched: the pass needs more than that many resident at a time (it has 256 when it runs
 // alone; concurrent kernels can take some away) — a pass that starves raises the look-back error flag (bounded
-// spins), and the callers redo the sort in plain ticket order (variant 33), which needs one.
+// spins), and the callers redo the sort in plain ticket order (RS_VARIANT_BIG), which needs one.
 constexpr int RS_GROUP = 8;
 
 struct NoVal {};
-
-// keys per thread of the small 256-thread configurations (cases 1 and 4 of radix_sort)
-template <typename K, typename V> struct RsTraits { static constexpr int IPT = 12; };
-template <> struct RsTraits<uint64_t, uint32_t> { static constexpr int IPT = 15; };
-template <> struct RsTraits<uint64_t, uint64_t> { static constexpr int IPT = 12; };
 
 // ---------------------------------------------------------------------------------------------
 // upfront histogram of every pass's digit (one read of the keys)
@@ -143,6 +138,40 @@ struct RsCfg {
     static constexpr int NT = NT_;            // threads per workgroup (>= 256, multiple of 64)
     static constexpr bool NONTEMP = NONTEMP_;  // streaming (non-temporal) global loads/stores
 };
+
+// ---- every configuration the library instantiates (the design points that were measured and dropped — other tile shapes,
+// look-back depths, tile orders, non-temporal accesses, timing ablations — are recorded in DESIGN.md §4.1 and can be re-run
+// with tools/experiments/pass_bench.hip).  A shape is spelled once, with ballot ranking; its twins are derived from it:
+// the one-atomic ranking (devices that passed rs_atomic_rank_ok) ...
+template <typename C>
+using RsAtomic = RsCfg<C::IPT, C::REUSE, C::EARLYV, C::NT, C::NONTEMP, C::MINW, C::ABL, C::LB, C::DMA, true>;
+// ... and the XCD-aware tile order on top of it (with the unpredicated load path that has the values in flight under the ranking)
+template <typename C>
+using RsGrouped = RsCfg<C::IPT, C::REUSE, C::EARLYV, C::NT, C::NONTEMP, C::MINW, C::ABL, C::LB, C::DMA, C::ATOMRANK, C::TICKET, 1, RS_GROUP>;
+// pairs and split records, three tile shapes:   IPT, REUSE, EARLYV, NT, NONTEMP, MINW, ABL, LB
+template <int IPT = 16>
+using RsBigBallot = RsCfg<IPT, true, true, 1024, false, 1, 0, 4>;   // 16 Ki-key tile, 1 WG/CU
+using RsMidBallot = RsCfg<18, true, true, 256, false, 1, 0, 4>;     // 4.5 Ki-key tile, 3 WG/CU
+using RsSmallBallot = RsCfg<15, true, true, 256, false, 1, 0, 1>;   // 3.75 Ki-key tile, 4 WG/CU
+template <int IPT = 16>
+using RsBig = RsAtomic<RsBigBallot<IPT>>;
+using RsMid = RsAtomic<RsMidBallot>;
+using RsSmall = RsAtomic<RsSmallBallot>;
+// the big tile of the split sort: with 8-byte values 12 keys per thread keep staging + auxiliary bytes inside the 160 KB of LDS
+template <typename V> constexpr int RS_SPLIT_BIG_IPT = sizeof(V) == 8 ? 12 : 16;
+// key-only: the same 16 Ki-key tile from 2^23 keys on, a 4 Ki-key tile below
+using RsKeyBigBallot = RsCfg<16, false, false, 1024, false, 1, 0, 4>;
+using RsKeySmallBallot = RsCfg<16, false, false>;
+using RsKeyBig = RsAtomic<RsKeyBigBallot>;
+using RsKeySmall = RsAtomic<RsKeySmallBallot>;
+// look-back-free generated passes (TextGen::tile_base): 512 threads x 16 keys, two workgroups per CU
+using RsGen8 = RsAtomic<RsCfg<16, true, true, 512, false, 1, 0, 4>>;
+// in-bucket passes of the MSD-first sort: records of 8 bytes, so keys AND values of a 16 Ki tile fit the staging buffer at once — one
+// write-out phase instead of two (3.45 instead of 3.62 ms per pass in tools/experiments/seg_bench.hip)
+using RsMsdBucket = RsAtomic<RsCfg<16, false, true, 1024, false, 1, 0, 4>>;
+// kept for A/B measurements (tools/sort_bench.py), pair sorts only, no generated first pass
+using RsFirstVersion = RsCfg<15, false, false, 256, false, 1, 0, 1>;  // round-1 first version
+using RsDmaLoads = RsCfg<16, true, true, 1024, false, 1, 0, 4, true>;  // 16 Ki tile, LDS-DMA loads, ballot ranking
 
 template <bool NT_, typename T> __device__ __forceinline__ T rs_load(const T* p) {
     if constexpr (NT_) return __builtin_nontemporal_load(p);
@@ -1464,9 +1493,95 @@ struct SortStats {
     int passes_run = 0, passes_skipped = 0;
 };
 
-// kernel configurations (radix_sort's `variant`) that have a generated first pass
-inline bool rs_variant_has_gen(int v) {
-    return v == 0 || v == 21 || v == 26 || v == 1 || v == 31 || v == 33 || v == 36 || v == 32;
+// ---- the variant table: what the `variant` of radix_sort / radix_sort_split (the sort_variant option) selects
+enum : int {
+    RS_VARIANT_BY_SIZE = 0,       // big tiles (the longest per-digit runs, so the best-coalesced scatter) need a few hundred
+                                  // tiles to fill 256 CUs: RsBig from RS_BIG_MIN_N keys on, RsMid from RS_MID_MIN_N, else RsSmall
+    RS_VARIANT_SMALL_BALLOT = 1,  // RsSmallBallot
+    RS_VARIANT_BIG_BALLOT = 21,   // RsBigBallot
+    RS_VARIANT_MID_BALLOT = 26,   // RsMidBallot
+    RS_VARIANT_BIG_GROUPED = 31,  // RsGrouped<RsBig>
+    RS_VARIANT_SMALL = 32,        // RsSmall
+    RS_VARIANT_BIG = 33,          // RsBig (plain ticket order)
+    RS_VARIANT_MID = 36,          // RsMid
+    RS_VARIANT_FIRST = 4,         // RsFirstVersion   (A/B only: pair sorts, no generated first pass)
+    RS_VARIANT_DMA = 41,          // RsDmaLoads       (A/B only)
+};
+constexpr uint64_t RS_BIG_MIN_N = 1ull << 23, RS_MID_MIN_N = 1ull << 19;
+
+// the production variants: every one of them has a generated first pass (the A/B configurations have none)
+inline bool rs_variant_production(int v) {
+    return v == RS_VARIANT_BY_SIZE || v == RS_VARIANT_SMALL_BALLOT || v == RS_VARIANT_BIG_BALLOT || v == RS_VARIANT_MID_BALLOT ||
+           v == RS_VARIANT_BIG_GROUPED || v == RS_VARIANT_SMALL || v == RS_VARIANT_BIG || v == RS_VARIANT_MID;
+}
+// true when the requested variant sorts n keys in 16 Ki-key one-atomic tiles (on a device that passed rs_atomic_rank_ok)
+inline bool rs_variant_big_atomic(int v, uint64_t n) {
+    return (v == RS_VARIANT_BY_SIZE && n >= RS_BIG_MIN_N) || v == RS_VARIANT_BIG_GROUPED || v == RS_VARIANT_BIG;
+}
+// ... or, the looser question of a caller that only prepares for such a pass: ANY variant counts from RS_BIG_MIN_N keys on (a forced
+// small-tile variant then finds the preparation unused: radix_sort_cfg's CAN_KEEP is false for it and keep_applied stays down)
+inline bool rs_variant_maybe_big_atomic(int v, uint64_t n) { return n >= RS_BIG_MIN_N || rs_variant_big_atomic(v, n); }
+
+// the variant that runs: by size for RS_VARIANT_BY_SIZE, plain ticket order where the caller may not use the grouped one, the
+// ballot twins on a device without the one-atomic ranking
+inline int rs_resolve_variant(hipStream_t s, const RadixWorkspace& ws, int v, uint64_t n) {
+    if (v == RS_VARIANT_BY_SIZE) v = n >= RS_BIG_MIN_N ? RS_VARIANT_BIG_GROUPED : (n >= RS_MID_MIN_N ? RS_VARIANT_MID : RS_VARIANT_SMALL);
+    if (v == RS_VARIANT_BIG_GROUPED && (!ws.allow_group || ws.plain_order)) v = RS_VARIANT_BIG;
+    if (rs_atomic_rank_ok(s)) return v;
+    return v == RS_VARIANT_BIG_GROUPED || v == RS_VARIANT_BIG ? RS_VARIANT_BIG_BALLOT
+         : v == RS_VARIANT_MID ? RS_VARIANT_MID_BALLOT : (v == RS_VARIANT_SMALL ? RS_VARIANT_SMALL_BALLOT : v);
+}
+// ... and its configuration: run(Cfg(), has_gen).  IPT_BIG = keys per thread of the big tile; AB = offer the A/B configurations
+// (any other number runs RsBigBallot)
+template <int IPT_BIG, bool AB, typename F>
+int rs_dispatch_variant(int resolved, F&& run) {
+    if constexpr (AB) {
+        if (resolved == RS_VARIANT_FIRST) return run(RsFirstVersion(), std::false_type());
+        if (resolved == RS_VARIANT_DMA) return run(RsDmaLoads(), std::false_type());
+    }
+    switch (resolved) {
+        default:
+        case RS_VARIANT_BIG_BALLOT: return run(RsBigBallot<IPT_BIG>(), std::true_type());
+        case RS_VARIANT_MID_BALLOT: return run(RsMidBallot(), std::true_type());
+        case RS_VARIANT_SMALL_BALLOT: return run(RsSmallBallot(), std::true_type());
+        case RS_VARIANT_BIG_GROUPED: return run(RsGrouped<RsBig<IPT_BIG>>(), std::true_type());
+        case RS_VARIANT_BIG: return run(RsBig<IPT_BIG>(), std::true_type());
+        case RS_VARIANT_MID: return run(RsMid(), std::true_type());
+        case RS_VARIANT_SMALL: return run(RsSmall(), std::true_type());
+    }
+}
+
+// ---- the one place that launches rs_onesweep_kernel: one pass over `tiles` tiles of Cfg.  Owns the grid (whole groups of
+// 8 * GROUP tiles in XCD-aware order), the pass's epoch, the ticket counter that goes with the order, status and error words.
+template <typename T> struct RsId { using type = T; };  // (input pointers may be a plain nullptr: K, V come from the outputs, W is named)
+template <typename Cfg, typename W = NoVal, typename K, typename V, typename Gen = NoGen, typename Seg = NoSeg>
+void rs_launch_pass(hipStream_t s, RadixWorkspace& ws, uint32_t tiles, typename RsId<const K*>::type kin, K* kout,
+                    typename RsId<const V*>::type vin, V* vout, uint64_t n, int shift, uint32_t dmask, const unsigned long long* digit_start,
+                    const Gen& gen = Gen(), typename RsId<const W*>::type win = nullptr, typename RsId<W*>::type wout = nullptr,
+                    int aux_shift = -1, const Seg& seg = Seg()) {
+    constexpr uint32_t G = 8u * Cfg::GROUP;
+    uint32_t grid = tiles;
+    if constexpr (G > 0) grid = (uint32_t)(ceil_div(tiles, G) * G);
+    const uint32_t e = ws.next_epoch(s);
+    hipLaunchKernelGGL((rs_onesweep_kernel<K, V, Cfg, Gen, W, Seg>), dim3(grid), dim3(Cfg::NT), 0, s, kin, kout, vin, vout, n, shift, dmask,
+                       digit_start, ws.status.as<uint64_t>(), G > 0 ? ws.xticket_ptr(e) : ws.ticket_ptr(e), e, ws.err_ptr(), gen, win, wout,
+                       aux_shift, seg);
+}
+// ... in the order the workspace allows: Cfg's grouped twin where the caller can redo the sort after a starved pass
+template <typename Cfg, typename W = NoVal, typename... A>
+void rs_launch_pass_ordered(hipStream_t s, RadixWorkspace& ws, A&&... a) {
+    if (ws.allow_group && !ws.plain_order) rs_launch_pass<RsGrouped<Cfg>, W>(s, ws, a...);
+    else rs_launch_pass<Cfg, W>(s, ws, a...);
+}
+
+// the per-tile document table of a generated pass over n positions in tiles of `tile` (gen.tile_doc)
+template <typename G>
+void rs_gen_tile_docs(hipStream_t s, RadixWorkspace& ws, G& gen, uint64_t n, uint64_t tile) {
+    const uint64_t tiles = ceil_div(n, tile);
+    ws.tile_doc.ensure((tiles + 1) * sizeof(uint64_t));
+    hipLaunchKernelGGL(rs_tiledoc_kernel, dim3((unsigned)ceil_div(tiles + 1, 256)), dim3(256), 0, s, gen.doc_start, gen.ndocs, n, tile, tiles,
+                       ws.tile_doc.as<uint64_t>());
+    gen.tile_doc = ws.tile_doc.as<uint64_t>();
 }
 
 struct SortPlan {
@@ -1497,7 +1612,7 @@ int radix_sort_cfg(hipStream_t s, RadixWorkspace& ws, Profiler& prof, K* k0, K* 
     else if constexpr (HAS_W) lead = lead_in;
     if (HAS_W && !GEN && !h_hist_in && !d_hist_in) throw InternalError("radix_sort: split records need caller-supplied histograms (internal)");
     const int LEAD = lead;
-    if (n == 0 || end_bit < begin_bit || (!LEAD && end_bit == begin_bit)) return 0;
+    if (n == 0 || end_bit < begin_bit || (!LEAD && end_bit == begin_bit)) return 0;  // (value_result / value_spare stay as the previous sort left them)
     const int nbits = end_bit - begin_bit;
     const int kpass = (int)ceil_div(nbits, dbits);  // passes over the key proper
     const int npass = kpass + LEAD;
@@ -1538,7 +1653,6 @@ int radix_sort_cfg(hipStream_t s, RadixWorkspace& ws, Profiler& prof, K* k0, K* 
     int cur = 0;
     bool materialised = !GEN;  // with a generator the input exists only after the first executed pass
     const uint32_t tiles = (uint32_t)ceil_div(n, (uint64_t)TILE);
-    const uint32_t grid_tiles = Cfg::GROUP > 0 ? (uint32_t)(ceil_div(tiles, 8u * Cfg::GROUP) * 8u * Cfg::GROUP) : tiles;
     const size_t pair_bytes = sizeof(K) + (HAS_V ? sizeof(V) : 0) + (HAS_W ? sizeof(W) : 0);
     // which passes run (a constant digit is skipped; the leading pass of a generated sort always runs: it
     // produces the records) and through which value buffers
@@ -1571,22 +1685,16 @@ int radix_sort_cfg(hipStream_t s, RadixWorkspace& ws, Profiler& prof, K* k0, K* 
         const int p = run[ri];
         V* const vin_p = vseq[ri];
         V* const vout_p = vseq[ri + 1];
-        const uint32_t e = ws.next_epoch(s);
         const uint32_t dmask = p == npass - 1 && kpass ? last_mask : ((1u << dbits) - 1u);
         const int shift = begin_bit + dbits * (p - LEAD);  // (unused by the leading passes of a split sort)
         const int aux_shift = p < LEAD ? dbits * p : -1;
+        const unsigned long long* dstart = d_start + p * 256;
         int t = prof.begin(s);
         if (!materialised) {
             if constexpr (GEN) {
                 Gen g2 = *gen;
-                ws.tile_doc.ensure(((size_t)tiles + 1) * sizeof(uint64_t));
-                hipLaunchKernelGGL(rs_tiledoc_kernel, dim3((unsigned)ceil_div((uint64_t)tiles + 1, 256)), dim3(256), 0, s,
-                                   g2.doc_start, g2.ndocs, n, (uint64_t)TILE, (uint64_t)tiles, ws.tile_doc.as<uint64_t>());
-                g2.tile_doc = ws.tile_doc.as<uint64_t>();
-                hipLaunchKernelGGL((rs_onesweep_kernel<K, V, Cfg, Gen, W>), dim3(grid_tiles), dim3(Cfg::NT), 0, s,
-                                   (const K*)nullptr, kb[cur ^ 1], (const V*)nullptr, vout_p, n, shift, dmask,
-                                   (const unsigned long long*)(d_start + p * 256), ws.status.as<uint64_t>(),
-                                   Cfg::GROUP > 0 ? ws.xticket_ptr(e) : ws.ticket_ptr(e), e, ws.err_ptr(), g2, (const W*)nullptr, wb[cur ^ 1], aux_shift);
+                rs_gen_tile_docs(s, ws, g2, n, TILE);
+                rs_launch_pass<Cfg, W>(s, ws, tiles, nullptr, kb[cur ^ 1], nullptr, vout_p, n, shift, dmask, dstart, g2, nullptr, wb[cur ^ 1], aux_shift);
             }
             prof.end(t, (std::string("rs_onesweep_textgen") + (HAS_W ? "_split" : "") + "_t" + std::to_string(TILE)).c_str(),
                      n * (1 + (kb[cur ^ 1] ? sizeof(K) : 0) + (HAS_V ? sizeof(V) : 0) + (HAS_W ? sizeof(W) : 0)), s);
@@ -1605,23 +1713,14 @@ int radix_sort_cfg(hipStream_t s, RadixWorkspace& ws, Profiler& prof, K* k0, K* 
                     ka.segs = ws.seg1.as<SegInfo>();
                     ka.tiles = tiles;
                     ka.start_stride = 0;
-                    hipLaunchKernelGGL((rs_onesweep_kernel<K, V, Cfg, NoGen, W, SegFinalKeepArgs>), dim3(grid_tiles), dim3(Cfg::NT), 0, s,
-                                       (const K*)kb[cur], kb[cur ^ 1], (const V*)vin_p, vout_p, n, shift, dmask,
-                                       (const unsigned long long*)(d_start + p * 256), ws.status.as<uint64_t>(),
-                                       Cfg::GROUP > 0 ? ws.xticket_ptr(e) : ws.ticket_ptr(e), e, ws.err_ptr(), NoGen(),
-                                       (const W*)wb[cur], wb[cur ^ 1], aux_shift, ka);
+                    rs_launch_pass<Cfg, W>(s, ws, tiles, kb[cur], kb[cur ^ 1], vin_p, vout_p, n, shift, dmask, dstart, NoGen(), wb[cur], wb[cur ^ 1], aux_shift, ka);
                     hipLaunchKernelGGL(rs_seg_edge_fix_kernel, dim3(tiles), dim3(256), 0, s, (const SegEdge*)ka.edges, (const uint32_t*)nullptr,
                                        (const SegInfo*)ws.seg1.as<SegInfo>(), tiles, ka.flags, ka.kbase, ka.kmagic, ka.tile_sums, ka.sums_tile, (const uint32_t*)ws.err_ptr());
                     kept = true;
                     ws.keep_applied = true;
                 }
             }
-            if (!kept)
-            hipLaunchKernelGGL((rs_onesweep_kernel<K, V, Cfg, NoGen, W>), dim3(grid_tiles), dim3(Cfg::NT), 0, s,
-                               (const K*)kb[cur], kb[cur ^ 1], (const V*)vin_p, vout_p, n, shift, dmask,
-                               (const unsigned long long*)(d_start + p * 256), ws.status.as<uint64_t>(),
-                               Cfg::GROUP > 0 ? ws.xticket_ptr(e) : ws.ticket_ptr(e), e,
-                               ws.err_ptr(), NoGen(), (const W*)wb[cur], wb[cur ^ 1], aux_shift);
+            if (!kept) rs_launch_pass<Cfg, W>(s, ws, tiles, kb[cur], kb[cur ^ 1], vin_p, vout_p, n, shift, dmask, dstart, NoGen(), wb[cur], wb[cur ^ 1], aux_shift);
             prof.end(t, (std::string(rs_kernel_name<K, V>()) + (HAS_W ? (sizeof(W) == 1 ? "_w8" : (sizeof(W) == 2 ? "_w16" : "_w32")) : "") +
                          (kept ? "_flags" : "") + "_t" + std::to_string(TILE)).c_str(),
                      2 * n * pair_bytes + (kept ? n : 0), s);
@@ -1640,58 +1739,25 @@ template <typename K, typename V>
 int radix_sort(hipStream_t s, RadixWorkspace& ws, Profiler& prof, K* k0, K* k1, V* v0, V* v1, uint64_t n,
                int begin_bit, int end_bit, SortStats* stats = nullptr, int variant = 0, int dbits = 8,
                const uint64_t* h_hist_in = nullptr, const TextGen* gen = nullptr, const unsigned long long* d_hist_in = nullptr) {
-    constexpr bool HAS_V = !std::is_same<V, NoVal>::value;
-    const bool atomrank = rs_atomic_rank_ok(s);
-    if constexpr (!HAS_V) {
-        if (n >= (1ull << 23)) {  // key-only: same 16 Ki-key tile as the pair sort
-            if (atomrank && variant != 21 && variant != 33 && ws.allow_group && !ws.plain_order)
-                return radix_sort_cfg<K, V, RsCfg<16, false, false, 1024, false, 1, 0, 4, false, true, true, 1, RS_GROUP>>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, stats, dbits, h_hist_in);
-            if (atomrank && variant != 21)
-                return radix_sort_cfg<K, V, RsCfg<16, false, false, 1024, false, 1, 0, 4, false, true>>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, stats, dbits, h_hist_in);
-            return radix_sort_cfg<K, V, RsCfg<16, false, false, 1024, false, 1, 0, 4>>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, stats, dbits, h_hist_in);
-        }
-        if (atomrank && variant != 21)
-            return radix_sort_cfg<K, V, RsCfg<16, false, false, 256, false, 1, 0, 1, false, true>>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, stats, dbits, h_hist_in);
-        return radix_sort_cfg<K, V, RsCfg<16, false, false>>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, stats, dbits, h_hist_in);
+    if constexpr (std::is_same<V, NoVal>::value) {
+        // key-only: RS_VARIANT_BIG_BALLOT forces the ballot ranking, RS_VARIANT_BIG the plain ticket order; no generated pass, and
+        // d_hist_in is not passed on (cdb_debug_radix_sort_ex refuses the flag for key-only sorts)
+        auto run = [&](auto cfg) { return radix_sort_cfg<K, V, decltype(cfg)>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, stats, dbits, h_hist_in); };
+        const bool atomrank = rs_atomic_rank_ok(s) && variant != RS_VARIANT_BIG_BALLOT;
+        if (n < RS_BIG_MIN_N) return atomrank ? run(RsKeySmall()) : run(RsKeySmallBallot());
+        if (!atomrank) return run(RsKeyBigBallot());
+        return variant != RS_VARIANT_BIG && ws.allow_group && !ws.plain_order ? run(RsGrouped<RsKeyBig>()) : run(RsKeyBig());
     } else {
-        // variant 0 picks by size: big tiles (16 Ki keys, one workgroup per CU) give the longest per-digit
-        // runs and therefore the best-coalesced scatter, but need >= a few hundred tiles to fill 256 CUs;
-        // 31/36/32 = the same tiles with one-atomic ranking (when the device passed rs_atomic_rank_ok)
-        if (variant == 0)
-            variant = atomrank ? (n >= (1ull << 23) ? 31 : (n >= (1ull << 19) ? 36 : 32))
-                               : (n >= (1ull << 23) ? 21 : (n >= (1ull << 19) ? 26 : 1));
-        if (variant == 31 && (!ws.allow_group || ws.plain_order)) variant = 33;
-        if (!atomrank && variant == 33) variant = 21;
-        if (!atomrank && (variant == 31 || variant == 36 || variant == 32)) variant -= variant == 32 ? 31 : 10;
-#define CDB_RS(...)                                                                                                      \
-    return radix_sort_cfg<K, V, RsCfg<__VA_ARGS__>>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, stats, dbits, h_hist_in, \
-                                                    (const NoGen*)nullptr, (NoVal*)nullptr, (NoVal*)nullptr, 0, d_hist_in)
-#define CDB_RS_GEN(...)                                                                                               \
-    if (gen)                                                                                                          \
-        return radix_sort_cfg<K, V, RsCfg<__VA_ARGS__>, TextGen>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, \
-                                                                 stats, dbits, h_hist_in, gen);                       \
-    CDB_RS(__VA_ARGS__)
-        if (gen && !rs_variant_has_gen(variant))
+        variant = rs_resolve_variant(s, ws, variant, n);
+        if (gen && !rs_variant_production(variant))
             throw InternalError("radix_sort: this kernel configuration has no generated first pass (internal)");
-        switch (variant) {
-            // production configurations: IPT, REUSE, EARLYV, NT, NONTEMP, MINW, ABL, LB
-            default:
-            case 21: CDB_RS_GEN(16, true, true, 1024, false, 1, 0, 4);   // 16 Ki-key tile, 1 WG/CU
-            case 26: CDB_RS_GEN(18, true, true, 256, false, 1, 0, 4);    // 4.5 Ki-key tile, 3 WG/CU
-            case 1: CDB_RS_GEN(15, true, true, 256, false, 1, 0, 1);     // 3.75 Ki-key tile, 4 WG/CU
-            // the same three with LDS-atomic ranking
-            case 31: CDB_RS_GEN(16, true, true, 1024, false, 1, 0, 4, false, true, true, 1, RS_GROUP);  // + XCD-aware tile order
-            case 33: CDB_RS_GEN(16, true, true, 1024, false, 1, 0, 4, false, true);                     // (plain ticket order)
-            case 36: CDB_RS_GEN(18, true, true, 256, false, 1, 0, 4, false, true);
-            case 32: CDB_RS_GEN(15, true, true, 256, false, 1, 0, 1, false, true);
-            // kept for A/B measurements (tools/sort_bench.py): the first version and the LDS-DMA load path; the other
-            // design points that were measured (tile shapes, look-back depths, tile orders, non-temporal accesses, timing
-            // ablations) are recorded in DESIGN.md §4.1 and can be re-run with tools/experiments/pass_bench.hip
-            case 4: CDB_RS(15, false, false, 256, false, 1, 0, 1);        // round-1 first version
-            case 41: CDB_RS(16, true, true, 1024, false, 1, 0, 4, true);  // 16 Ki tile, LDS-DMA loads, ballot ranking
-        }
-#undef CDB_RS
-#undef CDB_RS_GEN
+        return rs_dispatch_variant<16, true>(variant, [&](auto cfg, auto has_gen) {
+            using Cfg = decltype(cfg);
+            if constexpr (decltype(has_gen)::value)
+                if (gen) return radix_sort_cfg<K, V, Cfg, TextGen>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, stats, dbits, h_hist_in, gen);
+            return radix_sort_cfg<K, V, Cfg>(s, ws, prof, k0, k1, v0, v1, n, begin_bit, end_bit, stats, dbits, h_hist_in,
+                                             (const NoGen*)nullptr, (NoVal*)nullptr, (NoVal*)nullptr, 0, d_hist_in);
+        });
     }
 }
 
@@ -1725,36 +1791,13 @@ int radix_sort_split(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uint32_t
     // lead_digits: sort digits in the auxiliary array of materialised records (default: every byte of W); the bytes
     // above them are carried along untouched (the bucket-wise build keeps bits 32..39 of its entries there)
     const int lead_in = lead_digits >= 0 ? lead_digits : (int)sizeof(W);
-    const bool atomrank = rs_atomic_rank_ok(s);
-    // 8-byte values: a 12 Ki-key tile keeps staging + auxiliary bytes inside the 160 KB of LDS
-    constexpr int IPT_BIG = sizeof(V) == 8 ? 12 : 16;
-    if (variant == 0)
-        variant = atomrank ? (n >= (1ull << 23) ? 31 : (n >= (1ull << 19) ? 36 : 32))
-                           : (n >= (1ull << 23) ? 21 : (n >= (1ull << 19) ? 26 : 1));
-    if (variant == 31 && (!ws.allow_group || ws.plain_order)) variant = 33;
-    if (!atomrank && variant == 33) variant = 21;
-    if (!atomrank && (variant == 31 || variant == 36 || variant == 32)) variant -= variant == 32 ? 31 : 10;
-#define CDB_RS_SPLIT(...)                                                                                              \
-    if constexpr (sizeof(W) <= 2) { /* (a generated first pass produces one or two low digits) */                      \
-        if (gen)                                                                                                       \
-            return radix_sort_cfg<uint32_t, V, RsCfg<__VA_ARGS__>, TextGen, W>(s, ws, prof, k0, k1, v0, v1, n,          \
-                                                                               key_begin, hi_bits, stats, dbits,        \
-                                                                               h_hist, gen, w0, w1, 0, nullptr, keep);  \
-    }                                                                                                                  \
-    return radix_sort_cfg<uint32_t, V, RsCfg<__VA_ARGS__>, NoGen, W>(s, ws, prof, k0, k1, v0, v1, n, key_begin, hi_bits, \
-                                                                     stats, dbits, h_hist, (const NoGen*)nullptr, w0, w1, \
-                                                                     lead_in, d_hist, keep)
-    switch (variant) {
-        default:
-        case 21: CDB_RS_SPLIT(IPT_BIG, true, true, 1024, false, 1, 0, 4);
-        case 26: CDB_RS_SPLIT(18, true, true, 256, false, 1, 0, 4);
-        case 1: CDB_RS_SPLIT(15, true, true, 256, false, 1, 0, 1);
-        case 31: CDB_RS_SPLIT(IPT_BIG, true, true, 1024, false, 1, 0, 4, false, true, true, 1, RS_GROUP);
-        case 33: CDB_RS_SPLIT(IPT_BIG, true, true, 1024, false, 1, 0, 4, false, true);
-        case 36: CDB_RS_SPLIT(18, true, true, 256, false, 1, 0, 4, false, true);
-        case 32: CDB_RS_SPLIT(15, true, true, 256, false, 1, 0, 1, false, true);
-    }
-#undef CDB_RS_SPLIT
+    return rs_dispatch_variant<RS_SPLIT_BIG_IPT<V>, false>(rs_resolve_variant(s, ws, variant, n), [&](auto cfg, auto) {
+        using Cfg = decltype(cfg);
+        if constexpr (sizeof(W) <= 2)  // (a generated first pass produces one or two low digits)
+            if (gen) return radix_sort_cfg<uint32_t, V, Cfg, TextGen, W>(s, ws, prof, k0, k1, v0, v1, n, key_begin, hi_bits, stats, dbits, h_hist, gen, w0, w1, 0, nullptr, keep);
+        return radix_sort_cfg<uint32_t, V, Cfg, NoGen, W>(s, ws, prof, k0, k1, v0, v1, n, key_begin, hi_bits, stats, dbits, h_hist,
+                                                          (const NoGen*)nullptr, w0, w1, lead_in, d_hist, keep);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1821,10 +1864,6 @@ void radix_sort_segmented(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uin
     sa.tiles = tiles;
     sa.start_stride = 8 * 256;
     static_cast<SegArgs&>(fin) = sa;
-    const bool grouped = ws.allow_group && !ws.plain_order;
-    using CfgG = RsCfg<16, true, true, 1024, false, 1, 0, 4, false, true, true, 1, RS_GROUP>;
-    using CfgP = RsCfg<16, true, true, 1024, false, 1, 0, 4, false, true>;
-    const uint32_t grid = grouped ? (uint32_t)(ceil_div(tiles, 8u * RS_GROUP) * 8u * RS_GROUP) : tiles;
     uint32_t* kb[2] = {k0, k1};
     uint32_t* vb[2] = {v0, v1};
     W* wb[2] = {w0, w1};
@@ -1832,28 +1871,20 @@ void radix_sort_segmented(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uin
     const char* wn = sizeof(W) == 1 ? "_w8" : (sizeof(W) == 2 ? "_w16" : "_w32");
     const size_t rec = 8 + sizeof(W);
     for (int p = 0; p < npass; ++p) {
-        const uint32_t e = ws.next_epoch(s);
         const uint32_t dmask = p == npass - 1 ? last_mask : 0xFFu;
         const int shift = 8 * (p - lead);
         const int aux_shift = p < lead ? 8 * p : -1;
         const unsigned long long* dstart = d_starts + (size_t)p * 256;
-        uint32_t* tk = grouped ? ws.xticket_ptr(e) : ws.ticket_ptr(e);
         int t = prof.begin(s);
-#define CDB_SEG_LAUNCH(CFG, SEGT, SEGV)                                                                                       \
-    hipLaunchKernelGGL((rs_onesweep_kernel<uint32_t, uint32_t, CFG, NoGen, W, SEGT>), dim3(grid), dim3(1024), 0, s,            \
-                       (const uint32_t*)kb[cur], kb[cur ^ 1], (const uint32_t*)vb[cur], vb[cur ^ 1], m, shift, dmask, dstart, \
-                       ws.status.as<uint64_t>(), tk, e, ws.err_ptr(), NoGen(), (const W*)wb[cur], wb[cur ^ 1], aux_shift,     \
-                       SEGV)
         if (p == npass - 1) {
-            if (grouped) CDB_SEG_LAUNCH(CfgG, SegFinalArgs, fin);
-            else CDB_SEG_LAUNCH(CfgP, SegFinalArgs, fin);
+            rs_launch_pass_ordered<RsBig<>, W>(s, ws, tiles, kb[cur], kb[cur ^ 1], vb[cur], vb[cur ^ 1], m, shift, dmask, dstart, NoGen(), wb[cur],
+                                               wb[cur ^ 1], aux_shift, fin);
             prof.end(t, (std::string("rs_seg_final") + wn + "_t16384").c_str(), m * (rec + (fin.elo ? 6 : 9)), s);
         } else {
-            if (grouped) CDB_SEG_LAUNCH(CfgG, SegArgs, sa);
-            else CDB_SEG_LAUNCH(CfgP, SegArgs, sa);
+            rs_launch_pass_ordered<RsBig<>, W>(s, ws, tiles, kb[cur], kb[cur ^ 1], vb[cur], vb[cur ^ 1], m, shift, dmask, dstart, NoGen(), wb[cur],
+                                               wb[cur ^ 1], aux_shift, sa);
             prof.end(t, (std::string("rs_seg_k32_v32") + wn + "_t16384").c_str(), 2 * m * rec, s);
         }
-#undef CDB_SEG_LAUNCH
         cur ^= 1;
         if (stats) stats->passes_run++;
     }
@@ -2118,9 +2149,6 @@ inline void radix_sort_msd(hipStream_t s, RadixWorkspace& ws, MsdWorkspace& mw, 
     if (!rs_atomic_rank_ok(s)) throw InternalError("radix_sort_msd: needs the one-atomic ranking (internal)");
     constexpr int TILE = RS_SEG_TILE;
     constexpr int KPASS = 4;
-    using CfgG = RsCfg<16, true, true, 1024, false, 1, 0, 4, false, true, true, 1, RS_GROUP>;
-    using CfgP = RsCfg<16, true, true, 1024, false, 1, 0, 4, false, true>;
-    const bool grouped = ws.allow_group && !ws.plain_order;
     // segments = the non-empty buckets of the top digit
     std::vector<SegInfo> h_segs;
     uint32_t seg_tiles = 0;
@@ -2156,57 +2184,32 @@ inline void radix_sort_msd(hipStream_t s, RadixWorkspace& ws, MsdWorkspace& mw, 
         // look-back-free form: per-tile counts of the top digit (sa_build.hip: sa_tile_paircount_kernel, rs_tile_totals already ran on
         // them) -> tile bases; 8 Ki-key tiles, two workgroups per CU, no status words, no waiting for other tiles
         constexpr int GT = RS_GEN8_TILE;
-        using CfgG8 = RsCfg<16, true, true, 512, false, 1, 0, 4, false, true, true, 1, RS_GROUP>;
-        using CfgP8 = RsCfg<16, true, true, 512, false, 1, 0, 4, false, true>;
         const uint32_t gen_tiles8 = (uint32_t)ceil_div(n, (uint64_t)GT);
         TextGenPair gp;
         static_cast<TextGen&>(gp) = gen_in;
         gp.low_bits = 0;
         gp.tile_base = rs_tile_bases(s, *tbw, d_tile_counts, gen_tiles8, nullptr, (const unsigned long long*)d_start);
-        ws.tile_doc.ensure(((size_t)gen_tiles8 + 1) * sizeof(uint64_t));
-        hipLaunchKernelGGL(rs_tiledoc_kernel, dim3((unsigned)ceil_div((uint64_t)gen_tiles8 + 1, 256)), dim3(256), 0, s, gp.doc_start, gp.ndocs,
-                           n, (uint64_t)GT, (uint64_t)gen_tiles8, ws.tile_doc.as<uint64_t>());
-        gp.tile_doc = ws.tile_doc.as<uint64_t>();
-        const uint32_t e = ws.next_epoch(s);
-        const uint32_t grid = grouped ? (uint32_t)(ceil_div(gen_tiles8, 8u * RS_GROUP) * 8u * RS_GROUP) : gen_tiles8;
+        rs_gen_tile_docs(s, ws, gp, n, GT);
         int t = prof.begin(s);
         if (sweep_form)  // (no record crosses the LDS, three workgroups per CU; static XCD-aware tile map)
             hipLaunchKernelGGL(rs_sweep_msd_kernel, dim3((uint32_t)(ceil_div(gen_tiles8, 8u * RS_GROUP) * 8u * RS_GROUP)), dim3(512), 0, s,
                                static_cast<const TextGen&>(gp), n, gen_tiles8, k1, v1);
-        else if (grouped)
-            hipLaunchKernelGGL((rs_onesweep_kernel<uint32_t, uint32_t, CfgG8, TextGenPair, uint8_t>), dim3(grid), dim3(512), 0, s, (const uint32_t*)nullptr,
-                               k1, (const uint32_t*)nullptr, v1, n, 0, 0xFFu, (const unsigned long long*)d_start, ws.status.as<uint64_t>(),
-                               ws.xticket_ptr(e), e, ws.err_ptr(), gp, (const uint8_t*)nullptr, (uint8_t*)nullptr, 0);
         else
-            hipLaunchKernelGGL((rs_onesweep_kernel<uint32_t, uint32_t, CfgP8, TextGenPair, uint8_t>), dim3(grid), dim3(512), 0, s, (const uint32_t*)nullptr,
-                               k1, (const uint32_t*)nullptr, v1, n, 0, 0xFFu, (const unsigned long long*)d_start, ws.status.as<uint64_t>(),
-                               ws.ticket_ptr(e), e, ws.err_ptr(), gp, (const uint8_t*)nullptr, (uint8_t*)nullptr, 0);
+            rs_launch_pass_ordered<RsGen8, uint8_t>(s, ws, gen_tiles8, nullptr, k1, nullptr, v1, n, 0, 0xFFu, d_start, gp, nullptr, nullptr, 0);
         prof.end(t, sweep_form ? "rs_sweep_msd" : "rs_onesweep_textgen_msd_t8192", n * 9, s);
         if (stats) stats->passes_run++;
     } else {
         TextGen g2 = gen_in;
         g2.low_bits = 0;
-        ws.tile_doc.ensure(((size_t)gen_tiles + 1) * sizeof(uint64_t));
-        hipLaunchKernelGGL(rs_tiledoc_kernel, dim3((unsigned)ceil_div((uint64_t)gen_tiles + 1, 256)), dim3(256), 0, s, g2.doc_start, g2.ndocs,
-                           n, (uint64_t)TILE, (uint64_t)gen_tiles, ws.tile_doc.as<uint64_t>());
-        g2.tile_doc = ws.tile_doc.as<uint64_t>();
-        const uint32_t e = ws.next_epoch(s);
-        const uint32_t grid = grouped ? (uint32_t)(ceil_div(gen_tiles, 8u * RS_GROUP) * 8u * RS_GROUP) : gen_tiles;
+        rs_gen_tile_docs(s, ws, g2, n, TILE);
         int t = prof.begin(s);
-#define CDB_MSD_GEN(CFG, GENT, GENV, TICKET)                                                                                              \
-    hipLaunchKernelGGL((rs_onesweep_kernel<uint32_t, uint32_t, CFG, GENT, uint8_t>), dim3(grid), dim3(1024), 0, s, (const uint32_t*)nullptr, \
-                       k1, (const uint32_t*)nullptr, v1, n, 0, 0xFFu, (const unsigned long long*)d_start, ws.status.as<uint64_t>(), TICKET, \
-                       e, ws.err_ptr(), GENV, (const uint8_t*)nullptr, (uint8_t*)nullptr, 0)
         if (g2.msd_pair) {  // (the generator's form is part of the kernel's type)
             TextGenPair gp;
             static_cast<TextGen&>(gp) = g2;
-            if (grouped) CDB_MSD_GEN(CfgG, TextGenPair, gp, ws.xticket_ptr(e));
-            else CDB_MSD_GEN(CfgP, TextGenPair, gp, ws.ticket_ptr(e));
+            rs_launch_pass_ordered<RsBig<>, uint8_t>(s, ws, gen_tiles, nullptr, k1, nullptr, v1, n, 0, 0xFFu, d_start, gp, nullptr, nullptr, 0);
         } else {
-            if (grouped) CDB_MSD_GEN(CfgG, TextGen, g2, ws.xticket_ptr(e));
-            else CDB_MSD_GEN(CfgP, TextGen, g2, ws.ticket_ptr(e));
+            rs_launch_pass_ordered<RsBig<>, uint8_t>(s, ws, gen_tiles, nullptr, k1, nullptr, v1, n, 0, 0xFFu, d_start, g2, nullptr, nullptr, 0);
         }
-#undef CDB_MSD_GEN
         prof.end(t, "rs_onesweep_textgen_msd_t16384", n * 9, s);
         if (stats) stats->passes_run++;
     }
@@ -2231,36 +2234,19 @@ inline void radix_sort_msd(hipStream_t s, RadixWorkspace& ws, MsdWorkspace& mw, 
     static_cast<SegArgs&>(ka) = sa;
     ka.low_bits = 0;
     ka.msd_m = msd_m;
-    const uint32_t grid = grouped ? (uint32_t)(ceil_div(seg_tiles, 8u * RS_GROUP) * 8u * RS_GROUP) : seg_tiles;
     uint32_t* kb[2] = {k0, k1};
     uint32_t* vb[2] = {v0, v1};
     int cur = 1;
     for (int p = 0; p < KPASS; ++p) {
-        const uint32_t e = ws.next_epoch(s);
         const unsigned long long* dstart = mw.starts.as<unsigned long long>() + (size_t)p * 256;
-        uint32_t* tk = grouped ? ws.xticket_ptr(e) : ws.ticket_ptr(e);
         int t = prof.begin(s);
-        // (records of 8 bytes: keys AND values of a 16 Ki tile fit the staging buffer at once — one write-out phase instead
-        //  of two, 3.45 instead of 3.62 ms per pass in tools/experiments/seg_bench.hip)
-        using CfgG2 = RsCfg<16, false, true, 1024, false, 1, 0, 4, false, true, true, 1, RS_GROUP>;
-        using CfgP2 = RsCfg<16, false, true, 1024, false, 1, 0, 4, false, true>;
         if (p + 1 < KPASS) {
-#define CDB_MSD_LAUNCH(CFG)                                                                                                          \
-    hipLaunchKernelGGL((rs_onesweep_kernel<uint32_t, uint32_t, CFG, NoGen, NoVal, SegArgs>), dim3(grid), dim3(1024), 0, s,          \
-                       (const uint32_t*)kb[cur], kb[cur ^ 1], (const uint32_t*)vb[cur], vb[cur ^ 1], n, 8 * p, 0xFFu, dstart,        \
-                       ws.status.as<uint64_t>(), tk, e, ws.err_ptr(), NoGen(), (const NoVal*)nullptr, (NoVal*)nullptr, -1, sa)
-            if (grouped) CDB_MSD_LAUNCH(CfgG2);
-            else CDB_MSD_LAUNCH(CfgP2);
-#undef CDB_MSD_LAUNCH
+            rs_launch_pass_ordered<RsMsdBucket>(s, ws, seg_tiles, kb[cur], kb[cur ^ 1], vb[cur], vb[cur ^ 1], n, 8 * p, 0xFFu, dstart, NoGen(), nullptr,
+                                                nullptr, -1, sa);
             prof.end(t, "rs_seg_k32_v32_t16384", 2 * n * 8, s);
         } else {
-#define CDB_MSD_FINAL(CFG)                                                                                                           \
-    hipLaunchKernelGGL((rs_onesweep_kernel<uint32_t, uint32_t, CFG, NoGen, uint8_t, SegFinalKeepMsdArgs>), dim3(grid), dim3(1024), 0, s, \
-                       (const uint32_t*)kb[cur], kb[cur ^ 1], (const uint32_t*)vb[cur], vb[cur ^ 1], n, 8 * p, 0xFFu, dstart,        \
-                       ws.status.as<uint64_t>(), tk, e, ws.err_ptr(), NoGen(), (const uint8_t*)nullptr, wout, -1, ka)
-            if (grouped) CDB_MSD_FINAL(CfgG2);
-            else CDB_MSD_FINAL(CfgP2);
-#undef CDB_MSD_FINAL
+            rs_launch_pass_ordered<RsMsdBucket, uint8_t>(s, ws, seg_tiles, kb[cur], kb[cur ^ 1], vb[cur], vb[cur ^ 1], n, 8 * p, 0xFFu, dstart, NoGen(),
+                                                         nullptr, wout, -1, ka);
             prof.end(t, "rs_seg_k32_v32_flags_t16384", n * (8 + 9 + 1), s);
         }
         cur ^= 1;
@@ -2288,9 +2274,6 @@ void radix_gen_records(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uint32
                        const uint32_t* d_tile_counts = nullptr, const uint16_t* d_src_col = nullptr, TileBaseWorkspace* tbw = nullptr) {
     if (!rs_atomic_rank_ok(s)) throw InternalError("radix_gen_records: needs the one-atomic ranking (internal)");
     constexpr int TILE = RS_SEG_TILE;
-    using CfgG = RsCfg<16, true, true, 1024, false, 1, 0, 4, false, true, true, 1, RS_GROUP>;
-    using CfgP = RsCfg<16, true, true, 1024, false, 1, 0, 4, false, true>;
-    const bool grouped = ws.allow_group && !ws.plain_order;
     const uint32_t gen_tiles = (uint32_t)ceil_div(n, (uint64_t)TILE);
     ws.prepare((uint64_t)std::max(gen_tiles, seg_tiles) * TILE, TILE, s);
     unsigned long long* d_hist = ws.hist.as<unsigned long long>();
@@ -2301,42 +2284,19 @@ void radix_gen_records(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uint32
     CDB_HIP(hipMemsetAsync(d_hist_out, 0, (size_t)nseg * 8 * 256 * sizeof(uint64_t), s));
     TextGenRec g2;
     static_cast<TextGen&>(g2) = gen_in;
-    ws.tile_doc.ensure(((size_t)gen_tiles + 1) * sizeof(uint64_t));
-    hipLaunchKernelGGL(rs_tiledoc_kernel, dim3((unsigned)ceil_div((uint64_t)gen_tiles + 1, 256)), dim3(256), 0, s, g2.doc_start, g2.ndocs, n,
-                       (uint64_t)TILE, (uint64_t)gen_tiles, ws.tile_doc.as<uint64_t>());
-    g2.tile_doc = ws.tile_doc.as<uint64_t>();
-    const uint32_t e = ws.next_epoch(s);
-    const uint32_t grid = grouped ? (uint32_t)(ceil_div(gen_tiles, 8u * RS_GROUP) * 8u * RS_GROUP) : gen_tiles;
+    rs_gen_tile_docs(s, ws, g2, n, TILE);
     int t = prof.begin(s);
     if (d_tile_counts && tbw) {
         // look-back-free form (TextGen::tile_base): per-tile byte counts (sa_build.hip: sa_tile_bytecount_kernel), columns mapped
         // byte -> bucket slot, scanned over the tiles; 8 Ki-key tiles, two workgroups per CU
         constexpr int GT = RS_GEN8_TILE;
-        using CfgG8 = RsCfg<16, true, true, 512, false, 1, 0, 4, false, true, true, 1, RS_GROUP>;
-        using CfgP8 = RsCfg<16, true, true, 512, false, 1, 0, 4, false, true>;
         const uint32_t tiles8 = (uint32_t)ceil_div(n, (uint64_t)GT);
         g2.tile_base = rs_tile_bases(s, *tbw, d_tile_counts, tiles8, d_src_col, (const unsigned long long*)d_start);
-        ws.tile_doc.ensure(((size_t)tiles8 + 1) * sizeof(uint64_t));
-        hipLaunchKernelGGL(rs_tiledoc_kernel, dim3((unsigned)ceil_div((uint64_t)tiles8 + 1, 256)), dim3(256), 0, s, g2.doc_start, g2.ndocs, n,
-                           (uint64_t)GT, (uint64_t)tiles8, ws.tile_doc.as<uint64_t>());
-        g2.tile_doc = ws.tile_doc.as<uint64_t>();
-        const uint32_t grid8 = grouped ? (uint32_t)(ceil_div(tiles8, 8u * RS_GROUP) * 8u * RS_GROUP) : tiles8;
-        uint32_t* tk = grouped ? ws.xticket_ptr(e) : ws.ticket_ptr(e);
-#define CDB_REC8(CFG, GENT, GENV)                                                                                                      \
-    hipLaunchKernelGGL((rs_onesweep_kernel<uint32_t, uint32_t, CFG, GENT, W>), dim3(grid8), dim3(512), 0, s, (const uint32_t*)nullptr, k, \
-                       (const uint32_t*)nullptr, v, n, 0, 0xFFu, (const unsigned long long*)d_start, ws.status.as<uint64_t>(), tk, e,    \
-                       ws.err_ptr(), GENV, (const W*)nullptr, w, -1)
-        if (grouped) CDB_REC8(CfgG8, TextGenRec, g2);
-        else CDB_REC8(CfgP8, TextGenRec, g2);
-#undef CDB_REC8
-    } else if (grouped)
-        hipLaunchKernelGGL((rs_onesweep_kernel<uint32_t, uint32_t, CfgG, TextGenRec, W>), dim3(grid), dim3(1024), 0, s, (const uint32_t*)nullptr, k,
-                           (const uint32_t*)nullptr, v, n, 0, 0xFFu, (const unsigned long long*)d_start, ws.status.as<uint64_t>(),
-                           ws.xticket_ptr(e), e, ws.err_ptr(), g2, (const W*)nullptr, w, -1);
-    else
-        hipLaunchKernelGGL((rs_onesweep_kernel<uint32_t, uint32_t, CfgP, TextGenRec, W>), dim3(grid), dim3(1024), 0, s, (const uint32_t*)nullptr, k,
-                           (const uint32_t*)nullptr, v, n, 0, 0xFFu, (const unsigned long long*)d_start, ws.status.as<uint64_t>(),
-                           ws.ticket_ptr(e), e, ws.err_ptr(), g2, (const W*)nullptr, w, -1);
+        rs_gen_tile_docs(s, ws, g2, n, GT);  // (again, for this form's tiles)
+        rs_launch_pass_ordered<RsGen8, W>(s, ws, tiles8, nullptr, k, nullptr, v, n, 0, 0xFFu, d_start, g2, nullptr, w, -1);
+    } else {
+        rs_launch_pass_ordered<RsBig<>, W>(s, ws, gen_tiles, nullptr, k, nullptr, v, n, 0, 0xFFu, d_start, g2, nullptr, w, -1);
+    }
     prof.end(t, (std::string("rs_onesweep_textgen_records") + (sizeof(W) == 1 ? "_w8" : (sizeof(W) == 2 ? "_w16" : "_w32")) + "_t16384").c_str(),
              n * (1 + 8 + sizeof(W)), s);
     if (stats) stats->passes_run++;

@@ -1959,7 +1959,7 @@ void count_top_digits_aside(Index& ix, bool big, const Alphabet& al, TopCounts& 
     const int sigma = al.sigma;
     if (!(!big && sizeof(V) == 4 && n >= (1ull << 24) && ix.overlap_paircount && ix.msd_first && ix.msd_pair && ix.narrow_keys &&
           ix.fuse_keygen && ix.flags_in_last_pass && ix.initial_passes == 0 && ix.digit_bits == 0 && ix.key_coding != 1 && sigma + 1 <= 128 &&
-          (ix.sort_variant == 0 || ix.sort_variant == 31 || ix.sort_variant == 33) && rs_variant_has_gen(ix.sort_variant) && rs_atomic_rank_ok(s)))
+          rs_variant_big_atomic(ix.sort_variant, n) && rs_atomic_rank_ok(s)))
         return;
     if (!ix.aux_stream) CDB_HIP(hipStreamCreateWithFlags(&ix.aux_stream, hipStreamNonBlocking));
     for (hipEvent_t& e : ix.aux_ev)
@@ -2175,7 +2175,7 @@ DigitHist digit_histograms(Index& ix, bool big, const Alphabet& al, const KeyPla
     const bool dense = kp.dense;
     DigitHist dh;
     const bool fused = dh.fused = big || (ix.fuse_keygen && (dense || dbits == al.symbits) && nsym <= HC_MAXSYM &&
-                                          rs_variant_has_gen(ix.sort_variant));
+                                          rs_variant_production(ix.sort_variant));
     st.fused_keygen = fused ? 1 : 0;
     std::vector<uint64_t>& h_hist = dh.h_hist;
     // digit histograms of the dense keys, counted in one sweep over the text
@@ -2207,7 +2207,7 @@ DigitHist digit_histograms(Index& ix, bool big, const Alphabet& al, const KeyPla
     // one-atomic ranking, flags written by the last pass.  Only the TOP digit's histogram comes from the text sweep.
     const bool use_msd = dh.use_msd = fused && dense && !big && sizeof(V) == 4 && ix.narrow_keys && ix.msd_first && ix.flags_in_last_pass &&
                                       dbits == 8 && key_bits > 32 && key_bits <= 40 && rs_atomic_rank_ok(s) &&
-                                      ((ix.sort_variant == 0 && n >= (1ull << 23)) || ix.sort_variant == 31 || ix.sort_variant == 33);
+                                      rs_variant_big_atomic(ix.sort_variant, n);
     st.msd_first = use_msd ? 1 : 0;
     uint32_t& msd_span = dh.msd_span;
     if (use_msd && ix.msd_pair && nsym == 6 && kbase <= 128) {
@@ -2360,8 +2360,7 @@ InitialSort initial_sort_direct(Index& ix, const Alphabet& al, const KeyPlan& kp
             // per-tile counts of unresolved entries for the first compaction are counted on the way.
             SegFinalKeepArgs keep;
             DevBuf edges;
-            const bool want_keep = ix.flags_in_last_pass && dbits == 8 &&
-                                   (n >= (1ull << 23) || ix.sort_variant == 31 || ix.sort_variant == 33);  // (16 Ki-tile configurations)
+            const bool want_keep = ix.flags_in_last_pass && dbits == 8 && rs_variant_maybe_big_atomic(ix.sort_variant, n);  // (16 Ki-tile configurations)
             if (want_keep) {
                 const uint64_t nbt = ceil_div(n, (uint64_t)SC_TILE);
                 ix.scan_partials.ensure(scan_partials_slots(nbt) * sizeof(U2));
@@ -3301,6 +3300,7 @@ InitialSort initial_sort_bucketwise(Index& ix, Alphabet& al, const KeyPlan& kp, 
             int t = ix.prof.begin(s);
             br.sweep_base = rs_tile_bases(s, ix.tbw, al.d_tbc.as<uint32_t>(), al.tiles8, bk.d_src_col.as<uint16_t>(),
                                           (const unsigned long long*)d_slot_start.as<unsigned long long>());
+            // (a table of its own, not rs_gen_tile_docs: every bucket group reads it, and a generated pass in between rewrites the workspace's)
             br.sweep_doc.alloc(((size_t)al.tiles8 + 1) * sizeof(uint64_t));
             hipLaunchKernelGGL(rs_tiledoc_kernel, dim3((unsigned)ceil_div((uint64_t)al.tiles8 + 1, 256)), dim3(256), 0, s, doc_start, D, n,
                                (uint64_t)RS_SWEEP_TILE, (uint64_t)al.tiles8, br.sweep_doc.as<uint64_t>());

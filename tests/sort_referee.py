@@ -16,7 +16,8 @@ The contract:
   workspace    every executed pass takes the next epoch, 1..255; behind 255 the tags wrap and the next pass is epoch 1 again.
 
 CONFIGS is data about the contract under test (threads per workgroup, keys per thread of every kernel configuration), copied by
-hand from the switch statements of radix_sort() and radix_sort_split() — not an import from them.
+hand from the configuration block and the variant table of radix_sort.h (RsBig / RsMid / RsSmall and their ballot twins,
+RsKeyBig / RsKeySmall, RS_SPLIT_BIG_IPT; RS_VARIANT_*, rs_dispatch_variant) — not an import from them.
 """
 import numpy as np
 
