@@ -38,6 +38,7 @@ EXPORTS = [
     "cdb_filter", "cdb_rowset_free", "cdb_rowset_last_error", "cdb_rowset_size", "cdb_rowset_rows", "cdb_rowset_page", "cdb_rowset_cluster",
     "cdb_rowset_cluster_column", "cdb_rowset_get_stat", "cdb_debug_rowset_from_rows", "cdb_debug_rowset_set_option",
     "cdb_debug_rowset_profile_dump",
+    "cdb_debug_scan", "cdb_debug_scan_partials", "cdb_debug_stable_ranks",
 ]
 
 
@@ -1309,6 +1310,74 @@ def debug_radix_sort_split(d_keys_ptr, d_vals_ptr, d_aux_ptr, n, val_bytes, aux_
     if rc != 0:
         raise SortError("cdb_debug_radix_sort_split", rc)
     return _sort_result(r)
+
+
+SCAN_U64_ADD, SCAN_U64_MAX, SCAN_U2_ADD, SCAN_U2_SUMMAX, SCAN_DOCMAX, SCAN_FLAGS_ADD = range(6)
+
+
+class ScanError(RuntimeError):
+    """A scan hook failed; `status` is the CDB_E_* code of the error thrown inside the library."""
+
+    def __init__(self, what, status):
+        super().__init__(f"{what} failed ({status})")
+        self.status = status
+
+
+def _scan_item_shape(kind, n):
+    return (n,) if kind in (SCAN_U64_ADD, SCAN_U64_MAX) else (n, 2)
+
+
+def debug_scan(kind, items, device=-1):
+    """scan_totals + scan_apply as the library calls them (cdb_debug_scan).  items: uint64[n] for the two uint64 kinds, uint64[n, 2]
+    for the pair kinds, uint8[n] flag bytes for SCAN_FLAGS_ADD.  Returns (exclusive, inclusive, total) as uint64 arrays."""
+    lib = load_library()
+    lib.cdb_debug_scan.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    items = np.ascontiguousarray(items, dtype=np.uint8 if kind == SCAN_FLAGS_ADD else np.uint64)
+    n = items.shape[0]
+    if items.shape != ((n,) if kind == SCAN_FLAGS_ADD else _scan_item_shape(kind, n)):
+        raise ValueError(f"scan kind {kind}: items of shape {items.shape}")
+    ex = np.zeros(_scan_item_shape(kind, n), dtype=np.uint64)
+    inc = np.zeros_like(ex)
+    total = np.zeros(_scan_item_shape(kind, 1)[1:], dtype=np.uint64)
+    rc = lib.cdb_debug_scan(device, kind, items.ctypes.data if n else None, n, ex.ctypes.data if n else None,
+                            inc.ctypes.data if n else None, total.ctypes.data)
+    if rc != 0:
+        raise ScanError("cdb_debug_scan", rc)
+    return ex, inc, total
+
+
+def debug_scan_partials(kind, sums, guard_words=64, device=-1):
+    """scan_partials_inplace over raw tile sums (cdb_debug_scan_partials; kinds 0..4, items as for debug_scan).  Returns
+    (exclusive prefixes [nb], grand total, guard intact)."""
+    lib = load_library()
+    lib.cdb_debug_scan_partials.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_int)]
+    sums = np.ascontiguousarray(sums, dtype=np.uint64)
+    nb = sums.shape[0]
+    if kind == SCAN_FLAGS_ADD or sums.shape != _scan_item_shape(kind, nb):
+        raise ValueError(f"scan kind {kind}: sums of shape {sums.shape}")
+    buf = np.zeros(_scan_item_shape(kind, nb + 1), dtype=np.uint64)
+    buf[:nb] = sums
+    ok = C.c_int(0)
+    rc = lib.cdb_debug_scan_partials(device, kind, buf.ctypes.data, nb, guard_words, C.byref(ok))
+    if rc != 0:
+        raise ScanError("cdb_debug_scan_partials", rc)
+    return buf[:nb], buf[nb], bool(ok.value)
+
+
+def debug_stable_ranks(flags, device=-1):
+    """tile_bases + TileRanker over flag bytes (cdb_debug_stable_ranks).  Returns (flagged slots in front of every slot [n], in
+    front of every tile of 4096 slots, the total tile_bases returned)."""
+    lib = load_library()
+    lib.cdb_debug_stable_ranks.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    flags = np.ascontiguousarray(flags, dtype=np.uint8)
+    n = flags.shape[0]
+    before = np.zeros(n, dtype=np.uint64)
+    tile_base = np.zeros(max((n + 4095) // 4096, 1), dtype=np.uint64)
+    total = C.c_uint64(0)
+    rc = lib.cdb_debug_stable_ranks(device, flags.ctypes.data, n, before.ctypes.data, tile_base.ctypes.data, C.byref(total))
+    if rc != 0:
+        raise ScanError("cdb_debug_stable_ranks", rc)
+    return before, tile_base[:(n + 4095) // 4096], total.value
 
 
 def layout_rule(ndocs, longest):

@@ -331,9 +331,7 @@ __global__ __launch_bounds__(256) void q_search_fast_kernel(SearchArgs<V> a, con
     }
 }
 
-struct OpSumMax {  // (a, b) = (sum, max)
-    __device__ __forceinline__ U2 operator()(const U2& x, const U2& y) const { return U2{x.a + y.a, x.b > y.b ? x.b : y.b}; }
-};
+// (OpSumMax: scan.h)
 struct HitsIn2 {
     const uint64_t* hits;
     __device__ __forceinline__ U2 operator()(uint64_t j) const { return U2{hits[j], hits[j]}; }
@@ -749,14 +747,7 @@ __global__ __launch_bounds__(256) void q_scan_occ_kernel(const uint8_t* __restri
     }
 }
 
-struct DocMax {  // (document, running maximum of occurrence ends) — segmented max
-    uint64_t doc, mx;
-};
-struct OpDocMax {
-    __device__ __forceinline__ DocMax operator()(const DocMax& a, const DocMax& b) const {
-        return DocMax{b.doc, a.doc == b.doc ? (a.mx > b.mx ? a.mx : b.mx) : b.mx};
-    }
-};
+// (DocMax / OpDocMax, the segmented max of the span scan: scan.h)
 struct OccIn {
     const uint64_t* keys;
     const uint64_t* ends;

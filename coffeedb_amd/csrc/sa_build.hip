@@ -1143,28 +1143,7 @@ __global__ __launch_bounds__(256) void sa_assemble_entries_kernel(const uint32_t
     if (i < cnt) out[i] = ((uint64_t)((uint32_t)low[i] >> hi_shift) << 32) | (uint64_t)elo[i];
 }
 
-struct FlagIn {
-    const uint8_t* flags;
-    static __device__ __forceinline__ U2 decode(uint32_t f) {
-        const uint64_t u = (f >> 1) & 1u;
-        return U2{u, u & (uint64_t)(f & 1u)};
-    }
-    __device__ __forceinline__ U2 operator()(uint64_t i) const { return decode(flags[i]); }
-    // a thread's 16 consecutive flag bytes in one load (tiles start at multiples of 16; the flag array
-    // is a library allocation, so it is 16-byte aligned)
-    __device__ __forceinline__ void load8(uint64_t base, uint64_t n, const U2& identity, U2 (&v)[SC_IPT]) const {
-        static_assert(SC_IPT == 16, "flag loader assumes 16 items per thread");
-        if (base + 16 <= n) {
-            const uint4 w = *reinterpret_cast<const uint4*>(flags + base);
-            const uint32_t x[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v[k] = decode((x[k >> 2] >> (8 * (k & 3))) & 0xFFu);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v[k] = base + k < n ? decode(flags[base + k]) : identity;
-        }
-    }
-};
+// (FlagIn, the group flags as scan input with their 16-byte loader: scan.h)
 
 // compaction of the unresolved entries + construction of their sort keys
 // compaction of the unresolved entries: slot number, entry and group id of every unresolved entry
@@ -2618,14 +2597,8 @@ void choose_record_form(Index& ix, const Alphabet& al, const KeyPlan& kp, const 
             if (best_b && (ix.vl_keys != 2 || (shorter && best < 0.93 * cost_fixed))) {
                 vl_bits = best_b;
                 bbits = vl_bits;
-                std::vector<uint16_t> sym(256, 0), dec(128, (uint16_t)(0xFFu | ((unsigned)vlc.end_len << 8)));
-                for (int c = 0; c <= sigma; ++c) {
-                    sym[c] = (uint16_t)(vlc.bits[c] | ((unsigned)vlc.len[c] << 8));
-                    if (c == 0) continue;
-                    const int l = vlc.len[c];
-                    for (unsigned x = 0; x < (1u << (VL_MAX_LEN - l)); ++x)
-                        dec[((unsigned)vlc.bits[c] << (VL_MAX_LEN - l)) | x] = (uint16_t)(bk.h_slotmap[c] | ((unsigned)l << 8));
-                }
+                std::vector<uint16_t> sym(256), dec(128);
+                vl_fill_tables(vlc, bk.h_slotmap, sigma, sym.data(), dec.data());
                 rf.d_vl_sym.alloc(256 * sizeof(uint16_t));
                 rf.d_vl_dec.alloc(128 * sizeof(uint16_t));
                 CDB_HIP(hipMemcpyAsync(rf.d_vl_sym.p, sym.data(), 256 * sizeof(uint16_t), hipMemcpyHostToDevice, s));

@@ -23,6 +23,18 @@ struct U2 {
     uint64_t a, b;
     __host__ __device__ U2 operator+(const U2& o) const { return U2{a + o.a, b + o.b}; }
 };
+// (the operators of query.hip's offset and span scans live here so that the scan's test hook, debug_scan.hip, runs them themselves)
+struct OpSumMax {  // (a, b) = (sum, max)
+    __device__ __forceinline__ U2 operator()(const U2& x, const U2& y) const { return U2{x.a + y.a, x.b > y.b ? x.b : y.b}; }
+};
+struct DocMax {  // (document, running maximum of occurrence ends) — segmented max
+    uint64_t doc, mx;
+};
+struct OpDocMax {
+    __device__ __forceinline__ DocMax operator()(const DocMax& a, const DocMax& b) const {
+        return DocMax{b.doc, a.doc == b.doc ? (a.mx > b.mx ? a.mx : b.mx) : b.mx};
+    }
+};
 
 // 64-bit-safe lane shuffle for trivially copyable T (built from 32-bit DPP/bpermute moves)
 template <typename T>
@@ -69,6 +81,30 @@ __device__ __forceinline__ void scan_load8(const In& in, uint64_t base, uint64_t
 #pragma unroll
     for (int k = 0; k < SC_IPT; ++k) v[k] = base + k < n ? in(base + k) : identity;
 }
+
+// the group flags of the suffix-array build (sa_build.hip) as scan input: the one functor with a load8
+struct FlagIn {
+    const uint8_t* flags;
+    static __device__ __forceinline__ U2 decode(uint32_t f) {
+        const uint64_t u = (f >> 1) & 1u;
+        return U2{u, u & (uint64_t)(f & 1u)};
+    }
+    __device__ __forceinline__ U2 operator()(uint64_t i) const { return decode(flags[i]); }
+    // a thread's 16 consecutive flag bytes in one load (tiles start at multiples of 16; the flag array
+    // is a library allocation, so it is 16-byte aligned)
+    __device__ __forceinline__ void load8(uint64_t base, uint64_t n, const U2& identity, U2 (&v)[SC_IPT]) const {
+        static_assert(SC_IPT == 16, "flag loader assumes 16 items per thread");
+        if (base + 16 <= n) {
+            const uint4 w = *reinterpret_cast<const uint4*>(flags + base);
+            const uint32_t x[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = decode((x[k >> 2] >> (8 * (k & 3))) & 0xFFu);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = base + k < n ? decode(flags[base + k]) : identity;
+        }
+    }
+};
 
 template <typename T, typename In, typename Op>
 __global__ __launch_bounds__(SC_NT) void scan_reduce_kernel(In in, uint64_t n, Op op, T identity, T* partials) {

@@ -16,8 +16,10 @@
 // continuation.  reference: the keys are the radix-node symbols of src/index.cpp:96-126 / src/index.h:66-73 under another
 // order-preserving coding; DESIGN.md §4.2 "Variable-length keys".
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 namespace cdb {
@@ -143,6 +145,22 @@ inline bool vl_build(const uint64_t* counts, int sigma, VlCode& out) {
     }
     out.rate = std::log2(lo);
     return true;
+}
+
+// The two tables the records sweep reads (records_sweep.h), from a code of vl_build over sigma symbols.  sym[c] = the word of symbol
+// code c (0 = END) in the low byte, its length in the high byte; codes above sigma stay 0.  dec[w], for every window w of VL_MAX_LEN
+// code bits = the symbol whose word starts it: its bucket slot slot_of_code[c] in the low byte, the word's length in the high byte.
+// Windows that start with END's word keep 0xFF beside END's length (the end of a document has no bucket slot).
+inline void vl_fill_tables(const VlCode& code, const uint8_t* slot_of_code, int sigma, uint16_t sym[256], uint16_t dec[1 << VL_MAX_LEN]) {
+    for (int c = 0; c < 256; ++c) sym[c] = 0;
+    for (int w = 0; w < (1 << VL_MAX_LEN); ++w) dec[w] = (uint16_t)(0xFFu | ((unsigned)code.end_len << 8));
+    for (int c = 0; c <= sigma; ++c) {
+        sym[c] = (uint16_t)(code.bits[c] | ((unsigned)code.len[c] << 8));
+        if (c == 0) continue;
+        const int l = code.len[c];
+        for (unsigned x = 0; x < (1u << (VL_MAX_LEN - l)); ++x)
+            dec[((unsigned)code.bits[c] << (VL_MAX_LEN - l)) | x] = (uint16_t)(slot_of_code[c] | ((unsigned)l << 8));
+    }
 }
 
 }  // namespace cdb

@@ -698,6 +698,28 @@ int cdb_debug_radix_sort_ex(int device, cdb_debug_sort_ws* ws, void* d_keys, voi
 int cdb_debug_radix_sort_split(int device, cdb_debug_sort_ws* ws, void* d_keys, void* d_vals, void* d_aux, uint64_t n, int val_bytes,
                                int aux_bytes, int hi_bits, int lead_digits, int variant, unsigned flags, cdb_debug_sort_result* out);
 
+/* Test hooks for the device-wide scan (scan.h) and the stable tile ranks (stable_tiles.h), called the way the library itself calls
+ * them (tests/test_gpu_scan_edges.py; debug_scan.hip).  Not part of the stable ABI.  Every array lies in HOST memory; an item is a
+ * uint64_t, or for the pair kinds two uint64_t (16 bytes: U2 = (a, b), DocMax = (document, maximum)).  kind = the value type and
+ * operator of a production instantiation: */
+#define CDB_DEBUG_SCAN_U64_ADD 0    /* uint64_t, sum modulo 2^64, identity 0 */
+#define CDB_DEBUG_SCAN_U64_MAX 1    /* uint64_t, maximum, identity 0 */
+#define CDB_DEBUG_SCAN_U2_ADD 2     /* pairs, both halves summed, identity (0, 0) */
+#define CDB_DEBUG_SCAN_U2_SUMMAX 3  /* pairs, (sum, maximum), identity (0, 0) */
+#define CDB_DEBUG_SCAN_DOCMAX 4     /* pairs, maximum inside runs of equal documents; {~0, 0} is a LEFT identity only */
+#define CDB_DEBUG_SCAN_FLAGS_ADD 5  /* input = n flag BYTES f read 16 at a time, item = (f >> 1 & 1, f >> 1 & f & 1), summed as pairs */
+/* scan_totals then scan_apply over n items: out_exclusive[i] = fold of items [0, i), out_inclusive[i] = fold of items [0, i],
+ * *out_total = what scan_totals returned (the fold of everything, begun from the identity).  n = 0 is legal. */
+int cdb_debug_scan(int device, int kind, const void* in, uint64_t n, void* out_exclusive, void* out_inclusive, void* out_total);
+/* scan_partials_inplace over nb raw tile sums (kinds 0..4), in a device block of exactly the elements scan_totals reserves for nb
+ * tiles with guard_words poisoned elements behind them.  partials_inout[nb + 1]: the sums in; their exclusive prefixes and, in slot
+ * nb, the grand total out.  *out_guard_ok = 1 when the poison is untouched. */
+int cdb_debug_scan_partials(int device, int kind, void* partials_inout, uint64_t nb, uint64_t guard_words, int* out_guard_ok);
+/* tile_bases + TileRanker over n >= 1 flag bytes (non-zero = flagged; n = 0: CDB_E_INVALID): out_before[i] = flagged slots in front
+ * of slot i, for every slot; out_tile_base[t] = flagged slots in front of tile t of 4096 slots (ceil(n / 4096) entries); *out_total =
+ * what tile_bases returned. */
+int cdb_debug_stable_ranks(int device, const uint8_t* flags, uint64_t n, uint64_t* out_before, uint64_t* out_tile_base, uint64_t* out_total);
+
 /* Measurement hook: wall time of `reps` back-to-back cdb_query calls for each of `nkw` keywords (blob + offsets like
  * cdb_query_batch), taken inside the library with a steady clock — what a C++ caller such as database.cpp:392 sees,
  * without a language binding in between.  us_out[nkw] receives the MEDIAN microseconds per call of every keyword;
