@@ -325,6 +325,11 @@ struct SegFinalArgs : SegArgs {
     int low_bits = 0;           // key = (k32 << low_bits) | (aux & (2^low_bits - 1))
     uint32_t kbase = 2;
     unsigned long long kmagic = 0;
+    // carried bits (records_sweep.h: VlTables::carry): the aux word may hold code-stream bits above the entry's high bits; they
+    // leave in bits 2.. of the flag byte, and the entry takes the aux high part masked to its real width
+    uint32_t hi_mask = 0xFFFFFFFFu;  // entry bits 32.. = (aux >> hi_shift) & hi_mask
+    uint32_t carry_mask = 0;         // flag byte = f | ((aux >> carry_shift) & carry_mask) << 2
+    int carry_shift = 0;
 };
 
 // The last pass of an ordinary (single-segment) sort of split records can do the same and still write its records (the
@@ -1190,6 +1195,7 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::MINW) void rs_onesweep_kernel(
                         if (!exhausted) f |= 2u;
                     }
                     if constexpr (FINAL) {
+                        f |= (((uint32_t)s_aux[HAS_W ? i : 0] >> seg.carry_shift) & seg.carry_mask) << 2;
                         if (!(RS_SEG_ABL & 1)) seg.flags[rs_seg_rotated(si, s_gbase[dd] + i)] = (uint8_t)f;
                         continue;
                     } else {
@@ -1234,7 +1240,7 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::MINW) void rs_onesweep_kernel(
             if constexpr (FINAL) {
                 if (i < valid && !(RS_SEG_ABL & 2)) {
                     const unsigned long long slot = rs_seg_rotated(si, s_gbase[dig[j]] + i);
-                    const uint32_t hi32 = (uint32_t)s_aux[HAS_W ? i : 0] >> seg.hi_shift;
+                    const uint32_t hi32 = ((uint32_t)s_aux[HAS_W ? i : 0] >> seg.hi_shift) & seg.hi_mask;
                     if (seg.elo) {  // (uniform) 5 bytes per entry instead of 8
                         seg.elo[slot] = (uint32_t)s_vals[i];
                         seg.ehi[slot] = (uint8_t)hi32;

@@ -18,6 +18,7 @@
 // restated as dense numbers per first-symbol bucket; DESIGN.md §4.2.
 #pragma once
 #include "radix_sort.h"
+#include "vl_code.h"
 
 namespace cdb {
 
@@ -365,6 +366,8 @@ struct VlTables {
     const uint16_t* dec = nullptr;  // [128] the next 7 stream bits -> bucket slot | length << 8 of the code word that starts there
     int key_bits = 0;               // B (whole key incl. the "continues" bit)
     int end_len = 0;                // length of END's (all-zero) word
+    int carry = 0;                  // X: stream bits behind the key that ride in the aux word above the entry's high bits (0 = none)
+    int carry_shift = 0;            // ... at this bit of the aux word (rec_low_bits + the entry's bits above 32)
 };
 constexpr uint32_t RS_VL_BITW = ((RS_GEN8_TILE + RS_GEN_LOOK) * 7 + 31) / 32 + 4;  // words of the tile's bit stream
 
@@ -598,7 +601,8 @@ __global__ __launch_bounds__(512, 6) void rs_sweep_records_vl_kernel(TextGen gen
 
     // ---- phase B: the kept positions in output order
     const int KB1 = vl.key_bits - 1;  // code bits of a key
-    const uint64_t lmask = (1ull << gen.rec_low_bits) - 1ull;
+    const int CX = vl.carry, KBX = KB1 + CX;  // carried bits (0: the records are exactly those of a build without them)
+    const uint64_t lmask = (1ull << gen.rec_low_bits) - 1ull, cmask = (1ull << CX) - 1ull;
     auto emit = [&](uint32_t p, uint32_t li, uint64_t e64, uint32_t endbit) {
         // 64 stream bits at the position's offset: its own code word (<= 7 bits: slot and length from the table), then the key
         const uint32_t o0 = s_boff[li];
@@ -609,14 +613,18 @@ __global__ __launch_bounds__(512, 6) void rs_sweep_records_vl_kernel(TextGen gen
         const uint32_t dv = s_dec[(uint32_t)(top >> 57)];
         const uint32_t sl = dv & 0xFFu, len = dv >> 8;
         const uint32_t avail = endbit - (o0 + len);  // code bits between the bucket symbol and the end of the document
-        const uint32_t take = avail < (uint32_t)KB1 ? avail : (uint32_t)KB1;
-        uint64_t kb = (top << len) >> (64 - KB1);                   // the next KB1 stream bits
-        kb &= ~0ull << ((uint32_t)KB1 - take);                      // ... of which the document holds `take`: zeros behind its end
+        // the key's KB1 bits and the CX carried bits behind them in one piece (len + KB1 + CX <= 64: the host caps CX; the
+        // look-ahead of RS_GEN_LOOK = 64 symbols stages at least 64 stream bits behind every position of the tile)
+        const uint32_t take = avail < (uint32_t)KBX ? avail : (uint32_t)KBX;
+        uint64_t kbx = (top << len) >> (64 - KBX);                  // the next KB1 + CX stream bits
+        kbx &= ~0ull << ((uint32_t)KBX - take);                     // ... of which the document holds `take`: zeros behind its end
+        const uint64_t kb = kbx >> CX;
         const uint64_t key = (kb << 1) | (uint64_t)(avail + (uint32_t)vl.end_len > (uint32_t)KB1 ? 1u : 0u);
         const uint64_t dst = s_gbase[sl] + (uint64_t)p;
         kout[dst] = (uint32_t)(key >> gen.rec_low_bits);
         vout[dst] = (uint32_t)e64;
-        wout[dst] = (W)((key & lmask) | ((e64 >> 32) << gen.rec_low_bits));
+        // (the carried bits sit above the entry's high bits: digit_of, rs_seg_hist and the flag compare read aux through masks)
+        wout[dst] = (W)((key & lmask) | ((e64 >> 32) << gen.rec_low_bits) | ((kbx & cmask) << vl.carry_shift));
     };
     if (docs_in_lds && s_flag == 0 && valid == (uint32_t)TILE) {
         const int bits = gen.bits;
@@ -971,6 +979,9 @@ void radix_sweep_records_vl(hipStream_t s, Profiler& prof, uint32_t* k, uint32_t
                             SortStats* stats) {
     if (!gen_in.tile_base || !gen_in.tile_doc || !d_codeslot || !vl.sym || !vl.dec) throw InternalError("radix_sweep_records_vl: tables missing (internal)");
     if (vl.key_bits < 16 || vl.key_bits > 56) throw InternalError("radix_sweep_records_vl: key width (internal)");
+    // (a position's 64 stream bits hold its own code word, the key's bits and the carried ones; the aux word holds them all)
+    if (vl.carry < 0 || VL_MAX_LEN + vl.key_bits - 1 + vl.carry > 64 || (vl.carry && vl.carry_shift + vl.carry > 8 * (int)sizeof(W)))
+        throw InternalError("radix_sweep_records_vl: carried bits (internal)");
     const uint32_t tiles8 = (uint32_t)ceil_div(n, (uint64_t)RS_SWEEP_TILE);
     const uint32_t grid = (uint32_t)(ceil_div(tiles8, 8u * RS_GROUP) * 8u * RS_GROUP);
     CDB_HIP(hipMemsetAsync(d_hist_out, 0, (size_t)nseg * 8 * 256 * sizeof(uint64_t), s));

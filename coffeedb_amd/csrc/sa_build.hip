@@ -1166,6 +1166,26 @@ struct CompactOut {
     }
 };
 
+// The compaction of the CARRIED round (refine_groups): the minor key is complete at once — the code-stream bits the initial sort
+// left in bits 2.. of the entry's flag byte (the sweep has just read that byte: the line is hot), so no sa_round_keys launch follows.
+template <typename SAW, typename I>
+struct CompactCarriedOut {
+    using V = typename SAW::val;
+    SAW sa;
+    const uint8_t* flags;
+    I* U;
+    uint64_t* skey;
+    V* sval;
+    int kbits;  // = carried bits
+    __device__ __forceinline__ void operator()(uint64_t i, const U2& ex, const U2& in) const {
+        if (in.a == ex.a) return;  // not an unresolved entry
+        const uint64_t j = ex.a;
+        U[j] = (I)i;
+        skey[j] = ((in.b - 1) << kbits) | (uint64_t)(((uint32_t)flags[i] >> 2) & ((1u << kbits) - 1u));
+        sval[j] = sa.load(i);
+    }
+};
+
 // The same compaction from the PREVIOUS round's list (text-extension rounds behind the first): only entries of that list can still be
 // open, and sa_update left their new flag bytes in list order (`lf`), so the wave-autonomous flag sweeps run over m bytes instead of
 // the array's n, and the entries come from the sorted list instead of a gather through the suffix array.
@@ -1454,7 +1474,10 @@ __global__ __launch_bounds__(256) void sa_newhead_kernel(const uint64_t* __restr
     nh[j] = (uint8_t)(oldhead || j == 0 || skey[j] != skey[j - 1]);
 }
 
-template <typename SAW, typename I, bool WANT_POS = true>
+// CARRIED: the write-back of the carried round (refine_groups) — its depth is a number of code bits, not of symbols, so "the
+// suffix ends inside the compared prefix" is not tested: a group of several stays open and the text round behind it closes it
+// (no gather from the document table at all)
+template <typename SAW, typename I, bool WANT_POS = true, bool CARRIED = false>
 __device__ __forceinline__ void sa_place(uint64_t j, uint64_t m, const typename SAW::val* sval, const I* U, const uint8_t* nh,
                                          const uint64_t* doc_start, int bits, uint64_t mask, uint64_t hnew, SAW sa,
                                          uint8_t* flags, uint64_t& ext_pos, unsigned long long* still_open,
@@ -1469,7 +1492,7 @@ __device__ __forceinline__ void sa_place(uint64_t j, uint64_t m, const typename 
     //  document table are the kernel's only gathers — skipped unless the caller wants the entry's text position)
     uint64_t ds = 0;
     bool exhausted = false;
-    if (WANT_POS || !(head && last)) {
+    if (!CARRIED && (WANT_POS || !(head && last))) {
         ds = doc_start[d];
         exhausted = doc_start[d + 1] - ds - off < hnew;
     }
@@ -1477,11 +1500,13 @@ __device__ __forceinline__ void sa_place(uint64_t j, uint64_t m, const typename 
     sa.store(i, v);
     flags[i] = (uint8_t)((head ? 1 : 0) | (open ? 2 : 0));
     if (lf) lf[j] = (uint8_t)((head ? 1 : 0) | (open ? 2 : 0));  // (the same byte in list order: the next round compacts from the list)
-    if (open) atomicAdd(still_open, 1ull);  // the compiler folds this into one add per wave
+    // (the carried round leaves a share of its entries open — millions of adds to one address — and its successor counts its
+    //  list anyway: not counted there)
+    if (!CARRIED && open) atomicAdd(still_open, 1ull);  // the compiler folds this into one add per wave
     ext_pos = ds + d + off;
 }
 
-template <typename SAW, typename I>
+template <typename SAW, typename I, bool CARRIED = false>
 __global__ __launch_bounds__(256) void sa_update_kernel(const typename SAW::val* __restrict__ sval, const I* __restrict__ U,
                                                         const uint8_t* __restrict__ nh, uint64_t m,
                                                         const uint64_t* __restrict__ doc_start, int bits,
@@ -1492,7 +1517,7 @@ __global__ __launch_bounds__(256) void sa_update_kernel(const typename SAW::val*
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
     uint64_t q;
-    sa_place<SAW, I, false>(j, m, sval, U, nh, doc_start, bits, mask, hnew, sa, flags, q, still_open, hcov, h_add, lf);
+    sa_place<SAW, I, false, CARRIED>(j, m, sval, U, nh, doc_start, bits, mask, hnew, sa, flags, q, still_open, hcov, h_add, lf);
 }
 
 template <typename I>
@@ -2287,6 +2312,7 @@ struct InitialSort {
     uint64_t refine_depth0 = 0;  // symbols every key of the initial sort covers for certain (0: nsym; variable-length keys: fewer)
     DevBuf d_vl_bytelen;         // variable-length keys: text byte -> code-word length (the refinement recovers every group's exact depth)
     uint32_t vl_kb1 = 0;
+    uint32_t carry = 0;          // carried bits: the next `carry` code-stream bits behind the key sit in bits 2.. of every flag byte
 };
 
 // builds below 2^32: one radix sort of every suffix's key, then the group flags
@@ -2814,6 +2840,19 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
         const int blow = rf.blow, bpass = br.bpass, lowb = br.lowb, recb = br.recb;
         const bool fuse_rec = rf.fuse_rec, sweep_rec = rf.sweep_rec, sweep_fused = rf.sweep_fused, tile_bytes = al.tile_bytes;
         const bool pack_seg = rf.pack_E;
+        // carried bits: entries narrower than the 8 bits the aux word keeps for their top leave room there, and a position's 64
+        // stream bits hold more than its own word and the key — the sweep writes the next bits of the code stream into that room,
+        // the last pass hands them on in bits 2.. of the flag byte, and the refinement's first round sorts the tied groups on them
+        // without reading the text (refine_groups: the carried round).  Only here: variable-length keys, the sweep, this last pass.
+        const int ehb = std::max(0, (int)ix.bits + ix.off_bits - 32);  // entry bits above 32
+        int carry = 0;
+        if (rf.vl_bits && (sweep_rec || sweep_fused)) {
+            carry = std::min({8 - ehb, 6, 64 - VL_MAX_LEN - (rf.vl_bits - 1)});
+            if (ix.carried_bits >= 0) carry = std::min(carry, ix.carried_bits);
+            carry = std::max(carry, 0);
+        }
+        out.carry = (uint32_t)carry;
+        st.carried_key_bits = carry;
         std::vector<Depth1Fold>& depth1 = out.depth1;
         struct Group {
             uint32_t b0, b1, tiles, cells;
@@ -2932,6 +2971,8 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
                     vt.dec = rf.d_vl_dec.as<uint16_t>();
                     vt.key_bits = rf.vl_bits;
                     vt.end_len = rf.vlc.end_len;
+                    vt.carry = carry;
+                    vt.carry_shift = blow + ehb;
                     radix_sweep_records_vl<W>(s, ix.prof, kbp[0], ebp[0], wb[0].as<W>(), n, rg, (const uint16_t*)br.d_codeslot.as<uint16_t>(), vt,
                                               g.b0, g.b1, g.gstart, g.elems, (const uint32_t*)tile_seg.as<uint32_t>(),
                                               (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, lowb, bpass,
@@ -2986,6 +3027,11 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
             fin.low_bits = blow;
             fin.kbase = br.fbase;
             fin.kmagic = br.bmagic;
+            if (carry) {
+                fin.hi_mask = (1u << ehb) - 1u;
+                fin.carry_mask = (1u << carry) - 1u;
+                fin.carry_shift = blow + ehb;
+            }
             radix_sort_segmented<W>(s, ix.rws, ix.prof, kbp[0], kbp[1], ebp[0], ebp[1], wb[0].as<W>(), wb[1].as<W>(), g.elems,
                                     (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), (const uint32_t*)tile_seg.as<uint32_t>(), gb,
                                     g.tiles, (const unsigned long long*)d_bh2.as<unsigned long long>(),
@@ -3186,6 +3232,9 @@ InitialSort initial_sort_bucketwise(Index& ix, Alphabet& al, const KeyPlan& kp, 
     InitialSort out;
     TextGen gen{text, doc_start, al.d_symmap.as<uint16_t>(), D, (int)ix.bits, kbase, nsym, 0, ix.text_padded};
     double ta = now_ms();
+    // flag byte of slot i: bit 0 = first of a group of equal keys, bit 1 = the group is still unresolved, bits 2..7 = the carried
+    // bits of the entry the initial sort put there (run_segmented; zero without them).  The refinement rewrites bits 0..1 only
+    // where a round touches a slot — as a whole byte, so bits 2.. are then zero — and every reader masks bits 0 and 1.
     out.flags.alloc(n);
     DevBuf E, KT[2], ET;  // (E: allocated below, once it is known whether the entries are partitioned at all)
     const int top_shift = (nsym - 1) * symbits;
@@ -3466,13 +3515,23 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
     int list_rs = 0;
     d_gs_state.alloc(2 * sizeof(unsigned long long));
     bool group_sort_on = ix.group_sort;
-    for (;;) {
-        if (st.rounds > 0) {
+    // The carried round: where the initial sort left `carry` more code-stream bits of every entry in its flag byte (run_segmented),
+    // the first round sorts the tied groups on those bits — a round like any other (compaction, sort inside the groups, new heads,
+    // write-back, list) without one read of the text.  It counts in carried_rounds only: rounds, ext_rounds, list_rounds and
+    // group_sorts, and the limits of the text-or-doubling rule below, see the text and doubling rounds alone.
+    const uint32_t carry = is.carry;
+    bool carried_pending = carry > 0, list_is_carried = false;
+    uint32_t kb_shared = vl_kb1;  // code bits every member of a group shares (equal bits decode alike: where hcov starts)
+    st.carried_rounds = 0;
+    for (uint32_t iter = 0;; ++iter) {
+        if (iter > 0 && !list_is_carried) {  // (the carried round does not count its open entries: the flag count below does)
             uint64_t still = 0;
             CDB_HIP(hipMemcpyAsync(&still, d_open.p, sizeof(still), hipMemcpyDeviceToHost, s));
             CDB_HIP(hipStreamSynchronize(s));
             if (still == 0) break;
         }
+        const bool carried = carried_pending;
+        carried_pending = false;
         CDB_HIP(hipMemsetAsync(d_open.p, 0, sizeof(uint64_t), s));
         auto flag_tile_sums = [&]() {  // raw tile sums of the flag array into the scan's partials (wave-autonomous sweep)
             const uint64_t nb = ceil_div(n, SC_TILE);
@@ -3497,14 +3556,15 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
         U2 tot = scan_totals_from_partials<U2>(s, ix.scan_partials, from_list ? m_list : n, OpAdd{}, U2{0, 0});
         is.tile_sums_ready = false;
         uint64_t m = tot.a, G = tot.b;
-        if (st.rounds == 0) st.unresolved_initial = m;
+        if (iter == 0) st.unresolved_initial = st.unresolved_after_carried = m;
+        if (list_is_carried) st.unresolved_after_carried = m;
         st.unresolved_max = std::max(st.unresolved_max, m);
         if (m == 0) break;
         // (the per-entry kernels of a round address one thread per unresolved entry: a launch holds < 2^32 of them)
         if (m >= (1ull << 32) - 4096) throw InternalError("too many unresolved suffixes for one refinement round (internal limit: 2^32)");
         const int gbits = bit_width64(G - 1);
         int nsym2 = std::min((64 - gbits) / symbits, KG_LOOK);
-        if (!isa) {
+        if (!isa && !carried) {
             // Re-keying m suffixes from the text costs ~ m x (one random line + a sort); the inverse array of prefix
             // doubling costs n random writes before its first round.  Text extension therefore gets up to four
             // rounds while few suffixes are open, and two rounds even for a larger share (e.g. Zipf text, 5 % open
@@ -3529,7 +3589,7 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
                 (void)scan_totals_from_partials<U2>(s, ix.scan_partials, n, OpAdd{}, U2{0, 0});
             }
         }
-        const int kbits = isa ? bit_width64(n) : nsym2 * symbits;
+        const int kbits = carried ? (int)carry : (isa ? bit_width64(n) : nsym2 * symbits);
         if (kbits + gbits > 64) throw InternalError("refinement key does not fit 64 bits (internal limit)");
         if (m > cap) {
             cap = m;
@@ -3556,14 +3616,21 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
                                    dim3(256), 0, s, (const uint8_t*)lf.as<uint8_t>(), m_list, (uint64_t)ceil_div(m_list, SC_TILE),
                                    (const U2*)ix.scan_partials.as<U2>(), co);
                 std::swap(U, U2b);
-                st.list_rounds++;
+                if (!list_is_carried) st.list_rounds++;
+            } else if (carried) {
+                CompactCarriedOut<SAW, I> co{sa, (const uint8_t*)flags.as<uint8_t>(), U.as<I>(), skey[0].as<uint64_t>(), sval[0].as<V>(), kbits};
+                hipLaunchKernelGGL((sa_flag_compact_kernel<decltype(co)>), dim3((unsigned)ceil_div(ceil_div(n, SC_TILE), (uint64_t)(4 * FC_TILES_PER_WAVE))),
+                                   dim3(256), 0, s, (const uint8_t*)flags.as<uint8_t>(), n, (uint64_t)ceil_div(n, SC_TILE),
+                                   (const U2*)ix.scan_partials.as<U2>(), co);
             } else {
             CompactOut<SAW, I> co{sa, U.as<I>(), skey[0].as<uint64_t>(), sval[0].as<V>(), kbits};
             hipLaunchKernelGGL((sa_flag_compact_kernel<decltype(co)>), dim3((unsigned)ceil_div(ceil_div(n, SC_TILE), (uint64_t)(4 * FC_TILES_PER_WAVE))),
                                dim3(256), 0, s, (const uint8_t*)flags.as<uint8_t>(), n, (uint64_t)ceil_div(n, SC_TILE),
                                (const U2*)ix.scan_partials.as<U2>(), co);
             }
-            if (isa)
+            if (carried) {
+                // (the minor keys are complete: no sa_round_keys launch)
+            } else if (isa)
                 hipLaunchKernelGGL((sa_round_keys_kernel<V, R, true>), dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, s,
                                    (const V*)sval[0].as<V>(), m, doc_start, text, (const uint16_t*)al.d_symmap.as<uint16_t>(),
                                    (const R*)rank.as<R>(), (int)ix.bits, ix.mask, h, nsym2, symbits, skey[0].as<uint64_t>(), n);
@@ -3571,7 +3638,7 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
                 hipLaunchKernelGGL((sa_round_keys_kernel<V, R, false>), dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, s,
                                    (const V*)sval[0].as<V>(), m, doc_start, text, (const uint16_t*)al.d_symmap.as<uint16_t>(),
                                    (const R*)nullptr, (int)ix.bits, ix.mask, h, nsym2, symbits, skey[0].as<uint64_t>(), n,
-                                   vl_kb1 ? (const uint8_t*)is.d_vl_bytelen.as<uint8_t>() : nullptr, vl_kb1, h_acc, vl_kb1 ? hcov.as<uint8_t>() : nullptr);
+                                   vl_kb1 ? (const uint8_t*)is.d_vl_bytelen.as<uint8_t>() : nullptr, kb_shared, h_acc, vl_kb1 ? hcov.as<uint8_t>() : nullptr);
             ix.prof.end(t, "sa_compact", n + m * (sizeof(I) + 8 + 2 * sizeof(V)), s);
         }
         int rs = -1;
@@ -3590,7 +3657,7 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
                 st.group_sort_fallbacks++;
             } else {
                 rs = 1;
-                st.group_sorts++;
+                if (!carried) st.group_sorts++;
             }
         }
         if (rs < 0) {
@@ -3604,7 +3671,17 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
         const uint64_t hnew = isa ? 2 * h : h + (uint64_t)nsym2;
         {
             int t = ix.prof.begin(s);
-            if (isa) {
+            if (carried) {
+                hipLaunchKernelGGL((sa_update_kernel<SAW, I, true>), dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, s,
+                                   (const V*)sval[rs].as<V>(), (const I*)U.as<I>(), (const uint8_t*)nh.as<uint8_t>(), m,
+                                   doc_start, (int)ix.bits, ix.mask, (uint64_t)0, sa, flags.as<uint8_t>(), (unsigned long long*)nullptr,
+                                   (const uint8_t*)nullptr, 0u, lf.as<uint8_t>());
+                st.carried_rounds++;
+                kb_shared = vl_kb1 + carry;  // (the groups now share the carried bits too)
+                have_list = true;
+                m_list = m;
+                list_rs = rs;
+            } else if (isa) {
                 HeadIn<I> hin{nh.as<uint8_t>(), U.as<I>()};
                 (void)scan_totals<uint64_t>(s, ix.scan_partials, hin, m, OpMax{}, (uint64_t)0);
                 UpdateOut<SAW, I, R> uo{sval[rs].as<V>(), U.as<I>(), nh.as<uint8_t>(), m, doc_start, (int)ix.bits,
@@ -3624,6 +3701,8 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
             }
             ix.prof.end(t, "sa_update", m * (2 * sizeof(V) + sizeof(I) + 2 + (isa ? sizeof(R) : 0)), s);
         }
+        list_is_carried = carried;
+        if (carried) continue;  // (no symbol was compared: h stays, and no round statistic counts this round)
         h = hnew;
         st.rounds++;
         if (st.rounds > 80) throw InternalError("suffix-array refinement did not converge (internal error)");
