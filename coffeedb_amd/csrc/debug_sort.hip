@@ -273,7 +273,7 @@ void cdb_debug_sort_ws_destroy(cdb_debug_sort_ws* h) {
 // 4-byte values and key-only (columns.hip: column build, range queries); the query paths' hit-list and ranked / OR sorts of
 // (u64, u64) pairs and key-only batches (query.hip); cluster's key-only u32 and u64 sorts and its (u64, u32) pairs (cluster.hip);
 // the suffix-array build's narrow-key sort radix_sort<uint32_t, V> and its 64-bit pair sorts with begin_bit / end_bit inside the
-// key and digits of 2..8 bits (sa_build.hip: the initial sort, the per-symbol bucket sort that passes top_shift as end_bit with
+// key and digits of 2..8 bits (sa_initial_direct.hip: the initial sort; sa_build.hip: the per-symbol bucket sort that passes top_shift as end_bit with
 // live bits above it); and the bucket-wise build's per-bucket sorts with device-side histograms and the third value buffer
 // (sa_build.hip: run_group, radix_sort<K, V> with hb and ix.rws.value_spare).  Under CDB_DEBUG_SORT_GROUPED it follows
 // build_suffix_array: allow_group, and after a LookbackTimeout the input restored and the sort redone with plain_order.

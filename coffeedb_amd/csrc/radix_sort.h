@@ -307,7 +307,7 @@ struct SegArgs {
 };
 // The LAST pass of a segmented sort of packed bucket records writes the finished suffix-array entries and their
 // group flags instead of the records: entry = (aux >> hi_shift) << 32 | value, flag bit0 = first of a group of equal
-// keys, bit1 = still unresolved (sa_build.hip: sa_flags_of).  A tile sees the neighbours of all its elements except
+// keys, bit1 = still unresolved (sa_initial_direct.hip: sa_flags_of).  A tile sees the neighbours of all its elements except
 // across the ends of its per-digit runs, whose true neighbours sit in other tiles: those elements get provisional
 // flags (head / tail assumed), every (tile, digit) run leaves an edge record, and rs_seg_edge_fix_kernel settles them.
 struct SegEdge {

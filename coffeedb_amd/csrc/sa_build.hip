@@ -29,13 +29,17 @@
 //                        stable and the initial order is text order they already ascend by document.
 //   5. reference order : for text with bytes >= 0x80 the reference's signed-bucket order is reproduced by
 //                        block rotations (apply_reference_order) unless reference_compat is switched off.
+//
+// The direct initial sort (builds below 2^32) lives in sa_initial_direct.hip, with the group-flag kernels and the sorts of 4-byte
+// entries that it shares with the phases here; the shared sorts of 8-byte entries are in sa_sorts.hip; sa_build_phases.h holds
+// what the phases hand to each other.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
-#include "index_impl.h"
+#include "sa_build_phases.h"
 #include "records_sweep.h"
 #include "vl_code.h"
 #include "scan.h"
@@ -47,6 +51,12 @@
 #endif
 
 namespace cdb {
+
+double now_ms() {
+    using namespace std::chrono;
+    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
 namespace {
 
 constexpr int KG_TILE = 2048;  // suffixes per workgroup in key generation
@@ -660,115 +670,6 @@ __global__ __launch_bounds__(256) void sa_keyhist3_kernel(const uint8_t* __restr
     __syncthreads();
     for (int p = 0; p < npass; ++p)
         if (s_hist[p][tid]) atomicAdd(&hist[p * 256 + tid], (unsigned long long)s_hist[p][tid]);
-}
-
-// ---------------------------------------------------------------------------------------------
-// group flags: bit0 = first entry of a group of equal prefixes, bit1 = still unresolved
-// ---------------------------------------------------------------------------------------------
-// k[0] = predecessor, k[1..4] = the four keys of slots i0..i0+3, k[5] = successor -> four flag bytes
-__device__ __forceinline__ uint32_t sa_flags_of(const uint64_t (&k)[6], uint64_t i0, uint64_t n, uint32_t kbase,
-                                                uint64_t kmagic) {
-    uint32_t out = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint64_t i = i0 + q;
-        if (i >= n) break;
-        const bool head = i == 0 || k[q] != k[q + 1];
-        const bool tail = i + 1 == n || k[q + 2] != k[q + 1];
-        // an end-of-document code (0) as the last symbol: key = 0 mod base.  kmagic = floor(2^64 / base) + 1
-        // makes the quotient one multiply (exact for keys < 2^56); 0 for a power-of-two base
-        const uint64_t kq = k[q + 1];
-        const bool exhausted = kmagic ? (kq - __umul64hi(kq, kmagic) * kbase) == 0 : (kq & (uint64_t)(kbase - 1u)) == 0;
-        out |= (uint32_t)((head ? 1 : 0) | ((!(head && tail) && !exhausted) ? 2 : 0)) << (8 * q);
-    }
-    return out;
-}
-
-__global__ __launch_bounds__(256) void sa_initflags_kernel(const uint64_t* __restrict__ keys, uint64_t n,
-                                                           uint32_t kbase, uint64_t kmagic,
-                                                           uint8_t* __restrict__ flags, bool flags_aligned) {
-    // four consecutive keys per thread (two 16-byte loads), four flag bytes in one store (bytewise when the
-    // flag range of a bucket does not start on a 4-byte boundary)
-    const uint64_t i0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i0 >= n) return;
-    uint64_t k[6];  // k[0] = predecessor, k[1..4] = own, k[5] = successor
-    if (i0 + 4 <= n) {
-        const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(keys + i0);
-        const ulonglong2 b = *reinterpret_cast<const ulonglong2*>(keys + i0 + 2);
-        k[1] = a.x; k[2] = a.y; k[3] = b.x; k[4] = b.y;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) k[1 + q] = i0 + q < n ? keys[i0 + q] : 0;
-    }
-    k[0] = i0 > 0 ? keys[i0 - 1] : ~k[1];
-    k[5] = i0 + 4 < n ? keys[i0 + 4] : 0;
-    const uint32_t out = sa_flags_of(k, i0, n, kbase, kmagic);
-    if (flags_aligned && i0 + 4 <= n) {
-        *reinterpret_cast<uint32_t*>(flags + i0) = out;
-    } else {
-        for (int q = 0; q < 4 && i0 + q < n; ++q) flags[i0 + q] = (uint8_t)(out >> (8 * q));
-    }
-}
-
-// the same for 32-bit keys, optionally extended by the separately stored low digit (split sort):
-// key = (k32 << low_bits) | low
-template <typename W>
-__global__ __launch_bounds__(256) void sa_initflags32_kernel(const uint32_t* __restrict__ k32,
-                                                             const W* __restrict__ low, int low_bits, uint64_t n,
-                                                             uint32_t kbase, uint64_t kmagic, uint8_t* __restrict__ flags,
-                                                             bool flags_aligned, U2* __restrict__ tile_sums = nullptr) {
-    // tile_sums (optional; `flags` is then the whole array): per scan tile of SC_TILE flags the number of unresolved
-    // entries and of unresolved group heads — the sums the first compaction would otherwise re-read every flag for
-    __shared__ uint32_t s_sum[2];
-    if (tile_sums) {  // (uniform)
-        if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
-        __syncthreads();
-    }
-    const uint64_t i0 = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i0 < n) {
-        const uint64_t lmask = (1ull << low_bits) - 1ull;  // (bytes of W above the digits carry other data: packed entries)
-        auto full = [&](uint64_t i) -> uint64_t {
-            return low ? (((uint64_t)k32[i] << low_bits) | ((uint64_t)low[i] & lmask)) : (uint64_t)k32[i];
-        };
-        uint64_t k[6];
-        if (i0 + 4 <= n) {
-            const uint4 a = *reinterpret_cast<const uint4*>(k32 + i0);
-            const uint32_t hi[4] = {a.x, a.y, a.z, a.w};
-            W l4[4] = {};
-            if (low) {
-                if constexpr (sizeof(W) == 1) *reinterpret_cast<uint32_t*>(l4) = *reinterpret_cast<const uint32_t*>(low + i0);
-                else if constexpr (sizeof(W) == 2) *reinterpret_cast<uint2*>(l4) = *reinterpret_cast<const uint2*>(low + i0);
-                else *reinterpret_cast<uint4*>(l4) = *reinterpret_cast<const uint4*>(low + i0);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) k[1 + q] = low ? (((uint64_t)hi[q] << low_bits) | ((uint64_t)l4[q] & lmask)) : (uint64_t)hi[q];
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) k[1 + q] = i0 + q < n ? full(i0 + q) : 0;
-        }
-        k[0] = i0 > 0 ? full(i0 - 1) : ~k[1];
-        k[5] = i0 + 4 < n ? full(i0 + 4) : 0;
-        const uint32_t out = sa_flags_of(k, i0, n, kbase, kmagic);
-        if (flags_aligned && i0 + 4 <= n) {
-            *reinterpret_cast<uint32_t*>(flags + i0) = out;
-        } else {
-            for (int q = 0; q < 4 && i0 + q < n; ++q) flags[i0 + q] = (uint8_t)(out >> (8 * q));
-        }
-        if (tile_sums) {
-            const uint32_t unres = (out >> 1) & 0x01010101u;  // (sa_flags_of leaves the bytes behind n zero)
-            const uint32_t a = __popc(unres), b = __popc(unres & out);
-            if (a) atomicAdd(&s_sum[0], a);
-            if (b) atomicAdd(&s_sum[1], b);
-        }
-    }
-    if (tile_sums) {
-        __syncthreads();
-        if (threadIdx.x == 0 && s_sum[0]) {  // (a workgroup's 1024 flags lie inside one scan tile)
-            U2* t = tile_sums + ((uint64_t)blockIdx.x * 1024) / SC_TILE;
-            atomicAdd(reinterpret_cast<unsigned long long*>(&t->a), (unsigned long long)s_sum[0]);
-            if (s_sum[1]) atomicAdd(reinterpret_cast<unsigned long long*>(&t->b), (unsigned long long)s_sum[1]);
-        }
-    }
 }
 
 // keys of one first-symbol bucket, gathered from the text for entries that already sit in text order
@@ -1597,10 +1498,6 @@ struct IsaOut {
 // plain unsigned order built above, the reference's order is reached by rotating the two byte blocks
 // of every "big" bucket, level by level down the trie.  compat_bounds_kernel finds, for one big bucket
 // at depth `depth`, where each of the 257 unsigned symbols starts (the bucket is sorted by that symbol).
-struct CompatBucket {
-    unsigned long long lo, hi;
-};
-
 template <typename V>
 __global__ __launch_bounds__(320) void compat_bounds_kernel(typename SaOf<V>::ptr sa,
                                                             const uint8_t* __restrict__ text,
@@ -1872,27 +1769,7 @@ bool apply_reference_order_oop(Index& ix, DevBuf& sa_buf, DevBuf* sa_hi, const s
     return true;
 }
 
-double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
 // ---- 1. alphabet -> order-preserving dense codes
-struct Alphabet {
-    DevBuf d_counts, d_symmap;
-    // bucket-wise builds with look-back-free generated passes count the bytes per 8 Ki-position tile (the rows become the tile
-    // bases of the records / partition pass, radix_sort.h: TextGen::tile_base); their column sums are the histogram
-    DevBuf d_tbc;
-    uint32_t tiles8 = 0;
-    bool tile_bytes = false;
-    DevBuf d_pair_hi;      // per byte value: positions whose next byte is >= 0x80 (counted beside the bytes, PAIR form)
-    bool pair_hi_counted = false;
-    uint64_t h_counts[256];
-    uint16_t h_map[256];
-    int sigma = 0, symbits = 1;
-    bool high_bytes = false;
-};
-
 template <typename V>
 void count_alphabet(Index& ix, bool big, Alphabet& al) {
     hipStream_t s = ix.stream;
@@ -1921,8 +1798,8 @@ void count_alphabet(Index& ix, bool big, Alphabet& al) {
             hipLaunchKernelGGL(sa_tile_bytecount_kernel<true>, dim3((unsigned)ceil_div((uint64_t)tiles8, (uint64_t)(4 * TBC_TILES_PER_WAVE))), dim3(256), 0, s, text, n,
                                tiles8, al.d_tbc.as<uint32_t>(), al.d_pair_hi.as<unsigned long long>());
         else
-        hipLaunchKernelGGL(sa_tile_bytecount_kernel<false>, dim3((unsigned)ceil_div((uint64_t)tiles8, (uint64_t)(4 * TBC_TILES_PER_WAVE))), dim3(256), 0, s, text, n,
-                           tiles8, al.d_tbc.as<uint32_t>(), (unsigned long long*)nullptr);
+            hipLaunchKernelGGL(sa_tile_bytecount_kernel<false>, dim3((unsigned)ceil_div((uint64_t)tiles8, (uint64_t)(4 * TBC_TILES_PER_WAVE))), dim3(256), 0, s, text, n,
+                               tiles8, al.d_tbc.as<uint32_t>(), (unsigned long long*)nullptr);
         d_count_src = rs_tile_totals(s, ix.tbw, al.d_tbc.as<uint32_t>(), tiles8, nullptr);
         ix.prof.end(t, "sa_tile_bytecount", n + (uint64_t)tiles8 * 2048, s);
     } else {
@@ -1941,17 +1818,6 @@ void count_alphabet(Index& ix, bool big, Alphabet& al) {
     al.symbits = std::max(1, bit_width64((uint64_t)al.sigma));
     CDB_HIP(hipMemcpyAsync(al.d_symmap.p, al.h_map, sizeof(al.h_map), hipMemcpyHostToDevice, s));
 }
-
-// per-tile top-digit counts of the MSD-first sort's look-back-free generated pass (option gen_prebased)
-struct TopCounts {
-    DevBuf d_tc;
-    const unsigned long long* totals = nullptr;  // their column sums: the top-digit histogram
-    bool counted = false;
-    struct AuxJoin {  // (declared after the buffer: an exception on the way still waits for the second stream before the
-        hipStream_t a = nullptr;  //  buffer goes back to the pool)
-        ~AuxJoin() { if (a) (void)hipStreamSynchronize(a); }
-    } aux_join;
-};
 
 // Speculative pair count of the MSD-first sort (pair form) on a SECOND stream, beside the key-width sample: both only
 // need the symbol codes, the sample is a chain of small latency-bound kernels (0.7 ms) and the count a 0.4 ms sweep.
@@ -2000,15 +1866,6 @@ void count_top_digits_aside(Index& ix, bool big, const Alphabet& al, TopCounts& 
 // sample pairs agreeing on their first k symbols gives the pair-collision probability c_k, hence
 // ~ n * c_k of all suffixes share their k-prefix with another one.  (An order-0 symbol model is far
 // too optimistic for correlated text such as multi-byte UTF-8.)  Small corpora use the order-0 model.
-struct KeyPlan {
-    int nsym = 0, dbits = 8, key_bits = 0;
-    uint32_t kbase = 0;
-    uint64_t kmagic = 0;
-    bool dense = false;
-    double est_k0 = 0;  // the sample's measured pair-collision probability at est_k0n symbols (>= 50 colliding pairs: meaningful)
-    int est_k0n = 0;
-};
-
 template <typename V>
 KeyPlan plan_keys(Index& ix, bool big, const Alphabet& al) {
     hipStream_t s = ix.stream;
@@ -2155,18 +2012,6 @@ KeyPlan plan_keys(Index& ix, bool big, const Alphabet& al) {
 }
 
 // ---- 2 + 3. keys + entries, initial sort
-// the digit histograms of the fused key generation, and the top-digit histogram of the MSD-first sort
-struct DigitHist {
-    bool fused = false, use_msd = false;
-    std::vector<uint64_t> h_hist;  // [nsym][256] digit histograms of the LSD passes (fused path)
-    std::vector<uint64_t> h_top;
-    // pair form: 6-symbol keys whose top digit is a function of the first two symbols (TextGen::msd_pair); otherwise the
-    // top digit is key >> 32, counted by the key sweep
-    unsigned long long msd_m = 1ull << 32;
-    uint32_t msd_span = 0;
-    struct { uint32_t pair_span = 0, pair_r = 0, pair_s = 0; } pair_consts;
-};
-
 template <typename V>
 DigitHist digit_histograms(Index& ix, bool big, const Alphabet& al, const KeyPlan& kp, TopCounts& tc) {
     hipStream_t s = ix.stream;
@@ -2293,189 +2138,22 @@ DigitHist digit_histograms(Index& ix, bool big, const Alphabet& al, const KeyPla
     return dh;
 }
 
-struct Depth1Fold {
-    uint64_t nend = 0, nlow = 0, nhigh = 0;
-    bool fold = false, done = false;  // done: the segmented sort really wrote the bucket with its blocks swapped
-};
+}  // namespace
 
-// what the initial sort hands to the refinement and the finish
-struct InitialSort {
-    DevBuf sa_buf, flags;
-    DevBuf sa_hi_buf;         // packed output (index_impl.h: Sa40): bits 32..39 of every entry; sa_buf then holds the low words
-    bool packed_out = false;
-    bool flags_by_sort = false;    // the sort's last pass wrote the group flags and the tile sums of the first compaction
-    bool tile_sums_ready = false;  // the raw tile sums of the first compaction are in scan_partials already
-    DevBuf sorted_keys, sorted_k32, sorted_low;
-    int low_bits = 0, low_bytes = 0;
-    std::vector<Depth1Fold> depth1;          // ... per bucket: how its suffixes split by the class of their second symbol
-    std::vector<CompatBucket> folded_roots;  // bucket-wise build in the reference's root order: the first-symbol buckets
-    uint64_t refine_depth0 = 0;  // symbols every key of the initial sort covers for certain (0: nsym; variable-length keys: fewer)
-    DevBuf d_vl_bytelen;         // variable-length keys: text byte -> code-word length (the refinement recovers every group's exact depth)
-    uint32_t vl_kb1 = 0;
-    uint32_t carry = 0;          // carried bits: the next `carry` code-stream bits behind the key sit in bits 2.. of every flag byte
-};
-
-// builds below 2^32: one radix sort of every suffix's key, then the group flags
 template <typename V>
-InitialSort initial_sort_direct(Index& ix, const Alphabet& al, const KeyPlan& kp, const DigitHist& dh, TopCounts& tc, SortStats& ss) {
+void generate_keys(Index& ix, const Alphabet& al, const KeyPlan& kp, uint64_t* keys, V* vals) {
     hipStream_t s = ix.stream;
-    const uint64_t n = ix.size, D = ix.ndocs;
-    BuildStats& st = ix.bstats;
-    const uint8_t* text = ix.d_text;
-    const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
-    const int nsym = kp.nsym, dbits = kp.dbits, key_bits = kp.key_bits;
-    const uint32_t kbase = kp.kbase;
-    const uint64_t kmagic = kp.kmagic;
-    const bool fused = dh.fused, use_msd = dh.use_msd;
-    const uint32_t msd_span = dh.msd_span;
-    InitialSort out;
-    TextGen gen{text, doc_start, al.d_symmap.as<uint16_t>(), D, (int)ix.bits, kbase, nsym, 0, ix.text_padded};
-    double ta = now_ms();
-    out.flags.alloc(n);
-    // Layout of the sort records.  WIDE: (u64 key, entry).  When the generated first pass can drop the digit it
-    // sorts on (it travels as one byte per element) and the rest of the key fits 32 bits, the other passes
-    // move 9 instead of 12 bytes per suffix (SPLIT); keys of <= 32 bits need no extra byte at all (NARROW).
-    enum { WIDE, NARROW, SPLIT, SPLIT2 } layout = WIDE;
-    if (fused && sizeof(V) == 4 && ix.narrow_keys) {
-        if (key_bits <= 32) layout = NARROW;
-        else if (key_bits - dbits <= 32) layout = SPLIT;
-        else if (key_bits - 2 * dbits <= 32) layout = SPLIT2;  // two low digits in a u16: 10 bytes per suffix
-    }
-    st.key_layout = (int)layout;
-    const int low_bits = out.low_bits = layout == SPLIT ? dbits : (layout == SPLIT2 ? 2 * dbits : 0);
-    const int low_bytes = out.low_bytes = layout == SPLIT ? 1 : (layout == SPLIT2 ? 2 : 0);
-    if (layout != WIDE) {
-        if constexpr (sizeof(V) == 4) {
-            DevBuf k32[2], vals[2], low[2];
-            k32[0].alloc(n * sizeof(uint32_t));
-            k32[1].alloc(n * sizeof(uint32_t));
-            vals[0].alloc(n * sizeof(V));
-            vals[1].alloc(n * sizeof(V));
-            if (low_bytes) {
-                if (!use_msd) low[0].alloc(n * low_bytes);  // (the MSD-first sort has no travelling byte: only its last pass writes one)
-                low[1].alloc(n * low_bytes);
-            }
-            st.alloc_ms += now_ms() - ta;
-            if (getenv("CDB_DEBUG_BUFS"))
-                std::fprintf(stderr, "[bufs] k32 %p %p vals %p %p low %p %p flags %p\n", k32[0].p, k32[1].p, vals[0].p, vals[1].p, low[0].p,
-                             low[1].p, out.flags.p);
-            int sel = 0;
-            // The last pass writes the group flags itself (radix_sort.h: SegFinalKeepArgs) where its kernel configuration
-            // can (16 Ki tiles, one-atomic ranking): the flag kernel — 5-6 B read per suffix — is then not needed, and the
-            // per-tile counts of unresolved entries for the first compaction are counted on the way.
-            SegFinalKeepArgs keep;
-            DevBuf edges;
-            const bool want_keep = ix.flags_in_last_pass && dbits == 8 && rs_variant_maybe_big_atomic(ix.sort_variant, n);  // (16 Ki-tile configurations)
-            if (want_keep) {
-                const uint64_t nbt = ceil_div(n, (uint64_t)SC_TILE);
-                ix.scan_partials.ensure(scan_partials_slots(nbt) * sizeof(U2));
-                CDB_HIP(hipMemsetAsync(ix.scan_partials.p, 0, nbt * sizeof(U2), s));
-                edges.alloc((ceil_div(n, (uint64_t)RS_SEG_TILE) + 256) * 256 * sizeof(SegEdge));  // (MSD-first: one ragged tile per bucket)
-                keep.flags = out.flags.as<uint8_t>();
-                keep.edges = edges.as<SegEdge>();
-                keep.low_bits = low_bits;
-                keep.kbase = kbase;
-                keep.kmagic = kmagic;
-                keep.tile_sums = ix.scan_partials.as<unsigned long long>();
-                keep.sums_tile = SC_TILE;
-            }
-            if (layout == SPLIT && use_msd && want_keep) {
-                // the final pass writes the kept keys in the split layout (u32 = key >> 8, low byte), entries and flags
-                if (msd_span) {
-                    gen.msd_pair = true;
-                    gen.pair_span = dh.pair_consts.pair_span;
-                    gen.pair_r = dh.pair_consts.pair_r;
-                    gen.pair_s = dh.pair_consts.pair_s;
-                } else {
-                    gen.msd_shift = 32;
-                }
-                const bool prebased = tc.counted && msd_span != 0;  // (the counts were made with this span: same rule, same alphabet)
-                radix_sort_msd(s, ix.rws, ix.msd_ws, ix.prof, k32[0].as<uint32_t>(), k32[1].as<uint32_t>(), vals[0].as<uint32_t>(),
-                               vals[1].as<uint32_t>(), low[1].as<uint8_t>(), n, dh.h_top.data(), gen, dh.msd_m, keep, &ss,
-                               prebased ? (const uint32_t*)tc.d_tc.as<uint32_t>() : nullptr, prebased ? &ix.tbw : nullptr, ix.sweep_records);
-                st.gen_prebased = prebased ? 1 : 0;
-                st.sweep_records = prebased && ix.sweep_records && gen.msd_pair ? 1 : 0;
-                tc.d_tc.release();
-                ix.tbw.base.release();
-                sel = 1;
-                out.sorted_low = std::move(low[1]);
-                out.flags_by_sort = ix.rws.keep_applied;
-            } else if (layout == SPLIT) {
-                gen.low_bits = low_bits;
-                sel = radix_sort_split<V, uint8_t>(s, ix.rws, ix.prof, k32[0].as<uint32_t>(), k32[1].as<uint32_t>(),
-                                                   vals[0].as<V>(), vals[1].as<V>(), low[0].as<uint8_t>(), low[1].as<uint8_t>(), n,
-                                                   key_bits - low_bits, &ss, ix.sort_variant, dbits, dh.h_hist.data(), &gen, 0, nullptr, -1,
-                                                   want_keep ? &keep : nullptr);
-                out.sorted_low = std::move(low[sel]);
-                out.flags_by_sort = ix.rws.keep_applied;
-            } else if (layout == SPLIT2) {
-                gen.low_bits = low_bits;
-                sel = radix_sort_split<V, uint16_t>(s, ix.rws, ix.prof, k32[0].as<uint32_t>(), k32[1].as<uint32_t>(),
-                                                    vals[0].as<V>(), vals[1].as<V>(), low[0].as<uint16_t>(), low[1].as<uint16_t>(),
-                                                    n, key_bits - low_bits, &ss, ix.sort_variant, dbits, dh.h_hist.data(), &gen, 0, nullptr, -1,
-                                                    want_keep ? &keep : nullptr);
-                out.sorted_low = std::move(low[sel]);
-                out.flags_by_sort = ix.rws.keep_applied;
-            } else {
-                sel = radix_sort<uint32_t, V>(s, ix.rws, ix.prof, k32[0].as<uint32_t>(), k32[1].as<uint32_t>(), vals[0].as<V>(),
-                                              vals[1].as<V>(), n, 0, key_bits, &ss, ix.sort_variant, dbits, dh.h_hist.data(), &gen);
-            }
-            CDB_HIP(hipStreamSynchronize(s));
-            out.sorted_k32 = std::move(k32[sel]);
-            out.sa_buf = std::move(vals[sel]);
-        }
-    } else {
-        DevBuf keys[2], vals[2];
-        keys[0].alloc(n * sizeof(uint64_t));
-        keys[1].alloc(n * sizeof(uint64_t));
-        vals[0].alloc(n * sizeof(V));
-        vals[1].alloc(n * sizeof(V));
-        st.alloc_ms += now_ms() - ta;
-        int sel;
-        if (fused) {
-            sel = radix_sort<uint64_t, V>(s, ix.rws, ix.prof, keys[0].as<uint64_t>(), keys[1].as<uint64_t>(), vals[0].as<V>(),
-                                          vals[1].as<V>(), n, 0, key_bits, &ss, ix.sort_variant, dbits, dh.h_hist.data(), &gen);
-        } else {
-            int t = ix.prof.begin(s);
-            hipLaunchKernelGGL((sa_keygen_kernel<V>), dim3((unsigned)ceil_div(n, KG_TILE)), dim3(256), 0, s, text,
-                               doc_start, D, n, (int)ix.bits, al.d_symmap.as<uint16_t>(), kbase, nsym, ix.text_padded,
-                               keys[0].as<uint64_t>(), vals[0].as<V>());
-            ix.prof.end(t, "sa_keygen", n * (1 + sizeof(uint64_t) + sizeof(V)), s);
-            sel = radix_sort<uint64_t, V>(s, ix.rws, ix.prof, keys[0].as<uint64_t>(), keys[1].as<uint64_t>(), vals[0].as<V>(),
-                                          vals[1].as<V>(), n, 0, key_bits, &ss, ix.sort_variant, dbits);
-        }
-        CDB_HIP(hipStreamSynchronize(s));
-        out.sorted_keys = std::move(keys[sel]);
-        out.sa_buf = std::move(vals[sel]);
-    }
-    out.tile_sums_ready = out.flags_by_sort;
-    st.flags_in_last_pass = out.flags_by_sort ? 1 : 0;
-    if (!out.flags_by_sort) {
-        int t = ix.prof.begin(s);
-        if (layout == WIDE)
-            hipLaunchKernelGGL(sa_initflags_kernel, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, s,
-                               (const uint64_t*)out.sorted_keys.as<uint64_t>(), n, kbase, kmagic, out.flags.as<uint8_t>(), true);
-        else {
-            // (the flag kernel leaves the per-tile counts of unresolved entries for the first compaction: no second sweep
-            //  over the flags for them)
-            const uint64_t nbt = ceil_div(n, (uint64_t)SC_TILE);
-            ix.scan_partials.ensure(scan_partials_slots(nbt) * sizeof(U2));
-            CDB_HIP(hipMemsetAsync(ix.scan_partials.p, 0, nbt * sizeof(U2), s));
-            out.tile_sums_ready = true;
-            if (layout == SPLIT2)
-                hipLaunchKernelGGL(sa_initflags32_kernel<uint16_t>, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, s,
-                                   (const uint32_t*)out.sorted_k32.as<uint32_t>(), (const uint16_t*)out.sorted_low.as<uint16_t>(), low_bits,
-                                   n, kbase, kmagic, out.flags.as<uint8_t>(), true, ix.scan_partials.as<U2>());
-            else
-                hipLaunchKernelGGL(sa_initflags32_kernel<uint8_t>, dim3((unsigned)ceil_div(n, 1024)), dim3(256), 0, s,
-                                   (const uint32_t*)out.sorted_k32.as<uint32_t>(),
-                                   layout == SPLIT ? (const uint8_t*)out.sorted_low.as<uint8_t>() : (const uint8_t*)nullptr, low_bits,
-                                   n, kbase, kmagic, out.flags.as<uint8_t>(), true, ix.scan_partials.as<U2>());
-        }
-        ix.prof.end(t, "sa_initflags", n * (layout == WIDE ? 9 : 5 + low_bytes), s);
-    }
-    return out;
+    const uint64_t n = ix.size;
+    int t = ix.prof.begin(s);
+    hipLaunchKernelGGL((sa_keygen_kernel<V>), dim3((unsigned)ceil_div(n, KG_TILE)), dim3(256), 0, s, ix.d_text,
+                       ix.d_doc_start.as<uint64_t>(), ix.ndocs, n, (int)ix.bits, al.d_symmap.as<uint16_t>(), kp.kbase, kp.nsym, ix.text_padded,
+                       keys, vals);
+    ix.prof.end(t, "sa_keygen", n * (1 + sizeof(uint64_t) + sizeof(V)), s);
 }
+template void generate_keys<uint32_t>(Index&, const Alphabet&, const KeyPlan&, uint64_t*, uint32_t*);
+template void generate_keys<uint64_t>(Index&, const Alphabet&, const KeyPlan&, uint64_t*, uint64_t*);
+
+namespace {
 
 // ---- bucket-wise build: the first-symbol buckets
 // Every position starts a suffix, and a suffix is never empty: the first symbol is never "end of document", so
@@ -3137,14 +2815,12 @@ void run_per_bucket(Index& ix, const Alphabet& al, const KeyPlan& kp, const Buck
                 if (ix.rws.value_result == 1) CDB_HIP(hipMemcpyAsync(eb, ET.p, cnt * sizeof(V), hipMemcpyDeviceToDevice, s));
             }
             if constexpr (sizeof(K) == 8)
-                hipLaunchKernelGGL(sa_initflags_kernel, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
-                                   (const uint64_t*)(r ? k32t.as<uint64_t>() : (uint64_t*)kb), cnt, bbase, bmagic,
-                                   out.flags.as<uint8_t>() + start, (start & 3) == 0);
+                write_group_flags(s, (const uint64_t*)(r ? k32t.as<uint64_t>() : (uint64_t*)kb), cnt, bbase, bmagic,
+                                  out.flags.as<uint8_t>() + start, (start & 3) == 0);
             else
-                hipLaunchKernelGGL(sa_initflags32_kernel<FW>, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
-                                   (const uint32_t*)(r ? k32t.as<uint32_t>() : (uint32_t*)kb),
-                                   HAS_W ? (const FW*)(r ? lowt.as<FW>() : lb) : (const FW*)nullptr, blow, cnt, bbase, bmagic,
-                                   out.flags.as<uint8_t>() + start, (start & 3) == 0);
+                write_group_flags32<FW>(s, (const uint32_t*)(r ? k32t.as<uint32_t>() : (uint32_t*)kb),
+                                        HAS_W ? (const FW*)(r ? lowt.as<FW>() : lb) : (const FW*)nullptr, blow, cnt, bbase, bmagic,
+                                        out.flags.as<uint8_t>() + start, (start & 3) == 0);
         }
     };
     auto run_group_packed = [&](auto wtag, uint32_t b0, uint32_t b1) {  // buckets [b0, b1), packed entries
@@ -3193,9 +2869,8 @@ void run_per_bucket(Index& ix, const Alphabet& al, const KeyPlan& kp, const Buck
                 hipLaunchKernelGGL(sa_assemble_entries_kernel<W>, dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, s,
                                    (const uint32_t*)(vr ? elot.as<uint32_t>() : vb), ls, blow, cnt, E.as<uint64_t>() + start);
                 ix.prof.end(t, "sa_assemble_entries", cnt * (4 + sizeof(W) + 8), s);
-                hipLaunchKernelGGL(sa_initflags32_kernel<W>, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
-                                   (const uint32_t*)(r ? k32t.as<uint32_t>() : kb), lowb ? ls : (const W*)nullptr, blow, cnt,
-                                   bbase, bmagic, out.flags.as<uint8_t>() + start, (start & 3) == 0);
+                write_group_flags32<W>(s, (const uint32_t*)(r ? k32t.as<uint32_t>() : kb), lowb ? ls : (const W*)nullptr, blow, cnt,
+                                       bbase, bmagic, out.flags.as<uint8_t>() + start, (start & 3) == 0);
             }
         }
     };
@@ -3403,9 +3078,7 @@ InitialSort initial_sort_bucketwise(Index& ix, Alphabet& al, const KeyPlan& kp, 
                                         top_shift, &ss, ix.sort_variant, dbits);
             if (r == 1) CDB_HIP(hipMemcpyAsync(eb, ET.p, cnt * sizeof(V), hipMemcpyDeviceToDevice, s));
         }
-        hipLaunchKernelGGL(sa_initflags_kernel, dim3((unsigned)ceil_div(cnt, 1024)), dim3(256), 0, s,
-                           (const uint64_t*)KT[r].as<uint64_t>(), cnt, kbase, kmagic, out.flags.as<uint8_t>() + start,
-                           (start & 3) == 0);
+        write_group_flags(s, (const uint64_t*)KT[r].as<uint64_t>(), cnt, kbase, kmagic, out.flags.as<uint8_t>() + start, (start & 3) == 0);
         start += cnt;
     }
     }
