@@ -39,6 +39,7 @@ EXPORTS = [
     "cdb_rowset_cluster_column", "cdb_rowset_get_stat", "cdb_debug_rowset_from_rows", "cdb_debug_rowset_set_option",
     "cdb_debug_rowset_profile_dump",
     "cdb_debug_scan", "cdb_debug_scan_partials", "cdb_debug_stable_ranks",
+    "cdb_debug_sweep_records", "cdb_debug_vl_tables",
 ]
 
 
@@ -1378,6 +1379,101 @@ def debug_stable_ranks(flags, device=-1):
     if rc != 0:
         raise ScanError("cdb_debug_stable_ranks", rc)
     return before, tile_base[:(n + 4095) // 4096], total.value
+
+
+class CdbDebugSweepArgs(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("n", C.c_uint64), ("doc_start", C.c_void_p), ("ndocs", C.c_uint64), ("bits", C.c_int),
+                ("padded", C.c_int), ("codeslot", C.c_void_p), ("slotmap", C.c_void_p), ("src_col", C.c_void_p),
+                ("slot_start", C.c_void_p), ("vl", C.c_int), ("base", C.c_uint32), ("nsym", C.c_int), ("part_m", C.c_uint32),
+                ("vl_sym", C.c_void_p), ("vl_dec", C.c_void_p), ("key_bits", C.c_int), ("end_len", C.c_int), ("carry", C.c_int),
+                ("carry_shift", C.c_int), ("rec_low_bits", C.c_int), ("aux_bytes", C.c_int), ("g0", C.c_uint32), ("g1", C.c_uint32),
+                ("gstart", C.c_uint64), ("gelems", C.c_uint64), ("seg_begin", C.c_void_p), ("seg_end", C.c_void_p),
+                ("seg_tile_begin", C.c_void_p), ("lead", C.c_int), ("npass", C.c_int), ("tile_counts", C.c_void_p),
+                ("out_k", C.c_void_p), ("out_v", C.c_void_p), ("out_w", C.c_void_p), ("out_hist", C.c_void_p),
+                ("out_tile_base", C.c_void_p), ("out_tile_doc", C.c_void_p), ("out_guard_ok", C.POINTER(C.c_int))]
+
+
+class SweepError(RuntimeError):
+    """A sweep hook failed; `status` is the CDB_E_* code of the error thrown inside the library."""
+
+    def __init__(self, what, status):
+        super().__init__(f"{what} failed ({status})")
+        self.status = status
+
+
+def debug_sweep_records(text, doc_start, bits, padded, codeslot, slotmap, src_col, slot_start, rec_low_bits, aux_bytes, g0, g1, gstart,
+                        gelems, seg_begin, seg_end, seg_tile_begin, lead, npass, tile_counts, dense=None, vl=None, device=-1):
+    """One bucket group through the build's record sweep and histogram sweep (cdb_debug_sweep_records).  dense = (base, nsym,
+    part_m) or vl = (vl_sym[256], vl_dec[128], key_bits, end_len, carry, carry_shift).  Returns a dict: k, v (uint32[gelems]), w
+    (uint8 / uint16 / uint32 [gelems]), hist (uint64[g1 - g0, 8, 256]), tile_base (uint64[tiles, 256]), tile_doc (uint64[tiles + 1]),
+    guard_ok."""
+    if (dense is None) == (vl is None):
+        raise ValueError("exactly one of dense / vl")
+    lib = load_library()
+    lib.cdb_debug_sweep_records.argtypes = [C.c_int, C.POINTER(CdbDebugSweepArgs)]
+    keep = []
+
+    def arr(x, dtype, shape=None):
+        x = np.ascontiguousarray(x, dtype=dtype)
+        if shape is not None and x.shape != shape:
+            raise ValueError(f"array of shape {x.shape}, expected {shape}")
+        keep.append(x)
+        return x.ctypes.data
+
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    n = int(text.shape[0])
+    doc_start = np.ascontiguousarray(doc_start, dtype=np.uint64)
+    tiles, nseg = (n + 8191) // 8192, int(g1) - int(g0)
+    a = CdbDebugSweepArgs()
+    a.text, a.n = arr(text, np.uint8), n
+    a.doc_start, a.ndocs = arr(doc_start, np.uint64), doc_start.shape[0] - 1
+    a.bits, a.padded = int(bits), int(padded)
+    a.codeslot = arr(codeslot, np.uint16, (256,))
+    a.slotmap = arr(slotmap, np.uint8, (257,))
+    a.src_col = arr(src_col, np.uint16, (256,))
+    a.slot_start = arr(slot_start, np.uint64, (256,))
+    if dense is not None:
+        a.vl, (a.base, a.nsym, a.part_m) = 0, (int(x) for x in dense)
+    else:
+        a.vl = 1
+        a.vl_sym, a.vl_dec = arr(vl[0], np.uint16, (256,)), arr(vl[1], np.uint16, (128,))
+        a.key_bits, a.end_len, a.carry, a.carry_shift = (int(x) for x in vl[2:])
+    a.rec_low_bits, a.aux_bytes = int(rec_low_bits), int(aux_bytes)
+    a.g0, a.g1, a.gstart, a.gelems = int(g0), int(g1), int(gstart), int(gelems)
+    a.seg_begin, a.seg_end = arr(seg_begin, np.uint64, (nseg,)), arr(seg_end, np.uint64, (nseg,))
+    a.seg_tile_begin = arr(seg_tile_begin, np.uint32, (nseg,))
+    a.lead, a.npass = int(lead), int(npass)
+    a.tile_counts = arr(tile_counts, np.uint32, (tiles, 256))
+    wtype = {1: np.uint8, 2: np.uint16, 4: np.uint32}[int(aux_bytes)]
+    out = {"k": np.zeros(int(gelems), np.uint32), "v": np.zeros(int(gelems), np.uint32), "w": np.zeros(int(gelems), wtype),
+           "hist": np.zeros((max(nseg, 0), 8, 256), np.uint64), "tile_base": np.zeros((tiles, 256), np.uint64),
+           "tile_doc": np.zeros(tiles + 1, np.uint64)}
+    a.out_k, a.out_v, a.out_w, a.out_hist = (out[x].ctypes.data for x in ("k", "v", "w", "hist"))
+    a.out_tile_base, a.out_tile_doc = out["tile_base"].ctypes.data, out["tile_doc"].ctypes.data
+    ok = C.c_int(0)
+    a.out_guard_ok = C.pointer(ok)
+    rc = lib.cdb_debug_sweep_records(device, C.byref(a))
+    if rc != 0:
+        raise SweepError("cdb_debug_sweep_records", rc)
+    out["guard_ok"] = bool(ok.value)
+    return out
+
+
+def debug_vl_tables(counts, slot_of_code):
+    """The variable-length code the build would choose (cdb_debug_vl_tables; host only).  counts[0] = documents, counts[c] =
+    occurrences of symbol code c; slot_of_code[c] = bucket slot of code c.  Returns (sym uint16[256], dec uint16[128], end_len)."""
+    lib = load_library()
+    lib.cdb_debug_vl_tables.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    sigma = counts.shape[0] - 1
+    slot_of_code = np.ascontiguousarray(slot_of_code, dtype=np.uint8)
+    if slot_of_code.shape != (sigma + 1,):
+        raise ValueError("slot_of_code: one entry per symbol code, END included")
+    sym, dec, end_len = np.zeros(256, np.uint16), np.zeros(128, np.uint16), C.c_int(0)
+    rc = lib.cdb_debug_vl_tables(counts.ctypes.data, sigma, slot_of_code.ctypes.data, sym.ctypes.data, dec.ctypes.data, C.byref(end_len))
+    if rc != 0:
+        raise SweepError("cdb_debug_vl_tables", rc)
+    return sym, dec, end_len.value
 
 
 def layout_rule(ndocs, longest):

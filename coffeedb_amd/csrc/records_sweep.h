@@ -668,6 +668,9 @@ __global__ __launch_bounds__(512, 6) void rs_sweep_records_vl_kernel(TextGen gen
 // waves' counters (one read less per position in the scatter), the top digits of the staging thread ignore document ends
 // (the few ends are patched afterwards by the lanes that hold one), and the byte behind a thread's 16 comes from its neighbour
 // lane instead of a global load.
+// (the one non-template kernel of this header: a second translation unit that includes it — debug_sweep.hip — defines
+//  RS_SWEEP_NO_MSD_KERNEL in front of the include and leaves the strong symbol to sa_build.hip)
+#ifndef RS_SWEEP_NO_MSD_KERNEL
 __global__ __launch_bounds__(512, 8) void rs_sweep_msd_kernel(TextGen gen, uint64_t n, uint32_t tiles, uint32_t* __restrict__ kout,
                                                               uint32_t* __restrict__ vout) {
     constexpr int NT = 512, IPT = 16, TILE = RS_SWEEP_TILE, NW = NT / 64;
@@ -921,6 +924,7 @@ __global__ __launch_bounds__(512, 8) void rs_sweep_msd_kernel(TextGen gen, uint6
         }
     }
 }
+#endif  // RS_SWEEP_NO_MSD_KERNEL
 
 // whether the sweep's arithmetic applies: codes are bytes weighted by B in a dot4 (B <= 255), the key's nsym - 1 symbols come
 // from three code windows (<= 10 symbols: two or three 4-byte windows)

@@ -720,6 +720,55 @@ int cdb_debug_scan_partials(int device, int kind, void* partials_inout, uint64_t
  * what tile_bases returned. */
 int cdb_debug_stable_ranks(int device, const uint8_t* flags, uint64_t n, uint64_t* out_before, uint64_t* out_tile_base, uint64_t* out_total);
 
+/* Test hook for the record sweeps of the bucket-wise build (records_sweep.h) and the bucket histograms counted from their records
+ * (tests/test_gpu_sweep_edges.py; debug_sweep.hip).  Not part of the stable ABI.  Every array lies in HOST memory.  The hook runs
+ * ONE bucket group the way the build does: tile bases from the per-tile byte counts, the tile -> document table, the tile ->
+ * segment map, then the dense (vl = 0) or the variable-length (vl = 1) sweep with aux_bytes-wide auxiliary words and the histogram
+ * sweep.  It refuses (CDB_E_INVALID) tables under which a record could land outside the group: tile_counts must be the text's, a
+ * byte whose slot lies in [g0, g1) must be src_col of that slot and be named by slotmap / vl_dec again, slot d's records are
+ * [slot_start[d] - gstart, ... + its count) = segment d - g0, inside [0, gelems), tile_begin in running order.  CDB_E_INTERNAL on a
+ * device without the one-atomic ranking, as the build would not sweep there. */
+typedef struct cdb_debug_sweep_args {
+    const uint8_t* text;        /* [n] */
+    uint64_t n;
+    const uint64_t* doc_start;  /* [ndocs + 1], doc_start[ndocs] = n */
+    uint64_t ndocs;
+    int bits;                   /* entry = (offset << bits) + document */
+    int padded;                 /* 0: a device buffer of exactly n bytes; 1: n + 128 bytes, those behind n filled with 0xA5 */
+    const uint16_t* codeslot;   /* [256] byte -> symbol code | bucket slot << 8 */
+    const uint8_t* slotmap;     /* [257] symbol code -> bucket slot */
+    const uint16_t* src_col;    /* [256] bucket slot -> the byte whose counts feed it (0xFFFF: none) */
+    const uint64_t* slot_start; /* [256] array-wide first record of every bucket slot */
+    int vl;
+    uint32_t base;              /* dense keys: nsym - 1 symbols behind the bucket symbol in base `base`, */
+    int nsym;
+    uint32_t part_m;            /* ... times part_m plus the next symbol quantised to part_m levels (1: none) */
+    const uint16_t* vl_sym;     /* variable-length keys: [256] and [128], the tables of cdb_debug_vl_tables */
+    const uint16_t* vl_dec;
+    int key_bits, end_len, carry, carry_shift;
+    int rec_low_bits;           /* key bits kept in the auxiliary word */
+    int aux_bytes;              /* 1, 2 or 4 */
+    uint32_t g0, g1;            /* the group's bucket slots */
+    uint64_t gstart, gelems;    /* its first record array-wide, its records */
+    const uint64_t* seg_begin;  /* [g1 - g0] group-local record range and first tile (of 16384 records) of every bucket */
+    const uint64_t* seg_end;
+    const uint32_t* seg_tile_begin;
+    int lead, npass;            /* histogram: digit p < lead = byte p of the auxiliary word, digit lead + q = byte q of the key */
+    const uint32_t* tile_counts;  /* [ceil(n / 8192)][256] bytes of every text tile */
+    uint32_t* out_k;            /* [gelems] */
+    uint32_t* out_v;            /* [gelems] */
+    void* out_w;                /* [gelems] of aux_bytes */
+    uint64_t* out_hist;         /* [g1 - g0][8][256] */
+    uint64_t* out_tile_base;    /* optional [tiles][256] */
+    uint64_t* out_tile_doc;     /* optional [tiles + 1] */
+    int* out_guard_ok;          /* 1: the 4096 poisoned records in front of and behind k, v and w are untouched */
+} cdb_debug_sweep_args;
+int cdb_debug_sweep_records(int device, const cdb_debug_sweep_args* args);
+/* vl_build + vl_fill_tables (vl_code.h), host only: the code the build would choose for counts[0] documents and counts[c]
+ * occurrences of symbol code c = 1 .. sigma (2 <= sigma <= 127), as the sweep's tables sym_out[256] / dec_out[128] with
+ * slot_of_code[c] the bucket slot of code c; *end_len_out = length of END's word.  CDB_E_INVALID: no code. */
+int cdb_debug_vl_tables(const uint64_t* counts, int sigma, const uint8_t* slot_of_code, uint16_t* sym_out, uint16_t* dec_out, int* end_len_out);
+
 /* Measurement hook: wall time of `reps` back-to-back cdb_query calls for each of `nkw` keywords (blob + offsets like
  * cdb_query_batch), taken inside the library with a steady clock — what a C++ caller such as database.cpp:392 sees,
  * without a language binding in between.  us_out[nkw] receives the MEDIAN microseconds per call of every keyword;
