@@ -40,6 +40,7 @@ EXPORTS = [
     "cdb_debug_rowset_profile_dump",
     "cdb_debug_scan", "cdb_debug_scan_partials", "cdb_debug_stable_ranks",
     "cdb_debug_sweep_records", "cdb_debug_vl_tables",
+    "cdb_debug_carried_inplace",
 ]
 
 
@@ -1379,6 +1380,38 @@ def debug_stable_ranks(flags, device=-1):
     if rc != 0:
         raise ScanError("cdb_debug_stable_ranks", rc)
     return before, tile_base[:(n + 4095) // 4096], total.value
+
+
+CARRIED_PACKED40, CARRIED_U32, CARRIED_U64 = range(3)
+
+
+class CarriedError(RuntimeError):
+    """The carried-round hook failed; `status` is the CDB_E_* code of the error thrown inside the library."""
+
+    def __init__(self, what, status):
+        super().__init__(f"{what} failed ({status})")
+        self.status = status
+
+
+def debug_carried_inplace(entries, flags, xbits, form=CARRIED_PACKED40, device=-1):
+    """The in-place carried round over (entries, flag bytes) as the build launches it (cdb_debug_carried_inplace).  Returns
+    (entries uint64[n], flags uint8[n], partials uint64[tiles, 2], open entries met, entries moved, guards intact)."""
+    lib = load_library()
+    lib.cdb_debug_carried_inplace.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_int)]
+    entries = np.array(entries, dtype=np.uint64)   # (copies: the hook works in place)
+    flags = np.array(flags, dtype=np.uint8)
+    n = entries.shape[0]
+    if entries.shape != (n,) or flags.shape != (n,):
+        raise ValueError(f"entries of shape {entries.shape}, flags of shape {flags.shape}")
+    partials = np.zeros(((n + 4095) // 4096, 2), dtype=np.uint64)
+    counts = np.zeros(2, dtype=np.uint64)
+    ok = C.c_int(0)
+    rc = lib.cdb_debug_carried_inplace(device, form, entries.ctypes.data if n else None, flags.ctypes.data if n else None, n, xbits,
+                                       partials.ctypes.data, counts.ctypes.data, C.byref(ok))
+    if rc != 0:
+        raise CarriedError("cdb_debug_carried_inplace", rc)
+    return entries, flags, partials, int(counts[0]), int(counts[1]), bool(ok.value)
 
 
 class CdbDebugSweepArgs(C.Structure):

@@ -43,6 +43,7 @@
 #include "records_sweep.h"
 #include "vl_code.h"
 #include "scan.h"
+#include "carried_inplace.h"
 
 // Timing-only ablations of the record gather (WRONG records): compile-time only (-DRS_GATHER_ABL=<bits>, a library of its own loaded
 // through CDB_LIB_PATH by tools/big_ablate.sh), never a run-time switch of the product build.
@@ -1185,26 +1186,7 @@ __global__ __launch_bounds__(256) void sa_round_keys_kernel(const V* __restrict_
 // with wave shuffles and takes its tiles one after the other: no LDS, no workgroup barrier, millions of 4 KiB workgroups less
 // (the compaction itself stays bound by its gather of the unresolved entries).  sa_flag_count_kernel leaves the raw tile sums (unresolved entries, unresolved group
 // heads) in the partials of scan.h's layout; sa_flag_compact_kernel uses their exclusive scan.
-constexpr uint32_t FC_TILES_PER_WAVE = 4;
-__device__ __forceinline__ void fc_load(const uint8_t* __restrict__ flags, uint64_t n, uint64_t base, uint32_t (&x)[4]) {
-    x[0] = x[1] = x[2] = x[3] = 0;
-    if (base + 16 <= n) {
-        const uint4 w = *reinterpret_cast<const uint4*>(flags + base);
-        x[0] = w.x; x[1] = w.y; x[2] = w.z; x[3] = w.w;
-    } else if (base < n) {
-        for (int k = 0; k < 16 && base + k < n; ++k) x[k >> 2] |= (uint32_t)flags[base + k] << (8 * (k & 3));
-    }
-}
-__device__ __forceinline__ uint32_t fc_count(const uint32_t (&x)[4]) {  // unresolved entries | unresolved group heads << 16
-    uint32_t cu = 0, ch = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint32_t u = (x[q] >> 1) & 0x01010101u;
-        cu += __popc(u);
-        ch += __popc(u & x[q] & 0x01010101u);
-    }
-    return cu | (ch << 16);
-}
+// (FC_TILES_PER_WAVE, fc_load, fc_count: carried_inplace.h, shared with the in-place carried round)
 __global__ __launch_bounds__(256) void sa_flag_count_kernel(const uint8_t* __restrict__ flags, uint64_t n, uint64_t tiles, U2* __restrict__ partials) {
     static_assert(SC_TILE == 4096, "flag compaction assumes 4096-flag tiles");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2908,8 +2890,10 @@ InitialSort initial_sort_bucketwise(Index& ix, Alphabet& al, const KeyPlan& kp, 
     TextGen gen{text, doc_start, al.d_symmap.as<uint16_t>(), D, (int)ix.bits, kbase, nsym, 0, ix.text_padded};
     double ta = now_ms();
     // flag byte of slot i: bit 0 = first of a group of equal keys, bit 1 = the group is still unresolved, bits 2..7 = the carried
-    // bits of the entry the initial sort put there (run_segmented; zero without them).  The refinement rewrites bits 0..1 only
-    // where a round touches a slot — as a whole byte, so bits 2.. are then zero — and every reader masks bits 0 and 1.
+    // bits of the entry the initial sort put there (run_segmented; zero without them).  The in-place carried round
+    // (carried_inplace.h) moves bits 2.. with the entries it moves: behind it they still belong to the entry in the slot.  The list
+    // rounds rewrite bits 0..1 only where they touch a slot — as a whole byte, so bits 2.. are then zero — and every reader masks
+    // bits 0 and 1.
     out.flags.alloc(n);
     DevBuf E, KT[2], ET;  // (E: allocated below, once it is known whether the entries are partitioned at all)
     const int top_shift = (nsym - 1) * symbits;
@@ -3117,6 +3101,7 @@ struct RefineBuffers {
     DevBuf d_open;  // entries still unresolved after the last round (saves a full flag scan to learn "none")
     DevBuf U2b, lf;       // list-based rounds: the other list of positions, the flag bytes of the current list in list order
     DevBuf d_gs_state;  // sa_group_sort_kernel: [0] it gave up (groups too long for it), [1] members walked by its long walks
+    DevBuf d_inplace;   // sa_carried_inplace_kernel: its count words (open entries met, entries moved)
 };
 
 // slot order of the array as the bucket-wise build laid it out -> plain unsigned order (ranks of prefix doubling)
@@ -3196,6 +3181,31 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
     bool carried_pending = carry > 0, list_is_carried = false;
     uint32_t kb_shared = vl_kb1;  // code bits every member of a group shares (equal bits decode alike: where hcov starts)
     st.carried_rounds = 0;
+    // The carried round IN PLACE (carried_inplace.h) in front of it: one sweep over the flag bytes settles every tied group that lies
+    // inside one tile of the sweep and has at most 64 members — a permutation of neighbouring slots — and leaves the raw tile sums
+    // of what is still open, so the list round below compacts the few groups left (those across a tile boundary, the long ones
+    // and the ones whose carried bits are equal) without a flag count.  It is a no-op on the settled groups: they are in order and
+    // their carried bits moved with them.
+    const bool inplace = carry > 0 && n > 0 && n < CI_MAX_N && (ix.carried_inplace < 0 ? n >= CARRIED_INPLACE_MIN_N : ix.carried_inplace != 0);
+    uint64_t met_inplace = 0;
+    st.carried_inplace = 0;
+    if (inplace) {
+        const uint64_t nb = ceil_div(n, SC_TILE);
+        ix.scan_partials.ensure(scan_partials_slots(nb) * sizeof(U2));
+        rb.d_inplace.alloc(CI_COUNT_SLOTS * sizeof(unsigned long long));
+        CDB_HIP(hipMemsetAsync(rb.d_inplace.p, 0, CI_COUNT_SLOTS * sizeof(unsigned long long), s));
+        int t = ix.prof.begin(s);
+        launch_carried_inplace(s, flags.as<uint8_t>(), n, (int)carry, sa, ix.scan_partials.as<U2>(), rb.d_inplace.as<unsigned long long>());
+        ix.prof.end(t, "sa_carried_inplace", n, s);
+        unsigned long long cnt[CI_COUNT_SLOTS] = {};
+        CDB_HIP(hipMemcpyAsync(cnt, rb.d_inplace.p, sizeof(cnt), hipMemcpyDeviceToHost, s));
+        CDB_HIP(hipStreamSynchronize(s));
+        uint64_t moved_inplace = 0;
+        carried_inplace_totals(cnt, met_inplace, moved_inplace);
+        if (t >= 0) ix.prof.pending[t].bytes = n + moved_inplace * 2 * (std::is_same<SAW, Sa40RW>::value ? 5 : sizeof(V));
+        is.tile_sums_ready = true;
+        st.carried_inplace = 1;
+    }
     for (uint32_t iter = 0;; ++iter) {
         if (iter > 0 && !list_is_carried) {  // (the carried round does not count its open entries: the flag count below does)
             uint64_t still = 0;
@@ -3229,7 +3239,12 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
         U2 tot = scan_totals_from_partials<U2>(s, ix.scan_partials, from_list ? m_list : n, OpAdd{}, U2{0, 0});
         is.tile_sums_ready = false;
         uint64_t m = tot.a, G = tot.b;
-        if (iter == 0) st.unresolved_initial = st.unresolved_after_carried = m;
+        if (iter == 0) {
+            st.unresolved_initial = inplace ? met_inplace : m;
+            st.unresolved_after_inplace = st.unresolved_after_carried = m;
+            if (inplace && met_inplace > 0) st.carried_rounds = 1;  // (also where the sweep left nothing open)
+            st.unresolved_max = std::max(st.unresolved_max, st.unresolved_initial);
+        }
         if (list_is_carried) st.unresolved_after_carried = m;
         st.unresolved_max = std::max(st.unresolved_max, m);
         if (m == 0) break;
@@ -3349,7 +3364,7 @@ uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, c
                                    (const V*)sval[rs].as<V>(), (const I*)U.as<I>(), (const uint8_t*)nh.as<uint8_t>(), m,
                                    doc_start, (int)ix.bits, ix.mask, (uint64_t)0, sa, flags.as<uint8_t>(), (unsigned long long*)nullptr,
                                    (const uint8_t*)nullptr, 0u, lf.as<uint8_t>());
-                st.carried_rounds++;
+                st.carried_rounds = 1;  // (sweep, list round or both: one carried round)
                 kb_shared = vl_kb1 + carry;  // (the groups now share the carried bits too)
                 have_list = true;
                 m_list = m;

@@ -769,6 +769,19 @@ int cdb_debug_sweep_records(int device, const cdb_debug_sweep_args* args);
  * slot_of_code[c] the bucket slot of code c; *end_len_out = length of END's word.  CDB_E_INVALID: no code. */
 int cdb_debug_vl_tables(const uint64_t* counts, int sigma, const uint8_t* slot_of_code, uint16_t* sym_out, uint16_t* dec_out, int* end_len_out);
 
+/* Test hook for the in-place carried round of the refinement (carried_inplace.h: sa_carried_inplace_kernel;
+ * tests/test_gpu_carried_inplace.py; debug_carried.hip).  Not part of the stable ABI.  Every array lies in HOST memory.  The hook
+ * uploads n entries (one uint64_t each; stored on the device in the form named below) and their n flag bytes (bit 0 = head of a
+ * group, bit 1 = open, bits 2.. = the carried bits, of which the low xbits = 1..6 are the sort key), launches the sweep the way the
+ * build does and returns the entries and flag bytes as it leaves them, out_partials[tile] = (open entries, open heads) of every tile
+ * of 4096 slots (two uint64_t each, ceil(n / 4096) tiles), out_counts[0] = open entries met and out_counts[1] = entries moved.
+ * *out_guard_ok = 1 when the 4096 poisoned bytes in front of and behind every device array are untouched.  n = 0: CDB_E_INVALID. */
+#define CDB_DEBUG_CARRIED_PACKED40 0  /* 5-byte entries: a uint32_t array and a byte array (bits 32..39) */
+#define CDB_DEBUG_CARRIED_U32 1       /* plain uint32_t entries */
+#define CDB_DEBUG_CARRIED_U64 2       /* plain uint64_t entries */
+int cdb_debug_carried_inplace(int device, int form, uint64_t* entries_inout, uint8_t* flags_inout, uint64_t n, int xbits,
+                              uint64_t* out_partials, uint64_t* out_counts, int* out_guard_ok);
+
 /* Measurement hook: wall time of `reps` back-to-back cdb_query calls for each of `nkw` keywords (blob + offsets like
  * cdb_query_batch), taken inside the library with a steady clock — what a C++ caller such as database.cpp:392 sees,
  * without a language binding in between.  us_out[nkw] receives the MEDIAN microseconds per call of every keyword;
