@@ -34,6 +34,7 @@ EXPORTS = [
     "cdb_render_rows", "cdb_shards_render_rows", "cdb_rendered_free",
     "cdb_remove", "cdb_column_remove",
     "cdb_append", "cdb_debug_verify_keys",
+    "cdb_shards_remove", "cdb_shards_append", "cdb_shards_cluster",
     "cdb_debug_sort_ws_create", "cdb_debug_sort_ws_destroy", "cdb_debug_radix_sort_ex", "cdb_debug_radix_sort_split",
     "cdb_filter", "cdb_rowset_free", "cdb_rowset_last_error", "cdb_rowset_size", "cdb_rowset_rows", "cdb_rowset_page", "cdb_rowset_cluster",
     "cdb_rowset_cluster_column", "cdb_rowset_get_stat", "cdb_debug_rowset_from_rows", "cdb_debug_rowset_set_option",
@@ -255,6 +256,9 @@ def load_library():
     lib.cdb_column_remove.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     lib.cdb_append.argtypes = [vp, vp, vp, vp, u64, C.POINTER(u64)]
     lib.cdb_debug_verify_keys.argtypes = [vp, C.POINTER(u64)]
+    lib.cdb_shards_remove.argtypes = lib.cdb_remove.argtypes
+    lib.cdb_shards_append.argtypes = lib.cdb_append.argtypes
+    lib.cdb_shards_cluster.argtypes = lib.cdb_cluster.argtypes
     rows_out = [C.POINTER(C.POINTER(i64)), C.POINTER(C.POINTER(i64)), C.POINTER(C.c_size_t)]
     lib.cdb_filter.argtypes = [C.POINTER(CdbKeyQuery), C.c_int, C.POINTER(CdbColumnKey), C.c_int, C.c_int, i64, i64, C.POINTER(vp)]
     lib.cdb_rowset_free.argtypes = [vp]
@@ -317,6 +321,46 @@ def _render_rows(self, fn, ids, keywords, left, right, text, spans, raw):
         return found, texts, spans_, int(r.missing)
     finally:
         self._lib.cdb_rendered_free(C.byref(r))
+
+
+def _cluster_strings(self, fn, ids, with_values):
+    """cdb_cluster / cdb_shards_cluster behind GpuStringIndex.cluster and GpuShards.cluster"""
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    r = CdbClusters()
+    self._check(fn(self._h, _ptr(ids) if len(ids) else None, len(ids), 1 if with_values else 0, C.byref(r)))
+    try:
+        ng = int(r.ngroups)
+        values = None
+        if with_values:
+            vp_ = _array(r.value_ptr, ng + 1, np.uint64)
+            blob = C.string_at(r.value_blob, int(vp_[ng])) if ng else b""
+            values = [blob[int(vp_[g]):int(vp_[g + 1])] for g in range(ng)]
+        return values, _array(r.counts, ng, np.int64), _array(r.rep_ids, ng, np.int64), int(r.missing)
+    finally:
+        self._lib.cdb_clusters_free(C.byref(r))
+
+
+def _remove_ids(self, fn, ids):
+    """cdb_remove / cdb_shards_remove behind GpuStringIndex.remove and GpuShards.remove"""
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    removed, missing = C.c_uint64(0), C.c_uint64(0)
+    self._check(fn(self._h, _ptr(ids) if len(ids) else None, len(ids), C.byref(removed), C.byref(missing)))
+    return int(removed.value), int(missing.value)
+
+
+def _append_docs(self, fn, ids, blob, doc_start):
+    """cdb_append / cdb_shards_append behind GpuStringIndex.append and GpuShards.append"""
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    doc_start = np.ascontiguousarray(doc_start, dtype=np.uint64)
+    assert len(doc_start) == len(ids) + 1
+    if len(doc_start) and int(doc_start[-1]) > len(blob):   # (the C ABI takes plain pointers: a short blob would be read past its end)
+        raise ValueError(f"blob holds {len(blob)} bytes, doc_start[-1] = {int(doc_start[-1])}")
+    if not len(blob):
+        blob = np.zeros(1, dtype=np.uint8)   # (empty documents only: the C ABI still wants a pointer)
+    appended = C.c_uint64(0)
+    self._check(fn(self._h, _ptr(ids) if len(ids) else None, _ptr(blob), _ptr(doc_start), len(ids), C.byref(appended)))
+    return int(appended.value)
 
 
 class GpuStringIndex:
@@ -580,19 +624,7 @@ class GpuStringIndex:
         """cdb_cluster (database.cpp:442-460 for this string field): the rows `ids` grouped by their document, groups in
         std::string order.  Returns (values: list of bytes, or None without with_values; counts int64; rep_ids int64: the smallest
         id of each group among the rows; missing: rows whose id the index does not hold)."""
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        r = CdbClusters()
-        self._check(self._lib.cdb_cluster(self._h, _ptr(ids) if len(ids) else None, len(ids), 1 if with_values else 0, C.byref(r)))
-        try:
-            ng = int(r.ngroups)
-            values = None
-            if with_values:
-                vp_ = _array(r.value_ptr, ng + 1, np.uint64)
-                blob = C.string_at(r.value_blob, int(vp_[ng])) if ng else b""
-                values = [blob[int(vp_[g]):int(vp_[g + 1])] for g in range(ng)]
-            return values, _array(r.counts, ng, np.int64), _array(r.rep_ids, ng, np.int64), int(r.missing)
-        finally:
-            self._lib.cdb_clusters_free(C.byref(r))
+        return _cluster_strings(self, self._lib.cdb_cluster, ids, with_values)
 
     def render_rows(self, ids, keywords, left=b"", right=b"", text=True, spans=True, raw=False):
         """cdb_render_rows (the tail of select(), database.cpp:394-441): the rows `ids` in the caller's order, each rendered as
@@ -605,26 +637,13 @@ class GpuStringIndex:
         """cdb_remove: the documents `ids` leave the built index on the device (no rebuild, nothing uploaded but the ids); the handle
         then equals a fresh one built over the survivors.  Returns (removed: distinct documents dropped, missing: entries of `ids`
         the index does not hold)."""
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        removed, missing = C.c_uint64(0), C.c_uint64(0)
-        self._check(self._lib.cdb_remove(self._h, _ptr(ids) if len(ids) else None, len(ids), C.byref(removed), C.byref(missing)))
-        return int(removed.value), int(missing.value)
+        return _remove_ids(self, self._lib.cdb_remove, ids)
 
     def append(self, ids, blob, doc_start):
         """cdb_append: the documents (ids, blob, doc_start as for build_view) join the built index on the device — only they are
         uploaded and sorted; the handle then equals a fresh one built over the old documents followed by the new ones.  Returns the
         number of documents that joined."""
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        doc_start = np.ascontiguousarray(doc_start, dtype=np.uint64)
-        assert len(doc_start) == len(ids) + 1
-        if len(doc_start) and int(doc_start[-1]) > len(blob):   # (the C ABI takes plain pointers: a short blob would be read past its end)
-            raise ValueError(f"blob holds {len(blob)} bytes, doc_start[-1] = {int(doc_start[-1])}")
-        if not len(blob):
-            blob = np.zeros(1, dtype=np.uint8)   # (empty documents only: the C ABI still wants a pointer)
-        appended = C.c_uint64(0)
-        self._check(self._lib.cdb_append(self._h, _ptr(ids) if len(ids) else None, _ptr(blob), _ptr(doc_start), len(ids), C.byref(appended)))
-        return int(appended.value)
+        return _append_docs(self, self._lib.cdb_append, ids, blob, doc_start)
 
     def verify_keys(self):
         """GPU-side check of the kept search keys against the text (cdb_debug_verify_keys); checked = 0: no keys are kept."""
@@ -799,6 +818,20 @@ class GpuShards:
 
     def load(self, path):
         self._check(self._lib.cdb_shards_load(self._h, os.fsencode(path)))
+
+    def remove(self, ids):
+        """cdb_shards_remove: GpuStringIndex.remove over all shards, all or nothing.  Returns (removed, missing); an emptied shard
+        stays in place."""
+        return _remove_ids(self, self._lib.cdb_shards_remove, ids)
+
+    def append(self, ids, blob, doc_start):
+        """cdb_shards_append: GpuStringIndex.append at the end of the sharded column — into the last shard while it stays within
+        max_shard_bytes, else onto the idle device slots (`count` grows).  Returns the number of documents that joined."""
+        return _append_docs(self, self._lib.cdb_shards_append, ids, blob, doc_start)
+
+    def cluster(self, ids, with_values=True):
+        """cdb_shards_cluster: GpuStringIndex.cluster over all shards (equal strings of different shards form one group)."""
+        return _cluster_strings(self, self._lib.cdb_shards_cluster, ids, with_values)
 
 
 class GpuColumn:

@@ -955,8 +955,9 @@ int cdb_build_device(cdb_index* h, const void* d_text, const uint64_t* doc_start
  * (a memcpy into fresh pages: 180 ms per GiB, 3x the build it feeds).  The column goes to the device through the
  * chunked pinned upload; afterwards the handle owns device copies only (cdb_add* fetch them back when needed). */
 namespace {
-// the body of cdb_build_view, with ix.mu held and the device set (cdb_append on a handle that holds nothing is this build)
-void build_view_locked(Index& ix, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs) {
+// the prepare half of cdb_build_view, with ix.mu held and the device set: the column checked and uploaded into col beside whatever
+// the handle serves (cdb_append on a handle that holds nothing is this build; install() builds the array)
+void build_view_prepare(Index& ix, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs, NewColumn& col) {
     const uint64_t first = ndocs ? doc_start[0] : 0;
     // The text starts travelling FIRST, on a helper thread, into a block nothing refers to yet; the document tables are
     // copied and validated meanwhile (1-2 ms per million documents on one core — it used to sit in front of the upload).
@@ -976,7 +977,7 @@ void build_view_locked(Index& ix, const int64_t* ids, const char* blob, const ui
             (void)hipGetLastError();
         }
     }
-    replace_column(ix, [&](NewColumn& col) {
+    drained_on_failure(ix, [&] {
         alloc_padded_text(ix, col.text, n_claimed);
         col.upload_t0 = wall_ms();
         std::exception_ptr uerr;
@@ -1001,6 +1002,11 @@ void build_view_locked(Index& ix, const int64_t* ids, const char* blob, const ui
         //  with the chunk copies: 21.4 instead of 20.1 ms)
         upload_tables(ix, col.doc_start, col.ids, ndocs, col.d_start, col.d_ids);
     });
+}
+void build_view_locked(Index& ix, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs) {
+    NewColumn c;
+    build_view_prepare(ix, ids, blob, doc_start, ndocs, c);
+    install(ix, c);
 }
 }  // namespace
 
@@ -1076,10 +1082,148 @@ int cdb_build_resident(cdb_index* h, const void* d_text, const uint64_t* d_doc_s
     });
 }
 
+// cdb_remove and cdb_append in two halves (index_impl.h): prepare makes everything new beside the old index, commit installs it.
+// The single-handle entry points run them back to back; a sharded column prepares on every shard before it commits on any.
+}  // extern "C"
+namespace cdb {
+struct ColumnChange {
+    Index* ix = nullptr;
+    NewColumn col;
+    double t0 = 0;          // wall_ms() when the call began (remove_ms / append_ms)
+    bool is_remove = false;
+    bool kept_array = false;  // remove: compacted; append: merged
+    uint64_t docs = 0, bytes = 0;
+};
+void ColumnChangeDelete::operator()(ColumnChange* c) const {
+    if (!c) return;
+    {   // a prepared column that is dropped hands its blocks back on its own device and stream
+        (void)hipSetDevice(c->ix->device);
+        StreamScope ss(c->ix->stream);
+        delete c;
+    }
+}
+void reserve_wait() { reserve_join(); }
+
 // Documents leave a built index without a rebuild (remove.hip).  The survivors' array is the old one with the removed documents'
 // entries dropped and the rest re-encoded in the same order; an array in the reference's order (bytes >= 0x80 under
 // reference_compat) depends on bucket sizes that change with n, so there only text and tables are compacted and the array is
 // built over them on the device.  Either way nothing is uploaded but the ids.
+ColumnChangePtr remove_prepare(Index& ix, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
+    DeviceScope dscope(ix);
+    const double t0 = wall_ms();
+    const uint64_t built_docs = built_docs_or_refuse(ix, "remove");
+    if (!nids) return nullptr;
+    if (!built_docs) {  // never built, or built over nothing: the index holds no id
+        if (missing) *missing = nids;
+        return nullptr;
+    }
+    RemovePlan p;
+    drained_on_failure(ix, [&] { remove_mark(ix, ids, nids, p); });
+    if (removed) *removed = p.removed;
+    if (missing) *missing = p.missing;
+    if (!p.removed) {  // (the scan's total synchronised the stream and nothing was queued behind it)
+        ix.prof.resolve();
+        return nullptr;
+    }
+    const Layout L = layout_from(p.ndocs, p.size, p.longest);  // (a smaller column: the capacity errors cannot fire)
+    ColumnChangePtr c(new ColumnChange());
+    c->ix = &ix;
+    c->t0 = t0;
+    c->is_remove = true;
+    c->kept_array = ix.sa_sorted;
+    c->docs = p.removed;
+    c->bytes = ix.size - L.size;
+    drained_on_failure(ix, [&] {
+        NewColumn& col = c->col;
+        col.L = L;
+        col.host = NewColumn::HOST_NONE;  // (a staging copy that equals the built column goes: cdb_add* fetch the survivors back)
+        remove_text(ix, p);
+        if (c->kept_array) remove_compact(ix, p, (int)L.bits, L.width, layout_packable(ix, L));
+        adopt_blocks(ix, col, p);
+    });
+    return c;
+}
+
+// Documents join a built index without a rebuild (append.hip).  The array over "old documents, then new documents" is the stable
+// merge of the old array and the new documents' own array, ties old first; an array in the reference's order (bytes >= 0x80 under
+// reference_compat) depends on bucket sizes that change with n, so there text and tables are extended on the device and the array
+// is built over them.  Either way only the new documents are uploaded.
+ColumnChangePtr append_prepare(Index& ix, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs) {
+    DeviceScope dscope(ix);
+    const double t0 = wall_ms();
+    const uint64_t built_docs = built_docs_or_refuse(ix, "append");
+    if (!ndocs) return nullptr;
+    const uint64_t first = doc_start[0];
+    if (doc_start[ndocs] < first || doc_start[ndocs] - first >= (1ull << 48)) throw Error("doc_start must be non-decreasing");
+    const uint64_t m = doc_start[ndocs] - first;
+    ColumnChangePtr c(new ColumnChange());
+    c->ix = &ix;
+    c->t0 = t0;
+    c->docs = ndocs;
+    c->bytes = m;
+    if (!built_docs) {  // never built, or built over nothing: a build of the given documents
+        build_view_prepare(ix, ids, blob, doc_start, ndocs, c->col);
+        return c;
+    }
+    const uint64_t n = ix.size, D = ix.ndocs;
+    AppendPlan p;
+    std::vector<uint64_t> new_start(ndocs + 1);  // the new documents behind the old text
+    new_start[0] = n;
+    for (uint64_t d = 0; d < ndocs; ++d) {
+        if (doc_start[d + 1] < doc_start[d]) throw Error("doc_start must be non-decreasing");
+        p.longest = std::max(p.longest, doc_start[d + 1] - doc_start[d]);
+        new_start[d + 1] = n + (doc_start[d + 1] - first);
+    }
+    p.ndocs = ndocs;
+    p.size = m;
+    drained_on_failure(ix, [&] { append_old_longest(ix, p); });
+    // the reference's capacity errors (index.cpp:195-200): nothing has been touched yet
+    const Layout L = layout_from(D + ndocs, n + m, std::max(p.old_longest, p.longest));
+    const Layout Li = layout_from(ndocs, m, p.longest);
+    p.in_bits = Li.bits;
+    p.in_mask = Li.mask;
+    p.in_width = Li.width;
+    p.in_off_bits = Li.off_bits;
+    drained_on_failure(ix, [&] {
+        NewColumn& col = c->col;
+        col.L = L;
+        col.host = NewColumn::HOST_NONE;  // (a staging copy that equals the built column goes: cdb_add* / cdb_save fetch the column back)
+        append_tables(ix, p, ids, new_start.data());
+        append_text_old(ix, p);
+        if (m) upload_pageable(p.text.as<uint8_t>() + n, blob + first, m, ix.stream, ix.device, upload_stream(ix));
+        append_scan_bytes(ix, p);
+        // the merge is exact where the fresh array would be globally sorted; the reference's order is rebuilt
+        const bool valid = n > 0 && ix.sa_sorted && (!ix.reference_compat || !p.high_bytes);
+        c->kept_array = valid && ix.debug_append_path != 2;
+        if (c->kept_array) append_merge(ix, p, (int)L.bits, L.mask, L.width, layout_packable(ix, L));
+        adopt_blocks(ix, col, p);
+    });
+    return c;
+}
+
+// The commit half: the old index stops serving (install), then the call counts itself (behind the build or the commit: the
+// handle's keys are the new column's).  A failure in here — only a build over the new text can fail — leaves a "never built" handle.
+void column_commit(Index& ix, ColumnChange& c) {
+    DeviceScope dscope(ix);
+    install(ix, c.col);
+    if (c.is_remove) {
+        ix.rm.calls += 1;
+        (c.kept_array ? ix.rm.compactions : ix.rm.rebuilds) += 1;
+        ix.rm.docs = c.docs;
+        ix.rm.bytes = c.bytes;
+        ix.rm.last_ms = wall_ms() - c.t0;
+    } else {
+        ix.ap.calls += 1;
+        (c.kept_array ? ix.ap.merges : ix.ap.rebuilds) += 1;
+        ix.ap.docs = c.docs;
+        ix.ap.bytes = c.bytes;
+        ix.ap.with_keys = ix.key_nsym ? 1 : 0;
+        ix.ap.last_ms = wall_ms() - c.t0;
+    }
+}
+}  // namespace cdb
+extern "C" {
+
 int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
     if (!h || (nids && !ids)) return CDB_E_INVALID;
     if (removed) *removed = 0;
@@ -1088,44 +1232,11 @@ int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* remove
     return guarded(h, [&] {
         Index& ix = h->ix;
         std::lock_guard<std::mutex> g(ix.mu);
-        DeviceScope dscope(ix);
-        const double t0 = wall_ms();
-        const uint64_t built_docs = built_docs_or_refuse(ix, "remove");
-        if (!nids) return;
-        if (!built_docs) {  // never built, or built over nothing: the index holds no id
-            if (missing) *missing = nids;
-            return;
-        }
-        RemovePlan p;
-        drained_on_failure(ix, [&] { remove_mark(ix, ids, nids, p); });
-        if (removed) *removed = p.removed;
-        if (missing) *missing = p.missing;
-        if (!p.removed) {  // (the scan's total synchronised the stream and nothing was queued behind it)
-            ix.prof.resolve();
-            return;
-        }
-        const Layout L = layout_from(p.ndocs, p.size, p.longest);  // (a smaller column: the capacity errors cannot fire)
-        const bool compact = ix.sa_sorted;
-        const uint64_t old_size = ix.size;
-        replace_column(ix, [&](NewColumn& col) {
-            col.L = L;
-            col.host = NewColumn::HOST_NONE;  // (a staging copy that equals the built column goes: cdb_add* fetch the survivors back)
-            remove_text(ix, p);
-            if (compact) remove_compact(ix, p, (int)L.bits, L.width, layout_packable(ix, L));
-            adopt_blocks(ix, col, p);
-        });
-        ix.rm.calls += 1;
-        (compact ? ix.rm.compactions : ix.rm.rebuilds) += 1;
-        ix.rm.docs = p.removed;
-        ix.rm.bytes = old_size - L.size;
-        ix.rm.last_ms = wall_ms() - t0;
+        ColumnChangePtr c = remove_prepare(ix, ids, nids, removed, missing);
+        if (c) column_commit(ix, *c);
     });
 }
 
-// Documents join a built index without a rebuild (append.hip).  The array over "old documents, then new documents" is the stable
-// merge of the old array and the new documents' own array, ties old first; an array in the reference's order (bytes >= 0x80 under
-// reference_compat) depends on bucket sizes that change with n, so there text and tables are extended on the device and the array
-// is built over them.  Either way only the new documents are uploaded.
 int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs, uint64_t* appended) {
     if (!h || (ndocs && (!ids || !blob || !doc_start))) return CDB_E_INVALID;
     if (appended) *appended = 0;
@@ -1133,61 +1244,10 @@ int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_
     return guarded(h, [&] {
         Index& ix = h->ix;
         std::lock_guard<std::mutex> g(ix.mu);
-        DeviceScope dscope(ix);
-        const double t0 = wall_ms();
-        const uint64_t built_docs = built_docs_or_refuse(ix, "append");
-        if (!ndocs) return;
-        const uint64_t first = doc_start[0];
-        if (doc_start[ndocs] < first || doc_start[ndocs] - first >= (1ull << 48)) throw Error("doc_start must be non-decreasing");
-        const uint64_t m = doc_start[ndocs] - first;
-        auto count = [&](bool merged) {  // (behind the build or the commit: the handle's keys are the new column's)
-            ix.ap.calls += 1;
-            (merged ? ix.ap.merges : ix.ap.rebuilds) += 1;
-            ix.ap.docs = ndocs;
-            ix.ap.bytes = m;
-            ix.ap.with_keys = ix.key_nsym ? 1 : 0;
-            ix.ap.last_ms = wall_ms() - t0;
-            if (appended) *appended = ndocs;
-        };
-        if (!built_docs) {  // never built, or built over nothing: a build of the given documents
-            build_view_locked(ix, ids, blob, doc_start, ndocs);
-            count(false);
-            return;
-        }
-        const uint64_t n = ix.size, D = ix.ndocs;
-        AppendPlan p;
-        std::vector<uint64_t> new_start(ndocs + 1);  // the new documents behind the old text
-        new_start[0] = n;
-        for (uint64_t d = 0; d < ndocs; ++d) {
-            if (doc_start[d + 1] < doc_start[d]) throw Error("doc_start must be non-decreasing");
-            p.longest = std::max(p.longest, doc_start[d + 1] - doc_start[d]);
-            new_start[d + 1] = n + (doc_start[d + 1] - first);
-        }
-        p.ndocs = ndocs;
-        p.size = m;
-        drained_on_failure(ix, [&] { append_old_longest(ix, p); });
-        // the reference's capacity errors (index.cpp:195-200): nothing has been touched yet
-        const Layout L = layout_from(D + ndocs, n + m, std::max(p.old_longest, p.longest));
-        const Layout Li = layout_from(ndocs, m, p.longest);
-        p.in_bits = Li.bits;
-        p.in_mask = Li.mask;
-        p.in_width = Li.width;
-        p.in_off_bits = Li.off_bits;
-        bool merged = false;
-        replace_column(ix, [&](NewColumn& col) {
-            col.L = L;
-            col.host = NewColumn::HOST_NONE;  // (a staging copy that equals the built column goes: cdb_add* / cdb_save fetch the column back)
-            append_tables(ix, p, ids, new_start.data());
-            append_text_old(ix, p);
-            if (m) upload_pageable(p.text.as<uint8_t>() + n, blob + first, m, ix.stream, ix.device, upload_stream(ix));
-            append_scan_bytes(ix, p);
-            // the merge is exact where the fresh array would be globally sorted; the reference's order is rebuilt
-            const bool valid = n > 0 && ix.sa_sorted && (!ix.reference_compat || !p.high_bytes);
-            merged = valid && ix.debug_append_path != 2;
-            if (merged) append_merge(ix, p, (int)L.bits, L.mask, L.width, layout_packable(ix, L));
-            adopt_blocks(ix, col, p);
-        });
-        count(merged);
+        ColumnChangePtr c = append_prepare(ix, ids, blob, doc_start, ndocs);
+        if (!c) return;
+        column_commit(ix, *c);
+        if (appended) *appended = ndocs;
     });
 }
 

@@ -534,6 +534,23 @@ void append_tables(Index& ix, AppendPlan& p, const int64_t* ids, const uint64_t*
 void append_text_old(Index& ix, AppendPlan& p);     // p.text allocated, the old bytes copied in front, the padding zeroed
 void append_scan_bytes(Index& ix, AppendPlan& p);   // the byte values of the new text (behind its upload); synchronises
 void append_merge(Index& ix, AppendPlan& p, int new_bits, uint64_t new_mask, int new_width, bool new_packed);  // inner build, rank, merge; synchronises
+// capi.hip — cdb_remove and cdb_append in two halves.  Prepare checks the call and makes everything new (text, tables, and where the
+// array is kept its compacted / merged form) in fresh blocks beside the old index, which goes on serving; it throws what the entry
+// point reports, and returns nullptr where there is nothing to commit (nids / ndocs = 0, no held id, a handle that holds nothing on
+// remove: *removed / *missing are complete either way).  column_commit installs a prepared change and counts the call in the
+// handle's stats; only a build over the new text (the reference-order path, or an append to a handle that held nothing) can fail in
+// it, and leaves the handle "never built".  A change that is dropped uncommitted releases its blocks; the handle never knew of it.
+// All three take ix.mu from the caller and set the device and stream themselves.  cdb_remove / cdb_append call the halves back to
+// back; cdb_shards_remove / cdb_shards_append prepare on every shard before they commit on any.
+struct ColumnChange;
+struct ColumnChangeDelete {
+    void operator()(ColumnChange* c) const;
+};
+using ColumnChangePtr = std::unique_ptr<ColumnChange, ColumnChangeDelete>;
+ColumnChangePtr remove_prepare(Index& ix, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
+ColumnChangePtr append_prepare(Index& ix, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs);
+void column_commit(Index& ix, ColumnChange& c);
+void reserve_wait();  // a cdb_reserve still running in the background has finished (every build entry point waits for it first)
 // out = {slots whose kept key differs from the key recomputed from the suffix, slots checked (0: no keys kept)}
 void verify_kept_keys(Index& ix, uint64_t out[2]);
 

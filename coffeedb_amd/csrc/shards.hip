@@ -28,6 +28,7 @@
 #include <thread>
 
 #include "../../include/coffeedb_gpu.h"
+#include "cluster_merge.h"
 #include "index_impl.h"
 #include "scan.h"
 
@@ -904,39 +905,50 @@ int cdb_shards_build(cdb_shards* h) {
 
 // The same from the caller's own strings (string_index's views): nothing is staged in the handle, every shard gathers its
 // documents straight into its pinned upload chunks.  A later cdb_shards_add fetches the column back from the shards.
+}  // extern "C"
+namespace {
+void drop_staging(cdb_shards* h) {  // the column lives on the devices (fetch_staging brings it back on demand)
+    h->ids.clear();
+    h->doc_start.assign(1, 0);
+    std::string().swap(h->text);
+    h->staging_valid = false;
+}
+// ... with h->staging_mu held (cdb_shards_append to a set that was never built is this build)
+void build_views_locked(cdb_shards* h, const int64_t* ids, const char* const* ptrs, const uint64_t* lens, uint64_t ndocs) {
+    std::vector<uint64_t> ds(ndocs + 1, 0);
+    for (uint64_t d = 0; d < ndocs; ++d) ds[d + 1] = ds[d] + lens[d];
+    const int G = (int)h->devices.size();
+    const uint64_t total = ds[ndocs];
+    int used = h->use_all ? G : (int)std::min<uint64_t>((uint64_t)G, std::max<uint64_t>(1, ceil_div(total, h->max_shard_bytes)));
+    used = std::max(1, std::min<int>(used, (int)std::max<uint64_t>(ndocs, 1)));
+    std::vector<uint64_t> b = shard_bounds(ds, used);
+    size_t opts_seen = 0;
+    std::vector<cdb_index*> fresh = fresh_handles(h, &opts_seen);
+    std::vector<std::unique_ptr<MergeRank>> ranks;
+    std::shared_ptr<Transport> tr;
+    try {
+        parallel_shards(used, [&](int i) {
+            const uint64_t d0 = b[i], d1 = b[i + 1];
+            check_handle(fresh[i], cdb_build_views(fresh[i], ids + d0, ptrs + d0, lens + d0, d1 - d0));
+        });
+        make_merge(h->devices, fresh, used, ranks, tr);
+    } catch (...) {
+        ranks.clear();
+        tr.reset();
+        for (cdb_index* p : fresh) cdb_destroy(p);
+        throw;
+    }
+    std::unique_lock<StateLock> st(h->state);
+    install(h, fresh, used, b, ranks, tr, opts_seen);
+    drop_staging(h);  // (the column lives on the devices and with the caller)
+}
+}  // namespace
+extern "C" {
 int cdb_shards_build_views(cdb_shards* h, const int64_t* ids, const char* const* ptrs, const uint64_t* lens, uint64_t ndocs) {
     if (!h || (ndocs && (!ids || !ptrs || !lens))) return CDB_E_INVALID;
     return guarded_on(h, [&] {
         std::lock_guard<std::mutex> sg(h->staging_mu);
-        std::vector<uint64_t> ds(ndocs + 1, 0);
-        for (uint64_t d = 0; d < ndocs; ++d) ds[d + 1] = ds[d] + lens[d];
-        const int G = (int)h->devices.size();
-        const uint64_t total = ds[ndocs];
-        int used = h->use_all ? G : (int)std::min<uint64_t>((uint64_t)G, std::max<uint64_t>(1, ceil_div(total, h->max_shard_bytes)));
-        used = std::max(1, std::min<int>(used, (int)std::max<uint64_t>(ndocs, 1)));
-        std::vector<uint64_t> b = shard_bounds(ds, used);
-        size_t opts_seen = 0;
-        std::vector<cdb_index*> fresh = fresh_handles(h, &opts_seen);
-        std::vector<std::unique_ptr<MergeRank>> ranks;
-        std::shared_ptr<Transport> tr;
-        try {
-            parallel_shards(used, [&](int i) {
-                const uint64_t d0 = b[i], d1 = b[i + 1];
-                check_handle(fresh[i], cdb_build_views(fresh[i], ids + d0, ptrs + d0, lens + d0, d1 - d0));
-            });
-            make_merge(h->devices, fresh, used, ranks, tr);
-        } catch (...) {
-            ranks.clear();
-            tr.reset();
-            for (cdb_index* p : fresh) cdb_destroy(p);
-            throw;
-        }
-        std::unique_lock<StateLock> st(h->state);
-        install(h, fresh, used, b, ranks, tr, opts_seen);
-        h->ids.clear();
-        h->doc_start.assign(1, 0);
-        std::string().swap(h->text);
-        h->staging_valid = false;  // (the column lives on the devices and with the caller)
+        build_views_locked(h, ids, ptrs, lens, ndocs);
     });
 }
 
@@ -1434,6 +1446,214 @@ int cdb_shards_query_batch_offsets(cdb_shards* h, const char* blob, const uint64
                                    cdb_hits* hits) {
     if (!hits) return CDB_E_INVALID;
     return shards_batch_impl(h, blob, offsets, npat, out, hits);
+}
+
+// ---- remove, append and cluster on a sharded column (include/coffeedb_gpu.h) ---------------------------------------------------
+// Remove and append change WHICH documents the shards hold, so they are writers like a build: staging_mu, then the exclusive
+// state lock for the whole call (no query runs meanwhile), then the ix.mu of the shards they touch in ascending order.  All or
+// nothing: every shard PREPARES its new column beside the serving one (index_impl.h: remove_prepare / append_prepare); one
+// failure drops every prepared column and the old ones go on serving; only when all stand does every shard commit.
+namespace {
+// cdb_remove's / cdb_append's refusal for the set: documents staged with cdb_shards_add* since the last build or load
+void refuse_pending(const cdb_shards* h, const char* op) {
+    const uint64_t built = h->used ? h->bounds[h->used] : 0;
+    if (h->staging_valid && h->ids.size() > built) throw Error(std::string(op) + ": documents were added since the last build");
+}
+// the bounds follow the documents every shard in use holds now (an emptied or "never built" shard holds none and stays in place)
+void recount_bounds(cdb_shards* h) {
+    std::vector<uint64_t> b{0};
+    for (int i = 0; i < h->used; ++i) {
+        const Index& ix = h->shard[i]->ix;
+        b.push_back(b.back() + (ix.width ? ix.ndocs : 0));
+    }
+    h->bounds.swap(b);
+}
+// ch[i]: shard i's prepared change (null: that shard stays as it is).  Exclusive state lock and the shards' ix.mu held.
+void commit_changes(cdb_shards* h, std::vector<ColumnChangePtr>& ch) {
+    bool any = false;
+    for (const ColumnChangePtr& c : ch) any = any || c;
+    if (!any) return;
+    try {
+        parallel_shards((int)ch.size(), [&](int i) {
+            if (ch[i]) column_commit(h->shard[i]->ix, *ch[i]);
+        });
+    } catch (...) {  // a build over the new text failed on some shard (it is "never built" now); the others committed
+        recount_bounds(h);
+        drop_staging(h);
+        throw;
+    }
+    recount_bounds(h);
+    drop_staging(h);
+}
+}  // namespace
+
+int cdb_shards_remove(cdb_shards* h, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
+    if (!h || (nids && !ids)) return CDB_E_INVALID;
+    if (removed) *removed = 0;
+    if (missing) *missing = 0;
+    reserve_wait();
+    return guarded_on(h, [&] {
+        std::lock_guard<std::mutex> sg(h->staging_mu);
+        std::unique_lock<StateLock> st(h->state);
+        refuse_pending(h, "remove");
+        if (!nids) return;
+        const int G = h->used;
+        if (!G) {  // never built: the set holds no id
+            if (missing) *missing = nids;
+            return;
+        }
+        std::vector<std::unique_lock<std::mutex>> locks;  // ascending shard order
+        for (int i = 0; i < G; ++i) locks.emplace_back(h->shard[i]->ix.mu);
+        std::vector<ColumnChangePtr> ch(G);  // (dropped on a failure, before the locks go)
+        std::vector<uint64_t> rem(G, 0), mis(G, 0);
+        parallel_shards(G, [&](int i) { ch[i] = remove_prepare(h->shard[i]->ix, ids, nids, &rem[i], &mis[i]); });
+        uint64_t r = 0, m = 0;
+        for (int i = 0; i < G; ++i) {
+            r += rem[i];
+            m += mis[i];
+        }
+        // Object ids are disjoint across shards: an entry of `ids` held by one shard is missing in the other G - 1, an entry held
+        // by none is missing in all G.  So sum(missing_s) = (G - 1) * held + G * unheld = (G - 1) * nids + unheld.
+        if (removed) *removed = r;
+        if (missing) *missing = m - (uint64_t)(G - 1) * nids;
+        commit_changes(h, ch);
+    });
+}
+
+int cdb_shards_append(cdb_shards* h, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs, uint64_t* appended) {
+    if (!h || (ndocs && (!ids || !blob || !doc_start))) return CDB_E_INVALID;
+    if (appended) *appended = 0;
+    reserve_wait();
+    return guarded_on(h, [&] {
+        std::lock_guard<std::mutex> sg(h->staging_mu);  // (every writer holds it: h->used and h->ids stand still below)
+        refuse_pending(h, "append");
+        if (!ndocs) return;
+        const uint64_t first = doc_start[0];
+        for (uint64_t d = 0; d < ndocs; ++d)
+            if (doc_start[d + 1] < doc_start[d]) throw Error("doc_start must be non-decreasing");
+        if (doc_start[ndocs] - first >= (1ull << 48)) throw Error("doc_start must be non-decreasing");
+        const uint64_t m = doc_start[ndocs] - first;
+        if (!h->used) {  // never built: a build of the given documents
+            std::vector<const char*> ptrs(ndocs);
+            std::vector<uint64_t> lens(ndocs);
+            for (uint64_t d = 0; d < ndocs; ++d) {
+                ptrs[d] = blob + doc_start[d];
+                lens[d] = doc_start[d + 1] - doc_start[d];
+            }
+            build_views_locked(h, ids, ptrs.data(), lens.data(), ndocs);
+            if (appended) *appended = ndocs;
+            return;
+        }
+        std::unique_lock<StateLock> st(h->state);
+        const int G = (int)h->devices.size(), used = h->used;
+        Index& lx = h->shard[used - 1]->ix;
+        const uint64_t last_bytes = lx.width ? lx.size : 0;
+        // The new documents are numbered behind all old ones: they belong at the end of the column.  They join the last shard in use
+        // while it stays within max_shard_bytes — or when no idle device slot is left, as the initial build's min(G, ...) lets its
+        // last shard grow ...
+        if (last_bytes + m <= h->max_shard_bytes || used == G) {
+            std::unique_lock<std::mutex> lk(lx.mu);
+            std::vector<ColumnChangePtr> ch(used);
+            ch[used - 1] = append_prepare(lx, ids, blob, doc_start, ndocs);  // (capacity errors fire here: nothing was touched)
+            commit_changes(h, ch);
+            if (appended) *appended = ndocs;
+            return;
+        }
+        // ... otherwise the last shard stays as it is and the batch opens new shards on the idle slots: cut at document boundaries
+        // into pieces of at most max_shard_bytes (a lone larger document is its own piece; the last slot takes the remainder)
+        const int slots = G - used;
+        std::vector<uint64_t> cut{0};
+        uint64_t acc = 0;
+        for (uint64_t d = 0; d < ndocs; ++d) {
+            const uint64_t len = doc_start[d + 1] - doc_start[d];
+            if (d > cut.back() && acc + len > h->max_shard_bytes && (int)cut.size() < slots) {
+                cut.push_back(d);
+                acc = 0;
+            }
+            acc += len;
+        }
+        cut.push_back(ndocs);
+        const int pieces = (int)cut.size() - 1;
+        // the new shards are built on fresh handles that carry the options set so far (the state lock keeps cdb_shards_set_option
+        // waiting: it then reaches them through h->shard); a failure destroys them and nothing has changed
+        std::vector<std::pair<std::string, int64_t>> options;
+        {
+            std::lock_guard<std::mutex> g(h->opt_mu);
+            options = h->options;
+        }
+        std::vector<cdb_index*> fresh(pieces, nullptr);
+        struct Destroyer {
+            std::vector<cdb_index*>& v;
+            ~Destroyer() { for (cdb_index* p : v) cdb_destroy(p); }  // (after the commit: the idle handles that were replaced)
+        } destroyer{fresh};
+        for (int p = 0; p < pieces; ++p) {
+            if (cdb_create(&fresh[p], h->devices[used + p]) != CDB_OK) throw DeviceError("HIP error: cannot create a shard handle");
+            for (auto& kv : options) (void)cdb_set_option(fresh[p], kv.first.c_str(), kv.second);
+        }
+        parallel_shards(pieces, [&](int p) {
+            check_handle(fresh[p], cdb_build_view(fresh[p], ids + cut[p], blob, doc_start + cut[p], cut[p + 1] - cut[p]));
+        });
+        // more shards: the merge ranks and the transport (the LocalTransport's board, the RCCL communicator) are sized by the count
+        std::vector<cdb_index*> next(h->shard);
+        for (int p = 0; p < pieces; ++p) next[used + p] = fresh[p];
+        std::vector<std::unique_ptr<MergeRank>> ranks;
+        std::shared_ptr<Transport> tr;
+        make_merge(h->devices, next, used + pieces, ranks, tr);
+        h->ranks.swap(ranks);  // the commit: nothing below fails
+        h->tr.swap(tr);
+        for (int p = 0; p < pieces; ++p) std::swap(h->shard[used + p], fresh[p]);
+        h->used = used + pieces;
+        recount_bounds(h);
+        drop_staging(h);
+        if (appended) *appended = ndocs;
+    });
+}
+
+// A query: every shard groups the rows it holds and hands over the groups' strings; the lists meet on the host (cluster_merge.h).
+// The strings of a with_values result cross PCIe anyway, and a merge that reads every byte once costs less than that download.
+int cdb_shards_cluster(cdb_shards* h, const int64_t* ids, uint64_t nrows, int with_values, cdb_clusters* out) {
+    if (!h || !out || (nrows && !ids)) return CDB_E_INVALID;
+    *out = cdb_clusters{};
+    const int rc = guarded_on(h, [&] {
+        std::shared_lock<StateLock> st(h->state);
+        const int G = std::max(h->used, 1);
+        if (G == 1) {
+            check_shard(h, 0, cdb_cluster(h->shard[0], ids, nrows, with_values, out));
+            return;
+        }
+        std::vector<cdb_clusters> parts(G);
+        for (auto& x : parts) x = cdb_clusters{};
+        struct Cleanup {
+            std::vector<cdb_clusters>& p;
+            ~Cleanup() { for (auto& x : p) cdb_clusters_free(&x); }
+        } cleanup{parts};
+        parallel_shards(G, [&](int i) { check_shard(h, i, cdb_cluster(h->shard[i], ids, nrows, 1, &parts[i])); });
+        std::vector<ClusterList> lists(G);
+        uint64_t miss = 0;
+        for (int i = 0; i < G; ++i) {
+            lists[i] = ClusterList{parts[i].ngroups, parts[i].counts, parts[i].rep_ids, parts[i].value_ptr, parts[i].value_blob};
+            miss += parts[i].missing;
+        }
+        MergedClusters mc;
+        merge_cluster_lists(lists.data(), lists.size(), mc);
+        const uint64_t ng = mc.ngroups();
+        out->ngroups = ng;
+        out->missing = miss - (uint64_t)(G - 1) * nrows;  // (a row held by one shard is missing in the other G - 1: as in cdb_shards_remove)
+        out->counts = (int64_t*)host_alloc(ng * 8);
+        out->rep_ids = (int64_t*)host_alloc(ng * 8);
+        if (ng) {
+            std::memcpy(out->counts, mc.counts.data(), ng * 8);
+            std::memcpy(out->rep_ids, mc.rep_ids.data(), ng * 8);
+        }
+        if (with_values) {
+            out->value_ptr = (uint64_t*)host_alloc((ng + 1) * 8);
+            out->value_blob = (char*)host_alloc(mc.value_blob.size());
+            std::memcpy(out->value_ptr, mc.value_ptr.data(), (ng + 1) * 8);
+            if (!mc.value_blob.empty()) std::memcpy(out->value_blob, mc.value_blob.data(), mc.value_blob.size());
+        }
+    });
+    if (rc != CDB_OK) cdb_clusters_free(out);
+    return rc;
 }
 
 }  // extern "C"

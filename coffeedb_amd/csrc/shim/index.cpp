@@ -256,6 +256,7 @@ void string_index::build() {
     if (shards) {
         const int rc = cdb_shards_build_views(shards, ids.data(), ptrs.data(), lens.data(), ids.size());
         if (rc != CDB_OK) rethrow(shards, rc);
+        built = ids.size();
         return;
     }
     const int rc = cdb_build_views(handle, ids.data(), ptrs.data(), lens.data(), ids.size());
@@ -264,9 +265,14 @@ void string_index::build() {
 }
 
 bool string_index::remove(const std::vector<int64_t>& gone_ids) {
-    if (!handle || ids.size() != built) return false;
-    const int rc = cdb_remove(handle, gone_ids.data(), gone_ids.size(), nullptr, nullptr);
-    if (rc != CDB_OK) rethrow(handle, rc);
+    if (ids.size() != built) return false;
+    if (shards) {
+        const int rc = cdb_shards_remove(shards, gone_ids.data(), gone_ids.size(), nullptr, nullptr);
+        if (rc != CDB_OK) rethrow(shards, rc);
+    } else {
+        const int rc = cdb_remove(handle, gone_ids.data(), gone_ids.size(), nullptr, nullptr);
+        if (rc != CDB_OK) rethrow(handle, rc);
+    }
     std::vector<int64_t> gone(gone_ids);
     std::sort(gone.begin(), gone.end());
     size_t k = 0;
@@ -284,15 +290,20 @@ bool string_index::remove(const std::vector<int64_t>& gone_ids) {
 }
 
 bool string_index::append() {
-    if (!handle || ids.size() == built) return false;
+    if (ids.size() == built) return false;
     const size_t fresh = ids.size() - built;
     std::string blob;  // (cdb_append takes one blob: the staging copy of the NEW documents only)
     std::vector<uint64_t> doc_start(fresh + 1, 0);
     for (size_t k = 0; k < fresh; ++k) doc_start[k + 1] = doc_start[k] + lens[built + k];
     blob.reserve(doc_start[fresh] + 1);
     for (size_t k = 0; k < fresh; ++k) blob.append(ptrs[built + k], lens[built + k]);
-    const int rc = cdb_append(handle, ids.data() + built, blob.data(), doc_start.data(), fresh, nullptr);
-    if (rc != CDB_OK) rethrow(handle, rc);
+    if (shards) {
+        const int rc = cdb_shards_append(shards, ids.data() + built, blob.data(), doc_start.data(), fresh, nullptr);
+        if (rc != CDB_OK) rethrow(shards, rc);
+    } else {
+        const int rc = cdb_append(handle, ids.data() + built, blob.data(), doc_start.data(), fresh, nullptr);
+        if (rc != CDB_OK) rethrow(handle, rc);
+    }
     built = ids.size();
     return true;
 }
@@ -316,13 +327,17 @@ index::result_type string_index::query(const std::string& keyword) const {
 }
 
 index::cluster_type string_index::cluster(const result_type& rows) const {
-    if (!handle) throw std::logic_error("cluster: not available on a sharded string index (COFFEEDB_GPUS)");
     std::vector<int64_t> ids;
     ids.reserve(rows.size());
     for (const auto& r : rows) ids.push_back(r.first);
     clusters_guard g;
-    const int rc = cdb_cluster(handle, ids.data(), ids.size(), 1, &g.cl);
-    if (rc != CDB_OK) rethrow(handle, rc);
+    if (shards) {
+        const int rc = cdb_shards_cluster(shards, ids.data(), ids.size(), 1, &g.cl);
+        if (rc != CDB_OK) rethrow(shards, rc);
+    } else {
+        const int rc = cdb_cluster(handle, ids.data(), ids.size(), 1, &g.cl);
+        if (rc != CDB_OK) rethrow(handle, rc);
+    }
     return cdb_shim::cluster_rows(g.cl);
 }
 

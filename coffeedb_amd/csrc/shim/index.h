@@ -140,17 +140,18 @@ public:
     std::vector<std::optional<std::string>> render_rows(const result_type& rows, const std::vector<std::string>& keywords,
                                                         const std::string& left, const std::string& right) const;
     // NEW: database.cpp:442-460 for this field — the result rows grouped by their whole document on the device (cdb_cluster),
-    // in std::string order.  One GPU only (std::logic_error with COFFEEDB_GPUS).
+    // in std::string order; with COFFEEDB_GPUS every shard groups its rows and the lists are merged (cdb_shards_cluster).
     cluster_type cluster(const result_type& rows) const;
     // NEW: "remove + build" for this field (interface.cpp:274-285, database.cpp:461-466 followed by :170-282) without the build — the
     // documents `ids` leave the built index on the device (cdb_remove) and the views add() collected for them are forgotten, so a
-    // later build() does not bring them back.  Ids the index does not hold are ignored.  false = not available — a sharded index
-    // (COFFEEDB_GPUS), or documents were added since the last build(): nothing changed, the caller rebuilds as the reference does.
+    // later build() does not bring them back.  Ids the index does not hold are ignored.  With COFFEEDB_GPUS every shard drops the
+    // documents it holds (cdb_shards_remove).  false = documents were added since the last build(): nothing changed, the caller
+    // rebuilds as the reference does.
     bool remove(const std::vector<int64_t>& ids);
     // NEW: "insert ... build" for this field (interface.cpp:157-180, :286-288) without the rebuild — the views add() collected since
     // the last build() join the built index on the device (cdb_append: only they are gathered, uploaded and sorted).  The strings
-    // must stay valid until the call has returned, as for build().  false = nothing was pending, or not available (a sharded index,
-    // COFFEEDB_GPUS): nothing changed, the caller builds as the reference does.
+    // must stay valid until the call has returned, as for build().  With COFFEEDB_GPUS they go to the end of the sharded column
+    // (cdb_shards_append).  false = nothing was pending: nothing changed.
     bool append();
     // NEW (no counterpart in the reference): announce a string column of roughly `bytes` bytes BEFORE the data is loaded —
     // start_server() calls init() and then build() (server.cpp:43-44); called at the start of init() with the size of the raw

@@ -255,7 +255,7 @@ int cdb_debug_column_profile_dump(cdb_column* c, char* buf, size_t cap);
  * while the handle's lock is held; for a column of mostly distinct documents that is nearly the whole text (254 ms for 256 MiB
  * of distinct 256-byte documents on an MI355X host), once per build.  Pure ASCII text and reference_compat = 0 skip that step.
  * cdb_debug_column_set_option "debug_cluster_path" (0 automatic, 1 sort + run lengths, 2 counters per position) forces one of
- * the column's two paths (tests, tools/bench_cluster.py).  Not available on cdb_shards. */
+ * the column's two paths (tests, tools/bench_cluster.py).  A sharded string column clusters with cdb_shards_cluster. */
 typedef struct cdb_clusters {
     uint64_t ngroups;
     uint64_t missing;      /* input rows whose id the column / index does not hold (skipped) */
@@ -392,7 +392,7 @@ void cdb_rendered_free(cdb_rendered* r);
  * array is treated like damage behind a build.
  *   Stats: "removes" (calls that dropped something), "remove_compactions", "remove_rebuilds", and of the last such call "remove_docs",
  * "remove_bytes" (text bytes dropped), "remove_ms" (wall, under the lock); with option profile the kernels are timed as rm_*.
- * Not available on cdb_shards (each shard's document bounds would have to be re-cut): rebuild there. */
+ * A sharded string column removes with cdb_shards_remove. */
 int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
 /* The same for a column, with the same counting rules: the rows leave the built and the staged rows, and the column's own build (a
  * device sort of milliseconds) runs over the rest.  The result equals a fresh column built from the surviving rows; a failed build
@@ -436,7 +436,7 @@ int cdb_column_remove(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t
  *   Stats: "appends" (calls that added something), "append_merges", "append_rebuilds", and of the last such call "append_docs",
  * "append_bytes" (text bytes added), "append_ms" (wall, under the lock), "append_keys_kept"; with option profile the kernels are
  * timed as ap_*.
- * Not available on cdb_shards (each shard's document bounds would have to be re-cut): rebuild there. */
+ * A sharded string column appends with cdb_shards_append. */
 int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs, uint64_t* appended);
 
 /* Batched query with patterns and results left in device memory (multi-GPU merge over RCCL, HBM-
@@ -520,6 +520,57 @@ int cdb_shards_query_and(const cdb_shards_key_query* keys, int nkeys, int ranked
 int cdb_shards_add_raw_dir(cdb_shards* h, const char* dir, const char* key, uint64_t* records, uint64_t* added);
 int cdb_shards_save(cdb_shards* h, const char* path);
 int cdb_shards_load(cdb_shards* h, const char* path);
+/* cdb_remove, cdb_append and cdb_cluster for the sharded column.  Arguments, NULL rules, error codes and messages are those of the
+ * single-handle calls; errors are read with cdb_shards_last_error, and a shard's failure keeps its own code and text.
+ *   The contract.  After a successful call every cdb_shards_* query entry point (query, query_batch and query_batch_offsets with the
+ * host merge and with device_merge = 1, query_or, query_ranked, query_and, query_spans, render_rows, cluster, save followed by load)
+ * answers as ONE cdb_index over the same documents in the same order would: the survivors in their original order after a remove,
+ * the old documents and then the new ones after an append.  It is about answers, not about where the cuts lie: a fresh
+ * cdb_shards_build of the same documents may cut them differently.  One limit, which a plain cdb_shards_build shares: where the
+ * arrays are in the reference's order (reference_compat = 1 and bytes >= 0x80) the answers follow the reference's own search over
+ * each array, and above its bucket size (4096 suffixes, index.cpp:218) they depend on how many suffixes ONE array holds — there a
+ * sharded set and a single index differ even when both were just built, and what holds is that every shard equals a fresh index
+ * over its own documents.
+ *   All or nothing.  Both writers hold the set exclusively (queries wait, as during the swap of a build) and the locks of the shards
+ * they touch.  Every shard first PREPARES its new column beside the serving one; if any shard fails there, every prepared column is
+ * dropped, the call returns that shard's error and the old column goes on serving on every shard.  Only when all stand does every
+ * shard commit.  One step can still fail behind the commit point: on the reference-order path (reference_compat = 1 and bytes >= 0x80,
+ * see cdb_remove / cdb_append "Paths") and for an append into a shard that holds nothing, the array is built over the new text AFTER
+ * the shard's commit.  The single-handle rule then applies per shard.  What a caller finds after such a failure: the call returns the
+ * failing shard's error; that shard is "never built" (it answers {} and holds no document: the documents it served are gone from the
+ * column); every other shard has committed its change; cdb_shards_count is unchanged and cdb_shards_first_doc describes exactly the
+ * documents that are still served; the host staging copy is dropped.  The column is consistent and answers every query, but it is
+ * neither the old nor the new one: rebuild it from the source.
+ *   Pending additions.  Documents staged with cdb_shards_add* since the last build or load make remove and append fail with
+ * CDB_E_INVALID and cdb_remove's / cdb_append's message ("remove: / append: documents were added since the last build"); nothing
+ * changes.  After a call that changed the column the ONE host staging copy is dropped; cdb_shards_add* and cdb_shards_build fetch the
+ * column back from the shards on demand, so "remove, add, rebuild" works.
+ *
+ * cdb_shards_remove.  Every shard removes the ids it holds (cdb_remove's paths, the shards in parallel).  *removed is the sum over the
+ * shards; *missing is the number of entries of `ids` that no shard holds (a held id given twice is removed once and is not missing).
+ * The document bounds are recomputed from the shards' surviving documents and cdb_shards_first_doc follows.  A shard that loses all
+ * its documents STAYS IN PLACE, empty: cdb_shards_count does not change, nothing is re-cut, and every query path (the device merge
+ * included) answers correctly with an empty shard in the middle or at either end.  nids = 0 changes nothing; a set that was never
+ * built answers every id missing; removing every document leaves a column that answers like an empty one.  Per-shard stats
+ * ("removes", "remove_compactions", ...) are read through cdb_shards_get.
+ *
+ * cdb_shards_append.  The new documents are numbered behind all old ones, so they go to the end of the column.  If no shard is in use
+ * the call is cdb_shards_build_views over the given documents.  Otherwise, if the last shard in use stays within max_shard_bytes with
+ * the new bytes, or no idle device slot is left (as the initial build lets its last shards grow once all devices are in use), they
+ * join that shard through cdb_append.  Otherwise the last shard stays as it is: the new documents are cut at document boundaries into
+ * pieces of at most max_shard_bytes (a lone larger document is its own piece; when the slots run out the last slot takes the rest)
+ * and built on the next idle slots — cdb_shards_count grows, and the merge ranks and the transport are remade for the new count.
+ * The options set so far reach the new shards.  ndocs = 0 changes nothing; the reference's capacity errors fire before anything is
+ * touched.  *appended (may be NULL) = the documents that joined.
+ *
+ * cdb_shards_cluster.  A query (it runs beside other queries).  Every shard clusters the rows it holds; the per-shard group lists,
+ * each in std::string order whatever reference_compat is, are merged on the host (csrc/cluster_merge.h): groups with equal strings
+ * fuse, their counts add, rep_id is the minimum; missing = rows no shard holds; sum(counts) + missing == nrows always.  The strings are
+ * fetched from every shard even with with_values = 0 (the merge compares them); value_ptr / value_blob are then NULL.  `values` is
+ * always NULL.  nrows = 0 and a set that was never built behave as in cdb_cluster.  Release the result with cdb_clusters_free. */
+int cdb_shards_remove(cdb_shards* h, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
+int cdb_shards_append(cdb_shards* h, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs, uint64_t* appended);
+int cdb_shards_cluster(cdb_shards* h, const int64_t* ids, uint64_t nrows, int with_values, cdb_clusters* out);
 /* introspection: shards in use after build, the handle of shard i (per-shard parity: its suffix array is that of its
  * documents alone), its first document, and how the shards exchange ("rccl" / "device copies" / "none") */
 int cdb_shards_count(const cdb_shards* h);
