@@ -41,7 +41,7 @@ EXPORTS = [
     "cdb_debug_rowset_profile_dump",
     "cdb_debug_scan", "cdb_debug_scan_partials", "cdb_debug_stable_ranks",
     "cdb_debug_sweep_records", "cdb_debug_vl_tables",
-    "cdb_debug_carried_inplace",
+    "cdb_debug_carried_inplace", "cdb_debug_segsort",
 ]
 
 
@@ -1445,6 +1445,42 @@ def debug_carried_inplace(entries, flags, xbits, form=CARRIED_PACKED40, device=-
     if rc != 0:
         raise CarriedError("cdb_debug_carried_inplace", rc)
     return entries, flags, partials, int(counts[0]), int(counts[1]), bool(ok.value)
+
+
+SEGSORT_FIVE_PASS, SEGSORT_TOP_FIRST = range(2)
+
+
+class SegsortError(RuntimeError):
+    """The segmented-sort hook failed; `status` is the CDB_E_* code of the error thrown inside the library."""
+
+    def __init__(self, what, status):
+        super().__init__(f"{what} failed ({status})")
+        self.status = status
+
+
+def debug_segsort(form, bucket_begin, k32, v32, w16, ehb, carry, packed=True, device=-1):
+    """One bucket group through the segmented sort in the given form (cdb_debug_segsort).  Returns (entries uint64[n],
+    flags uint8[n], cells uint64[ncells, 3] = (begin, end, tile_begin) — empty for the five-pass form —, guards intact)."""
+    lib = load_library()
+    lib.cdb_debug_segsort.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_int)]
+    bb = np.ascontiguousarray(bucket_begin, dtype=np.uint64)
+    k32 = np.ascontiguousarray(k32, dtype=np.uint32)
+    v32 = np.ascontiguousarray(v32, dtype=np.uint32)
+    w16 = np.ascontiguousarray(w16, dtype=np.uint16)
+    n, nb = k32.shape[0], bb.shape[0] - 1
+    if v32.shape != (n,) or w16.shape != (n,) or nb < 1:
+        raise ValueError("record arrays of different lengths, or no bucket")
+    entries = np.zeros(max(n, 1), dtype=np.uint64)
+    flags = np.zeros(max(n, 1), dtype=np.uint8)
+    cells = np.zeros((nb * 256, 3), dtype=np.uint64)
+    ncells, ok = C.c_uint32(0), C.c_int(0)
+    rc = lib.cdb_debug_segsort(device, form, 1 if packed else 0, n, nb, bb.ctypes.data, k32.ctypes.data, v32.ctypes.data, w16.ctypes.data,
+                               ehb, carry, entries.ctypes.data, flags.ctypes.data, cells.ctypes.data, nb * 256, C.byref(ncells), C.byref(ok))
+    if rc != 0:
+        raise SegsortError("cdb_debug_segsort", rc)
+    return entries[:n], flags[:n], cells[:ncells.value].copy(), bool(ok.value)
 
 
 class CdbDebugSweepArgs(C.Structure):

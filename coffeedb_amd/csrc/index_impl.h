@@ -46,6 +46,8 @@ struct BuildStats {
     uint64_t unresolved_after_carried = 0;  // entries still open behind that round (= unresolved_initial where none ran)
     int carried_inplace = 0;     // the carried round's in-place sweep ran (carried_inplace.h): 0 / 1
     uint64_t unresolved_after_inplace = 0;  // entries still open behind that sweep, in front of the carried list round (= unresolved_initial where it did not run)
+    int top_first = 0;           // segmented sort: top key digit first, then 9-byte records inside (bucket, top byte) cells (0 / 1)
+    uint64_t top_first_cells = 0;  // ... non-empty cells of all bucket groups
     int partial_levels = 0;      // ... leftover key bits hold the next symbol quantised to this many levels (sweep form; 0 / 1 = none)
     int vl_key_bits = 0;         // ... keys = the first vl_key_bits - 1 bits of the alphabetic code stream + a "continues" bit (vl_code.h); 0 = dense keys
     double vl_avg_len = 0, vl_rate = 0, vl_est_unresolved = 0, fixed_est_unresolved = 0;
@@ -310,6 +312,8 @@ struct Index {
     bool fuse_records = true;  // bucket-wise build with ONE bucket group: the generated pass writes the records (0 = partition + gather)
     bool fuse_pairclass = true; // bucket-wise build of text with bytes >= 0x80: next-byte classes counted by the tile byte count (0 = separate sweep)
     int carried_inplace = -1;   // the carried round's in-place sweep in front of its list round: -1 = from CARRIED_INPLACE_MIN_N suffixes upward, 0 = off, 1 = on
+    int top_digit_first = -1;   // segmented sort of 40-bit variable-length keys: top key byte first, the other passes per (bucket, top byte) cell
+                                // over 9-byte records (run_segmented): -1 = from TOP_FIRST_MIN_N suffixes upward, 0 = off, 1 = on where it applies
     int carried_bits = -1;      // code-stream bits carried behind variable-length keys (sa_build.hip: carried round): -1 = as many as fit, 0 = none, 1..6 = at most
     bool list_rounds = true;    // text-extension rounds behind the first compact from the previous round's list (0 = from the flag array)
     int group_sort_cap = 4096;  // ... members of a group on one side of an entry beyond which the pass gives up (its work is also bounded, sa_build.hip)

@@ -305,6 +305,11 @@ struct SegArgs {
     uint32_t tiles = 0;                  // tiles of all segments together
     uint32_t start_stride = 0;           // digit starts of segment g at digit_start[g * start_stride + d]
 };
+// A segmented pass on the low byte of u16 aux words that writes them WITHOUT that byte, as bytes: the top-digit-first sort
+// (radix_sort_top_first) sorts on the key's top byte here, and the cell a record lands in implies it from then on.
+struct SegShrinkArgs : SegArgs {
+    uint8_t* wout8 = nullptr;  // [m] aux >> 8 of every record, in output order (the pass's own wout is not written)
+};
 // The LAST pass of a segmented sort of packed bucket records writes the finished suffix-array entries and their
 // group flags instead of the records: entry = (aux >> hi_shift) << 32 | value, flag bit0 = first of a group of equal
 // keys, bit1 = still unresolved (sa_initial_direct.hip: sa_flags_of).  A tile sees the neighbours of all its elements except
@@ -418,6 +423,8 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::MINW) void rs_onesweep_kernel(
     constexpr bool KEEPM = std::is_same<Seg, SegFinalKeepMsdArgs>::value;  // ... of an MSD-first sort (no auxiliary input)
     constexpr bool KEEP = std::is_same<Seg, SegFinalKeepArgs>::value || KEEPM;  // flags + edge records beside the ordinary record write-out
     constexpr bool FLAGS = FINAL || KEEP;
+    constexpr bool SHRINK = std::is_same<Seg, SegShrinkArgs>::value;  // the aux word leaves without its low byte, as a byte (seg.wout8)
+    static_assert(!SHRINK || (std::is_same<W, uint16_t>::value && Cfg::REUSE && !std::is_same<V, NoVal>::value), "shrinking pass: u16 aux words, shared staging");
     static_assert(!SEG || (!GEN && !Cfg::DMA), "segmented passes: materialised records");
     static_assert(!FLAGS || Cfg::REUSE || KEEPM, "flag-writing passes: shared staging (the MSD-first last pass also runs with keys and values staged at once)");
     constexpr bool HAS_V = !std::is_same<V, NoVal>::value;
@@ -1214,7 +1221,9 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::MINW) void rs_onesweep_kernel(
                     continue;
                 }
                 if (!GEN || kout) rs_store<NTM>(kout + s_gbase[dd] + i, k);
-                if constexpr (HAS_W && !W32G) {
+                if constexpr (SHRINK) {  // the digit this pass sorted on leaves the record: the cell implies it from here on
+                    seg.wout8[s_gbase[dd] + i] = (uint8_t)((uint32_t)s_aux[i] >> 8);
+                } else if constexpr (HAS_W && !W32G) {
                     if (!GEN || wout) rs_store<NTM>(wout + s_gbase[dd] + i, (W)s_aux[i]);
                 }
             }
@@ -1915,8 +1924,10 @@ void radix_sort_segmented(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uin
 constexpr int RS_MSD_HIST_TILES = 32;  // consecutive tiles per workgroup of the histogram sweep
 
 // hist[g][p][d] (the [nseg][8][256] layout of rs_seg_digit_start_kernel) from the materialised records of every segment:
-// digit p < lead is byte p of the auxiliary word, digit lead + q byte q of the key (the order the segmented passes sort in)
-template <typename W>
+// digit p < lead is byte p of the auxiliary word, digit lead + q byte q of the key (the order the segmented passes sort in).
+// KEYS = false: only auxiliary digits are counted (npass <= lead) and the keys are never loaded — sizeof(W) bytes per record
+// (the top-digit histogram of radix_sort_top_first)
+template <typename W, bool KEYS = true>
 __global__ __launch_bounds__(1024) void rs_seg_hist_kernel(const uint32_t* __restrict__ keys, const W* __restrict__ aux, int lead, int npass,
                                                            const uint32_t* __restrict__ tile_seg, const SegInfo* __restrict__ segs,
                                                            uint32_t tiles, unsigned long long* __restrict__ hist) {
@@ -1968,10 +1979,11 @@ __global__ __launch_bounds__(1024) void rs_seg_hist_kernel(const uint32_t* __res
         const uint64_t a0 = (base + 3) & ~3ull;  // (the arrays are 256-byte aligned blocks: index alignment = address alignment)
         const uint64_t q0 = a0 < end ? a0 : end;
         const uint32_t nquad = (uint32_t)((end - q0) / 4);
-        if ((uint64_t)tid < q0 - base) count(keys[base + tid], lead > 0 ? (uint32_t)aux[base + tid] : 0u);
+        constexpr bool need_k = KEYS;
+        if ((uint64_t)tid < q0 - base) count(need_k ? keys[base + tid] : 0u, lead > 0 ? (uint32_t)aux[base + tid] : 0u);
         {
             const uint64_t tb = q0 + 4ull * nquad;
-            if ((uint64_t)tid < end - tb) count(keys[tb + tid], lead > 0 ? (uint32_t)aux[tb + tid] : 0u);
+            if ((uint64_t)tid < end - tb) count(need_k ? keys[tb + tid] : 0u, lead > 0 ? (uint32_t)aux[tb + tid] : 0u);
         }
         constexpr int QPT = RS_SEG_TILE / 4 / 1024;  // quads per thread of a full tile
         uint4 kq[QPT];
@@ -1982,7 +1994,7 @@ __global__ __launch_bounds__(1024) void rs_seg_hist_kernel(const uint32_t* __res
             kq[r] = make_uint4(0, 0, 0, 0);
             aq[r][0] = aq[r][1] = aq[r][2] = aq[r][3] = 0;
             if (g < nquad) {
-                kq[r] = *reinterpret_cast<const uint4*>(keys + q0 + 4ull * g);
+                if (need_k) kq[r] = *reinterpret_cast<const uint4*>(keys + q0 + 4ull * g);
                 if (lead > 0) {
                     if constexpr (sizeof(W) == 4) {
                         const uint4 w = *reinterpret_cast<const uint4*>(aux + q0 + 4ull * g);
@@ -2009,6 +2021,131 @@ __global__ __launch_bounds__(1024) void rs_seg_hist_kernel(const uint32_t* __res
         }
     }
     flush();
+}
+
+// ---------------------------------------------------------------------------------------------
+// segmented sort, top key digit first (bucket-wise builds with 40-bit keys in (u32, u32, u16) records)
+// ---------------------------------------------------------------------------------------------
+// The five-pass form sorts on the key's low byte first and then carries it through four more passes, because the group flags
+// of the last pass need the whole key.  Here the records hold the key's TOP byte in the aux word's low byte and its low 32
+// bits in k32 (VlTables::top_in_aux); one stable pass per bucket sorts on that byte and drops it (SegShrinkArgs), a CELL =
+// (bucket, top byte) implies it from then on, and the other four passes run per cell over (u32, u32, u8) records — the same
+// order, ties included, as five stable LSD passes.  Equal keys never span cells, so flags and the edge fix work per cell.
+// The cells come from the top-digit histogram on the HOST (one synchronise per bucket group).
+constexpr uint64_t TOP_FIRST_MIN_N = 1ull << 26;
+struct TopFirstWork {
+    DevBuf cells, tile_seg, hist, starts;  // capacities: cell_cap cells, tile_cap tiles (radix_sort_top_first checks them)
+    uint32_t cell_cap = 0, tile_cap = 0;
+    std::vector<SegInfo> h_cells;            // (stays alive until the caller has synchronised: source of an asynchronous upload)
+    std::vector<unsigned long long> h_hist;
+    void alloc(uint32_t cells_max, uint32_t tiles_max) {
+        cell_cap = cells_max;
+        tile_cap = tiles_max;
+        cells.alloc((size_t)cells_max * sizeof(SegInfo));
+        tile_seg.alloc((size_t)tiles_max * sizeof(uint32_t));
+        hist.alloc((size_t)cells_max * 8 * 256 * sizeof(uint64_t));
+        starts.alloc((size_t)cells_max * 8 * 256 * sizeof(uint64_t));
+    }
+};
+// the non-empty cells of a bucket group in (bucket, digit) order from its top-digit counts top[b][8][256] (row 0 of every bucket);
+// returns their tiles.  Throws where the counts do not add up to the buckets or the tiles leave 32 bits.
+inline uint32_t rs_top_first_cells(const SegInfo* h_segs, uint32_t nseg, const unsigned long long* top, std::vector<SegInfo>& cells) {
+    cells.clear();
+    uint64_t tiles = 0;
+    for (uint32_t b = 0; b < nseg; ++b) {
+        unsigned long long at = h_segs[b].begin;
+        for (uint32_t d = 0; d < 256; ++d) {
+            const unsigned long long c = top[((size_t)b * 8) * 256 + d];
+            if (!c) continue;
+            cells.push_back(SegInfo{at, at + c, (uint32_t)tiles, d, 0ull, 0ull});
+            tiles += ceil_div((uint64_t)c, (uint64_t)RS_SEG_TILE);
+            at += c;
+            if (tiles > 0xFFFFFFFFull) throw InternalError("radix_sort_top_first: tile count (internal)");
+        }
+        if (at != h_segs[b].end) throw InternalError("radix_sort_top_first: top-digit counts do not add up to the bucket (internal)");
+    }
+    return (uint32_t)tiles;
+}
+// ... checked once more by an independent walk before anything is launched over it: a cell table whose tiles do not cover its
+// cells would let a pass scatter outside the record buffers
+inline void rs_check_cells(const std::vector<SegInfo>& cells, uint32_t tiles, const SegInfo* h_segs, uint32_t nseg) {
+    uint64_t t = 0;
+    size_t c = 0;
+    for (uint32_t b = 0; b < nseg; ++b) {
+        unsigned long long at = h_segs[b].begin;
+        while (c < cells.size() && cells[c].begin == at && at < h_segs[b].end) {
+            const SegInfo& ci = cells[c];
+            if (ci.end <= ci.begin || ci.end > h_segs[b].end || (uint64_t)ci.tile_begin != t || ci.rot_b)
+                throw InternalError("radix_sort_top_first: cell table (internal)");
+            t += (ci.end - ci.begin + (uint64_t)RS_SEG_TILE - 1) / (uint64_t)RS_SEG_TILE;
+            at = ci.end;
+            ++c;
+        }
+        if (at != h_segs[b].end) throw InternalError("radix_sort_top_first: cells do not cover their bucket (internal)");
+    }
+    if (c != cells.size() || t != (uint64_t)tiles) throw InternalError("radix_sort_top_first: cell tiles (internal)");
+}
+// the last pass's view of the byte-wide aux word behind the top pass: entry bits 32.. | carried bits, nothing of the key
+inline void rs_top_first_fin(SegFinalArgs& fin, int ehb) {
+    fin.hi_shift = 0;
+    fin.low_bits = 0;
+    fin.hi_mask = (1u << ehb) - 1u;
+    fin.carry_shift = ehb;
+}
+// Records of m elements in buffers 0 (w0: u16 = top key byte | everything else << 8), the buckets as for radix_sort_segmented
+// (h_segs: their host copy, no rotations); d_hist / d_starts: scratch [nseg][8][256].  The passes leave buffers 0 and 1 as the
+// five-pass form does (the last pass reads buffers 0); fin as for radix_sort_segmented over (u32, u32, u8) records.
+template <typename W>  // (uint16_t; a template so that only the build instantiates its kernels)
+uint32_t radix_sort_top_first(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uint32_t* k0, uint32_t* k1, uint32_t* v0, uint32_t* v1,
+                                     W* w0, W* w1, uint64_t m, const SegInfo* d_segs, const SegInfo* h_segs, const uint32_t* d_tile_seg,
+                                     uint32_t nseg, uint32_t tiles, unsigned long long* d_hist, unsigned long long* d_starts, TopFirstWork& tw,
+                                     SegFinalArgs fin, SortStats* stats) {
+    static_assert(std::is_same<W, uint16_t>::value, "top digit first: (u32, u32, u16) records");
+    if (!rs_atomic_rank_ok(s)) throw InternalError("radix_sort_top_first: needs the one-atomic ranking (internal)");
+    for (uint32_t b = 0; b < nseg; ++b)
+        if (h_segs[b].rot_b) throw InternalError("radix_sort_top_first: rotated bucket (internal)");
+    // top-digit histogram of every bucket (2 B per record) and the pass on it
+    CDB_HIP(hipMemsetAsync(d_hist, 0, (size_t)nseg * 8 * 256 * sizeof(uint64_t), s));
+    int t = prof.begin(s);
+    hipLaunchKernelGGL((rs_seg_hist_kernel<W, false>), dim3((unsigned)ceil_div(tiles, (uint32_t)RS_MSD_HIST_TILES)), dim3(1024), 0, s,
+                       (const uint32_t*)k0, (const W*)w0, 1, 1, d_tile_seg, d_segs, tiles, d_hist);
+    prof.end(t, "rs_seg_hist_top", m * sizeof(W), s);
+    tw.h_hist.resize((size_t)nseg * 8 * 256);
+    CDB_HIP(hipMemcpyAsync(tw.h_hist.data(), d_hist, tw.h_hist.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    CDB_HIP(hipStreamSynchronize(s));  // (the counts are on the host; the top pass is launched next and runs while the cells are built)
+    hipLaunchKernelGGL(rs_seg_digit_start_kernel, dim3(nseg), dim3(256), 0, s, (const unsigned long long*)d_hist, d_segs, 1, d_starts);
+    ws.prepare((uint64_t)tiles * RS_SEG_TILE, RS_SEG_TILE, s);
+    SegShrinkArgs sh;
+    sh.tile_seg = d_tile_seg;
+    sh.segs = d_segs;
+    sh.tiles = tiles;
+    sh.start_stride = 8 * 256;
+    sh.wout8 = reinterpret_cast<uint8_t*>(w1);
+    t = prof.begin(s);
+    rs_launch_pass_ordered<RsBig<>, W>(s, ws, tiles, k0, k1, v0, v1, m, -8, 0xFFu, (const unsigned long long*)d_starts, NoGen(), w0, w1, 0, sh);
+    prof.end(t, "rs_seg_top_w16_t16384", m * (10 + 9), s);
+    if (stats) stats->passes_run++;
+    // the cells, built and checked on the host while the top pass runs; the synchronise behind them waits for that pass alone
+    const uint32_t ctiles = rs_top_first_cells(h_segs, nseg, tw.h_hist.data(), tw.h_cells);
+    rs_check_cells(tw.h_cells, ctiles, h_segs, nseg);
+    CDB_HIP(hipStreamSynchronize(s));
+    const uint32_t ncell = (uint32_t)tw.h_cells.size();
+    if (ncell == 0 || ncell > tw.cell_cap || ctiles > tw.tile_cap) throw InternalError("radix_sort_top_first: cell scratch (internal)");
+    CDB_HIP(hipMemcpyAsync(tw.cells.p, tw.h_cells.data(), (size_t)ncell * sizeof(SegInfo), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(rs_seg_tilemap_kernel, dim3((unsigned)ceil_div(ctiles, 256u)), dim3(256), 0, s, (const SegInfo*)tw.cells.as<SegInfo>(), ncell,
+                       ctiles, tw.tile_seg.as<uint32_t>());
+    // key-digit histograms per cell (4 B per record), then four passes over (u32, u32, u8) records from buffers 1
+    uint8_t* const b0 = reinterpret_cast<uint8_t*>(w0);
+    uint8_t* const b1 = reinterpret_cast<uint8_t*>(w1);
+    CDB_HIP(hipMemsetAsync(tw.hist.p, 0, (size_t)ncell * 8 * 256 * sizeof(uint64_t), s));
+    t = prof.begin(s);
+    hipLaunchKernelGGL((rs_seg_hist_kernel<uint8_t>), dim3((unsigned)ceil_div(ctiles, (uint32_t)RS_MSD_HIST_TILES)), dim3(1024), 0, s, (const uint32_t*)k1,
+                       (const uint8_t*)b1, 0, 4, (const uint32_t*)tw.tile_seg.as<uint32_t>(), (const SegInfo*)tw.cells.as<SegInfo>(), ctiles,
+                       tw.hist.as<unsigned long long>());
+    prof.end(t, "rs_seg_hist_cells", m * sizeof(uint32_t), s);
+    radix_sort_segmented<uint8_t>(s, ws, prof, k1, k0, v1, v0, b1, b0, m, (const SegInfo*)tw.cells.as<SegInfo>(), (const uint32_t*)tw.tile_seg.as<uint32_t>(), ncell,
+                                  ctiles, (const unsigned long long*)tw.hist.as<unsigned long long>(), tw.starts.as<unsigned long long>(), 32, 0, fin, stats);
+    return ncell;
 }
 
 // ---------------------------------------------------------------------------------------------

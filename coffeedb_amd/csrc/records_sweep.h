@@ -368,6 +368,8 @@ struct VlTables {
     int end_len = 0;                // length of END's (all-zero) word
     int carry = 0;                  // X: stream bits behind the key that ride in the aux word above the entry's high bits (0 = none)
     int carry_shift = 0;            // ... at this bit of the aux word (rec_low_bits + the entry's bits above 32)
+    int top_in_aux = 0;             // 1 (40-bit keys, rec_low_bits = 8): k32 = the key's LOW 32 bits and the aux word's low byte its TOP byte —
+                                    // the records of the top-digit-first segmented sort (sa_build.hip: run_segmented); 0: as ever
 };
 constexpr uint32_t RS_VL_BITW = ((RS_GEN8_TILE + RS_GEN_LOOK) * 7 + 31) / 32 + 4;  // words of the tile's bit stream
 
@@ -621,10 +623,10 @@ __global__ __launch_bounds__(512, 6) void rs_sweep_records_vl_kernel(TextGen gen
         const uint64_t kb = kbx >> CX;
         const uint64_t key = (kb << 1) | (uint64_t)(avail + (uint32_t)vl.end_len > (uint32_t)KB1 ? 1u : 0u);
         const uint64_t dst = s_gbase[sl] + (uint64_t)p;
-        kout[dst] = (uint32_t)(key >> gen.rec_low_bits);
+        kout[dst] = vl.top_in_aux ? (uint32_t)key : (uint32_t)(key >> gen.rec_low_bits);
         vout[dst] = (uint32_t)e64;
         // (the carried bits sit above the entry's high bits: digit_of, rs_seg_hist and the flag compare read aux through masks)
-        wout[dst] = (W)((key & lmask) | ((e64 >> 32) << gen.rec_low_bits) | ((kbx & cmask) << vl.carry_shift));
+        wout[dst] = (W)(((vl.top_in_aux ? key >> 32 : key) & lmask) | ((e64 >> 32) << gen.rec_low_bits) | ((kbx & cmask) << vl.carry_shift));
     };
     if (docs_in_lds && s_flag == 0 && valid == (uint32_t)TILE) {
         const int bits = gen.bits;
@@ -980,7 +982,8 @@ template <typename W>
 void radix_sweep_records_vl(hipStream_t s, Profiler& prof, uint32_t* k, uint32_t* v, W* w, uint64_t n, const TextGen& gen_in, const uint16_t* d_codeslot,
                             const VlTables& vl, uint32_t g0, uint32_t g1, uint64_t gstart, uint64_t gelems, const uint32_t* d_tile_seg,
                             const SegInfo* d_segs, uint32_t nseg, uint32_t seg_tiles, int lead, int npass, unsigned long long* d_hist_out,
-                            SortStats* stats) {
+                            SortStats* stats, bool with_hist = true) {
+    if (vl.top_in_aux && (vl.key_bits != 40 || gen_in.rec_low_bits != 8 || sizeof(W) != 2)) throw InternalError("radix_sweep_records_vl: top byte in the aux word (internal)");
     if (!gen_in.tile_base || !gen_in.tile_doc || !d_codeslot || !vl.sym || !vl.dec) throw InternalError("radix_sweep_records_vl: tables missing (internal)");
     if (vl.key_bits < 16 || vl.key_bits > 56) throw InternalError("radix_sweep_records_vl: key width (internal)");
     // (a position's 64 stream bits hold its own code word, the key's bits and the carried ones; the aux word holds them all)
@@ -994,6 +997,10 @@ void radix_sweep_records_vl(hipStream_t s, Profiler& prof, uint32_t* k, uint32_t
     prof.end(t, (std::string("rs_sweep_records_vl") + (sizeof(W) == 1 ? "_w8" : (sizeof(W) == 2 ? "_w16" : "_w32")) + "_t8192").c_str(),
              n + gelems * (8 + sizeof(W)), s);
     if (stats) stats->passes_run++;
+    if (!with_hist) {  // (the top-digit-first sort counts its own histograms: one aux digit per bucket, then the key digits per cell)
+        CDB_HIP(hipGetLastError());
+        return;
+    }
     t = prof.begin(s);
     hipLaunchKernelGGL((rs_seg_hist_kernel<W>), dim3((unsigned)ceil_div(seg_tiles, (uint32_t)RS_MSD_HIST_TILES)), dim3(1024), 0, s, (const uint32_t*)k,
                        (const W*)w, lead, npass, d_tile_seg, d_segs, seg_tiles, d_hist_out);

@@ -2214,6 +2214,7 @@ struct RecordForm {
     int blow = 0;
     bool fuse_rec = false, want_pack = false, sweep_rec = false, sweep_fused = false, pack_E = false;
     DevBuf fr_kv[2], fr_e[2], fr_w[2];  // fused form: the record buffers, allocated when it was chosen
+    bool top_first_wanted = false;      // the key shape and the options allow the top-digit-first segmented sort (run_segmented decides)
 };
 
 // (variable-length keys exist in the sweep kernels only: build_suffix_array redoes the build with dense keys)
@@ -2355,6 +2356,11 @@ void choose_record_form(Index& ix, const Alphabet& al, const KeyPlan& kp, const 
     // packed output (index_impl.h: Sa40): the last pass writes u32 low words over the KEY half it does not read and the high
     // bytes into their own array — 5 instead of 8 bytes written per suffix, and the index keeps 5 n bytes instead of 8 n
     const bool want_pack = rf.want_pack = sizeof(V) == 8 && sa_packable(ix);
+    // top key digit first (radix_sort.h: radix_sort_top_first): 40-bit variable-length keys, one low digit, records from the sweep,
+    // and no bucket that the last pass writes rotated — those are found only behind this point (fold_root_buckets), so a build in
+    // the reference's root order stays out altogether: the record buffers allocated below then never have to change
+    rf.top_first_wanted = sizeof(V) == 8 && vl_bits == 40 && bbits == 40 && blow == 8 && tile_bytes && ix.sweep_records && !bk.root_folded &&
+                          (ix.top_digit_first < 0 ? n >= TOP_FIRST_MIN_N : ix.top_digit_first != 0);
     // (allocate the record buffers NOW: if the device cannot provide them after all — fragmentation, other handles —
     //  nothing has happened yet and the build takes partition + gather instead of failing)
     if (fuse_rec) {
@@ -2367,7 +2373,8 @@ void choose_record_form(Index& ix, const Alphabet& al, const KeyPlan& kp, const 
                 } else {
                     rf.fr_kv[q].alloc(n * 2 * sizeof(uint32_t));
                 }
-                rf.fr_w[q].alloc(n * auxb0);
+                // (top digit first: buffer 1 only ever holds byte-wide aux words)
+                rf.fr_w[q].alloc(n * (q == 1 && rf.top_first_wanted ? 1 : auxb0));
             }
             if (want_pack) out.sa_hi_buf.alloc(n);
         } catch (const std::exception&) {
@@ -2556,6 +2563,20 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
         }
         uint64_t max_elems = 0;
         for (const Group& g : groups) max_elems = std::max(max_elems, g.elems);
+        // top key digit first (radix_sort.h: radix_sort_top_first): 40-bit variable-length keys in (u32, u32, u16) records from the
+        // sweep, no bucket written rotated — chosen here, in front of the sweep, because the sweep splits the key differently
+        bool top_first = false;
+        if constexpr (std::is_same<W, uint16_t>::value) {
+            top_first = rf.top_first_wanted && rf.vl_bits == 40 && rf.bbits == 40 && blow == 8 && lowb == 1 && bpass == 5 &&
+                        (sweep_rec || sweep_fused) && br.bmagic == 0;
+            for (uint32_t b = 0; b < nb; ++b)
+                if (top_first && h_segs[b].rot_b) throw InternalError("run_segmented: rotated bucket under the top-digit-first form (internal)");
+            if (top_first && (uint64_t)max_tiles + (uint64_t)max_gb * 256 > 0xFFFFFFFFull) top_first = false;
+        }
+        st.top_first = top_first ? 1 : 0;
+        st.top_first_cells = 0;
+        const uint32_t cell_tiles_max = max_tiles + (top_first ? max_gb * 256u : 0u);  // (every non-empty cell ends in at most one ragged tile)
+        TopFirstWork tfw;
         DevBuf kb[2], eb[2], wb[2], edges, d_starts, d_segs, tile_seg, cell_off, lists, d_items2, d_bh2;
         uint32_t *kbp[2], *ebp[2];
         // fused form: key and entry halves of a record buffer are ONE block, so that the last pass can write the
@@ -2573,6 +2594,7 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
                     ebp[q] = kbp[q] + max_elems;
                 }
                 wb[q] = std::move(rf.fr_w[q]);
+                if (wb[q].bytes < max_elems * (top_first && q == 1 ? 1 : sizeof(W))) throw InternalError("run_segmented: aux buffer of the fused form (internal)");
                 continue;
             } else {
                 kb[q].alloc(max_elems * sizeof(uint32_t));
@@ -2580,9 +2602,10 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
                 kbp[q] = kb[q].as<uint32_t>();
                 ebp[q] = eb[q].as<uint32_t>();
             }
-            wb[q].alloc(max_elems * sizeof(W));
+            wb[q].alloc(max_elems * (top_first && q == 1 ? 1 : sizeof(W)));  // (top digit first: buffer 1 only ever holds byte-wide aux words)
         }
-        edges.alloc((size_t)max_tiles * 256 * sizeof(SegEdge));
+        edges.alloc((size_t)cell_tiles_max * 256 * sizeof(SegEdge));
+        if (top_first) tfw.alloc(max_gb * 256u, cell_tiles_max);
         d_starts.alloc((size_t)max_gb * 8 * 256 * sizeof(uint64_t));
         d_bh2.alloc((size_t)max_gb * 8 * 256 * sizeof(uint64_t));
         d_segs.alloc((size_t)nb * sizeof(SegInfo));
@@ -2633,10 +2656,11 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
                     vt.end_len = rf.vlc.end_len;
                     vt.carry = carry;
                     vt.carry_shift = blow + ehb;
+                    vt.top_in_aux = top_first ? 1 : 0;
                     radix_sweep_records_vl<W>(s, ix.prof, kbp[0], ebp[0], wb[0].as<W>(), n, rg, (const uint16_t*)br.d_codeslot.as<uint16_t>(), vt,
                                               g.b0, g.b1, g.gstart, g.elems, (const uint32_t*)tile_seg.as<uint32_t>(),
                                               (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), gb, g.tiles, lowb, bpass,
-                                              d_bh2.as<unsigned long long>(), &ss);
+                                              d_bh2.as<unsigned long long>(), &ss, !top_first);
                 } else
                 radix_sweep_records<W>(s, ix.prof, kbp[0], ebp[0], wb[0].as<W>(), n, rg, (const uint16_t*)br.d_codeslot.as<uint16_t>(), g.b0, g.b1,
                                        g.gstart, g.elems,
@@ -2691,6 +2715,17 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
                 fin.hi_mask = (1u << ehb) - 1u;
                 fin.carry_mask = (1u << carry) - 1u;
                 fin.carry_shift = blow + ehb;
+            }
+            if constexpr (std::is_same<W, uint16_t>::value) {
+                if (top_first) {  // (the aux word behind the top pass: entry bits 32.. | carried bits, nothing of the key)
+                    rs_top_first_fin(fin, ehb);
+                    st.top_first_cells += radix_sort_top_first(s, ix.rws, ix.prof, kbp[0], kbp[1], ebp[0], ebp[1], wb[0].as<W>(), wb[1].as<W>(),
+                                                               g.elems, (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), h_segs.data() + g.b0,
+                                                               (const uint32_t*)tile_seg.as<uint32_t>(), gb, g.tiles, d_bh2.as<unsigned long long>(),
+                                                               d_starts.as<unsigned long long>(), tfw, fin, &ss);
+                    st.bucket_groups++;
+                    continue;
+                }
             }
             radix_sort_segmented<W>(s, ix.rws, ix.prof, kbp[0], kbp[1], ebp[0], ebp[1], wb[0].as<W>(), wb[1].as<W>(), g.elems,
                                     (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), (const uint32_t*)tile_seg.as<uint32_t>(), gb,

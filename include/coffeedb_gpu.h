@@ -833,6 +833,21 @@ int cdb_debug_vl_tables(const uint64_t* counts, int sigma, const uint8_t* slot_o
 int cdb_debug_carried_inplace(int device, int form, uint64_t* entries_inout, uint8_t* flags_inout, uint64_t n, int xbits,
                               uint64_t* out_partials, uint64_t* out_counts, int* out_guard_ok);
 
+/* Test hook for the segmented sort of bucket records (radix_sort.h: radix_sort_segmented, radix_sort_top_first;
+ * tests/test_gpu_segsort_top_first.py; debug_segsort.hip).  Not part of the stable ABI.  Every array lies in HOST memory.  n records
+ * (u32 k32, u32 v32 = entry bits 0..31, u16 w16) in nb buckets, bucket b = records [bucket_begin[b], bucket_begin[b + 1]), with
+ * 40-bit variable-length keys in the split the form sorts: FIVE_PASS: k32 = key >> 8, w16 = key & 0xFF | hi << 8; TOP_FIRST:
+ * k32 = (uint32_t)key, w16 = key >> 32 | hi << 8; hi = entry bits 32.. (ehb of them) | carried bits << ehb (carry of them,
+ * ehb + carry <= 8, carry <= 6).  The hook runs the form as the build does for one bucket group and returns the entries
+ * (packed = 1: written as 5-byte entries and put together again here) and the flag bytes (bit 0 head, bit 1 open, bits 2.. the
+ * carried bits); TOP_FIRST also returns its cells as (begin, end, tile_begin) triples in out_cells (cells_cap >= 256 nb) and
+ * their count.  *out_guard_ok = 1 when the poisoned elements around every record and output array are untouched. */
+#define CDB_DEBUG_SEGSORT_FIVE_PASS 0
+#define CDB_DEBUG_SEGSORT_TOP_FIRST 1
+int cdb_debug_segsort(int device, int form, int packed, uint64_t n, uint32_t nb, const uint64_t* bucket_begin, const uint32_t* k32,
+                      const uint32_t* v32, const uint16_t* w16, int ehb, int carry, uint64_t* out_entries, uint8_t* out_flags,
+                      uint64_t* out_cells, uint32_t cells_cap, uint32_t* out_ncells, int* out_guard_ok);
+
 /* Measurement hook: wall time of `reps` back-to-back cdb_query calls for each of `nkw` keywords (blob + offsets like
  * cdb_query_batch), taken inside the library with a steady clock — what a C++ caller such as database.cpp:392 sees,
  * without a language binding in between.  us_out[nkw] receives the MEDIAN microseconds per call of every keyword;
