@@ -32,7 +32,7 @@ EXPORTS = [
     "cdb_column_query_any", "cdb_query_and_columns", "cdb_column_get_stat", "cdb_debug_column_set_option", "cdb_debug_column_profile_dump",
     "cdb_column_cluster", "cdb_cluster", "cdb_clusters_free",
     "cdb_render_rows", "cdb_shards_render_rows", "cdb_rendered_free",
-    "cdb_remove", "cdb_column_remove",
+    "cdb_remove", "cdb_column_remove", "cdb_column_append", "cdb_debug_column_arrays",
     "cdb_append", "cdb_debug_verify_keys",
     "cdb_shards_remove", "cdb_shards_append", "cdb_shards_cluster",
     "cdb_debug_sort_ws_create", "cdb_debug_sort_ws_destroy", "cdb_debug_radix_sort_ex", "cdb_debug_radix_sort_split",
@@ -254,6 +254,8 @@ def load_library():
     lib.cdb_rendered_free.restype = None
     lib.cdb_remove.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     lib.cdb_column_remove.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    lib.cdb_column_append.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
+    lib.cdb_debug_column_arrays.argtypes = [vp, vp, vp, vp, vp]
     lib.cdb_append.argtypes = [vp, vp, vp, vp, u64, C.POINTER(u64)]
     lib.cdb_debug_verify_keys.argtypes = [vp, C.POINTER(u64)]
     lib.cdb_shards_remove.argtypes = lib.cdb_remove.argtypes
@@ -906,9 +908,32 @@ class GpuColumn:
         finally:
             self._lib.cdb_free(ids)
 
+    def _values(self, values):
+        vals = np.asarray(values)
+        return np.ascontiguousarray(vals != 0 if self.kind == 0 else vals, dtype=self.DTYPES[self.kind])
+
+    def append(self, ids, values):
+        """cdb_column_append: the rows join the built column on the device (only they are uploaded and sorted); the column then
+        equals one that got them by add_bulk() + build().  Returns the number of rows appended."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        vals = self._values(values)
+        if len(ids) != len(vals):
+            raise ValueError("append: ids and values differ in length")
+        appended = C.c_uint64(0)
+        self._check(self._lib.cdb_column_append(self._h, _ptr(ids) if len(ids) else None, _ptr(vals) if len(ids) else None, len(ids),
+                                                C.byref(appended)))
+        return int(appended.value)
+
+    def arrays(self):
+        """Test hook (cdb_debug_column_arrays): the device arrays (keys_v uint64, ids_v int64, id_sorted int64, vpos uint32)."""
+        n = int(self.stat("rows"))
+        out = (np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint32))
+        self._check(self._lib.cdb_debug_column_arrays(self._h, *[_ptr(a) if n else None for a in out]))
+        return out
+
     def remove(self, ids):
-        """cdb_column_remove: the rows `ids` leave the column (built and staged rows alike), which is rebuilt over the rest.
-        Returns (removed, missing) as GpuStringIndex.remove does."""
+        """cdb_column_remove: the rows `ids` leave the column (built and staged rows alike) — compacted on the device, or, with
+        staged rows, filtered on the host and rebuilt.  Returns (removed, missing) as GpuStringIndex.remove does."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         removed, missing = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.cdb_column_remove(self._h, _ptr(ids) if len(ids) else None, len(ids), C.byref(removed), C.byref(missing)))
@@ -936,7 +961,8 @@ class GpuColumn:
         return v.value
 
     def set_option(self, name, value):
-        """Test / measurement hook (cdb_debug_column_set_option): "profile", "debug_query_path", "debug_cluster_path"."""
+        """Test / measurement hook (cdb_debug_column_set_option): "profile", "debug_query_path", "debug_cluster_path",
+        "debug_maintain_path"."""
         self._check(self._lib.cdb_debug_column_set_option(self._h, name.encode(), int(value)))
 
     def profile(self):

@@ -25,7 +25,7 @@ using namespace cdb;
 namespace {
 
 constexpr uint64_t SIGN = 1ull << 63;
-constexpr uint64_t MAX_ROWS = 0xFFFFFFFFull;  // vpos and the carried ranks are 32-bit
+constexpr uint64_t MAX_ROWS = COLUMN_MAX_ROWS;
 // Dense when k > n * DENSE_NUM / DENSE_DEN (k = rows inside the windows, overlaps counted).  Measured on MI355X over 10^8 rows with
 // timestamp ids, both paths forced at 19 selectivities from 0.2 % to 95 %: sparse still wins at 60 % (1.75 vs
 // 1.78 ms), dense wins from 65 % on (1.81 vs 1.84 ms; 2.28 vs 2.59 ms at 95 %) — the crossover lies between, 5/8 is its middle.
@@ -239,44 +239,28 @@ struct Windows {
     uint64_t k = 0;                  // sum of b - a (overlaps counted)
 };
 
-struct ColumnScope {
-    StreamScope ss;
-    explicit ColumnScope(cdb_column* c) : ss(c->ws.stream) { CDB_HIP(hipSetDevice(c->ws.device)); }
-};
-
-
 // ---- build -------------------------------------------------------------------------------------------------------------
 // Every row of the column — the previous build's, in its key order (for bool that is insertion order within each value, which the
 // stable sort by value keeps ahead of the rows added since), then the staged ones — is sorted twice: by id (skipped when the ids
 // already ascend: they are insertion timestamps), then stably by key carrying the id rank (bool: the insertion index), so that
-// equal keys ascend by id (bool: keep insertion order).
-void column_build(cdb_column* c) {
+// equal keys ascend by id (bool: keep insertion order).  column_sort_rows is that pair of sorts over rows already on the device
+// (cdb_column_append sorts its batch with it), column_build feeds it the old rows and the staged ones and publishes.
+}  // namespace
+
+void cdb::column_sort_rows(cdb_column* c, DevBuf& idk0, DevBuf& key0, uint64_t n, uint64_t first_new, const char* who, ColumnArrays& out) {
     Index& ws = c->ws;
     hipStream_t s = ws.stream;
     Profiler& prof = ws.prof;
-    const double t0 = wall_ms();
-    const uint64_t n_old = c->n, n_new = c->staged_ids.size(), n = n_old + n_new;
-    if (n > MAX_ROWS) throw Error("cdb_column_build: a column holds at most 2^32 - 1 rows");
     const bool is_bool = c->kind == 0;
     const uint64_t cap = std::max<uint64_t>(n, 1);
-    DevBuf idk0, idk1, key0, key1, car0, car1, v0, v1, rank_of, flags;
-    DevBuf keys_v, ids_v, id_sorted, vpos;
-    idk0.alloc(cap * 8);
-    key0.alloc(cap * 8);
+    DevBuf idk1, key1, car0, car1, v0, v1, rank_of, flags;
+    DevBuf ids_v, id_sorted, vpos;
     key1.alloc(cap * 8);
     flags.alloc(32);
     CDB_HIP(hipMemsetAsync(flags.p, 0, 32, s));
-    if (n_old) {
-        CDB_HIP(hipMemcpyAsync(idk0.p, c->ids_v.p, n_old * 8, hipMemcpyDeviceToDevice, s));
-        CDB_HIP(hipMemcpyAsync(key0.p, c->keys_v.p, n_old * 8, hipMemcpyDeviceToDevice, s));
-    }
-    if (n_new) {
-        CDB_HIP(hipMemcpyAsync(idk0.as<uint64_t>() + n_old, c->staged_ids.data(), n_new * 8, hipMemcpyHostToDevice, s));
-        CDB_HIP(hipMemcpyAsync(key0.as<uint64_t>() + n_old, c->staged_raw.data(), n_new * 8, hipMemcpyHostToDevice, s));
-    }
     int t = prof.begin(s);
-    hipLaunchKernelGGL(col_prepare_kernel, dim3(grid_for(n)), dim3(256), 0, s, idk0.as<uint64_t>(), key0.as<uint64_t>(), n, n_old, c->kind);
-    prof.end(t, "col_prepare", n * 16 + n_new * 8, s);
+    hipLaunchKernelGGL(col_prepare_kernel, dim3(grid_for(n)), dim3(256), 0, s, idk0.as<uint64_t>(), key0.as<uint64_t>(), n, first_new, c->kind);
+    prof.end(t, "col_prepare", n * 16 + (n - first_new) * 8, s);
     t = prof.begin(s);
     hipLaunchKernelGGL(col_order_kernel, dim3(grid_for(n)), dim3(256), 0, s, (const uint64_t*)idk0.as<uint64_t>(), n, flags.as<unsigned int>());
     prof.end(t, "col_order", n * 8, s);
@@ -313,7 +297,7 @@ void column_build(cdb_column* c) {
             rmap = rank_of.as<uint32_t>();
         }
     }
-    c->id_sort_skipped = unordered ? 0 : 1;
+    out.id_sort_skipped = unordered ? 0 : 1;
     id_sorted.alloc(cap * 8);
     t = prof.begin(s);
     hipLaunchKernelGGL(col_id_rank_kernel, dim3(grid_for(n)), dim3(256), 0, s, idk, n, id_sorted.as<int64_t>(),
@@ -322,7 +306,7 @@ void column_build(cdb_column* c) {
     unsigned long long dup[2] = {0, 0};
     CDB_HIP(hipMemcpyAsync(dup, flags.as<unsigned long long>() + 1, 16, hipMemcpyDeviceToHost, s));
     CDB_HIP(hipStreamSynchronize(s));
-    if (dup[0]) throw Error("cdb_column_build: duplicate object id " + std::to_string((long long)dup[1]) + " in one column");
+    if (dup[0]) throw Error(std::string(who) + ": duplicate object id " + std::to_string((long long)dup[1]) + " in one column");
     // by key, stable, carrying the id rank / insertion index
     v0.alloc(cap * 4);
     v1.alloc(cap * 4);
@@ -344,7 +328,7 @@ void column_build(cdb_column* c) {
     radix_check_error(s, ws.rws);
     // the sorted keys stay where the sort left them
     DevBuf& kbuf = (sel ? kspare : kcur) == key0.as<uint64_t>() ? key0 : key1;
-    keys_v = std::move(kbuf);
+    DevBuf keys_v = std::move(kbuf);
     // bool: rows with value false = the lower bound of (true, INT64_MIN)
     uint64_t n_false = 0;
     if (is_bool && n) {
@@ -362,20 +346,53 @@ void column_build(cdb_column* c) {
     }
     CDB_HIP(hipStreamSynchronize(s));
     prof.resolve();
-    // publish
-    c->keys_v = std::move(keys_v);
-    c->ids_v = std::move(ids_v);
-    c->id_sorted = std::move(id_sorted);
-    c->vpos = std::move(vpos);
-    c->n = n;
-    c->n_false = n_false;
+    out.keys_v = std::move(keys_v);
+    out.ids_v = std::move(ids_v);
+    out.id_sorted = std::move(id_sorted);
+    out.vpos = std::move(vpos);
+    out.n = n;
+    out.n_false = n_false;
+}
+
+void cdb::column_publish(cdb_column* c, ColumnArrays& a) {
+    c->keys_v = std::move(a.keys_v);
+    c->ids_v = std::move(a.ids_v);
+    c->id_sorted = std::move(a.id_sorted);
+    c->vpos = std::move(a.vpos);
+    c->n = a.n;
+    c->n_false = a.n_false;
     ++c->generation;  // (cluster.hip keeps a table per build)
+}
+
+void cdb::column_build(cdb_column* c, const char* who) {
+    hipStream_t s = c->ws.stream;
+    const double t0 = wall_ms();
+    const uint64_t n_old = c->n, n_new = c->staged_ids.size(), n = n_old + n_new;
+    if (n > MAX_ROWS) throw Error(std::string(who) + ": a column holds at most 2^32 - 1 rows");
+    const uint64_t cap = std::max<uint64_t>(n, 1);
+    DevBuf idk0, key0;
+    idk0.alloc(cap * 8);
+    key0.alloc(cap * 8);
+    if (n_old) {
+        CDB_HIP(hipMemcpyAsync(idk0.p, c->ids_v.p, n_old * 8, hipMemcpyDeviceToDevice, s));
+        CDB_HIP(hipMemcpyAsync(key0.p, c->keys_v.p, n_old * 8, hipMemcpyDeviceToDevice, s));
+    }
+    if (n_new) {
+        CDB_HIP(hipMemcpyAsync(idk0.as<uint64_t>() + n_old, c->staged_ids.data(), n_new * 8, hipMemcpyHostToDevice, s));
+        CDB_HIP(hipMemcpyAsync(key0.as<uint64_t>() + n_old, c->staged_raw.data(), n_new * 8, hipMemcpyHostToDevice, s));
+    }
+    ColumnArrays a;
+    column_sort_rows(c, idk0, key0, n, n_old, who, a);
+    c->id_sort_skipped = a.id_sort_skipped;
+    column_publish(c, a);
     c->staged_ids.clear();
     c->staged_ids.shrink_to_fit();
     c->staged_raw.clear();
     c->staged_raw.shrink_to_fit();
     c->build_ms = wall_ms() - t0;
 }
+
+namespace {
 
 // ---- ranges -> windows -------------------------------------------------------------------------------------------------
 std::string range_text(const char* blob, const uint64_t* offsets, uint64_t j) {
@@ -563,6 +580,68 @@ int64_t* download_ids(hipStream_t s, const int64_t* d, uint64_t n) {
 
 }  // namespace
 
+std::vector<uint64_t> cdb::column_raw_values(int kind, const void* values, uint64_t n, const char* who) {
+    std::vector<uint64_t> raw(n);
+    if (kind == 0) {
+        const uint8_t* v = (const uint8_t*)values;
+        for (uint64_t i = 0; i < n; ++i) raw[i] = v[i] ? 1 : 0;
+    } else {
+        std::memcpy(raw.data(), values, n * 8);
+        if (kind == 2)
+            for (uint64_t i = 0; i < n; ++i)
+                if (std::isnan(((const double*)values)[i]))
+                    throw Error(std::string(who) + ": NaN is not a valid value (row " + std::to_string(i) + ")");
+    }
+    return raw;
+}
+
+// The host path of cdb_column_remove: the built rows come back in key order (bool: insertion order within each value, which the
+// stable sort by value restores), join the rows staged since, the removed ids are dropped and the column's own build runs over
+// the rest.  A failed build leaves the column as it was.
+void cdb::column_remove_host(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
+    hipStream_t s = c->ws.stream;
+    const uint64_t n_old = c->n, n_staged = c->staged_ids.size();
+    std::vector<int64_t> all_ids(n_old + n_staged);
+    std::vector<uint64_t> all_raw(n_old + n_staged);
+    if (n_old) {
+        CDB_HIP(hipMemcpyAsync(all_ids.data(), c->ids_v.p, n_old * 8, hipMemcpyDeviceToHost, s));
+        CDB_HIP(hipMemcpyAsync(all_raw.data(), c->keys_v.p, n_old * 8, hipMemcpyDeviceToHost, s));
+        CDB_HIP(hipStreamSynchronize(s));
+        for (uint64_t i = 0; i < n_old; ++i) all_raw[i] = column_key_raw(c->kind, all_raw[i]);
+    }
+    std::copy(c->staged_ids.begin(), c->staged_ids.end(), all_ids.begin() + n_old);
+    std::copy(c->staged_raw.begin(), c->staged_raw.end(), all_raw.begin() + n_old);
+    std::vector<int64_t> held(all_ids), gone(ids, ids + nids);
+    std::sort(held.begin(), held.end());
+    std::sort(gone.begin(), gone.end());
+    uint64_t miss = 0;
+    for (int64_t id : gone) miss += std::binary_search(held.begin(), held.end(), id) ? 0 : 1;
+    gone.erase(std::unique(gone.begin(), gone.end()), gone.end());
+    uint64_t kept = 0;
+    for (uint64_t i = 0; i < all_ids.size(); ++i) {
+        if (std::binary_search(gone.begin(), gone.end(), all_ids[i])) continue;
+        all_ids[kept] = all_ids[i];
+        all_raw[kept++] = all_raw[i];
+    }
+    const uint64_t dropped = all_ids.size() - kept;
+    *removed = dropped;
+    *missing = miss;
+    if (!dropped) return;
+    all_ids.resize(kept);
+    all_raw.resize(kept);
+    c->staged_ids.swap(all_ids);  // (all_ids / all_raw now hold the rows staged before the call)
+    c->staged_raw.swap(all_raw);
+    c->n = 0;
+    try {
+        column_build(c);
+    } catch (...) {
+        c->n = n_old;
+        c->staged_ids.swap(all_ids);
+        c->staged_raw.swap(all_raw);
+        throw;
+    }
+}
+
 extern "C" {
 
 int cdb_column_create(cdb_column** out, int device, int kind) {
@@ -603,17 +682,7 @@ const char* cdb_column_last_error(const cdb_column* c) {
 int cdb_column_add_bulk(cdb_column* c, const int64_t* ids, const void* values, uint64_t n) {
     if (!c || (n && (!ids || !values))) return CDB_E_INVALID;
     return guarded_ix(c->ws, [&] {
-        std::vector<uint64_t> raw(n);
-        if (c->kind == 0) {
-            const uint8_t* v = (const uint8_t*)values;
-            for (uint64_t i = 0; i < n; ++i) raw[i] = v[i] ? 1 : 0;
-        } else {
-            std::memcpy(raw.data(), values, n * 8);
-            if (c->kind == 2)
-                for (uint64_t i = 0; i < n; ++i)
-                    if (std::isnan(((const double*)values)[i]))
-                        throw Error("cdb_column_add_bulk: NaN is not a valid value (row " + std::to_string(i) + ")");
-        }
+        const std::vector<uint64_t> raw = column_raw_values(c->kind, values, n, "cdb_column_add_bulk");
         std::lock_guard<std::mutex> g(c->ws.mu);
         if (c->n + c->staged_ids.size() + n > MAX_ROWS) throw Error("cdb_column_add_bulk: a column holds at most 2^32 - 1 rows");
         c->staged_ids.insert(c->staged_ids.end(), ids, ids + n);
@@ -630,9 +699,8 @@ int cdb_column_build(cdb_column* c) {
     });
 }
 
-// Rows leave a column: the built rows come back in key order (bool: insertion order within each value, which the stable sort by
-// value restores), join the rows staged since, the removed ids are dropped and the column's own build runs over the rest — a
-// device sort of milliseconds, so its derived arrays are not compacted one by one.  A failed build leaves the column as it was.
+// Rows leave a column.  With no rows staged since the last build the four arrays are compacted on the device
+// (column_maintain.hip); otherwise — and with debug_maintain_path = 2 — the host path below runs.
 int cdb_column_remove(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
     if (!c || (nids && !ids)) return CDB_E_INVALID;
     if (removed) *removed = 0;
@@ -641,47 +709,18 @@ int cdb_column_remove(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t
         std::lock_guard<std::mutex> g(c->ws.mu);
         ColumnScope cs(c);
         if (!nids) return;
-        hipStream_t s = c->ws.stream;
-        const uint64_t n_old = c->n, n_staged = c->staged_ids.size();
-        std::vector<int64_t> all_ids(n_old + n_staged);
-        std::vector<uint64_t> all_raw(n_old + n_staged);
-        if (n_old) {
-            CDB_HIP(hipMemcpyAsync(all_ids.data(), c->ids_v.p, n_old * 8, hipMemcpyDeviceToHost, s));
-            CDB_HIP(hipMemcpyAsync(all_raw.data(), c->keys_v.p, n_old * 8, hipMemcpyDeviceToHost, s));
-            CDB_HIP(hipStreamSynchronize(s));
-            for (uint64_t i = 0; i < n_old; ++i) all_raw[i] = column_key_raw(c->kind, all_raw[i]);
-        }
-        std::copy(c->staged_ids.begin(), c->staged_ids.end(), all_ids.begin() + n_old);
-        std::copy(c->staged_raw.begin(), c->staged_raw.end(), all_raw.begin() + n_old);
-        std::vector<int64_t> held(all_ids), gone(ids, ids + nids);
-        std::sort(held.begin(), held.end());
-        std::sort(gone.begin(), gone.end());
-        uint64_t miss = 0;
-        for (int64_t id : gone) miss += std::binary_search(held.begin(), held.end(), id) ? 0 : 1;
-        gone.erase(std::unique(gone.begin(), gone.end()), gone.end());
-        uint64_t kept = 0;
-        for (uint64_t i = 0; i < all_ids.size(); ++i) {
-            if (std::binary_search(gone.begin(), gone.end(), all_ids[i])) continue;
-            all_ids[kept] = all_ids[i];
-            all_raw[kept++] = all_raw[i];
-        }
-        const uint64_t dropped = all_ids.size() - kept;
-        if (removed) *removed = dropped;
+        const double t0 = wall_ms();
+        const bool device = c->staged_ids.empty() && c->debug_maintain_path != 2;
+        uint64_t rem = 0, miss = 0;
+        if (device) column_remove_device(c, ids, nids, &rem, &miss);
+        else column_remove_host(c, ids, nids, &rem, &miss);
+        if (removed) *removed = rem;
         if (missing) *missing = miss;
-        if (!dropped) return;
-        all_ids.resize(kept);
-        all_raw.resize(kept);
-        c->staged_ids.swap(all_ids);  // (all_ids / all_raw now hold the rows staged before the call)
-        c->staged_raw.swap(all_raw);
-        c->n = 0;
-        try {
-            column_build(c);
-        } catch (...) {
-            c->n = n_old;
-            c->staged_ids.swap(all_ids);
-            c->staged_raw.swap(all_raw);
-            throw;
-        }
+        if (!rem) return;
+        ++c->removes;
+        ++(device ? c->remove_compactions : c->remove_rebuilds);
+        c->remove_rows = rem;
+        c->remove_ms = wall_ms() - t0;
     });
 }
 
@@ -917,6 +956,10 @@ int cdb_column_get_stat(const cdb_column* c, const char* name, double* value) {
         {"materialised_keys", (double)c->materialised_keys}, {"last_k", (double)c->last_k}, {"kind", (double)c->kind},
         {"last_union_ms", c->last_union_ms}, {"sparse_clusters", (double)c->sparse_clusters}, {"dense_clusters", (double)c->dense_clusters},
         {"cluster_ms", c->cluster_ms},
+        {"appends", (double)c->appends}, {"append_merges", (double)c->append_merges}, {"append_rebuilds", (double)c->append_rebuilds},
+        {"append_rows", (double)c->append_rows}, {"append_ms", c->append_ms}, {"append_id_concat", (double)c->append_id_concat},
+        {"removes", (double)c->removes}, {"remove_compactions", (double)c->remove_compactions},
+        {"remove_rebuilds", (double)c->remove_rebuilds}, {"remove_rows", (double)c->remove_rows}, {"remove_ms", c->remove_ms},
     };
     for (auto& e : tab)
         if (!std::strcmp(e.n, name)) {
@@ -939,6 +982,10 @@ int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value) 
     }
     if (!std::strcmp(name, "debug_cluster_path") && value >= 0 && value <= 2) {
         c->debug_cluster_path = (int)value;
+        return CDB_OK;
+    }
+    if (!std::strcmp(name, "debug_maintain_path") && value >= 0 && value <= 2) {
+        c->debug_maintain_path = (int)value;
         return CDB_OK;
     }
     return CDB_E_INVALID;

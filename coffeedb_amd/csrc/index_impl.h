@@ -669,9 +669,37 @@ struct cdb_column {
     int debug_cluster_path = 0;  // 0 = automatic, 1 = always sparse, 2 = always dense
     uint64_t sparse_clusters = 0, dense_clusters = 0;
     double cluster_ms = 0;
+    // column_maintain.hip: cdb_column_append / cdb_column_remove
+    int debug_maintain_path = 0;  // 0 = automatic, 1 = the device path wherever it is valid, 2 = the host filter / stage + column_build
+    uint64_t appends = 0, append_merges = 0, append_rebuilds = 0, append_rows = 0, append_id_concat = 0;
+    uint64_t removes = 0, remove_compactions = 0, remove_rebuilds = 0, remove_rows = 0;
+    double append_ms = 0, remove_ms = 0;
 };
 struct cdb_key_query;
 namespace cdb {
+// columns.hip — the four arrays of a column (layout: columns.hip's head) while they are made, before they are published
+struct ColumnArrays {
+    DevBuf keys_v, ids_v, id_sorted, vpos;
+    uint64_t n = 0, n_false = 0;
+    int id_sort_skipped = 0;
+};
+constexpr uint64_t COLUMN_MAX_ROWS = 0xFFFFFFFFull;  // vpos and the carried ranks are 32-bit
+// The sort part of a build: idk (object ids) and key (order keys below first_new, raw values from there on), n rows each on the
+// device, become the four arrays.  Both inputs are consumed.  `who` names the entry point in the duplicate-id error.
+void column_sort_rows(cdb_column* c, DevBuf& idk, DevBuf& key, uint64_t n, uint64_t first_new, const char* who, ColumnArrays& out);
+// the raw values of staged rows as add_bulk keeps them (NaN refused; `who` names the entry point)
+std::vector<uint64_t> column_raw_values(int kind, const void* values, uint64_t n, const char* who);
+// the arrays replace the column's own; the stream is idle.  Bumps `generation` (cluster.hip remakes its run table).
+void column_publish(cdb_column* c, ColumnArrays& a);
+void column_build(cdb_column* c, const char* who = "cdb_column_build");
+// cdb_column_remove's host path: download, filter on the host, column_build over the rest (built and staged rows alike)
+void column_remove_host(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
+// column_maintain.hip — the device path (no staged rows): mark, two stable compactions, one gather of the positions
+void column_remove_device(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
+struct ColumnScope {  // the column's stream and device for the calling thread
+    StreamScope ss;
+    explicit ColumnScope(cdb_column* c) : ss(c->ws.stream) { CDB_HIP(hipSetDevice(c->ws.device)); }
+};
 // the value (bit pattern) behind a column's order-preserving key (columns.hip: order_key; kind: 0 bool, 1 int64, 2 double)
 __host__ __device__ __forceinline__ uint64_t column_key_raw(int kind, uint64_t key) {
     constexpr uint64_t S = 1ull << 63;

@@ -82,6 +82,16 @@ bool column_remove(cdb_column* c, std::vector<int64_t>& staged_ids, std::vector<
     forget_staged(staged_ids, staged_vals, gone);
     return true;
 }
+// the rows belong to the column once the call has taken them; a refused call (a duplicate id) leaves them pending
+template <typename V>
+bool column_append(cdb_column* c, std::vector<int64_t>& staged_ids, std::vector<V>& staged_vals) {
+    if (!c || staged_ids.empty()) return false;
+    const int rc = cdb_column_append(c, staged_ids.data(), staged_vals.data(), staged_ids.size(), nullptr);
+    if (rc != CDB_OK) rethrow_column(c, rc);
+    staged_ids.clear();
+    staged_vals.clear();
+    return true;
+}
 }  // namespace
 
 // ---- numeric indexes: sorted (value, id) pairs, half-open lower_bound window (index.cpp:63-74, 129-173)
@@ -125,6 +135,10 @@ template <typename T, int8_t Tag>
 bool numeric_index<T, Tag>::remove(const std::vector<int64_t>& ids) {
     return column_remove(col, staged_ids, staged_vals, ids);
 }
+template <typename T, int8_t Tag>
+bool numeric_index<T, Tag>::append() {
+    return column_append(col, staged_ids, staged_vals);
+}
 template class numeric_index<int64_t, 1>;
 template class numeric_index<double, 2>;
 
@@ -166,6 +180,7 @@ index::result_type bool_index::query(const std::string& range) const {
 
 index::cluster_type bool_index::cluster(const result_type& rows) const { return column_cluster(col, number, rows); }
 bool bool_index::remove(const std::vector<int64_t>& ids) { return column_remove(col, staged_ids, staged_vals, ids); }
+bool bool_index::append() { return column_append(col, staged_ids, staged_vals); }
 
 // ---- string index: forwards to the GPU library
 namespace {

@@ -59,6 +59,10 @@ public:
     // NEW: the rows `ids` leave the column on the device (cdb_column_remove; rows staged since the last build() go too).  false = not
     // available (the CPU class): the caller rebuilds as the reference does (database.cpp:461-466, then build()).
     bool remove(const std::vector<int64_t>& ids);
+    // NEW: "insert ... build" for this field without the rebuild — the rows add() collected since the last build() join the built
+    // column on the device (cdb_column_append: only they are uploaded and sorted).  false = not available (the CPU class) or
+    // nothing was pending: nothing changed.
+    bool append();
 
 private:
     std::array<std::vector<int64_t>, 2> data;
@@ -89,6 +93,7 @@ public:
     cdb_column* column() const { return col; }
     cluster_type cluster(const result_type& rows) const;  // NEW: as bool_index::cluster
     bool remove(const std::vector<int64_t>& ids);          // NEW: as bool_index::remove
+    bool append();                                         // NEW: as bool_index::append
 
 protected:
     std::vector<std::pair<T, int64_t>> rows;

@@ -219,13 +219,16 @@ int cdb_query_and_columns(const cdb_key_query* keys, int nkeys, const cdb_column
 /* "rows", "staged_rows", "build_ms", "id_sort_skipped", "sparse_queries", "dense_queries", "probe_filters",
  * "materialised_keys", "last_k" (rows inside the last query's windows), "last_union_ms" (the last query_any's or
  * materialised key's union on the device, result download excluded), "sparse_clusters", "dense_clusters", "cluster_ms" (the last
- * cdb_column_cluster: ids uploaded .. groups on the host) */
+ * cdb_column_cluster: ids uploaded .. groups on the host), and the append_* / remove_* stats named at cdb_column_append and
+ * cdb_column_remove */
 int cdb_column_get_stat(const cdb_column* c, const char* name, double* value);
 /* Test and measurement hooks of the columns — NOT part of the stable ABI (like the other cdb_debug_* entry points they may change
  * or go without notice; the library chooses every path itself, a caller never needs them):
  * cdb_debug_column_set_option: "profile" (0/1: time the column's kernels with HIP events, read by cdb_debug_column_profile_dump as
  * "name ms launches bytes" lines) and "debug_query_path" (0 = automatic, 1 = always sparse, 2 = always dense: the tests of both
- * union paths and the crossover measurement of tools/bench_columns.py). */
+ * union paths and the crossover measurement of tools/bench_columns.py); "debug_maintain_path" (0 = automatic,
+ * 1 = the device path of cdb_column_append / cdb_column_remove wherever it is valid, 2 = stage + build / host filter + build:
+ * DESIGN.md §7.8). */
 int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value);
 int cdb_debug_column_profile_dump(cdb_column* c, char* buf, size_t cap);
 
@@ -394,10 +397,41 @@ void cdb_rendered_free(cdb_rendered* r);
  * "remove_bytes" (text bytes dropped), "remove_ms" (wall, under the lock); with option profile the kernels are timed as rm_*.
  * A sharded string column removes with cdb_shards_remove. */
 int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
-/* The same for a column, with the same counting rules: the rows leave the built and the staged rows, and the column's own build (a
- * device sort of milliseconds) runs over the rest.  The result equals a fresh column built from the surviving rows; a failed build
- * leaves the column as it was. */
+/* The same for a column, with the same counting rules.  The result equals a fresh column built from the surviving rows; a failure
+ * leaves the column as it was.
+ *   Paths.  With no rows staged since the last build the four arrays are compacted on the device (column_maintain.hip): only `ids`
+ * is uploaded, one lane per id marks its row in id order and in value order, both orders are compacted stably (stable_tiles.h) and
+ * the positions follow through one gather; fresh blocks are published as a build publishes them.  With staged rows the rows leave
+ * the built and the staged rows alike on the host path: the built rows are downloaded, filtered with the staged ones and the
+ * column's own build runs over the rest.  Option "debug_maintain_path" (cdb_debug_column_set_option) = 2 forces the host path.
+ *   Stats: "removes" (calls that dropped something), "remove_compactions" (device path), "remove_rebuilds" (host path), and of the
+ * last such call "remove_rows" and "remove_ms" (wall, under the lock); with option profile the kernels are timed as col_rm_*. */
 int cdb_column_remove(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
+
+/* Rows join a built column on the device, without sorting the old rows again — "insert ... build" for a numeric or bool field.
+ * values is as for cdb_column_add_bulk (uint8_t / int64_t / double by kind); NaN is refused ("cdb_column_append: NaN is not a valid
+ * value (row i)").  Only the new rows are uploaded and sorted; they are ranked against the old (value, id) order and the old id order
+ * by binary search and merged in stably (column_maintain.hip).  A new bool row lands behind every old row of its value.
+ *   Result.  After a successful call the column cannot be told from one that got the same rows by cdb_column_add_bulk +
+ * cdb_column_build: every query entry point, cdb_column_cluster, cdb_query_and_columns, cdb_filter, the stats "rows" and "kind";
+ * the device arrays are equal bit for bit.  *appended (may be NULL) = n.
+ *   Edges.  n = 0 is valid and changes nothing.  On a column that was never built, or holds no rows, the call is the build of the
+ * batch.  An id the column already holds, or one given twice in the batch, is refused with CDB_E_INVALID and "cdb_column_append:
+ * duplicate object id N in one column"; more than 2^32 - 1 rows in all are refused before anything is touched.  With n > 0 neither
+ * ids nor values may be NULL (CDB_E_INVALID).
+ *   Pending additions.  Rows staged with cdb_column_add_bulk and not yet built make the call fail with CDB_E_INVALID and "append:
+ * rows were added since the last build"; nothing changes.
+ *   Locking and failure.  The call is exclusive, like a build.  Everything new is made in fresh blocks while the old arrays stand;
+ * a failure leaves the old column serving (cdb_column_last_error tells why).
+ *   Paths.  "debug_maintain_path" = 2 stages the rows and runs the column's own build over old and new rows (the path of
+ * cdb_column_add_bulk + cdb_column_build); 0 and 1 merge wherever the column holds rows.
+ *   Stats: "appends", "append_merges", "append_rebuilds" (the build of the batch, and path 2), "append_id_concat" (merges whose new
+ * ids all exceeded the old ones: the id order was a concatenation), and of the last call "append_rows", "append_ms" (wall, under
+ * the lock); with option profile the kernels are timed as col_ap_*. */
+int cdb_column_append(cdb_column* c, const int64_t* ids, const void* values, uint64_t n, uint64_t* appended);
+/* Test hook, NOT part of the stable ABI: the four device arrays of a built column (keys_v u64, ids_v i64, id_sorted i64, vpos u32;
+ * "rows" entries each, any pointer may be NULL) copied to the host. */
+int cdb_debug_column_arrays(cdb_column* c, uint64_t* keys_v, int64_t* ids_v, int64_t* id_sorted, uint32_t* vpos);
 
 /* Documents join a built index on the device, without a rebuild — replaces "insert ... build" (interface.cpp:157-180, :286-288, and
  * database.cpp:276-280, which constructs the next generation beside the serving one) for one string key.  The arguments are those of
