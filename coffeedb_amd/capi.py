@@ -39,6 +39,7 @@ EXPORTS = [
     "cdb_filter", "cdb_rowset_free", "cdb_rowset_last_error", "cdb_rowset_size", "cdb_rowset_rows", "cdb_rowset_page", "cdb_rowset_cluster",
     "cdb_rowset_cluster_column", "cdb_rowset_get_stat", "cdb_debug_rowset_from_rows", "cdb_debug_rowset_set_option",
     "cdb_debug_rowset_profile_dump",
+    "cdb_column_values", "cdb_rowset_select", "cdb_selected_free",
     "cdb_debug_scan", "cdb_debug_scan_partials", "cdb_debug_stable_ranks",
     "cdb_debug_sweep_records", "cdb_debug_vl_tables",
     "cdb_debug_carried_inplace", "cdb_debug_segsort",
@@ -90,6 +91,24 @@ class CdbRendered(C.Structure):
 
 
 RENDER_TEXT, RENDER_SPANS = 1, 2
+
+
+class CdbSelectField(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("shards", C.c_void_p), ("column", C.c_void_p),
+                ("kw_blob", C.c_void_p), ("kw_offsets", C.c_void_p), ("nkw", C.c_uint64)]
+
+
+class CdbSelectedField(C.Structure):
+    _fields_ = [("kind", C.c_int), ("missing", C.c_uint64), ("found", C.POINTER(C.c_uint8)), ("values", C.POINTER(C.c_uint64)),
+                ("text_ptr", C.POINTER(C.c_uint64)), ("text_blob", C.POINTER(C.c_char))]
+
+
+class CdbSelected(C.Structure):
+    _fields_ = [("nrows", C.c_uint64), ("nfields", C.c_int), ("ids", C.POINTER(C.c_int64)), ("counts", C.POINTER(C.c_int64)),
+                ("fields", C.POINTER(CdbSelectedField))]
+
+
+SELECT_STRING = 3   # cdb_selected_field.kind of a string field (the reference's tag)
 
 
 class CdbDeviceHits(C.Structure):
@@ -277,6 +296,10 @@ def load_library():
     lib.cdb_debug_rowset_from_rows.argtypes = [C.c_int, vp, vp, u64, C.POINTER(vp)]
     lib.cdb_debug_rowset_set_option.argtypes = [vp, cp, i64]
     lib.cdb_debug_rowset_profile_dump.argtypes = [vp, C.c_char_p, C.c_size_t]
+    lib.cdb_column_values.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
+    lib.cdb_rowset_select.argtypes = [vp, u64, u64, C.POINTER(CdbSelectField), C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(CdbSelected)]
+    lib.cdb_selected_free.argtypes = [C.POINTER(CdbSelected)]
+    lib.cdb_selected_free.restype = None
     _LIB = lib
     return lib
 
@@ -954,6 +977,22 @@ class GpuColumn:
         finally:
             self._lib.cdb_clusters_free(C.byref(r))
 
+    def _typed(self, raw):
+        """raw uint64 values (cdb_clusters.values, cdb_column_values) as the column's dtype"""
+        return raw.astype(np.bool_) if self.kind == 0 else raw.view(np.int64 if self.kind == 1 else np.float64)
+
+    def values(self, ids, with_missing=False, raw=False):
+        """cdb_column_values (data[id][field] of database.cpp:406-415): the value of every row of `ids`, in the caller's order.  Returns
+        (values as the column's dtype, found bool array); a row the column does not hold has found False and value 0.  raw=True
+        leaves the values as the uint64 the C side returns; with_missing=True appends the count of rows not found."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        n = len(ids)
+        vals, found, missing = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint8), C.c_uint64(0)
+        self._check(self._lib.cdb_column_values(self._h, _ptr(ids) if n else None, n, _ptr(vals) if n else None, _ptr(found) if n else None,
+                                                C.byref(missing)))
+        out = (vals if raw else self._typed(vals), found.astype(bool))
+        return out + (int(missing.value),) if with_missing else out
+
     def stat(self, name):
         v = C.c_double(0)
         if self._lib.cdb_column_get_stat(self._h, name.encode(), C.byref(v)) != 0:
@@ -1166,7 +1205,8 @@ def query_and(keys, ranked=False, lo=1, hi=(1 << 62), limit=0):
 class GpuRowSet:
     """A filtered row set that stays on the device (cdb_rowset_*): made by filter_rows() or debug_rowset_from_rows().  `size` is the
     `count` operation; rows() all rows ascending by id; page(first, last) rows [first, last) of the ranking (descending count as
-    signed int64, ties ascending id); cluster(field) groups the rows by a GpuStringIndex or GpuColumn without uploading them.
+    signed int64, ties ascending id); cluster(field) groups the rows by a GpuStringIndex or GpuColumn without uploading them;
+    select(first, last, fields) is page() plus the fields of its rows, read on the device in the same call.
     rows() and page() return (ids, counts) as numpy int64 arrays."""
 
     def __init__(self, handle):
@@ -1237,6 +1277,58 @@ class GpuRowSet:
             return values, counts, reps, int(r.missing)
         finally:
             self._lib.cdb_clusters_free(C.byref(r))
+
+    def select(self, first, last, fields, left=b"", right=b"", raw=False):
+        """cdb_rowset_select: rows [first, last) of the ranking (page()'s rules) with their fields, read on the device in one call.
+        `fields` is a list of (GpuStringIndex | GpuShards, keywords) pairs — keywords may be empty: the plain document — and
+        GpuColumn objects.  Returns (ids, counts, per-field results in the caller's order): a string field gives
+        (texts: list of bytes, found bool array, missing), a column (values as its dtype, found, missing).  raw=True leaves every
+        field as a dict of the C arrays ("kind", "found", "missing", and "values" uint64 or "text_ptr" / "text_blob")."""
+        packed, keep = (CdbSelectField * max(len(fields), 1))(), []
+        for k, f in enumerate(fields):
+            q = packed[k]
+            if isinstance(f, GpuColumn):
+                q.column = f._h
+                continue
+            handle, keywords = f
+            if isinstance(handle, GpuShards):
+                q.shards = handle._h
+            elif isinstance(handle, GpuStringIndex):
+                q.index = handle._h
+            else:
+                raise TypeError(f"GpuRowSet.select: field {k}: {type(handle).__name__} is neither a GpuStringIndex nor a GpuShards")
+            keywords = [bytes(x) for x in keywords]
+            blob = np.frombuffer(b"".join(keywords), dtype=np.uint8)
+            offs = np.zeros(len(keywords) + 1, dtype=np.uint64)
+            np.cumsum([len(x) for x in keywords], out=offs[1:])
+            keep += [blob, offs]
+            q.kw_blob, q.kw_offsets, q.nkw = (blob.ctypes.data if len(blob) else None), offs.ctypes.data, len(keywords)
+        left, right = bytes(left), bytes(right)
+        r = CdbSelected()
+        self._check(self._lib.cdb_rowset_select(self._h, int(first), int(last), packed, len(fields), left if left else None, len(left),
+                                                right if right else None, len(right), C.byref(r)))
+        try:
+            n = int(r.nrows)
+            out = []
+            for k, f in enumerate(fields):
+                g = r.fields[k]
+                found = _array(g.found, n, np.uint8).astype(bool)
+                if g.kind == SELECT_STRING:
+                    tp = _array(g.text_ptr, n + 1, np.uint64)
+                    tb = C.string_at(g.text_blob, int(tp[n]))
+                    if raw:
+                        out.append({"kind": g.kind, "found": found, "missing": int(g.missing), "text_ptr": tp, "text_blob": tb})
+                    else:
+                        out.append(([tb[int(tp[i]):int(tp[i + 1])] for i in range(n)], found, int(g.missing)))
+                else:
+                    vals = _array(g.values, n, np.uint64)
+                    if raw:
+                        out.append({"kind": g.kind, "found": found, "missing": int(g.missing), "values": vals})
+                    else:
+                        out.append((f._typed(vals), found, int(g.missing)))
+            return _array(r.ids, n, np.int64), _array(r.counts, n, np.int64), out
+        finally:
+            self._lib.cdb_selected_free(C.byref(r))
 
     def stat(self, name):
         v = C.c_double(0)

@@ -675,8 +675,35 @@ struct cdb_column {
     uint64_t removes = 0, remove_compactions = 0, remove_rebuilds = 0, remove_rows = 0;
     double append_ms = 0, remove_ms = 0;
 };
+// ... and behind cdb_rowset (rowset.hip makes and pages it, select.hip reads a page's fields)
+struct cdb_rowset {
+    cdb::Index ws;  // stream, device, lock, error text, radix / scan work spaces, profiler
+    cdb::DevBuf ids, counts;  // m rows, ascending id
+    uint64_t m = 0;
+    cdb::DevBuf state;        // ST_* words
+    uint64_t key_diff = 0;    // bits in which the rows' keys differ
+    int debug_page_path = 0;  // 0 automatic, 1 select (where K < m), 2 sort
+    uint64_t page_selects = 0, page_sorts = 0, select_passes = 0, clusters = 0;
+    double page_ms = 0, cluster_ms = 0;
+    uint64_t selects = 0, select_rows = 0;  // select.hip: cdb_rowset_select calls, and the rows of the last one
+    double select_ms = 0;
+};
 struct cdb_key_query;
 namespace cdb {
+// rowset.hip — a page in two halves: rows [first, min(last, m)) of the ranking left in device buffers on the row set's stream
+// (nothing is synchronised; the sort's buffers live on in the page until it goes), and rows from the device into result arrays
+// (synchronises).  cdb_rowset_page is the two back to back; cdb_rowset_select keeps the device ids for its fields.  The caller
+// holds the row set's lock and has its stream and device set.
+struct DevicePage {
+    DevBuf k0, k1, v0, v1, ids, counts;
+    uint64_t n = 0;  // rows in ids / counts (0: neither is allocated)
+};
+void rowset_page_device(cdb_rowset* rs, uint64_t first, uint64_t last, DevicePage& pg);
+void rowset_download_rows(hipStream_t s, const int64_t* d_ids, const int64_t* d_counts, uint64_t n, int64_t** ids, int64_t** counts, size_t* nrows);
+// render.hip — cdb_render_rows over ids that already lie in device memory on the handle's GPU (complete when the call is made; the
+// caller keeps them unchanged during it).  Takes the handle's lock and throws.
+void render_index_device_rows(cdb_index* h, const int64_t* d_ids, uint64_t nrows, const char* blob, const uint64_t* offsets, uint64_t nkw,
+                              const char* left, uint64_t left_len, const char* right, uint64_t right_len, int what, cdb_rendered* out);
 // columns.hip — the four arrays of a column (layout: columns.hip's head) while they are made, before they are published
 struct ColumnArrays {
     DevBuf keys_v, ids_v, id_sorted, vpos;

@@ -311,8 +311,9 @@ struct Keywords {  // validated on the host: kw j = blob[off[j] .. off[j + 1])
     uint64_t n;
 };
 
-void render_rows(Index& ix, const int64_t* ids, uint64_t nrows, const Keywords& kws, const char* left, uint64_t L, const char* right, uint64_t R,
-                 int what, Rendered& res) {
+// the rows as the caller's host ids, or (d_rows != nullptr) as ids that already lie on the handle's device: only the upload differs
+void render_rows(Index& ix, const int64_t* ids, const int64_t* d_rows, uint64_t nrows, const Keywords& kws, const char* left, uint64_t L,
+                 const char* right, uint64_t R, int what, Rendered& res) {
     hipStream_t s = ix.stream;
     const double t0 = wall_ms();
     const bool want_text = (what & CDB_RENDER_TEXT) != 0, want_spans = (what & CDB_RENDER_SPANS) != 0;
@@ -341,15 +342,18 @@ void render_rows(Index& ix, const int64_t* ids, uint64_t nrows, const Keywords& 
 
     // 1. rows -> documents -> page offsets
     DevBuf d_ids, d_out, d_doc, d_found, d_page;
-    d_ids.alloc(nrows * 8);
-    CDB_HIP(hipMemcpyAsync(d_ids.p, ids, nrows * 8, hipMemcpyHostToDevice, s));
+    if (!d_rows) {
+        d_ids.alloc(nrows * 8);
+        CDB_HIP(hipMemcpyAsync(d_ids.p, ids, nrows * 8, hipMemcpyHostToDevice, s));
+        d_rows = d_ids.as<int64_t>();
+    }
     d_out.alloc(16);
     CDB_HIP(hipMemsetAsync(d_out.p, 0, 16, s));
     d_doc.alloc(nrows * 4);
     d_found.alloc(nrows);
     d_page.alloc((nrows + 1) * 8);
     int t = ix.prof.begin(s);
-    hipLaunchKernelGGL(rnd_lookup_kernel, dim3(grid_for(nrows)), dim3(256), 0, s, (const int64_t*)d_ids.as<int64_t>(), nrows, id_tab, id_doc, ndocs,
+    hipLaunchKernelGGL(rnd_lookup_kernel, dim3(grid_for(nrows)), dim3(256), 0, s, d_rows, nrows, id_tab, id_doc, ndocs,
                        doc_start, d_doc.as<uint32_t>(), d_found.as<uint8_t>(), d_out.as<unsigned long long>());
     CDB_HIP(hipGetLastError());
     RowLenIn lin{d_doc.as<uint32_t>(), doc_start};
@@ -494,6 +498,15 @@ void render_rows(Index& ix, const int64_t* ids, uint64_t nrows, const Keywords& 
 
 }  // namespace
 
+void cdb::render_index_device_rows(cdb_index* h, const int64_t* d_ids, uint64_t nrows, const char* blob, const uint64_t* offsets, uint64_t nkw,
+                                   const char* left, uint64_t left_len, const char* right, uint64_t right_len, int what, cdb_rendered* out) {
+    std::lock_guard<std::mutex> g(h->ix.mu);
+    IndexScope scope(h->ix);
+    Rendered res(h->ix.stream);
+    render_rows(h->ix, nullptr, d_ids, nrows, Keywords{blob, offsets, nkw}, left, left_len, right, right_len, what, res);
+    res.hand_over(out);
+}
+
 extern "C" {
 
 int cdb_render_rows(cdb_index* h, const int64_t* ids, uint64_t nrows, const char* blob, const uint64_t* offsets, uint64_t nkw, const char* left,
@@ -507,7 +520,7 @@ int cdb_render_rows(cdb_index* h, const int64_t* ids, uint64_t nrows, const char
         std::lock_guard<std::mutex> g(h->ix.mu);
         IndexScope scope(h->ix);
         Rendered res(h->ix.stream);
-        render_rows(h->ix, ids, nrows, Keywords{blob, offsets, nkw}, left, left_len, right, right_len, what, res);
+        render_rows(h->ix, ids, nullptr, nrows, Keywords{blob, offsets, nkw}, left, left_len, right, right_len, what, res);
         res.hand_over(out);
     });
 }

@@ -11,7 +11,8 @@
 // stable compaction takes the rows with key < T and the first rows (in id order) with key == T that fill up K (two running counts:
 // scan.h's U2 over ballot-ranked tiles; stable_tiles.h ranks one flag and synchronises for its total, this take needs two counts
 // and no total); those K pairs are sorted and rows [first, K) go out.  K == m, or option debug_page_path = 2: every row is keyed
-// and sorted (the sort path).
+// and sorted (the sort path).  The page is made in two halves — rowset_page_device leaves ids and counts in device buffers,
+// rowset_download_rows fetches them — so that cdb_rowset_select (select.hip) can read the page's fields from the device ids.
 #include <cstring>
 
 #include "../../include/coffeedb_gpu.h"
@@ -19,17 +20,6 @@
 #include "scan.h"
 
 using namespace cdb;
-
-struct cdb_rowset {
-    cdb::Index ws;  // stream, device, lock, error text, radix / scan work spaces, profiler
-    cdb::DevBuf ids, counts;  // m rows, ascending id
-    uint64_t m = 0;
-    cdb::DevBuf state;        // ST_* words
-    uint64_t key_diff = 0;    // bits in which the rows' keys differ
-    int debug_page_path = 0;  // 0 automatic, 1 select (where K < m), 2 sort
-    uint64_t page_selects = 0, page_sorts = 0, select_passes = 0, clusters = 0;
-    double page_ms = 0, cluster_ms = 0;
-};
 
 namespace {
 
@@ -275,7 +265,9 @@ void rowset_adopt(cdb_rowset* rs, hipStream_t s, const int64_t* src_ids, const i
     rs->key_diff = bits[ST_OR] & ~bits[ST_AND];
 }
 
-void download_rows(hipStream_t s, const int64_t* d_ids, const int64_t* d_counts, uint64_t n, int64_t** ids, int64_t** counts, size_t* nrows) {
+}  // namespace
+
+void cdb::rowset_download_rows(hipStream_t s, const int64_t* d_ids, const int64_t* d_counts, uint64_t n, int64_t** ids, int64_t** counts, size_t* nrows) {
     int64_t* hi = (int64_t*)host_alloc(n * 8);
     int64_t* hc = nullptr;
     try {
@@ -296,6 +288,8 @@ void download_rows(hipStream_t s, const int64_t* d_ids, const int64_t* d_counts,
     *nrows = (size_t)n;
 }
 
+namespace {
+
 // The automatic rule (profiles/bench_page.jsonl, one MI355X run over 2^16, 2^20 .. 2^24 rows, three count
 // distributions, page ends from 10 to m / 2): below 2^22 rows both paths are bound by their launches and the sort path, which has
 // fewer, wins (select / sort 1.00-1.34 at 2^16 and 2^20, 0.94-1.25 at 2^21); at 2^22 select wins every page end up to 1000
@@ -306,22 +300,20 @@ bool page_selects(const cdb_rowset* rs, uint64_t K) {
     return rs->debug_page_path == 1 || rs->m >= AUTO_SELECT_MIN_ROWS;
 }
 
-void rowset_page(cdb_rowset* rs, uint64_t first, uint64_t last, int64_t** ids, int64_t** counts, size_t* nrows) {
+}  // namespace
+
+void cdb::rowset_page_device(cdb_rowset* rs, uint64_t first, uint64_t last, DevicePage& pg) {
     Index& ws = rs->ws;
     hipStream_t s = ws.stream;
-    const double t0 = wall_ms();
     const uint64_t m = rs->m, K = std::min(last, m);
-    if (first >= K) {
-        download_rows(s, nullptr, nullptr, 0, ids, counts, nrows);
-        rs->page_ms = wall_ms() - t0;
-        return;
-    }
+    pg.n = 0;
+    if (first >= K) return;
+    DevBuf &k0 = pg.k0, &k1 = pg.k1, &v0 = pg.v0, &v1 = pg.v1, &o_ids = pg.ids, &o_counts = pg.counts;
     const int64_t* d_ids = rs->ids.as<int64_t>();
     const int64_t* d_counts = rs->counts.as<int64_t>();
     unsigned long long* st = rs->state.as<unsigned long long>();
     const bool select = page_selects(rs, K);
     const uint64_t nsort = select ? K : m;
-    DevBuf k0, k1, v0, v1, o_ids, o_counts;
     k0.alloc(nsort * 8); k1.alloc(nsort * 8); v0.alloc(nsort * 8); v1.alloc(nsort * 8);
     if (select) {
         // prefix, mask, rank to skip; and the digit counters cleared (a page that failed between a histogram and its pick left some)
@@ -373,8 +365,17 @@ void rowset_page(cdb_rowset* rs, uint64_t first, uint64_t last, int64_t** ids, i
     ws.prof.end(t, "pg_out", n_out * 32, s);
     CDB_HIP(hipGetLastError());
     radix_check_error(s, ws.rws);
-    download_rows(s, o_ids.as<int64_t>(), o_counts.as<int64_t>(), n_out, ids, counts, nrows);
-    ws.prof.resolve();
+    pg.n = n_out;
+}
+
+namespace {
+
+void rowset_page(cdb_rowset* rs, uint64_t first, uint64_t last, int64_t** ids, int64_t** counts, size_t* nrows) {
+    const double t0 = wall_ms();
+    DevicePage pg;
+    rowset_page_device(rs, first, last, pg);
+    rowset_download_rows(rs->ws.stream, pg.ids.as<int64_t>(), pg.counts.as<int64_t>(), pg.n, ids, counts, nrows);
+    if (pg.n) rs->ws.prof.resolve();
     rs->page_ms = wall_ms() - t0;
 }
 
@@ -443,7 +444,7 @@ int cdb_rowset_rows(cdb_rowset* rs, int64_t** ids, int64_t** counts, size_t* nro
     return guarded_ix(rs->ws, [&] {
         std::lock_guard<std::mutex> g(rs->ws.mu);
         SetScope scope(rs);
-        download_rows(rs->ws.stream, rs->ids.as<int64_t>(), rs->counts.as<int64_t>(), rs->m, ids, counts, nrows);
+        rowset_download_rows(rs->ws.stream, rs->ids.as<int64_t>(), rs->counts.as<int64_t>(), rs->m, ids, counts, nrows);
     });
 }
 
@@ -491,7 +492,8 @@ int cdb_rowset_get_stat(const cdb_rowset* rs, const char* name, double* value) {
     struct { const char* n; double v; } tab[] = {
         {"rows", (double)rs->m}, {"page_selects", (double)rs->page_selects}, {"page_sorts", (double)rs->page_sorts},
         {"select_passes", (double)rs->select_passes}, {"page_ms", rs->page_ms}, {"clusters", (double)rs->clusters},
-        {"cluster_ms", rs->cluster_ms},
+        {"cluster_ms", rs->cluster_ms}, {"selects", (double)rs->selects}, {"select_ms", rs->select_ms},
+        {"select_rows", (double)rs->select_rows},
     };
     for (auto& e : tab)
         if (!std::strcmp(e.n, name)) {

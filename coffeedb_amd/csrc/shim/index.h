@@ -167,6 +167,10 @@ public:
     // adjacent pair against the text) and the mapping of the device memory a rebuild beside this index will ask for — and says
     // whether the order is proved.  Nothing needs to call it: queries are answered meanwhile, a later build() joins it (cdb_proof_wait).
     bool settle() const;
+    // NEW: the device objects behind this field — exactly one of the two is set (COFFEEDB_GPUS decides which); what cdb_shim::select
+    // (select.h) hands to cdb_rowset_select
+    cdb_index* gpu_index() const { return handle; }
+    cdb_shards* gpu_shards() const { return shards; }
 
 private:
     std::vector<int64_t> ids;        // index.h:58-59: ids and (non-owning) views of the documents, in add() order

@@ -305,7 +305,7 @@ int cdb_rowset_page(cdb_rowset* rs, uint64_t first, uint64_t last, int64_t** ids
 int cdb_rowset_cluster(cdb_rowset* rs, cdb_index* field, int with_values, cdb_clusters* out);
 int cdb_rowset_cluster_column(cdb_rowset* rs, cdb_column* field, cdb_clusters* out);
 /* "rows", "page_selects", "page_sorts" (pages answered by either path; a page without rows runs neither), "select_passes" (key
- * bytes the last select visited), "page_ms", "clusters", "cluster_ms" */
+ * bytes the last select visited), "page_ms", "clusters", "cluster_ms", "selects", "select_ms", "select_rows" (cdb_rowset_select) */
 int cdb_rowset_get_stat(const cdb_rowset* rs, const char* name, double* value);
 /* Test and measurement hooks — NOT part of the stable ABI: a row set over the caller's rows (ids ascending, taken as given);
  * options "debug_page_path" (0 automatic: select from 2^22 rows on; 1 select wherever the page ends before the last row; 2 always sort) and "profile" (the
@@ -367,6 +367,59 @@ typedef struct cdb_rendered {
 int cdb_render_rows(cdb_index* h, const int64_t* ids, uint64_t nrows, const char* blob, const uint64_t* offsets, uint64_t nkw,
                     const char* left, size_t left_len, const char* right, size_t right_len, int what, cdb_rendered* out);
 void cdb_rendered_free(cdb_rendered* r);
+
+/* ---- select (select.hip) -------------------------------------------------------------------------------
+ * The value of row `id` in a built column — replaces data[id][field] of select() for a numeric or bool field (database.cpp:406-409 with
+ * keys, :413-415 without).  ids is in any order and may repeat; row i answers ids[i].  A row whose id the column does not hold gets
+ * found[i] = 0 and values[i] = 0 and is counted in *missing (may be NULL); a column that was never built answers every row missing, as
+ * cdb_column_cluster does; rows staged since the last build are not seen.  nrows = 0 is valid.  values[i] is what cdb_clusters.values
+ * holds for a group: the int64, the double's bit pattern, or 0 / 1.
+ * KNOWN DIVERGENCE: a double column folds -0.0 onto +0.0 when it is built (see cdb_column_cluster), so a row added as -0.0 reads +0.0.
+ * The call is a query: it waits out a build under the column's lock.  With option profile the kernel is timed as sel_values. */
+int cdb_column_values(cdb_column* c, const int64_t* ids, uint64_t nrows, uint64_t* values, uint8_t* found, uint64_t* missing);
+
+/* A page of a row set with its fields in one call — replaces the tail of the `query` operation (interface.cpp:225-248: span, then
+ * select(fields, highlight), database.cpp:394-441).  The page is cdb_rowset_page's in every respect: first / last, the clamping, the
+ * signed ranking with ties ascending id, the automatic select / sort rule and the counters "page_selects" / "page_sorts".  Its ids stay
+ * in device memory and every field is read where it lies; nfields = 0 is valid and is then cdb_rowset_page.
+ *   Fields, in the caller's order; exactly one of index / shards / column is set (else CDB_E_INVALID).
+ *   index: row i is what cdb_render_rows(index, page ids, keywords, left, right, CDB_RENDER_TEXT) returns — found and text; nkw = 0 gives
+ * the plain document (a string field without constraints, database.cpp:400-405); an empty keyword fails the call with "Empty keywords
+ * are not allowed".  Each string field has its own keyword list, as the reference keeps one automaton per key (database.cpp:396-399).
+ *   shards: the same through cdb_shards_render_rows with the host copy of the page's ids.
+ *   column: cdb_column_values of the page's ids; keywords on a column field are CDB_E_INVALID.  All column fields of a call are read by
+ * one kernel launch and come back in one copy.
+ *   An index or column on another GPU than the row set is CDB_E_INVALID, as for cdb_rowset_cluster.
+ *   Result.  kind = 3 for a string field (the reference's tag), else the column's kind.  All arrays are host memory owned by the library
+ * (pinned result cache when large; the values and found bytes of all column fields share ONE block): release with cdb_selected_free
+ * only.  A failed call leaves *out zeroed and nothing allocated; errors are reported on the row set (cdb_rowset_last_error; a sharded
+ * field's failure keeps its code and text).
+ *   Locks.  The row set's lock is held for the whole call; the columns' locks are taken together in address order and released before
+ * the string fields run, each of which takes its own handle's lock alone and waits out a rebuild as cdb_render_rows does.
+ *   Stats (cdb_rowset_get_stat): "selects", and of the last call "select_ms", "select_rows"; with option profile the column kernel is
+ * timed as sel_values next to the page's pg_*. */
+typedef struct cdb_select_field {
+    cdb_index*  index;    /* exactly one of index / shards / column is non-NULL */
+    struct cdb_shards* shards;   /* (cdb_shards, declared with the sharded entry points below) */
+    cdb_column* column;
+    const char* kw_blob; const uint64_t* kw_offsets; uint64_t nkw;   /* string fields: keywords to highlight; 0 = plain document */
+} cdb_select_field;
+typedef struct cdb_selected_field {
+    int kind;             /* 3 = string (the reference's tag), else the column's kind 0 / 1 / 2 */
+    uint64_t missing;     /* rows of the page whose id the field does not hold */
+    uint8_t*  found;      /* nrows */
+    uint64_t* values;     /* columns: nrows raw values exactly as cdb_clusters.values (column_key_raw); strings: NULL */
+    uint64_t* text_ptr;   /* strings: nrows + 1 offsets into text_blob; columns: NULL */
+    char*     text_blob;
+} cdb_selected_field;
+typedef struct cdb_selected {
+    uint64_t nrows; int nfields;
+    int64_t* ids; int64_t* counts;        /* the page, as cdb_rowset_page returns it */
+    cdb_selected_field* fields;           /* nfields, in the caller's order */
+} cdb_selected;
+int  cdb_rowset_select(cdb_rowset* rs, uint64_t first, uint64_t last, const cdb_select_field* fields, int nfields,
+                       const char* left, size_t left_len, const char* right, size_t right_len, cdb_selected* out);
+void cdb_selected_free(cdb_selected* r);
 
 /* Documents leave a built index on the device, without a rebuild — replaces "remove + build" (interface.cpp:274-285,
  * database.cpp:461-466 followed by :170-282) for one string key.  The reference deletes the raw files and the objects stay visible until
