@@ -40,6 +40,7 @@ EXPORTS = [
     "cdb_rowset_cluster_column", "cdb_rowset_get_stat", "cdb_debug_rowset_from_rows", "cdb_debug_rowset_set_option",
     "cdb_debug_rowset_profile_dump",
     "cdb_column_values", "cdb_rowset_select", "cdb_selected_free",
+    "cdb_rowset_remove", "cdb_rowset_all",
     "cdb_debug_scan", "cdb_debug_scan_partials", "cdb_debug_stable_ranks",
     "cdb_debug_sweep_records", "cdb_debug_vl_tables",
     "cdb_debug_carried_inplace", "cdb_debug_segsort",
@@ -106,6 +107,11 @@ class CdbSelectedField(C.Structure):
 class CdbSelected(C.Structure):
     _fields_ = [("nrows", C.c_uint64), ("nfields", C.c_int), ("ids", C.POINTER(C.c_int64)), ("counts", C.POINTER(C.c_int64)),
                 ("fields", C.POINTER(CdbSelectedField))]
+
+
+class CdbRemoveField(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("column", C.c_void_p), ("removed", C.c_uint64), ("missing", C.c_uint64),
+                ("status", C.c_int32), ("committed", C.c_int32)]
 
 
 SELECT_STRING = 3   # cdb_selected_field.kind of a string field (the reference's tag)
@@ -297,6 +303,8 @@ def load_library():
     lib.cdb_debug_rowset_set_option.argtypes = [vp, cp, i64]
     lib.cdb_debug_rowset_profile_dump.argtypes = [vp, C.c_char_p, C.c_size_t]
     lib.cdb_column_values.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
+    lib.cdb_rowset_remove.argtypes = [vp, C.POINTER(CdbRemoveField), C.c_int, C.POINTER(u64)]
+    lib.cdb_rowset_all.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.POINTER(vp)]
     lib.cdb_rowset_select.argtypes = [vp, u64, u64, C.POINTER(CdbSelectField), C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(CdbSelected)]
     lib.cdb_selected_free.argtypes = [C.POINTER(CdbSelected)]
     lib.cdb_selected_free.restype = None
@@ -1001,7 +1009,7 @@ class GpuColumn:
 
     def set_option(self, name, value):
         """Test / measurement hook (cdb_debug_column_set_option): "profile", "debug_query_path", "debug_cluster_path",
-        "debug_maintain_path"."""
+        "debug_maintain_path", "debug_fail_prepare"."""
         self._check(self._lib.cdb_debug_column_set_option(self._h, name.encode(), int(value)))
 
     def profile(self):
@@ -1330,6 +1338,29 @@ class GpuRowSet:
         finally:
             self._lib.cdb_selected_free(C.byref(r))
 
+    def remove(self, fields):
+        """cdb_rowset_remove: the rows of this set leave every field of `fields` (GpuStringIndex and GpuColumn objects), all or none;
+        the ids stay on the device.  Returns (rows, per-field dicts "removed", "missing", "status", "committed" in the caller's
+        order).  A failure raises RowSetRemoveError, a RuntimeError that carries the return code as `.code` and the per-field dicts as
+        `.fields`."""
+        packed = (CdbRemoveField * max(len(fields), 1))()
+        for k, f in enumerate(fields):
+            if isinstance(f, GpuColumn):
+                packed[k].column = f._h
+            elif isinstance(f, GpuStringIndex):
+                packed[k].index = f._h
+            else:
+                raise TypeError(f"GpuRowSet.remove: field {k}: {type(f).__name__} is neither a GpuStringIndex nor a GpuColumn")
+        rows = C.c_uint64(0)
+        rc_ = self._lib.cdb_rowset_remove(self._h, packed, len(fields), C.byref(rows))
+        out = [{"removed": int(q.removed), "missing": int(q.missing), "status": int(q.status), "committed": int(q.committed)}
+               for q in packed[:len(fields)]]
+        if rc_ != 0:
+            e = RowSetRemoveError(self._lib.cdb_rowset_last_error(self._h).decode(errors="replace"))
+            e.code, e.fields, e.rows = rc_, out, int(rows.value)
+            raise e
+        return int(rows.value), out
+
     def stat(self, name):
         v = C.c_double(0)
         if self._lib.cdb_rowset_get_stat(self._h, name.encode(), C.byref(v)) != 0:
@@ -1349,6 +1380,32 @@ class GpuRowSet:
             name, ms, launches, nbytes = line.split()
             out[name] = {"ms": float(ms), "launches": int(launches), "bytes": int(nbytes)}
         return out
+
+
+class RowSetRemoveError(RuntimeError):
+    """GpuRowSet.remove failed: `.code` is the library's return code, `.fields` the per-field results, `.rows` the set's size."""
+    code, fields, rows = 0, (), 0
+
+
+def rowset_all(fields):
+    """cdb_rowset_all: the GpuRowSet of every object the given fields (GpuStringIndex and GpuColumn objects) hold — the union of their
+    ids, ascending as signed int64, every count 0.  filter() without constraints."""
+    lib = load_library()
+    idx = [f for f in fields if isinstance(f, GpuStringIndex)]
+    cols = [f for f in fields if isinstance(f, GpuColumn)]
+    if len(idx) + len(cols) != len(fields):
+        raise TypeError("rowset_all: fields are GpuStringIndex and GpuColumn objects")
+    ai = (C.c_void_p * max(len(idx), 1))(*[f._h for f in idx])
+    ac = (C.c_void_p * max(len(cols), 1))(*[f._h for f in cols])
+    h = C.c_void_p()
+    rc_ = lib.cdb_rowset_all(ai if idx else None, len(idx), ac if cols else None, len(cols), C.byref(h))
+    if rc_ != 0:
+        lead = idx[0] if idx else (cols[0] if cols else None)
+        if lead is None:
+            raise RuntimeError(f"cdb_rowset_all failed (code {rc_}): no field given")
+        err = lib.cdb_last_error if idx else lib.cdb_column_last_error
+        raise RuntimeError(err(lead._h).decode(errors="replace"))
+    return GpuRowSet(h)
 
 
 def filter_rows(keys, corr=None):

@@ -317,13 +317,7 @@ void replace_column(Index& ix, Prepare&& prepare) {
     drained_on_failure(ix, [&] { prepare(c); });
     install(ix, c);
 }
-// cdb_remove / cdb_append change a built column only.  Returns its documents (0: never built, or built over nothing)
-uint64_t built_docs_or_refuse(const Index& ix, const char* op) {
-    const uint64_t built_docs = ix.width ? ix.ndocs : 0;
-    if (ix.host_text_valid && ix.ids.size() > built_docs) throw Error(std::string(op) + ": documents were added since the last build");
-    return built_docs;
-}
-// ... and end their prepare here: what the plan made beside the old index becomes the column, once the stream is idle
+// cdb_remove / cdb_append end their prepare here: what the plan made beside the old index becomes the column, once the stream is idle
 // (made.arr empty: only text and tables were made, the array is built over them)
 void adopt_blocks(Index& ix, NewColumn& col, ColumnBlocks& made) {
     if (made.arr.sa.p) {
@@ -1108,7 +1102,7 @@ void reserve_wait() { reserve_join(); }
 // entries dropped and the rest re-encoded in the same order; an array in the reference's order (bytes >= 0x80 under
 // reference_compat) depends on bucket sizes that change with n, so there only text and tables are compacted and the array is
 // built over them on the device.  Either way nothing is uploaded but the ids.
-ColumnChangePtr remove_prepare(Index& ix, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
+ColumnChangePtr remove_prepare(Index& ix, RowIds ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
     DeviceScope dscope(ix);
     const double t0 = wall_ms();
     const uint64_t built_docs = built_docs_or_refuse(ix, "remove");
@@ -1139,6 +1133,7 @@ ColumnChangePtr remove_prepare(Index& ix, const int64_t* ids, uint64_t nids, uin
         col.host = NewColumn::HOST_NONE;  // (a staging copy that equals the built column goes: cdb_add* fetch the survivors back)
         remove_text(ix, p);
         if (c->kept_array) remove_compact(ix, p, (int)L.bits, L.width, layout_packable(ix, L));
+        if (ix.debug_fail_prepare) throw DeviceError("debug: prepare failure requested (test hook)");
         adopt_blocks(ix, col, p);
     });
     return c;
@@ -1232,7 +1227,7 @@ int cdb_remove(cdb_index* h, const int64_t* ids, uint64_t nids, uint64_t* remove
     return guarded(h, [&] {
         Index& ix = h->ix;
         std::lock_guard<std::mutex> g(ix.mu);
-        ColumnChangePtr c = remove_prepare(ix, ids, nids, removed, missing);
+        ColumnChangePtr c = remove_prepare(ix, RowIds{ids, nullptr}, nids, removed, missing);
         if (c) column_commit(ix, *c);
     });
 }
@@ -1805,6 +1800,7 @@ int cdb_set_option(cdb_index* h, const char* name, int64_t value) {
     else if (!std::strcmp(name, "fuse_keygen")) ix.fuse_keygen = value != 0;
     else if (!std::strcmp(name, "force_big_path")) ix.force_big_path = value != 0;
     else if (!std::strcmp(name, "debug_fail_build")) ix.debug_fail_build = value != 0;
+    else if (!std::strcmp(name, "debug_fail_prepare")) ix.debug_fail_prepare = value != 0;
     else if (!std::strcmp(name, "debug_append_path")) ix.debug_append_path = value == 1 || value == 2 ? (int)value : 0;  // cdb_append: 0 automatic, 1 merge where valid, 2 rebuild
     else if (!std::strcmp(name, "debug_no_segcap")) ix.debug_no_segcap = value != 0;  // test hook: "a bucket does not fit the record memory"
     else if (!std::strcmp(name, "debug_starve_group")) ix.debug_starve_group = (int)value;  // 1 = reported after the sorts, 2 = error flag up before the initial sort

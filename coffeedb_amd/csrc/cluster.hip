@@ -379,19 +379,6 @@ struct Result {
     }
 };
 
-// the rows' ids: a host array, or an array that already lies on the field's GPU (a row set's: rowset.hip)
-struct RowIds {
-    const int64_t* host = nullptr;
-    const int64_t* device = nullptr;
-};
-// ... where the kernels read them: uploaded into d, or the caller's device array as it is
-const int64_t* resident_ids(hipStream_t s, DevBuf& d, RowIds ids, uint64_t nrows) {
-    if (ids.device) return ids.device;
-    d.alloc(nrows * 8);
-    CDB_HIP(hipMemcpyAsync(d.p, ids.host, nrows * 8, hipMemcpyHostToDevice, s));
-    return d.as<int64_t>();
-}
-
 // ---- columns: host side ------------------------------------------------------------------------------------------------------------
 void column_run_starts(cdb_column* c) {
     if (c->clu_generation == c->generation) return;

@@ -12,7 +12,9 @@
 //                      newpos_old[old position] = its slot
 //            id        the same over id_sorted — or, when the smallest new id exceeds the largest old one (ids are insertion
 //                      timestamps), a plain concatenation; vpos_new follows through newpos_old and the new rows' slots
-// Everything is written into fresh blocks while the old arrays stand and published at the end as column_build publishes.
+// Everything is written into fresh blocks while the old arrays stand and published at the end as column_build publishes.  A removal
+// does so in two halves (index_impl.h: column_remove_prepare / column_remove_commit): cdb_column_remove runs them back to back,
+// cdb_rowset_remove (rowset_maintain.hip) prepares every field of a call, from the row set's device ids, before it commits any.
 #include <algorithm>
 #include <cstring>
 
@@ -295,29 +297,29 @@ void column_append_device(cdb_column* c, const int64_t* ids, const std::vector<u
 
 }  // namespace
 
-void cdb::column_remove_device(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing) {
+void cdb::column_remove_prepare(cdb_column* c, RowIds ids, uint64_t nids, ColumnRemoval& r) {
     Index& ws = c->ws;
     hipStream_t s = ws.stream;
     Profiler& prof = ws.prof;
     const uint64_t n = c->n;
-    *removed = 0;
-    *missing = nids;
+    r.removed = 0;
+    r.missing = nids;
+    r.changed = false;
     if (!n) return;  // (never built, or built over nothing: every id is missing)
     const int64_t* id_sorted = c->id_sorted.as<int64_t>();
     const uint32_t* vpos = c->vpos.as<uint32_t>();
     // 1. mark
     DevBuf d_ids, d_out, dead_r, dead_v;
-    d_ids.alloc(nids * 8);
+    const int64_t* idp = resident_ids(s, d_ids, ids, nids);
     d_out.alloc(16);
     dead_r.alloc(n);
     dead_v.alloc(n);
-    CDB_HIP(hipMemcpyAsync(d_ids.p, ids, nids * 8, hipMemcpyHostToDevice, s));
     CDB_HIP(hipMemsetAsync(d_out.p, 0, 16, s));
     CDB_HIP(hipMemsetAsync(dead_r.p, 0, n, s));
     CDB_HIP(hipMemsetAsync(dead_v.p, 0, n, s));
     int t = prof.begin(s);
-    hipLaunchKernelGGL(col_rm_mark_kernel, dim3(grid_for(nids)), dim3(256), 0, s, (const int64_t*)d_ids.as<int64_t>(), nids, id_sorted, vpos, n,
-                       dead_r.as<uint8_t>(), dead_v.as<uint8_t>(), d_out.as<unsigned long long>());
+    hipLaunchKernelGGL(col_rm_mark_kernel, dim3(grid_for(nids)), dim3(256), 0, s, idp, nids, id_sorted, vpos, n, dead_r.as<uint8_t>(),
+                       dead_v.as<uint8_t>(), d_out.as<unsigned long long>());
     prof.end(t, "col_rm_mark", nids * (8 + 8 * (uint64_t)bit_width64(n) + 6), s);
     CDB_HIP(hipGetLastError());
     // 2. kept positions per tile
@@ -327,40 +329,56 @@ void cdb::column_remove_device(cdb_column* c, const int64_t* ids, uint64_t nids,
     unsigned long long miss = 0;
     CDB_HIP(hipMemcpyAsync(&miss, d_out.p, 8, hipMemcpyDeviceToHost, s));
     CDB_HIP(hipStreamSynchronize(s));
-    *missing = miss;
-    *removed = n - kept;
+    r.missing = miss;
+    r.removed = n - kept;
     if (kept == n) return;
     // 3. value order
     const uint64_t cap = std::max<uint64_t>(kept, 1);
-    ColumnArrays a;
+    ColumnArrays& a = r.a;
     DevBuf newpos;
-    a.keys_v.alloc(cap * 8);
-    a.ids_v.alloc(cap * 8);
-    a.id_sorted.alloc(cap * 8);
-    a.vpos.alloc(cap * 4);
-    newpos.alloc(n * 4);
-    t = prof.begin(s);
-    hipLaunchKernelGGL(col_rm_value_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, (const uint64_t*)c->keys_v.as<uint64_t>(),
-                       (const int64_t*)c->ids_v.as<int64_t>(), n, (const uint8_t*)dead_v.as<uint8_t>(), (const uint64_t*)tile_base.as<uint64_t>(),
-                       a.keys_v.as<uint64_t>(), a.ids_v.as<int64_t>(), newpos.as<uint32_t>(), c->n_false, d_out.as<uint64_t>() + 1);
-    prof.end(t, "col_rm_value", n * 17 + kept * 20 + ntiles * 8, s);
-    CDB_HIP(hipGetLastError());
-    // 4. id order
-    if (tile_bases(ws, "column remove", ByteClear{dead_r.as<uint8_t>()}, n, tile_base, "col_rm_count", n + ntiles * 8) != kept)
-        throw InternalError("column remove: kept id ranks and kept positions differ (internal)");
-    t = prof.begin(s);
-    hipLaunchKernelGGL(col_rm_id_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, id_sorted, vpos, n, (const uint8_t*)dead_r.as<uint8_t>(),
-                       (const uint64_t*)tile_base.as<uint64_t>(), (const uint32_t*)newpos.as<uint32_t>(), a.id_sorted.as<int64_t>(),
-                       a.vpos.as<uint32_t>());
-    prof.end(t, "col_rm_id", n * 13 + kept * 16 + ntiles * 8, s);
-    CDB_HIP(hipGetLastError());
-    uint64_t nf = 0;
-    CDB_HIP(hipMemcpyAsync(&nf, d_out.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, s));
-    CDB_HIP(hipStreamSynchronize(s));
-    prof.resolve();
-    a.n = kept;
-    a.n_false = c->kind != 0 ? 0 : (c->n_false == n ? kept : nf);  // (no slot n_false when every row is false)
-    column_publish(c, a);
+    try {
+        a.keys_v.alloc(cap * 8);
+        a.ids_v.alloc(cap * 8);
+        a.id_sorted.alloc(cap * 8);
+        a.vpos.alloc(cap * 4);
+        newpos.alloc(n * 4);
+        t = prof.begin(s);
+        hipLaunchKernelGGL(col_rm_value_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, (const uint64_t*)c->keys_v.as<uint64_t>(),
+                           (const int64_t*)c->ids_v.as<int64_t>(), n, (const uint8_t*)dead_v.as<uint8_t>(), (const uint64_t*)tile_base.as<uint64_t>(),
+                           a.keys_v.as<uint64_t>(), a.ids_v.as<int64_t>(), newpos.as<uint32_t>(), c->n_false, d_out.as<uint64_t>() + 1);
+        prof.end(t, "col_rm_value", n * 17 + kept * 20 + ntiles * 8, s);
+        CDB_HIP(hipGetLastError());
+        // 4. id order
+        if (tile_bases(ws, "column remove", ByteClear{dead_r.as<uint8_t>()}, n, tile_base, "col_rm_count", n + ntiles * 8) != kept)
+            throw InternalError("column remove: kept id ranks and kept positions differ (internal)");
+        t = prof.begin(s);
+        hipLaunchKernelGGL(col_rm_id_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, id_sorted, vpos, n, (const uint8_t*)dead_r.as<uint8_t>(),
+                           (const uint64_t*)tile_base.as<uint64_t>(), (const uint32_t*)newpos.as<uint32_t>(), a.id_sorted.as<int64_t>(),
+                           a.vpos.as<uint32_t>());
+        prof.end(t, "col_rm_id", n * 13 + kept * 16 + ntiles * 8, s);
+        CDB_HIP(hipGetLastError());
+        if (ws.debug_fail_prepare) throw DeviceError("debug: prepare failure requested (test hook)");
+        uint64_t nf = 0;
+        CDB_HIP(hipMemcpyAsync(&nf, d_out.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, s));
+        CDB_HIP(hipStreamSynchronize(s));
+        prof.resolve();
+        a.n = kept;
+        a.n_false = c->kind != 0 ? 0 : (c->n_false == n ? kept : nf);  // (no slot n_false when every row is false)
+    } catch (...) {  // the new blocks go back with the stream drained; the serving arrays were only read
+        (void)hipStreamSynchronize(s);
+        a = ColumnArrays{};
+        throw;
+    }
+    r.changed = true;
+}
+
+void cdb::column_remove_commit(cdb_column* c, ColumnRemoval& r) {
+    column_publish(c, r.a);
+    r.changed = false;
+    ++c->removes;
+    ++c->remove_compactions;
+    c->remove_rows = r.removed;
+    c->remove_ms = wall_ms() - r.t0;
 }
 
 extern "C" {

@@ -711,14 +711,22 @@ int cdb_column_remove(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t
         if (!nids) return;
         const double t0 = wall_ms();
         const bool device = c->staged_ids.empty() && c->debug_maintain_path != 2;
+        if (device) {  // the two halves back to back (cdb_rowset_remove prepares every field before it commits any)
+            ColumnRemoval r;
+            r.t0 = t0;
+            column_remove_prepare(c, RowIds{ids, nullptr}, nids, r);
+            if (removed) *removed = r.removed;
+            if (missing) *missing = r.missing;
+            if (r.changed) column_remove_commit(c, r);
+            return;
+        }
         uint64_t rem = 0, miss = 0;
-        if (device) column_remove_device(c, ids, nids, &rem, &miss);
-        else column_remove_host(c, ids, nids, &rem, &miss);
+        column_remove_host(c, ids, nids, &rem, &miss);
         if (removed) *removed = rem;
         if (missing) *missing = miss;
         if (!rem) return;
         ++c->removes;
-        ++(device ? c->remove_compactions : c->remove_rebuilds);
+        ++c->remove_rebuilds;
         c->remove_rows = rem;
         c->remove_ms = wall_ms() - t0;
     });
@@ -986,6 +994,10 @@ int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value) 
     }
     if (!std::strcmp(name, "debug_maintain_path") && value >= 0 && value <= 2) {
         c->debug_maintain_path = (int)value;
+        return CDB_OK;
+    }
+    if (!std::strcmp(name, "debug_fail_prepare")) {
+        c->ws.debug_fail_prepare = value != 0;
         return CDB_OK;
     }
     return CDB_E_INVALID;

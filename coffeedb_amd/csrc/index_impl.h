@@ -374,6 +374,7 @@ struct Index {
     bool debug_no_segcap = false;   // test hook: the bucket-wise build takes its per-bucket fallback ("a bucket does not fit the record memory")
     int debug_starve_group = 0;     // test hook: a build in XCD-aware tile order reports a look-back timeout once
     bool debug_fail_build = false;  // test hook: the build throws after its sorts (exercises the failure paths)
+    bool debug_fail_prepare = false;  // test hook: the prepare half of a removal throws behind its device work (index and column alike)
     bool force_big_path = false;  // test hook: use the >= 2^32 code path (u64 ranks, bucket-wise sort) at any size
     bool fuse_keygen = true;  // first radix pass computes keys from the text (no key/entry materialisation)
     int digit_bits = 0;
@@ -511,6 +512,20 @@ struct ColumnBlocks {
     ArrivedArray arr;             // empty: the array is built over them
 };
 
+// the rows' ids: a host array, or an array that already lies on the field's GPU (a row set's: rowset.hip), complete when the call
+// is made and unchanged during it
+struct RowIds {
+    const int64_t* host = nullptr;
+    const int64_t* device = nullptr;
+};
+// ... where the kernels read them: uploaded into d on s, or the caller's device array as it is
+inline const int64_t* resident_ids(hipStream_t s, DevBuf& d, RowIds ids, uint64_t nrows) {
+    if (ids.device) return ids.device;
+    d.alloc(nrows * 8);
+    CDB_HIP(hipMemcpyAsync(d.p, ids.host, nrows * 8, hipMemcpyHostToDevice, s));
+    return d.as<int64_t>();
+}
+
 // remove.hip — the pieces of cdb_remove (capi.hip commits them), all on ix.stream with ix.mu held.  Everything is made in fresh
 // blocks of the plan while the old index stands.
 struct RemovePlan : ColumnBlocks {
@@ -518,7 +533,7 @@ struct RemovePlan : ColumnBlocks {
     uint64_t ndocs = 0, size = 0, longest = 0;  // the surviving column
     DevBuf drop, newdoc, src_start;            // u8[old ndocs] flag, u32[old ndocs] old -> new document, u64[ndocs] old start of every survivor
 };
-void remove_mark(Index& ix, const int64_t* ids, uint64_t nids, RemovePlan& p);  // flags, counts, and (something to drop) the new tables; synchronises
+void remove_mark(Index& ix, RowIds ids, uint64_t nids, RemovePlan& p);  // flags, counts, and (something to drop) the new tables; synchronises
 void remove_text(Index& ix, RemovePlan& p);                                      // the kept documents gathered into p.text
 void remove_compact(Index& ix, RemovePlan& p, int new_bits, int new_width, bool new_packed);  // the array and its keys in the new layout
 // out (zeroed by the caller) = the longest document among those whose drop flag is 0 (drop = nullptr: among all), queued on s
@@ -551,9 +566,15 @@ struct ColumnChangeDelete {
     void operator()(ColumnChange* c) const;
 };
 using ColumnChangePtr = std::unique_ptr<ColumnChange, ColumnChangeDelete>;
-ColumnChangePtr remove_prepare(Index& ix, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
+ColumnChangePtr remove_prepare(Index& ix, RowIds ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
 ColumnChangePtr append_prepare(Index& ix, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs);
 void column_commit(Index& ix, ColumnChange& c);
+// cdb_remove / cdb_append change a built column only.  Returns its documents (0: never built, or built over nothing)
+inline uint64_t built_docs_or_refuse(const Index& ix, const char* op) {
+    const uint64_t built_docs = ix.width ? ix.ndocs : 0;
+    if (ix.host_text_valid && ix.ids.size() > built_docs) throw Error(std::string(op) + ": documents were added since the last build");
+    return built_docs;
+}
 void reserve_wait();  // a cdb_reserve still running in the background has finished (every build entry point waits for it first)
 // out = {slots whose kept key differs from the key recomputed from the suffix, slots checked (0: no keys kept)}
 void verify_kept_keys(Index& ix, uint64_t out[2]);
@@ -687,6 +708,10 @@ struct cdb_rowset {
     double page_ms = 0, cluster_ms = 0;
     uint64_t selects = 0, select_rows = 0;  // select.hip: cdb_rowset_select calls, and the rows of the last one
     double select_ms = 0;
+    // rowset_maintain.hip: cdb_rowset_remove calls that ran, and the fields and wall time of the last one; cdb_rowset_all: the fields
+    // and id-list entries the set was made from, and the wall time of that
+    uint64_t removes = 0, remove_fields = 0, all_fields = 0, all_input_rows = 0;
+    double remove_ms = 0, all_ms = 0;
 };
 struct cdb_key_query;
 namespace cdb {
@@ -699,6 +724,11 @@ struct DevicePage {
     uint64_t n = 0;  // rows in ids / counts (0: neither is allocated)
 };
 void rowset_page_device(cdb_rowset* rs, uint64_t first, uint64_t last, DevicePage& pg);
+// rowset.hip — an empty row set with a stream of its own on `device`; its end (stream drained and destroyed); and the end of a
+// set's creation when every count is equal (cdb_rowset_all: no key bit differs, no pass over the counts is needed; synchronises s)
+cdb_rowset* rowset_new(int device);
+void rowset_delete(cdb_rowset* rs);
+void rowset_adopt_equal_counts(cdb_rowset* rs, hipStream_t s, int64_t count);
 void rowset_download_rows(hipStream_t s, const int64_t* d_ids, const int64_t* d_counts, uint64_t n, int64_t** ids, int64_t** counts, size_t* nrows);
 // render.hip — cdb_render_rows over ids that already lie in device memory on the handle's GPU (complete when the call is made; the
 // caller keeps them unchanged during it).  Takes the handle's lock and throws.
@@ -721,12 +751,30 @@ void column_publish(cdb_column* c, ColumnArrays& a);
 void column_build(cdb_column* c, const char* who = "cdb_column_build");
 // cdb_column_remove's host path: download, filter on the host, column_build over the rest (built and staged rows alike)
 void column_remove_host(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
-// column_maintain.hip — the device path (no staged rows): mark, two stable compactions, one gather of the positions
-void column_remove_device(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
 struct ColumnScope {  // the column's stream and device for the calling thread
     StreamScope ss;
     explicit ColumnScope(cdb_column* c) : ss(c->ws.stream) { CDB_HIP(hipSetDevice(c->ws.device)); }
 };
+// column_maintain.hip — the device path of a removal (no staged rows) in two halves, as a string index has them (remove_prepare /
+// column_commit above).  Prepare: mark, two stable compactions, one gather of the positions, all into fresh blocks beside the
+// serving arrays; removed / missing are complete when it returns, `changed` says whether there is anything to commit; it throws
+// and leaves the column untouched.  Commit: column_publish plus the stats of a cdb_column_remove; it cannot fail.  A removal that
+// is dropped uncommitted hands its blocks back (release: on the column's device and stream); the column never knew of it.
+// The caller holds the column's lock and, for prepare and commit, a ColumnScope.
+struct ColumnRemoval {
+    ColumnArrays a;
+    uint64_t removed = 0, missing = 0;
+    bool changed = false;
+    double t0 = 0;  // wall_ms() when the call began (remove_ms)
+    void release(cdb_column* c) {
+        (void)hipSetDevice(c->ws.device);
+        StreamScope ss(c->ws.stream);
+        a = ColumnArrays{};
+        changed = false;
+    }
+};
+void column_remove_prepare(cdb_column* c, RowIds ids, uint64_t nids, ColumnRemoval& r);
+void column_remove_commit(cdb_column* c, ColumnRemoval& r);
 // the value (bit pattern) behind a column's order-preserving key (columns.hip: order_key; kind: 0 bool, 1 int64, 2 double)
 __host__ __device__ __forceinline__ uint64_t column_key_raw(int kind, uint64_t key) {
     constexpr uint64_t S = 1ull << 63;

@@ -183,7 +183,7 @@ void longest_document(hipStream_t s, const uint8_t* drop, const uint64_t* doc_st
     hipLaunchKernelGGL(longest_document_kernel, dim3(grid_for(ndocs)), dim3(256), 0, s, drop, doc_start, ndocs, out);
 }
 
-void remove_mark(Index& ix, const int64_t* ids, uint64_t nids, RemovePlan& p) {
+void remove_mark(Index& ix, RowIds ids, uint64_t nids, RemovePlan& p) {
     hipStream_t s = ix.stream;
     const uint64_t ndocs = ix.ndocs;
     id_table_prepare(ix);
@@ -191,14 +191,13 @@ void remove_mark(Index& ix, const int64_t* ids, uint64_t nids, RemovePlan& p) {
     const uint32_t* id_doc = ix.idt.ids_ascend ? nullptr : ix.idt.id_doc.as<uint32_t>();
     const uint64_t* doc_start = ix.d_doc_start.as<uint64_t>();
     DevBuf d_ids, d_out;
-    d_ids.alloc(nids * 8);
+    const int64_t* idp = resident_ids(s, d_ids, ids, nids);
     d_out.alloc(16);
     p.drop.alloc(ndocs);
-    CDB_HIP(hipMemcpyAsync(d_ids.p, ids, nids * 8, hipMemcpyHostToDevice, s));
     CDB_HIP(hipMemsetAsync(d_out.p, 0, 16, s));
     CDB_HIP(hipMemsetAsync(p.drop.p, 0, ndocs, s));
     int t = ix.prof.begin(s);
-    hipLaunchKernelGGL(rm_mark_kernel, dim3(grid_for(nids)), dim3(256), 0, s, (const int64_t*)d_ids.as<int64_t>(), nids, id_tab, id_doc, ndocs,
+    hipLaunchKernelGGL(rm_mark_kernel, dim3(grid_for(nids)), dim3(256), 0, s, idp, nids, id_tab, id_doc, ndocs,
                        p.drop.as<uint8_t>(), d_out.as<unsigned long long>());
     ix.prof.end(t, "rm_mark", nids * (8 + 8 * (uint64_t)bit_width64(ndocs) + 1), s);
     CDB_HIP(hipGetLastError());

@@ -222,7 +222,9 @@ struct SetScope {
     explicit SetScope(cdb_rowset* rs) : ss(rs->ws.stream) { CDB_HIP(hipSetDevice(rs->ws.device)); }
 };
 
-cdb_rowset* rowset_new(int device) {
+}  // namespace
+
+cdb_rowset* cdb::rowset_new(int device) {
     cdb_rowset* rs = new cdb_rowset();
     rs->ws.device = device;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&rs->ws.stream, hipStreamNonBlocking) != hipSuccess) {
@@ -233,7 +235,7 @@ cdb_rowset* rowset_new(int device) {
     return rs;
 }
 
-void rowset_delete(cdb_rowset* rs) {  // as cdb_column_destroy
+void cdb::rowset_delete(cdb_rowset* rs) {  // as cdb_column_destroy
     if (!rs) return;
     (void)hipSetDevice(rs->ws.device);
     hipStream_t s = rs->ws.stream;
@@ -245,6 +247,8 @@ void rowset_delete(cdb_rowset* rs) {  // as cdb_column_destroy
         (void)hipStreamDestroy(s);
     }
 }
+
+namespace {
 
 // The key bits of the rows in rs->ids / rs->counts (src == nullptr), or of the rows (src_ids, src_counts) on their way into them,
 // on stream s; synchronises.
@@ -266,6 +270,15 @@ void rowset_adopt(cdb_rowset* rs, hipStream_t s, const int64_t* src_ids, const i
 }
 
 }  // namespace
+
+void cdb::rowset_adopt_equal_counts(cdb_rowset* rs, hipStream_t s, int64_t count) {
+    rs->state.alloc(ST_WORDS * 8);
+    uint64_t init[ST_WORDS] = {};
+    init[ST_OR] = init[ST_AND] = page_key(count);
+    CDB_HIP(hipMemcpyAsync(rs->state.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+    CDB_HIP(hipStreamSynchronize(s));  // (init is read by the copy)
+    rs->key_diff = 0;
+}
 
 void cdb::rowset_download_rows(hipStream_t s, const int64_t* d_ids, const int64_t* d_counts, uint64_t n, int64_t** ids, int64_t** counts, size_t* nrows) {
     int64_t* hi = (int64_t*)host_alloc(n * 8);
@@ -493,7 +506,9 @@ int cdb_rowset_get_stat(const cdb_rowset* rs, const char* name, double* value) {
         {"rows", (double)rs->m}, {"page_selects", (double)rs->page_selects}, {"page_sorts", (double)rs->page_sorts},
         {"select_passes", (double)rs->select_passes}, {"page_ms", rs->page_ms}, {"clusters", (double)rs->clusters},
         {"cluster_ms", rs->cluster_ms}, {"selects", (double)rs->selects}, {"select_ms", rs->select_ms},
-        {"select_rows", (double)rs->select_rows},
+        {"select_rows", (double)rs->select_rows}, {"removes", (double)rs->removes}, {"remove_fields", (double)rs->remove_fields},
+        {"remove_ms", rs->remove_ms}, {"all_fields", (double)rs->all_fields}, {"all_input_rows", (double)rs->all_input_rows},
+        {"all_ms", rs->all_ms},
     };
     for (auto& e : tab)
         if (!std::strcmp(e.n, name)) {

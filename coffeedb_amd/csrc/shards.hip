@@ -1506,7 +1506,7 @@ int cdb_shards_remove(cdb_shards* h, const int64_t* ids, uint64_t nids, uint64_t
         for (int i = 0; i < G; ++i) locks.emplace_back(h->shard[i]->ix.mu);
         std::vector<ColumnChangePtr> ch(G);  // (dropped on a failure, before the locks go)
         std::vector<uint64_t> rem(G, 0), mis(G, 0);
-        parallel_shards(G, [&](int i) { ch[i] = remove_prepare(h->shard[i]->ix, ids, nids, &rem[i], &mis[i]); });
+        parallel_shards(G, [&](int i) { ch[i] = remove_prepare(h->shard[i]->ix, RowIds{ids, nullptr}, nids, &rem[i], &mis[i]); });
         uint64_t r = 0, m = 0;
         for (int i = 0; i < G; ++i) {
             r += rem[i];

@@ -65,6 +65,31 @@ public:
         return out;
     }
 
+    // `remove` (interface.cpp:274-285): the rows of the set leave every field given, all or none; ids stay on the device.  A field is
+    // a cdb_remove_field with `index` or `column` set (field_of below); the per-field results come back in the caller's order.  A
+    // failure throws with the library's text ("field <i>: ..."); after a failed prepare nothing has changed in any field.
+    static cdb_remove_field field_of(cdb_index* h) { return cdb_remove_field{h, nullptr, 0, 0, 0, 0}; }
+    static cdb_remove_field field_of(cdb_column* c) { return cdb_remove_field{nullptr, c, 0, 0, 0, 0}; }
+    std::vector<cdb_remove_field> remove(std::vector<cdb_remove_field> fields, uint64_t* removed_rows = nullptr) const {
+        uint64_t n = 0;
+        check(cdb_rowset_remove(h_, fields.data(), (int)fields.size(), &n));
+        if (removed_rows) *removed_rows = n;
+        return fields;
+    }
+    // filter() without constraints (interface.cpp:51-53 -> query(), database.cpp:380-386): every object the given fields hold, count 0.
+    // `count` without constraints is everything(...).size(); a `query` with `span` is everything(...).page(first, last)
+    static rowset everything(const std::vector<cdb_index*>& indexes, const std::vector<cdb_column*>& columns) {
+        cdb_rowset* h = nullptr;
+        const int rc = cdb_rowset_all(indexes.empty() ? nullptr : indexes.data(), (int)indexes.size(), columns.empty() ? nullptr : columns.data(),
+                                      (int)columns.size(), &h);
+        if (rc != CDB_OK) {
+            const char* why = !indexes.empty() && indexes[0] ? cdb_last_error(indexes[0])
+                              : !columns.empty() && columns[0] ? cdb_column_last_error(columns[0]) : "";
+            throw std::runtime_error(std::string("cdb_rowset_all: ") + (*why ? why : "invalid arguments"));
+        }
+        return rowset(h);
+    }
+
 private:
     void check(int rc) const {
         if (rc != CDB_OK) throw std::runtime_error(h_ ? cdb_rowset_last_error(h_) : "cdb_shim::rowset: empty");

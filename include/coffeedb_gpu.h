@@ -228,7 +228,8 @@ int cdb_column_get_stat(const cdb_column* c, const char* name, double* value);
  * "name ms launches bytes" lines) and "debug_query_path" (0 = automatic, 1 = always sparse, 2 = always dense: the tests of both
  * union paths and the crossover measurement of tools/bench_columns.py); "debug_maintain_path" (0 = automatic,
  * 1 = the device path of cdb_column_append / cdb_column_remove wherever it is valid, 2 = stage + build / host filter + build:
- * DESIGN.md §7.8). */
+ * DESIGN.md §7.8); "debug_fail_prepare" (0/1: the prepare half of a device removal throws a device error behind its queued work, the
+ * column stays as it was — like cdb_set_option's "debug_fail_build" and "debug_fail_prepare" for a string index: cdb_rowset_remove). */
 int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value);
 int cdb_debug_column_profile_dump(cdb_column* c, char* buf, size_t cap);
 
@@ -305,7 +306,8 @@ int cdb_rowset_page(cdb_rowset* rs, uint64_t first, uint64_t last, int64_t** ids
 int cdb_rowset_cluster(cdb_rowset* rs, cdb_index* field, int with_values, cdb_clusters* out);
 int cdb_rowset_cluster_column(cdb_rowset* rs, cdb_column* field, cdb_clusters* out);
 /* "rows", "page_selects", "page_sorts" (pages answered by either path; a page without rows runs neither), "select_passes" (key
- * bytes the last select visited), "page_ms", "clusters", "cluster_ms", "selects", "select_ms", "select_rows" (cdb_rowset_select) */
+ * bytes the last select visited), "page_ms", "clusters", "cluster_ms", "selects", "select_ms", "select_rows" (cdb_rowset_select),
+ * "removes", "remove_fields", "remove_ms" (cdb_rowset_remove), "all_fields", "all_input_rows", "all_ms" (cdb_rowset_all) */
 int cdb_rowset_get_stat(const cdb_rowset* rs, const char* name, double* value);
 /* Test and measurement hooks — NOT part of the stable ABI: a row set over the caller's rows (ids ascending, taken as given);
  * options "debug_page_path" (0 automatic: select from 2^22 rows on; 1 select wherever the page ends before the last row; 2 always sort) and "profile" (the
@@ -485,6 +487,69 @@ int cdb_column_append(cdb_column* c, const int64_t* ids, const void* values, uin
 /* Test hook, NOT part of the stable ABI: the four device arrays of a built column (keys_v u64, ids_v i64, id_sorted i64, vpos u32;
  * "rows" entries each, any pointer may be NULL) copied to the host. */
 int cdb_debug_column_arrays(cdb_column* c, uint64_t* keys_v, int64_t* ids_v, int64_t* id_sorted, uint32_t* vpos);
+
+/* ---- row sets that change and span the database (rowset_maintain.hip) ----------------------------------------
+ * cdb_rowset_remove — replaces the `remove` operation (interface.cpp:274-285: filter(), then database::remove of every row, :283 returns
+ * their number) for all fields of the objects at once.  The rows of the set leave every field given, ALL OR NONE: the ids are the set's
+ * own device array (nothing is downloaded, nothing uploaded), every field prepares its new column beside the serving one, and only
+ * when every field stands does any commit.  Before, the rows had to come down with cdb_rowset_rows and go up again once per field
+ * through cdb_remove / cdb_column_remove, and a failure in field 3 of 5 left fields 1 and 2 without the objects for good.
+ *   Fields.  Exactly one of index / column is set in every entry; nfields >= 1; no handle twice; every field on the set's GPU.
+ *   Results.  *rows (may be NULL) = the set's size, the count the reference returns.  Per field, removed / missing follow the rules of
+ * cdb_remove / cdb_column_remove; a set holds each id once, so removed + missing == *rows.  A field that was never built, or built
+ * over nothing, holds no id: missing = *rows, status CDB_OK, committed = 0 — as for any field that loses nothing.  An empty set
+ * changes nothing and counts no call in any field.  After a successful call every field cannot be told from one that lost the same
+ * ids through its own entry point, stats included ("removes", "remove_compactions" / "remove_rebuilds", ...).
+ *   Order of the call.  A cdb_reserve still running is waited for; the row set's lock; every field's lock together in address order
+ * (cdb_filter's rule, so a concurrent cdb_filter over the same fields cannot invert it); validation; every field PREPARES, one after
+ * another in the caller's order; every field commits; unlock.  Queries on the fields wait, as during cdb_remove.
+ *   Refused as a whole with CDB_E_INVALID before any device work: a field entry with none or both pointers set, nfields < 1, the same
+ * handle twice (these three like a NULL argument: the code alone, before any handle is read), a field on another GPU ("cdb_rowset_remove: the field lives on another GPU"), a column with rows staged since its last
+ * build ("remove: rows were added since the last build"), an index with pending additions ("remove: documents were added since the
+ * last build").  The column option debug_maintain_path is not consulted: this call has only the device path.
+ *   A failure in a prepare.  The call returns that field's code (the first in the caller's order; the prepares behind it do not run),
+ * cdb_rowset_last_error says "field <i>: <message>", that field's status carries the code, every committed and every removed / missing
+ * is 0, every prepared column is dropped and every field answers exactly as before.
+ *   One step can still fail behind the commit point: on the reference-order path (reference_compat = 1 and bytes >= 0x80, see
+ * cdb_remove "Paths") the array is built over the compacted text AFTER the field's commit.  The single-handle rule then applies per
+ * field.  What a caller finds after such a failure: the call returns the failing field's error; that field is "never built" (it
+ * answers {} and holds no document: the documents it served are gone from the column), its status carries the code and its
+ * committed is 1; every other field has committed its change.  The database is consistent and answers every query, but that field is
+ * neither the old nor the new one: rebuild it from the source.
+ *   Memory.  At the peak every field's new column stands beside its old one AT THE SAME TIME (the per-field calls hold one pair at a
+ * time).  A caller short of memory gets CDB_E_DEVICE and an unchanged database — that is the point of the call.
+ *   The row set itself is left as it is.  Its ids are simply no longer held by the fields: a later cdb_rowset_select finds nothing,
+ * a later cluster reports them missing.
+ *   Sharded string columns stay out: use cdb_rowset_rows + cdb_shards_remove as before.
+ *   Stats (cdb_rowset_get_stat): "removes" (calls that reached the commit), and of the last one "remove_fields", "remove_ms".
+ *   Test hook, NOT part of the stable ABI (beside debug_fail_build): option "debug_fail_prepare" of cdb_set_option and
+ * cdb_debug_column_set_option makes the prepare half of a removal from that field throw a device error after its device work has been
+ * queued and its blocks allocated, so that the release path runs. */
+typedef struct cdb_remove_field {
+    cdb_index*  index;      /* a string field, or NULL            — exactly one of the two */
+    cdb_column* column;     /* a numeric / bool field, or NULL                              */
+    uint64_t    removed;    /* out: rows of the set the field held and lost                 */
+    uint64_t    missing;    /* out: rows of the set the field did not hold                  */
+    int32_t     status;     /* out: CDB_OK, or the code of the failure that arose in this field */
+    int32_t     committed;  /* out: 1 = the field's old column no longer serves             */
+} cdb_remove_field;
+int cdb_rowset_remove(cdb_rowset* rs, cdb_remove_field* fields, int nfields, uint64_t* rows);
+/* cdb_rowset_all — the row set of every object: replaces query() of database.cpp:380-386 (every object with count 0), which filter()
+ * returns for a request without constraints (interface.cpp:51-53; README: "You can get all objects in the database by omitting
+ * `constraints`"; `count` without constraints is the size of the database).  "Every object" is the union of the ids the given fields
+ * hold: database.cpp:170-282 stores data[id][key] and calls add(id, value) side by side, so the union over all fields of a database is
+ * its object store.  Rows ascend by id as SIGNED int64, each id once, every count 0; the set owns its arrays as cdb_filter's does, and
+ * cdb_rowset_size / _page / _select / _cluster* / _remove work over it unchanged.  A page of it is the ids [first, last) in ascending
+ * order (all counts equal, ties ascending id).
+ *   Only built rows count, as for every query.  A field that was never built contributes nothing; all fields never built give a valid
+ * set of size 0.  nindexes + ncolumns < 1, a null entry, and fields on different GPUs ("cdb_rowset_all: all fields must live on one
+ * GPU") are CDB_E_INVALID; errors before a set exists are reported where cdb_filter reports them: on the first index's handle, or
+ * without one on the first column's.  Every field's lock is held, in address order, while its ids are read.
+ *   How.  The fields' ascending id lists (an index's id table, a column's id order) are laid end to end keyed id ^ 2^63, sorted key-only
+ * (one list alone is not sorted) and compacted to the first of every run of equal keys (stable_tiles.h); 16 bytes of scratch per listed
+ * id.  Stats: "all_fields", "all_input_rows" (ids listed by all fields together), "all_ms"; when the lead handle's option profile is on,
+ * the set's profile (cdb_debug_rowset_profile_dump) holds the kernels as all_* lines.  Sharded string columns stay out. */
+int cdb_rowset_all(cdb_index* const* indexes, int nindexes, cdb_column* const* columns, int ncolumns, cdb_rowset** out);
 
 /* Documents join a built index on the device, without a rebuild — replaces "insert ... build" (interface.cpp:157-180, :286-288, and
  * database.cpp:276-280, which constructs the next generation beside the serving one) for one string key.  The arguments are those of
