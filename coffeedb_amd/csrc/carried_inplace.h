@@ -1,5 +1,5 @@
 // carried_inplace.h — the flag sweeps' shared pieces (16-byte flag loader, SWAR counts) and the in-place form of the carried
-// round: sa_carried_inplace_kernel.  A header, because two translation units instantiate the kernel: sa_build.hip
+// round: sa_carried_inplace_kernel.  A header, because two translation units instantiate the kernel: sa_refine.hip
 // (refine_groups) and debug_carried.hip (the test hook).
 //
 // After the initial sort a tied group is a run of adjacent array slots — a head with flag bits 0 and 1 set, then members with

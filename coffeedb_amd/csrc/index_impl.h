@@ -314,9 +314,9 @@ struct Index {
     int carried_inplace = -1;   // the carried round's in-place sweep in front of its list round: -1 = from CARRIED_INPLACE_MIN_N suffixes upward, 0 = off, 1 = on
     int top_digit_first = -1;   // segmented sort of 40-bit variable-length keys: top key byte first, the other passes per (bucket, top byte) cell
                                 // over 9-byte records (run_segmented): -1 = from TOP_FIRST_MIN_N suffixes upward, 0 = off, 1 = on where it applies
-    int carried_bits = -1;      // code-stream bits carried behind variable-length keys (sa_build.hip: carried round): -1 = as many as fit, 0 = none, 1..6 = at most
+    int carried_bits = -1;      // code-stream bits carried behind variable-length keys (sa_refine.hip: carried round): -1 = as many as fit, 0 = none, 1..6 = at most
     bool list_rounds = true;    // text-extension rounds behind the first compact from the previous round's list (0 = from the flag array)
-    int group_sort_cap = 4096;  // ... members of a group on one side of an entry beyond which the pass gives up (its work is also bounded, sa_build.hip)
+    int group_sort_cap = 4096;  // ... members of a group on one side of an entry beyond which the pass gives up (its work is also bounded, sa_refine.hip)
     bool group_sort = true;     // refinement rounds: one pass inside the groups instead of the general sort (0 = always the general sort)
     bool partial_symbol = true; // bucket-wise build, dense keys in the sweep form: leftover key bits hold the next symbol, quantised (0 = off)
     int vl_keys = 2;           // bucket-wise build, variable-length keys (vl_code.h): 0 off, 2 when the cost model says so, 1 always, 16..56 always with that many key bits

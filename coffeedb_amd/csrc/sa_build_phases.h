@@ -2,7 +2,10 @@
 // functions that live in a file of their own.  No kernel and no launch lives here.
 //   sa_initial_direct.hip   initial_sort_direct, the group-flag kernels (write_group_flags*), the shared sorts of 4-byte entries
 //   sa_sorts.hip            the shared sorts of 8-byte entries
-//   sa_build.hip            every other phase, and generate_keys
+//   sa_refine.hip           refine_groups: the refinement rounds and their kernels
+//   sa_reference_order.hip  finish_reference_order: the walk into the reference's order (apply_reference_order*)
+//   sa_build.hip            the prologue (alphabet, key width, digit histograms, generate_keys), the bucket-wise initial sort
+//                           and the driver (build_typed, build_suffix_array)
 #pragma once
 #include <vector>
 
@@ -62,7 +65,7 @@ struct DigitHist {
     struct { uint32_t pair_span = 0, pair_r = 0, pair_s = 0; } pair_consts;
 };
 
-// a bucket of the reference-order walk: the array slots [lo, hi) (sa_build.hip: apply_reference_order)
+// a bucket of the reference-order walk: the array slots [lo, hi) (sa_reference_order.hip: apply_reference_order)
 struct CompatBucket {
     unsigned long long lo, hi;
 };
@@ -91,12 +94,31 @@ struct InitialSort {
     uint32_t carry = 0;          // carried bits: the next `carry` code-stream bits behind the key sit in bits 2.. of every flag byte
 };
 
-// ---- the phases that two files share.  V = entry type; each is instantiated in its own file for uint32_t and uint64_t.
+// the buffers of the refinement rounds: build_typed owns them, so that they live until the build ends (the reference-order
+// finish sizes its second array against the memory left)
+struct RefineBuffers {
+    DevBuf d_order;
+    DevBuf U, skey[2], sval[2], nh, rank, hcov;
+    DevBuf d_open;  // entries still unresolved after the last round (saves a full flag scan to learn "none")
+    DevBuf U2b, lf;       // list-based rounds: the other list of positions, the flag bytes of the current list in list order
+    DevBuf d_gs_state;  // sa_group_sort_kernel: [0] it gave up (groups too long for it), [1] members walked by its long walks
+    DevBuf d_inplace;   // sa_carried_inplace_kernel: its count words (open entries met, entries moved)
+};
+
+// ---- the phases that cross a file.  V = entry type, I = type of suffix-array slot numbers, R = type of ranks / extended text
+// positions; each is explicitly instantiated in its own file, for the forms build_typed uses.
 // (the unfused direct sort: every suffix's 64-bit key and entry, in text order — sa_build.hip: sa_keygen_kernel)
 template <typename V>
 void generate_keys(Index& ix, const Alphabet& al, const KeyPlan& kp, uint64_t* keys, V* vals);
 template <typename V>
 InitialSort initial_sort_direct(Index& ix, const Alphabet& al, const KeyPlan& kp, const DigitHist& dh, TopCounts& tc, SortStats& ss);
+// sa_refine.hip (SAW = how the array is stored: SaRW<V>, or Sa40RW for packed 8-byte entries); returns the depth every suffix
+// is sorted to
+template <typename V, typename I, typename R, typename SAW>
+uint64_t refine_groups(Index& ix, SAW sa, InitialSort& is, const Alphabet& al, const KeyPlan& kp, SortStats& ss, RefineBuffers& rb);
+// sa_reference_order.hip: the array goes to the index
+template <typename V>
+void finish_reference_order(Index& ix, InitialSort& is, Alphabet& al);
 
 // group flags of n sorted keys (sa_initial_direct.hip: sa_initflags_kernel / sa_initflags32_kernel) — the direct sort and the
 // bucket-wise build's per-bucket sorts both end in them

@@ -82,7 +82,7 @@ __device__ __forceinline__ void scan_load8(const In& in, uint64_t base, uint64_t
     for (int k = 0; k < SC_IPT; ++k) v[k] = base + k < n ? in(base + k) : identity;
 }
 
-// the group flags of the suffix-array build (sa_build.hip) as scan input: the one functor with a load8
+// the group flags of the suffix-array build (sa_refine.hip) as scan input: the one functor with a load8
 struct FlagIn {
     const uint8_t* flags;
     static __device__ __forceinline__ U2 decode(uint32_t f) {
