@@ -344,3 +344,148 @@ def test_two_process_rccl_merge():
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
     assert "MP_COMM_OK" in p.stdout
+
+
+def _dev_i64(ptr, n):
+    import torch
+    if int(n) == 0:
+        return np.zeros(0, dtype=np.int64)
+
+    class A:
+        __cuda_array_interface__ = {"shape": (int(n),), "typestr": "<i8", "data": (int(ptr), False), "version": 2}
+    return torch.as_tensor(A(), device="cuda").cpu().numpy()
+
+
+def _collective(fn, world):
+    # one host thread per rank, as tests/test_gpu_fullsize.py drives a group (a rank that never arrives fails the test, it does not hang it)
+    import threading
+    out, err = [None] * world, []
+
+    def run(r):
+        try:
+            out[r] = fn(r)
+        except Exception as e:  # noqa: BLE001
+            err.append(repr(e))
+    th = [threading.Thread(target=run, args=(r,), daemon=True) for r in range(world)]
+    [t.start() for t in th]
+    [t.join(120) for t in th]
+    assert not err and not any(t.is_alive() for t in th), err[:2]
+    return out
+
+
+def test_group_merge_of_three_ranks_at_small_shapes():
+    # cdb_comm_merge and cdb_comm_merge_counts over a three-rank group on one device (device copies), against ONE index over the
+    # whole column.  1, 256 and 257 patterns: one thread, one full block and the first thread of a second block of the 256-wide
+    # kernels.  The middle shard's documents use an alphabet of their own, so a batch drawn from the other two leaves it with no row
+    # at all (its count in the row exchange is 0), and a batch nobody answers leaves the merge with no row at all.
+    import torch
+    from coffeedb_amd import capi
+    G, per = 3, 100
+    texts = [W.ragged_corpus(per, 80, seed=31 + r, lo=(0x61, 0x65, 0x61)[r], hi=(0x64, 0x68, 0x64)[r]) for r in range(G)]
+    docs = [bytes(b[int(ds[d]):int(ds[d + 1])]) for b, ds in texts for d in range(per)]
+    docs[-1] = b"abqqqba"                                          # only the last shard holds "qqq"
+    ids = np.arange(G * per, dtype=np.int64) * 3 + 5                # global ids
+    ds = np.zeros(G * per + 1, dtype=np.uint64)
+    np.cumsum([len(d) for d in docs], out=ds[1:])
+    blob = np.frombuffer(b"".join(docs), dtype=np.uint8)
+    assert 30 * G * per < len(blob) < 50 * G * per                  # about 40 bytes a document
+
+    def index(lo, hi):
+        g = capi.GpuStringIndex()
+        g.add_bulk(ids[lo:hi], blob[int(ds[lo]):int(ds[hi])], ds[lo:hi + 1] - ds[lo])
+        g.build()
+        return g
+    shards, one = [index(r * per, (r + 1) * per) for r in range(G)], index(0, G * per)
+    comms = capi.ShardComm.group([0] * G)
+    assert all(c.world == G and c.transport == "device copies" for c in comms)
+
+    def substrings(r, n, seed):                                     # n substrings of shard r's documents
+        pb, po = W.sample_patterns(*texts[r], n, 2, 4, seed=seed, miss_frac=0)
+        return [bytes(pb[int(po[j]):int(po[j + 1])]) for j in range(n)]
+    outer = [b"qqq", b"zzz"] + [k for pair in zip(substrings(0, 130, 1), substrings(2, 130, 2)) for k in pair]
+    mixed = [b"zzz", b"qqq"] + [k for trio in zip(*(substrings(r, 90, 3 + r) for r in range(G))) for k in trio]
+    for kws, idle, total0 in [(outer[:1], (0, 1), False), (mixed[:1], (0, 1, 2), True), (outer[:256], (1,), False), (outer[:257], (1,), False),
+                              (mixed[:256], (), False), (mixed[:257], (), False)]:
+        npat = len(kws)
+        po = np.zeros(npat + 1, dtype=np.int64)
+        np.cumsum([len(k) for k in kws], out=po[1:])
+        d_blob = torch.from_numpy(np.frombuffer(b"".join(kws) + bytes(16), dtype=np.uint8).copy()).cuda()
+        d_offs = torch.from_numpy(po).cuda()
+        torch.cuda.synchronize()
+
+        def csr(g):
+            r = g.query_batch_device(d_blob.data_ptr(), d_offs.data_ptr(), npat, int(po[-1]))
+            return r, _dev_i64(r.d_row_ptr, npat + 1), _dev_i64(r.d_ids, r.nrows), _dev_i64(r.d_counts, r.nrows)
+        _, w_rp, w_ids, w_cnt = csr(one)
+        local = [csr(g) for g in shards]
+        # the batch holds what it is meant to hold
+        assert [r for r in range(G) if int(local[r][0].nrows) == 0] == list(idle) and (len(w_ids) == 0) == total0
+        for j, kw in enumerate(kws):
+            held = [int(l[1][j + 1] - l[1][j]) > 0 for l in local]
+            assert kw != b"zzz" or held == [False] * G              # a pattern no shard holds
+            assert kw != b"qqq" or held == [False, False, True]     # a pattern only the last shard holds
+        assert npat == 1 or (b"zzz" in kws and b"qqq" in kws)
+        merged = _collective(lambda r: comms[r].merge(local[r][0]), G)
+        for m in merged:                                            # every rank holds the single index's CSR
+            assert (int(m.npat), int(m.nrows)) == (npat, len(w_ids))
+            assert np.array_equal(_dev_i64(m.d_row_ptr, npat + 1), w_rp)
+            assert np.array_equal(_dev_i64(m.d_ids, m.nrows), w_ids) and np.array_equal(_dev_i64(m.d_counts, m.nrows), w_cnt)
+        slices = _collective(lambda r: comms[r].merge_counts(local[r][0]), G)
+        for r, sl in enumerate(slices):
+            _, l_rp, l_ids, l_cnt = local[r]
+            assert (int(sl.npat), int(sl.nrows_total), int(sl.nrows_local)) == (npat, len(w_ids), len(l_ids))
+            assert np.array_equal(_dev_i64(sl.d_row_ptr, npat + 1), w_rp)
+            n_j = l_rp[1:] - l_rp[:-1]                              # row_base puts the rank's rows of pattern j at the single index's rows
+            dest = np.repeat(_dev_i64(sl.d_row_base, npat) - l_rp[:-1], n_j) + np.arange(len(l_ids))
+            assert np.array_equal(w_ids[dest], l_ids) and np.array_equal(w_cnt[dest], l_cnt)
+    # the empty batch: no exchange, row_ptr = {0} on every rank
+    empty = capi.CdbDeviceResult()
+    for m in _collective(lambda r: comms[r].merge(empty), G):
+        assert (int(m.npat), int(m.nrows)) == (0, 0) and _dev_i64(m.d_row_ptr, 1)[0] == 0
+    for sl in _collective(lambda r: comms[r].merge_counts(empty), G):
+        assert (int(sl.npat), int(sl.nrows_total), int(sl.nrows_local)) == (0, 0, 0) and _dev_i64(sl.d_row_ptr, 1)[0] == 0
+    for x in comms + shards + [one]:
+        x.close()
+
+
+def test_replace_in_place_builds_over_an_empty_generation(tmp_path):
+    # replace_in_place: the serving shards are destroyed FIRST (an empty generation takes over), then the new ones are built
+    from coffeedb_amd import capi
+    blob, ds = W.ragged_corpus(400, 30, seed=17, lo=0x61, hi=0x64, empty_every=13)
+    ids = np.arange(400, dtype=np.int64) * 2 + 1
+    sh = capi.GpuShards([0, 0, 0])
+    sh.set_option("use_all_devices", 1)
+    sh.set_option("fast_search", 0)                                # a per-shard option, set before any shard is built
+    sh.add_bulk(ids, blob, ds)
+    sh.build()
+    sh.set_option("replace_in_place", 1)
+    sh.add(5000, b"abcdxyzabcd")
+    sh.build()
+    one = capi.GpuStringIndex()
+    one.set_option("fast_search", 0)
+    one.add_bulk(ids, blob, ds)
+    one.add(5000, b"abcdxyzabcd")
+    one.build()
+    bounds = [sh.first_doc(i) for i in range(4)]
+    assert sh.count == 3 and bounds[0] == 0 and bounds[-1] == 401 and bounds == sorted(set(bounds))
+    for kw in (b"a", b"ab", b"dcb", b"abcd", b"xyz", b"nowhere"):
+        assert sh.query(kw) == one.query(kw)
+    assert sh.query(b"xyz") == [(5000, 1)]
+    pats = W.sample_patterns(blob, ds, 120, 1, 5, seed=4)
+    got, want = sh.query_batch(*pats), one.query_batch(*pats)
+    assert got[3] == want[3] and all(np.array_equal(a, b) for a, b in zip(got[:3], want[:3]))
+    # options set earlier are in force on the new handles, as the rebuild in test_sharded_index_matches_single_index shows it: a
+    # requested failure fails the build.  Here the old shards went first, so what is left is the unbuilt window the caller accepted
+    sh.set_option("debug_fail_build", 1)
+    with pytest.raises(RuntimeError, match="build failure requested"):
+        sh.build()
+    assert sh.count == 0
+    sh.set_option("debug_fail_build", 0)
+    sh.build()
+    assert sh.count == 3 and sh.query(b"xyz") == [(5000, 1)] and sh.query(b"ab") == one.query(b"ab")
+    # load does not use the option: a failing load leaves the set answering
+    with pytest.raises(RuntimeError, match="Cannot open file"):
+        sh.load(str(tmp_path / "missing"))
+    assert sh.count == 3 and sh.query(b"xyz") == [(5000, 1)] and sh.query(b"ab") == one.query(b"ab")
+    for x in (sh, one):
+        x.close()
