@@ -1,17 +1,18 @@
-// capi.hip — the C ABI of libcoffeedb_gpu.so (include/coffeedb_gpu.h).  Host logic only: staging of
-// cdb_add, the reference's width rule, uploads/downloads and error translation.  All device work is in
-// sa_build.hip / query.hip / radix_sort.h.
+// capi.hip — the C ABI of libcoffeedb_gpu.so (include/coffeedb_gpu.h) on one string index, except its queries (capi_query.hip):
+// handle lifecycle, staging of cdb_add and the chunked upload, the reference's width rule, install and the build entry points,
+// save / load, reserve, remove / append, options, stats and the debug calls.  Host logic only: all device work is in
+// sa_build.hip / remove.hip / append.hip / verify.hip / radix_sort.h (the two kernels here lay out a resident build's tables and
+// fill cdb_reserve's synthetic text).
 #include <dirent.h>
 
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
 
 #include "../../include/coffeedb_gpu.h"
-#include "index_impl.h"
+#include "host_io.h"
 
 using namespace cdb;
 
@@ -19,11 +20,6 @@ namespace {
 
 static_assert((int)Status::Invalid == CDB_E_INVALID && (int)Status::Device == CDB_E_DEVICE && (int)Status::Internal == CDB_E_INTERNAL,
               "errors.h: Status restates the CDB_E_* codes");
-
-void set_error(Index& ix, const std::string& msg) {
-    std::lock_guard<std::mutex> g(ix.err_mu);
-    ix.err = msg;
-}
 
 template <typename F>
 int guarded(cdb_index* h, F&& f) {
@@ -329,13 +325,6 @@ void adopt_blocks(Index& ix, NewColumn& col, ColumnBlocks& made) {
     ix.prof.resolve();
     static_cast<ColumnBlocks&>(col) = std::move(made);
 }
-
-// every entry point that touches the device: make the handle's device current and tell the block cache which
-// stream this thread issues work on (common.h: blocks released meanwhile are tagged with it)
-struct DeviceScope {
-    StreamScope ss;
-    explicit DeviceScope(Index& ix) : ss(ix.stream) { CDB_HIP(hipSetDevice(ix.device)); }
-};
 
 // resident build: longest document, order check and re-basing of the caller's device tables
 __global__ __launch_bounds__(256) void layout_kernel(const uint64_t* __restrict__ src_start,
@@ -1248,482 +1237,6 @@ int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_
 
 void cdb_free(void* p) { host_free(p); }
 
-namespace {
-int query_batch_impl(cdb_index* h, const char* blob, const uint64_t* offsets, uint64_t npat, cdb_result* out,
-                     cdb_hits* hits) {
-    if (!h || !out || (npat && !offsets)) return CDB_E_INVALID;
-    std::memset(out, 0, sizeof(*out));
-    if (hits) std::memset(hits, 0, sizeof(*hits));
-    const int rc = guarded(h, [&] {
-        Index& ix = h->ix;
-        for (uint64_t j = 0; j < npat; ++j)
-            if (offsets[j + 1] <= offsets[j]) throw Error("Empty keywords are not allowed");  // index.cpp:239-241
-        std::lock_guard<std::mutex> g(ix.mu);
-        DeviceScope dscope(ix);
-        const double t0 = wall_ms();
-        hipStream_t s = ix.stream;
-        const uint64_t base = npat ? offsets[0] : 0;
-        const uint64_t nbytes = npat ? offsets[npat] - base : 0;
-        ix.q_pat.ensure(nbytes + 16);
-        ix.q_offs.ensure((npat + 1) * 8);
-        std::vector<uint64_t> rel(npat + 1);
-        for (uint64_t j = 0; j <= npat; ++j) rel[j] = npat ? offsets[j] - base : 0;
-        if (nbytes) CDB_HIP(hipMemcpyAsync(ix.q_pat.p, blob + base, nbytes, hipMemcpyHostToDevice, s));
-        CDB_HIP(hipMemcpyAsync(ix.q_offs.p, rel.data(), (npat + 1) * 8, hipMemcpyHostToDevice, s));
-        CDB_HIP(hipStreamSynchronize(s));
-        const double t1 = wall_ms();
-        const DeviceCsr r = query_batch_on_device(ix, ix.q_pat.as<uint8_t>(), ix.q_offs.as<uint64_t>(), npat, hits != nullptr);
-        CDB_HIP(hipStreamSynchronize(s));
-        const double t2 = wall_ms();
-        out->npat = npat;
-        out->nrows = r.nrows;
-        out->nhits = r.nhits;
-        out->row_ptr = (uint64_t*)host_alloc((npat + 1) * 8);
-        out->ids = (int64_t*)host_alloc(r.nrows * 8);
-        out->counts = (int64_t*)host_alloc(r.nrows * 8);
-        if (hits) {
-            hits->hit_ptr = (uint64_t*)host_alloc((r.nrows + 1) * 8, true);
-            hits->offsets = (uint64_t*)host_alloc(r.nhits * 8);
-        }
-        CDB_HIP(hipMemcpyAsync(out->row_ptr, ix.q_rowptr.p, (npat + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (r.nrows) {
-            CDB_HIP(hipMemcpyAsync(out->ids, ix.q_ids.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-            CDB_HIP(hipMemcpyAsync(out->counts, ix.q_counts.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-            if (hits) {
-                CDB_HIP(hipMemcpyAsync(hits->hit_ptr, ix.q_hitptr.p, (r.nrows + 1) * 8, hipMemcpyDeviceToHost, s));
-                CDB_HIP(hipMemcpyAsync(hits->offsets, ix.q_hitoff.p, r.nhits * 8, hipMemcpyDeviceToHost, s));
-            }
-        }
-        CDB_HIP(hipStreamSynchronize(s));
-        ix.qstats.query_ms = wall_ms() - t0;
-        ix.qstats.upload_ms = t1 - t0;
-        ix.qstats.device_ms = t2 - t1;
-        ix.qstats.download_ms = wall_ms() - t2;
-        ix.qstats.nhits = r.nhits;
-        ix.qstats.nrows = r.nrows;
-    });
-    if (rc != CDB_OK) {  // a later allocation or copy failed: nothing half-filled leaves the library
-        cdb_result_free(out);
-        if (hits) cdb_hits_free(hits);
-    }
-    return rc;
-}
-}  // namespace
-
-int cdb_query_batch(cdb_index* h, const char* blob, const uint64_t* offsets, uint64_t npat, cdb_result* out) {
-    return query_batch_impl(h, blob, offsets, npat, out, nullptr);
-}
-
-int cdb_query_batch_offsets(cdb_index* h, const char* blob, const uint64_t* offsets, uint64_t npat, cdb_result* out,
-                            cdb_hits* hits) {
-    if (!hits) return CDB_E_INVALID;
-    return query_batch_impl(h, blob, offsets, npat, out, hits);
-}
-
-void cdb_hits_free(cdb_hits* x) {
-    if (!x) return;
-    host_free(x->hit_ptr);
-    host_free(x->offsets);
-    std::memset(x, 0, sizeof(*x));
-}
-
-namespace {
-int query_or_impl(cdb_index* h, const char* blob, const uint64_t* offsets, uint64_t nkw, int64_t** ids, int64_t** counts,
-                  size_t* nrows, bool ranked, int64_t corr_lo, int64_t corr_hi, uint64_t limit) {
-    if (!h || !ids || !counts || !nrows || (nkw && !offsets)) return CDB_E_INVALID;
-    *ids = nullptr;
-    *counts = nullptr;
-    *nrows = 0;
-    return guarded(h, [&] {
-        Index& ix = h->ix;
-        if (nkw == 0) throw Error("The constraint list cannot be empty");  // interface.cpp:75-77
-        for (uint64_t j = 0; j < nkw; ++j)
-            if (offsets[j + 1] <= offsets[j]) throw Error("Empty keywords are not allowed");
-        std::lock_guard<std::mutex> g(ix.mu);
-        DeviceScope dscope(ix);
-        hipStream_t s = ix.stream;
-        const uint64_t base = offsets[0], nbytes = offsets[nkw] - base;
-        ix.q_pat.ensure(nbytes + 16);
-        ix.q_offs.ensure((nkw + 1) * 8);
-        std::vector<uint64_t> rel(nkw + 1);
-        for (uint64_t j = 0; j <= nkw; ++j) rel[j] = offsets[j] - base;
-        CDB_HIP(hipMemcpyAsync(ix.q_pat.p, blob + base, nbytes, hipMemcpyHostToDevice, s));
-        CDB_HIP(hipMemcpyAsync(ix.q_offs.p, rel.data(), (nkw + 1) * 8, hipMemcpyHostToDevice, s));
-        const DeviceCsr r = ranked ? query_ranked_on_device(ix, ix.q_pat.as<uint8_t>(), ix.q_offs.as<uint64_t>(), nkw, corr_lo, corr_hi, limit)
-                                   : query_or_on_device(ix, ix.q_pat.as<uint8_t>(), ix.q_offs.as<uint64_t>(), nkw);
-        int64_t* hi = (int64_t*)host_alloc(r.nrows * 8);
-        int64_t* hc = nullptr;
-        try {
-            hc = (int64_t*)host_alloc(r.nrows * 8);
-        } catch (...) {
-            host_free(hi);
-            throw;
-        }
-        try {
-            if (r.nrows) {
-                CDB_HIP(hipMemcpyAsync(hi, ix.q_ids.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-                CDB_HIP(hipMemcpyAsync(hc, ix.q_counts.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-                CDB_HIP(hipStreamSynchronize(s));
-            }
-        } catch (...) {
-            host_free(hi);
-            host_free(hc);
-            throw;
-        }
-        *ids = hi;
-        *counts = hc;
-        *nrows = (size_t)r.nrows;
-    });
-}
-}  // namespace
-
-int cdb_query_or(cdb_index* h, const char* blob, const uint64_t* offsets, uint64_t nkw, int64_t** ids, int64_t** counts,
-                 size_t* nrows) {
-    return query_or_impl(h, blob, offsets, nkw, ids, counts, nrows, false, 0, 0, 0);
-}
-
-int cdb_query_ranked(cdb_index* h, const char* blob, const uint64_t* offsets, uint64_t nkw, int64_t corr_lo, int64_t corr_hi,
-                     uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows) {
-    return query_or_impl(h, blob, offsets, nkw, ids, counts, nrows, true, corr_lo, corr_hi, limit);
-}
-
-int cdb_query_and(const cdb_key_query* keys, int nkeys, int ranked, int64_t corr_lo, int64_t corr_hi, uint64_t limit, int64_t** ids,
-                  int64_t** counts, size_t* nrows) {
-    if (!keys || nkeys < 1 || !ids || !counts || !nrows) return CDB_E_INVALID;
-    *ids = nullptr;
-    *counts = nullptr;
-    *nrows = 0;
-    cdb_index* lead = nullptr;  // the first string key: its stream runs the merge, its handle carries the error
-    for (int k = 0; k < nkeys; ++k)
-        if (keys[k].index && !lead) lead = keys[k].index;
-    if (!lead) return CDB_E_INVALID;
-    return cdb::query_and_with_lead(lead, keys, nkeys, ranked, corr_lo, corr_hi, limit, ids, counts, nrows);
-}
-}  // extern "C"
-
-// the merge behind cdb_query_and on `lead`'s device and stream (shards.hip: every key of a sharded AND arrives as a row
-// list resolved by its shards, and the first shard of the first key lends its device)
-int cdb::query_and_with_lead(cdb_index* lead, const cdb_key_query* keys, int nkeys, int ranked, int64_t corr_lo, int64_t corr_hi,
-                             uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows) {
-    {
-    return guarded(lead, [&] {
-        Index& ix = lead->ix;
-        for (int k = 0; k < nkeys; ++k) {
-            const cdb_key_query& q = keys[k];
-            if (q.index) {
-                if (q.index->ix.device != ix.device) throw Error("cdb_query_and: all string keys must live on one GPU");
-                if (q.nkw == 0) throw Error("The constraint list cannot be empty");  // interface.cpp:75-77
-                if (!q.offsets) throw Error("cdb_query_and: keyword offsets missing");
-                for (uint64_t j = 0; j < q.nkw; ++j)
-                    if (q.offsets[j + 1] <= q.offsets[j]) throw Error("Empty keywords are not allowed");
-            } else if (q.nrows && (!q.ids || !q.counts)) {
-                throw Error("cdb_query_and: row list missing");
-            }
-        }
-        // every handle involved stays locked until the merge has read its rows (address order: no lock inversion)
-        std::vector<cdb_index*> hs;
-        for (int k = 0; k < nkeys; ++k)
-            if (keys[k].index) hs.push_back(keys[k].index);
-        std::sort(hs.begin(), hs.end());
-        hs.erase(std::unique(hs.begin(), hs.end()), hs.end());
-        std::vector<std::unique_lock<std::mutex>> locks;
-        for (cdb_index* p : hs) locks.emplace_back(p->ix.mu);
-        DeviceScope dscope(ix);
-        hipStream_t s = ix.stream;
-        std::vector<DeviceRows> lists;
-        std::vector<DevBuf> held;  // copies of rows that would be overwritten by a later query on the same handle
-        for (int k = 0; k < nkeys; ++k) {
-            const cdb_key_query& q = keys[k];
-            DevBuf di, dc;
-            uint64_t n = 0;
-            if (q.index) {
-                Index& kx = q.index->ix;
-                StreamScope kss(kx.stream);
-                const uint64_t base = q.offsets[0], nbytes = q.offsets[q.nkw] - base;
-                kx.q_pat.ensure(nbytes + 16);
-                kx.q_offs.ensure((q.nkw + 1) * 8);
-                std::vector<uint64_t> rel(q.nkw + 1);
-                for (uint64_t j = 0; j <= q.nkw; ++j) rel[j] = q.offsets[j] - base;
-                CDB_HIP(hipMemcpyAsync(kx.q_pat.p, q.blob + base, nbytes, hipMemcpyHostToDevice, kx.stream));
-                CDB_HIP(hipMemcpyAsync(kx.q_offs.p, rel.data(), (q.nkw + 1) * 8, hipMemcpyHostToDevice, kx.stream));
-                const DeviceCsr r = query_or_on_device(kx, kx.q_pat.as<uint8_t>(), kx.q_offs.as<uint64_t>(), q.nkw);  // (synchronises)
-                n = r.nrows;
-                di.alloc(std::max<uint64_t>(n, 1) * 8);
-                dc.alloc(std::max<uint64_t>(n, 1) * 8);
-                if (n) {
-                    CDB_HIP(hipMemcpyAsync(di.p, kx.q_ids.p, n * 8, hipMemcpyDeviceToDevice, s));
-                    CDB_HIP(hipMemcpyAsync(dc.p, kx.q_counts.p, n * 8, hipMemcpyDeviceToDevice, s));
-                }
-            } else {  // rows resolved elsewhere (numeric / bool keys: index.cpp:63-74,129-173 return (id, 0) rows)
-                n = q.nrows;
-                di.alloc(std::max<uint64_t>(n, 1) * 8);
-                dc.alloc(std::max<uint64_t>(n, 1) * 8);
-                if (n) {
-                    CDB_HIP(hipMemcpyAsync(di.p, q.ids, n * 8, hipMemcpyHostToDevice, s));
-                    CDB_HIP(hipMemcpyAsync(dc.p, q.counts, n * 8, hipMemcpyHostToDevice, s));
-                }
-            }
-            lists.push_back(DeviceRows{di.as<int64_t>(), dc.as<int64_t>(), n});
-            held.push_back(std::move(di));
-            held.push_back(std::move(dc));
-        }
-        CDB_HIP(hipStreamSynchronize(s));  // (host rows are pageable)
-        const DeviceCsr r = and_merge_on_device(ix, lists, ranked != 0, corr_lo, corr_hi, limit);
-        int64_t* hi = (int64_t*)host_alloc(r.nrows * 8);
-        int64_t* hc = nullptr;
-        try {
-            hc = (int64_t*)host_alloc(r.nrows * 8);
-            if (r.nrows) {
-                CDB_HIP(hipMemcpyAsync(hi, ix.q_ids.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-                CDB_HIP(hipMemcpyAsync(hc, ix.q_counts.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-                CDB_HIP(hipStreamSynchronize(s));
-            }
-        } catch (...) {
-            host_free(hi);
-            host_free(hc);
-            throw;
-        }
-        *ids = hi;
-        *counts = hc;
-        *nrows = (size_t)r.nrows;
-    });
-    }
-}
-
-extern "C" {
-
-int cdb_query_spans(cdb_index* h, const char* blob, const uint64_t* offsets, uint64_t nkw, cdb_spans* out) {
-    if (!h || !out || (nkw && !offsets)) return CDB_E_INVALID;
-    std::memset(out, 0, sizeof(*out));
-    const int rc = guarded(h, [&] {
-        Index& ix = h->ix;
-        std::vector<uint64_t> rel{0};
-        std::string pat;
-        for (uint64_t j = 0; j < nkw; ++j) {  // empty highlight keywords never match (ac_automaton::insert)
-            if (offsets[j + 1] <= offsets[j]) continue;
-            pat.append(blob + offsets[j], offsets[j + 1] - offsets[j]);
-            rel.push_back(pat.size());
-        }
-        const uint64_t npat = rel.size() - 1;
-        std::lock_guard<std::mutex> g(ix.mu);
-        DeviceScope dscope(ix);
-        hipStream_t s = ix.stream;
-        SpanResult r;
-        if (npat) {
-            ix.q_pat.ensure(pat.size() + 16);
-            ix.q_offs.ensure((npat + 1) * 8);
-            CDB_HIP(hipMemcpyAsync(ix.q_pat.p, pat.data(), pat.size(), hipMemcpyHostToDevice, s));
-            CDB_HIP(hipMemcpyAsync(ix.q_offs.p, rel.data(), (npat + 1) * 8, hipMemcpyHostToDevice, s));
-            r = query_spans_on_device(ix, ix.q_pat.as<uint8_t>(), ix.q_offs.as<uint64_t>(), npat, pat.size());
-        }
-        out->ndocs = r.ndocs;
-        out->nspans = r.nspans;
-        out->ids = (int64_t*)host_alloc(r.ndocs * 8);
-        out->span_ptr = (uint64_t*)host_alloc((r.ndocs + 1) * 8, true);
-        out->begin = (uint64_t*)host_alloc(r.nspans * 8);
-        out->end = (uint64_t*)host_alloc(r.nspans * 8);
-        if (r.nspans) {
-            CDB_HIP(hipMemcpyAsync(out->ids, ix.q_ids.p, r.ndocs * 8, hipMemcpyDeviceToHost, s));
-            CDB_HIP(hipMemcpyAsync(out->span_ptr, ix.q_rowptr.p, (r.ndocs + 1) * 8, hipMemcpyDeviceToHost, s));
-            CDB_HIP(hipMemcpyAsync(out->begin, ix.q_keys0.p, r.nspans * 8, hipMemcpyDeviceToHost, s));
-            CDB_HIP(hipMemcpyAsync(out->end, ix.q_keys1.p, r.nspans * 8, hipMemcpyDeviceToHost, s));
-            CDB_HIP(hipStreamSynchronize(s));
-        }
-    });
-    if (rc != CDB_OK) cdb_spans_free(out);
-    return rc;
-}
-
-void cdb_spans_free(cdb_spans* r) {
-    if (!r) return;
-    host_free(r->ids);
-    host_free(r->span_ptr);
-    host_free(r->begin);
-    host_free(r->end);
-    std::memset(r, 0, sizeof(*r));
-}
-
-void cdb_result_free(cdb_result* r) {
-    if (!r) return;
-    host_free(r->row_ptr);
-    host_free(r->ids);
-    host_free(r->counts);
-    std::memset(r, 0, sizeof(*r));
-}
-
-// Single-keyword queries arrive from many host threads at once (the reference serves them from an
-// httplib pool under a shared lock, database.cpp:388) and one GPU round trip costs ~100 us, so
-// concurrent callers are coalesced: the first caller becomes the leader and resolves everything that
-// queued up as ONE batched GPU query, then the next batch, until the queue is empty; the others wait
-// for their slice of the result.  No artificial delay is added for a lone caller.
-namespace {
-struct PendingQuery {
-    const char* kw;
-    size_t len;
-    int64_t *ids = nullptr, *counts = nullptr;
-    size_t rows = 0;
-    int rc = CDB_OK;
-    bool done = false;
-};
-
-void run_coalesced(cdb_index* h, std::vector<PendingQuery*>& batch) {
-    if (batch.size() == 1) {  // a lone keyword: one wavefront, one launch (query.hip: q_single_kernel)
-        PendingQuery* q = batch[0];
-        int64_t *ids = nullptr, *counts = nullptr;
-        size_t rows = 0;
-        bool answered = false;
-        const int rc1 = guarded(h, [&] {
-            Index& ix = h->ix;
-            std::lock_guard<std::mutex> g(ix.mu);
-            DeviceScope dscope(ix);
-            const double t0 = wall_ms();
-            answered = query_single_on_device(ix, q->kw, q->len, &ids, &counts, &rows);
-            if (answered) ix.qstats.query_ms = wall_ms() - t0;
-        });
-        if (rc1 != CDB_OK) {
-            q->rc = rc1;
-            return;
-        }
-        if (answered) {
-            q->rows = rows;
-            q->ids = ids;
-            q->counts = counts;
-            q->rc = CDB_OK;
-            return;
-        }
-    }
-    std::string blob;
-    std::vector<uint64_t> offs{0};
-    for (auto* q : batch) {
-        blob.append(q->kw, q->len);
-        offs.push_back(blob.size());
-    }
-    cdb_result r;
-    const int rc = cdb_query_batch(h, blob.data(), offs.data(), batch.size(), &r);
-    for (size_t j = 0; j < batch.size(); ++j) {
-        PendingQuery* q = batch[j];
-        q->rc = rc;
-        if (rc != CDB_OK) continue;
-        const uint64_t a = r.row_ptr[j], b = r.row_ptr[j + 1];
-        q->rows = (size_t)(b - a);
-        q->ids = (int64_t*)std::malloc(std::max<size_t>(q->rows, 1) * 8);
-        q->counts = (int64_t*)std::malloc(std::max<size_t>(q->rows, 1) * 8);
-        if (!q->ids || !q->counts) {
-            q->rc = CDB_E_DEVICE;
-            continue;
-        }
-        std::memcpy(q->ids, r.ids + a, q->rows * 8);
-        std::memcpy(q->counts, r.counts + a, q->rows * 8);
-    }
-    if (rc == CDB_OK) cdb_result_free(&r);
-}
-}  // namespace
-
-int cdb_query(cdb_index* h, const char* keyword, size_t len, int64_t** ids, int64_t** counts, size_t* nrows) {
-    if (!h || !ids || !counts || !nrows) return CDB_E_INVALID;
-    *ids = nullptr;
-    *counts = nullptr;
-    *nrows = 0;
-    Index& ix = h->ix;
-    if (len == 0) {  // index.cpp:239-241
-        set_error(ix, "Empty keywords are not allowed");
-        return CDB_E_INVALID;
-    }
-    PendingQuery me{keyword, len};
-    if (!ix.coalesce_queries) {
-        std::vector<PendingQuery*> one{&me};
-        run_coalesced(h, one);
-    } else {
-        // Leader / follower: whoever finds no leader takes everything queued so far (its own query included),
-        // resolves it as ONE batched GPU query and then gives the leadership up — a waiter whose query arrived
-        // meanwhile takes over.  A leader therefore never serves more than the batch holding its own query (under
-        // sustained load it would otherwise never return), and leadership cannot be stranded by an exception.
-        std::unique_lock<std::mutex> lk(ix.qmu);
-        ix.qpending.push_back(&me);
-        while (!me.done) {
-            if (ix.qleader) {
-                ix.qcv.wait(lk, [&] { return me.done || !ix.qleader; });
-                continue;
-            }
-            ix.qleader = true;
-            std::vector<void*> taken;
-            taken.swap(ix.qpending);
-            lk.unlock();
-            try {
-                std::vector<PendingQuery*> batch;
-                batch.reserve(taken.size());
-                for (void* p : taken) batch.push_back(static_cast<PendingQuery*>(p));
-                run_coalesced(h, batch);
-            } catch (...) {  // (host allocation failure while assembling the batch)
-                const Failure fail = classify_current_exception();
-                for (void* p : taken) {
-                    PendingQuery* q = static_cast<PendingQuery*>(p);
-                    std::free(q->ids);
-                    std::free(q->counts);
-                    q->ids = q->counts = nullptr;
-                    q->rc = fail.code;
-                }
-                set_error(ix, fail.message);
-            }
-            lk.lock();
-            for (void* p : taken) static_cast<PendingQuery*>(p)->done = true;
-            ix.qleader = false;
-            ix.qcv.notify_all();
-        }
-    }
-    if (me.rc != CDB_OK) {
-        std::free(me.ids);
-        std::free(me.counts);
-        return me.rc;
-    }
-    *ids = me.ids;
-    *counts = me.counts;
-    *nrows = me.rows;
-    return CDB_OK;
-}
-
-namespace {
-int query_batch_device_impl(cdb_index* h, const void* d_blob, const uint64_t* d_offsets, uint64_t npat, cdb_device_result* out,
-                            cdb_device_hits* hits) {
-    if (!h || !out) return CDB_E_INVALID;
-    std::memset(out, 0, sizeof(*out));
-    if (hits) std::memset(hits, 0, sizeof(*hits));
-    return guarded(h, [&] {
-        Index& ix = h->ix;
-        std::lock_guard<std::mutex> g(ix.mu);
-        DeviceScope dscope(ix);
-        const double t0 = wall_ms();
-        const DeviceCsr r = query_batch_on_device(ix, static_cast<const uint8_t*>(d_blob), d_offsets, npat, hits != nullptr);
-        out->npat = npat;
-        out->nrows = r.nrows;
-        out->nhits = r.nhits;
-        out->d_row_ptr = ix.q_rowptr.as<uint64_t>();
-        out->d_ids = ix.q_ids.as<int64_t>();
-        out->d_counts = ix.q_counts.as<int64_t>();
-        if (hits) {
-            hits->d_hit_ptr = ix.q_hitptr.as<uint64_t>();
-            hits->d_offsets = ix.q_hitoff.as<uint64_t>();
-        }
-        ix.qstats.query_ms = wall_ms() - t0;
-        ix.qstats.nhits = r.nhits;
-        ix.qstats.nrows = r.nrows;
-    });
-}
-}  // namespace
-
-int cdb_query_batch_device(cdb_index* h, const void* d_blob, const uint64_t* d_offsets, uint64_t npat,
-                           uint64_t blob_bytes, cdb_device_result* out) {
-    (void)blob_bytes;
-    return query_batch_device_impl(h, d_blob, d_offsets, npat, out, nullptr);
-}
-
-int cdb_query_batch_offsets_device(cdb_index* h, const void* d_blob, const uint64_t* d_offsets, uint64_t npat,
-                                   uint64_t blob_bytes, cdb_device_result* out, cdb_device_hits* hits) {
-    (void)blob_bytes;
-    if (!hits) return CDB_E_INVALID;
-    return query_batch_device_impl(h, d_blob, d_offsets, npat, out, hits);
-}
-
 uint64_t cdb_size(const cdb_index* h) { return h ? h->ix.size : 0; }
 uint64_t cdb_bits(const cdb_index* h) { return h ? h->ix.bits : 0; }
 uint64_t cdb_mask(const cdb_index* h) { return h ? h->ix.mask : 0; }
@@ -1888,16 +1401,7 @@ int cdb_profile_get(cdb_index* h, const char* kernel, double* total_ms, uint64_t
 
 int cdb_profile_dump(cdb_index* h, char* buf, size_t cap) {
     if (!h || !buf || cap == 0) return CDB_E_INVALID;
-    std::lock_guard<std::mutex> g(h->ix.mu);
-    std::string s;
-    for (auto& kv : h->ix.prof.recs) {
-        char line[256];
-        std::snprintf(line, sizeof(line), "%s %.6f %llu %llu\n", kv.first.c_str(), kv.second.ms,
-                      (unsigned long long)kv.second.launches, (unsigned long long)kv.second.bytes);
-        s += line;
-    }
-    std::strncpy(buf, s.c_str(), cap - 1);
-    buf[cap - 1] = 0;
+    (void)profile_dump(h->ix, buf, cap);
     return CDB_OK;
 }
 

@@ -20,7 +20,7 @@
 #include <string_view>
 
 #include "../../include/coffeedb_gpu.h"
-#include "index_impl.h"
+#include "host_io.h"
 #include "scan.h"
 
 using namespace cdb;
@@ -342,42 +342,8 @@ struct PtrOut {
     }
 };
 
-struct IndexScope {
-    StreamScope ss;
-    explicit IndexScope(Index& ix) : ss(ix.stream) { CDB_HIP(hipSetDevice(ix.device)); }
-};
-
 // the result arrays: host blocks of the result cache, filled from the device
-struct Result {
-    cdb_clusters r{};
-    hipStream_t stream;  // (copies into the arrays may still be in flight when an error unwinds)
-    explicit Result(hipStream_t s) : stream(s) {}
-    ~Result() { release(); }
-    void release() {
-        if (r.counts || r.rep_ids || r.values || r.value_ptr || r.value_blob) (void)hipStreamSynchronize(stream);
-        host_free(r.counts);
-        host_free(r.rep_ids);
-        host_free(r.values);
-        host_free(r.value_ptr);
-        host_free(r.value_blob);
-        r = cdb_clusters{};
-    }
-    template <typename T> static T* fetch(hipStream_t s, const void* d, uint64_t count) {
-        T* h = (T*)host_alloc(count * sizeof(T));
-        if (count) {
-            const hipError_t e = hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, s);
-            if (e != hipSuccess) {
-                host_free(h);
-                CDB_HIP(e);
-            }
-        }
-        return h;
-    }
-    void hand_over(cdb_clusters* out) {
-        *out = r;
-        r = cdb_clusters{};
-    }
-};
+using Clusters = ResultOwner<cdb_clusters, cdb_clusters_free>;
 
 // ---- columns: host side ------------------------------------------------------------------------------------------------------------
 void column_run_starts(cdb_column* c) {
@@ -399,7 +365,7 @@ void column_run_starts(cdb_column* c) {
     c->clu_generation = c->generation;
 }
 
-void column_cluster(cdb_column* c, RowIds ids, uint64_t nrows, Result& res) {
+void column_cluster(cdb_column* c, RowIds ids, uint64_t nrows, Clusters& res) {
     Index& ws = c->ws;
     hipStream_t s = ws.stream;
     const double t0 = wall_ms();
@@ -477,9 +443,9 @@ void column_cluster(cdb_column* c, RowIds ids, uint64_t nrows, Result& res) {
         ws.prof.end(t, "clu_col_runs_hit", c->clu_runs * 48 + ng * 40, s);
         CDB_HIP(hipGetLastError());
         CDB_HIP(hipMemcpyAsync(&missing, d_out.p, 8, hipMemcpyDeviceToHost, s));
-        res.r.counts = Result::fetch<int64_t>(s, d_counts.p, ng);
-        res.r.rep_ids = Result::fetch<int64_t>(s, d_rep.p, ng);
-        res.r.values = Result::fetch<uint64_t>(s, d_values.p, ng);
+        res.r.counts = res.fetch<int64_t>(d_counts.p, ng);
+        res.r.rep_ids = res.fetch<int64_t>(d_rep.p, ng);
+        res.r.values = res.fetch<uint64_t>(d_values.p, ng);
         CDB_HIP(hipStreamSynchronize(s));
     } else {
         ++c->sparse_clusters;
@@ -512,9 +478,9 @@ void column_cluster(cdb_column* c, RowIds ids, uint64_t nrows, Result& res) {
         hipLaunchKernelGGL(clu_counts_kernel, dim3(grid_for(ng)), dim3(256), 0, s, (const uint64_t*)start.as<uint64_t>(), ng, m, d_counts.as<int64_t>());
         ws.prof.end(t, "clu_col_heads", m * 48 + ng * 40, s);
         CDB_HIP(hipGetLastError());
-        res.r.counts = Result::fetch<int64_t>(s, d_counts.p, ng);
-        res.r.rep_ids = Result::fetch<int64_t>(s, d_rep.p, ng);
-        res.r.values = Result::fetch<uint64_t>(s, d_values.p, ng);
+        res.r.counts = res.fetch<int64_t>(d_counts.p, ng);
+        res.r.rep_ids = res.fetch<int64_t>(d_rep.p, ng);
+        res.r.values = res.fetch<uint64_t>(d_values.p, ng);
         CDB_HIP(hipStreamSynchronize(s));
     }
     ws.prof.resolve();
@@ -671,7 +637,7 @@ void cluster_prepare(Index& ix) {
     ct.valid = true;
 }
 
-void index_cluster(Index& ix, RowIds ids, uint64_t nrows, bool with_values, Result& res) {
+void index_cluster(Index& ix, RowIds ids, uint64_t nrows, bool with_values, Clusters& res) {
     hipStream_t s = ix.stream;
     auto empty = [&] {
         res.r.missing = nrows;
@@ -732,8 +698,8 @@ void index_cluster(Index& ix, RowIds ids, uint64_t nrows, bool with_values, Resu
     hipLaunchKernelGGL(clu_counts_kernel, dim3(grid_for(ng)), dim3(256), 0, s, (const uint64_t*)start.as<uint64_t>(), ng, m, d_counts.as<int64_t>());
     ix.prof.end(t, "clu_str_heads", m * 32 + ng * 36, s);
     CDB_HIP(hipGetLastError());
-    res.r.counts = Result::fetch<int64_t>(s, d_counts.p, ng);
-    res.r.rep_ids = Result::fetch<int64_t>(s, d_rep.p, ng);
+    res.r.counts = res.fetch<int64_t>(d_counts.p, ng);
+    res.r.rep_ids = res.fetch<int64_t>(d_rep.p, ng);
     if (with_values) {
         DevBuf d_ptr, d_blob;
         d_ptr.alloc((ng + 1) * 8);
@@ -749,8 +715,8 @@ void index_cluster(Index& ix, RowIds ids, uint64_t nrows, bool with_values, Resu
                                (const uint64_t*)d_ptr.as<uint64_t>(), d_blob.as<uint8_t>());
         ix.prof.end(t, "clu_str_values", ng * 28 + 2 * total, s);
         CDB_HIP(hipGetLastError());
-        res.r.value_ptr = Result::fetch<uint64_t>(s, d_ptr.p, ng + 1);
-        res.r.value_blob = Result::fetch<char>(s, d_blob.p, total);
+        res.r.value_ptr = res.fetch<uint64_t>(d_ptr.p, ng + 1);
+        res.r.value_blob = res.fetch<char>(d_blob.p, total);
         CDB_HIP(hipStreamSynchronize(s));  // (the device blocks go back to the pool behind this scope)
     }
     CDB_HIP(hipStreamSynchronize(s));
@@ -762,15 +728,15 @@ void index_cluster(Index& ix, RowIds ids, uint64_t nrows, bool with_values, Resu
 
 void run_column_cluster(cdb_column* c, RowIds ids, uint64_t nrows, cdb_clusters* out) {
     std::lock_guard<std::mutex> g(c->ws.mu);
-    IndexScope scope(c->ws);
-    Result res(c->ws.stream);
+    DeviceScope scope(c->ws);
+    Clusters res(c->ws.stream);
     column_cluster(c, ids, nrows, res);
     res.hand_over(out);
 }
 void run_index_cluster(Index& ix, RowIds ids, uint64_t nrows, bool with_values, cdb_clusters* out) {
     std::lock_guard<std::mutex> g(ix.mu);
-    IndexScope scope(ix);
-    Result res(ix.stream);
+    DeviceScope scope(ix);
+    Clusters res(ix.stream);
     index_cluster(ix, ids, nrows, with_values, res);
     res.hand_over(out);
 }

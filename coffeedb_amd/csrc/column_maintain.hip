@@ -389,7 +389,7 @@ int cdb_column_append(cdb_column* c, const int64_t* ids, const void* values, uin
     return guarded_ix(c->ws, [&] {
         const std::vector<uint64_t> raw = column_raw_values(c->kind, values, n, "cdb_column_append");
         std::lock_guard<std::mutex> g(c->ws.mu);
-        ColumnScope cs(c);
+        DeviceScope cs(c->ws);
         if (!n) return;
         if (!c->staged_ids.empty()) throw Error("append: rows were added since the last build");
         if (c->n + n > COLUMN_MAX_ROWS) throw Error("cdb_column_append: a column holds at most 2^32 - 1 rows");
@@ -421,7 +421,7 @@ int cdb_debug_column_arrays(cdb_column* c, uint64_t* keys_v, int64_t* ids_v, int
     if (!c) return CDB_E_INVALID;
     return guarded_ix(c->ws, [&] {
         std::lock_guard<std::mutex> g(c->ws.mu);
-        ColumnScope cs(c);
+        DeviceScope cs(c->ws);
         hipStream_t s = c->ws.stream;
         const uint64_t n = c->n;
         if (!n) return;

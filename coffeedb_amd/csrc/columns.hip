@@ -16,7 +16,7 @@
 #include <cstring>
 
 #include "../../include/coffeedb_gpu.h"
-#include "index_impl.h"
+#include "host_io.h"
 #include "scan.h"
 #include "shim/range_parse.h"  // the one restatement of the reference's range grammar (utility.h:49-86)
 
@@ -694,7 +694,7 @@ int cdb_column_build(cdb_column* c) {
     if (!c) return CDB_E_INVALID;
     return guarded_ix(c->ws, [&] {
         std::lock_guard<std::mutex> g(c->ws.mu);
-        ColumnScope cs(c);
+        DeviceScope cs(c->ws);
         column_build(c);
     });
 }
@@ -707,7 +707,7 @@ int cdb_column_remove(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t
     if (missing) *missing = 0;
     return guarded_ix(c->ws, [&] {
         std::lock_guard<std::mutex> g(c->ws.mu);
-        ColumnScope cs(c);
+        DeviceScope cs(c->ws);
         if (!nids) return;
         const double t0 = wall_ms();
         const bool device = c->staged_ids.empty() && c->debug_maintain_path != 2;
@@ -738,7 +738,7 @@ int cdb_column_query(cdb_column* c, const char* range, size_t len, int64_t** ids
     *nrows = 0;
     return guarded_ix(c->ws, [&] {
         std::lock_guard<std::mutex> g(c->ws.mu);
-        ColumnScope cs(c);
+        DeviceScope cs(c->ws);
         const Windows w = column_windows(c, {std::string(range ? range : "", len)});
         const uint64_t a = w.a[0], cnt = w.b[0] - w.a[0];
         c->last_k = cnt;
@@ -753,7 +753,7 @@ int cdb_column_query_any(cdb_column* c, const char* blob, const uint64_t* offset
     *nrows = 0;
     return guarded_ix(c->ws, [&] {
         std::lock_guard<std::mutex> g(c->ws.mu);
-        ColumnScope cs(c);
+        DeviceScope cs(c->ws);
         const Windows w = column_windows(c, ranges_of(blob, offsets, nranges));
         c->last_k = w.k;
         DevBuf out;
@@ -765,7 +765,7 @@ int cdb_column_query_any(cdb_column* c, const char* blob, const uint64_t* offset
 
 }  // extern "C"
 
-// ---- the AND of cdb_query_and_columns and cdb_filter (rowset.hip), up to "rows in ix.q_ids / q_counts" ---------------------------
+// ---- the AND of cdb_query_and (capi_query.hip), cdb_query_and_columns and cdb_filter (rowset.hip), up to "rows in ix.q_ids / q_counts"
 // The handle that runs the merge and carries the error: the first string key (as in cdb_query_and); without one, the first
 // column.  nullptr: the keys are not a valid query (CDB_E_INVALID).
 Index* cdb::filter_lead(const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols) {
@@ -784,24 +784,24 @@ Index* cdb::filter_lead(const cdb_key_query* keys, int nkeys, const cdb_column_k
 
 // Validates the keys, locks every handle and column involved, resolves the keys and merges them on the lead's stream; `consume`
 // runs while the locks are held, with the rows in ix.q_ids / q_counts (ascending id, or filtered and ranked when `ranked`).
-void cdb::filter_rows_on_lead(Index& ix, const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols, bool ranked,
-                              int64_t corr_lo, int64_t corr_hi, uint64_t limit, const std::function<void(hipStream_t, DeviceCsr)>& consume) {
+// `names` = the entry point the refusals speak for (cdb_query_and passes no column keys).
+void cdb::filter_rows_on_lead(Index& ix, const FilterNames& names, const cdb_key_query* keys, int nkeys, const cdb_column_key* cols,
+                              int ncols, bool ranked, int64_t corr_lo, int64_t corr_hi, uint64_t limit,
+                              const std::function<void(hipStream_t, DeviceCsr)>& consume) {
+    const std::string who = names.who;
     for (int k = 0; k < nkeys; ++k) {
         const cdb_key_query& q = keys[k];
         if (q.index) {
-            if (q.index->ix.device != ix.device) throw Error("cdb_query_and_columns: all keys must live on one GPU");
-            if (q.nkw == 0) throw Error("The constraint list cannot be empty");  // interface.cpp:75-77
-            if (!q.offsets) throw Error("cdb_query_and_columns: keyword offsets missing");
-            for (uint64_t j = 0; j < q.nkw; ++j)
-                if (q.offsets[j + 1] <= q.offsets[j]) throw Error("Empty keywords are not allowed");
+            if (q.index->ix.device != ix.device) throw Error(names.one_gpu);
+            check_keywords(KeywordList{q.blob, q.offsets, q.nkw}, names.who, KW_LIST_NOT_EMPTY | KW_OFFSETS | KW_NONE_EMPTY);
         } else if (q.nrows && (!q.ids || !q.counts)) {
-            throw Error("cdb_query_and_columns: row list missing");
+            throw Error(who + ": row list missing");
         }
     }
     for (int j = 0; j < ncols; ++j) {
-        if (cols[j].column->ws.device != ix.device) throw Error("cdb_query_and_columns: all keys must live on one GPU");
+        if (cols[j].column->ws.device != ix.device) throw Error(names.one_gpu);
         if (cols[j].nranges == 0) throw Error("The constraint list cannot be empty");
-        if (!cols[j].offsets) throw Error("cdb_query_and_columns: range offsets missing");
+        if (!cols[j].offsets) throw Error(who + ": range offsets missing");
     }
     // every handle and column involved stays locked until the merge has read its rows (address order: no lock inversion)
     std::vector<std::mutex*> mus;
@@ -817,31 +817,25 @@ void cdb::filter_rows_on_lead(Index& ix, const cdb_key_query* keys, int nkeys, c
     std::vector<Windows> wins(ncols);
     for (int j = 0; j < ncols; ++j) {
         cdb_column* c = cols[j].column;
-        ColumnScope cs(c);
+        DeviceScope cs(c->ws);
         wins[j] = column_windows(c, ranges_of(cols[j].blob, cols[j].offsets, cols[j].nranges));
         c->last_k = wins[j].k;
     }
-    CDB_HIP(hipSetDevice(ix.device));
-    StreamScope lead_scope(ix.stream);
+    DeviceScope lead_scope(ix);
     hipStream_t s = ix.stream;
     std::vector<DeviceRows> lists;
-    std::vector<DevBuf> held;
+    std::vector<DevBuf> held;  // copies of rows that would be overwritten by a later query on the same handle
     uint64_t m_other = UINT64_MAX;
-    for (int k = 0; k < nkeys; ++k) {  // string keys and host rows exactly as cdb_query_and resolves them
+    for (int k = 0; k < nkeys; ++k) {
         const cdb_key_query& q = keys[k];
         DevBuf di, dc;
         uint64_t n = 0;
-        if (q.index) {
+        if (q.index) {  // a string key: the OR of its keywords on its own handle and stream, the rows copied on the lead's
             Index& kx = q.index->ix;
             StreamScope kss(kx.stream);
-            const uint64_t base = q.offsets[0], nbytes = q.offsets[q.nkw] - base;
-            kx.q_pat.ensure(nbytes + 16);
-            kx.q_offs.ensure((q.nkw + 1) * 8);
-            std::vector<uint64_t> rel(q.nkw + 1);
-            for (uint64_t j = 0; j <= q.nkw; ++j) rel[j] = q.offsets[j] - base;
-            CDB_HIP(hipMemcpyAsync(kx.q_pat.p, q.blob + base, nbytes, hipMemcpyHostToDevice, kx.stream));
-            CDB_HIP(hipMemcpyAsync(kx.q_offs.p, rel.data(), (q.nkw + 1) * 8, hipMemcpyHostToDevice, kx.stream));
-            const DeviceCsr r = query_or_on_device(kx, kx.q_pat.as<uint8_t>(), kx.q_offs.as<uint64_t>(), q.nkw);  // (synchronises)
+            const Rebased kw = rebase(KeywordList{q.blob, q.offsets, q.nkw});
+            const DeviceKeywords d = upload_keywords(kx, kw);
+            const DeviceCsr r = query_or_on_device(kx, d.pat, d.offs, q.nkw);  // (synchronises)
             n = r.nrows;
             di.alloc(std::max<uint64_t>(n, 1) * 8);
             dc.alloc(std::max<uint64_t>(n, 1) * 8);
@@ -849,7 +843,7 @@ void cdb::filter_rows_on_lead(Index& ix, const cdb_key_query* keys, int nkeys, c
                 CDB_HIP(hipMemcpyAsync(di.p, kx.q_ids.p, n * 8, hipMemcpyDeviceToDevice, s));
                 CDB_HIP(hipMemcpyAsync(dc.p, kx.q_counts.p, n * 8, hipMemcpyDeviceToDevice, s));
             }
-        } else {
+        } else {  // rows resolved elsewhere (numeric / bool keys: index.cpp:63-74,129-173 return (id, 0) rows)
             n = q.nrows;
             di.alloc(std::max<uint64_t>(n, 1) * 8);
             dc.alloc(std::max<uint64_t>(n, 1) * 8);
@@ -875,7 +869,7 @@ void cdb::filter_rows_on_lead(Index& ix, const cdb_key_query* keys, int nkeys, c
             DevBuf di, dc;
             uint64_t n = 0;
             {
-                ColumnScope cs(c);
+                DeviceScope cs(c->ws);
                 n = column_union(c, wins[j], di);
                 ++c->materialised_keys;
             }
@@ -932,25 +926,10 @@ int cdb_query_and_columns(const cdb_key_query* keys, int nkeys, const cdb_column
     if (!lead) return CDB_E_INVALID;
     Index& ix = *lead;
     return guarded_ix(ix, [&] {
-        filter_rows_on_lead(ix, keys, nkeys, cols, ncols, ranked != 0, corr_lo, corr_hi, limit, [&](hipStream_t s, DeviceCsr r) {
-            int64_t* hi = (int64_t*)host_alloc(r.nrows * 8);
-            int64_t* hc = nullptr;
-            try {
-                hc = (int64_t*)host_alloc(r.nrows * 8);
-                if (r.nrows) {
-                    CDB_HIP(hipMemcpyAsync(hi, ix.q_ids.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-                    CDB_HIP(hipMemcpyAsync(hc, ix.q_counts.p, r.nrows * 8, hipMemcpyDeviceToHost, s));
-                    CDB_HIP(hipStreamSynchronize(s));
-                }
-            } catch (...) {
-                host_free(hi);
-                host_free(hc);
-                throw;
-            }
-            *ids = hi;
-            *counts = hc;
-            *nrows = (size_t)r.nrows;
-        });
+        filter_rows_on_lead(ix, QUERY_AND_COLUMNS_NAMES, keys, nkeys, cols, ncols, ranked != 0, corr_lo, corr_hi, limit,
+                            [&](hipStream_t s, DeviceCsr r) {
+                                download_rows(s, ix.q_ids.as<int64_t>(), ix.q_counts.as<int64_t>(), r.nrows, ids, counts, nrows);
+                            });
     });
 }
 
@@ -1005,16 +984,7 @@ int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value) 
 
 int cdb_debug_column_profile_dump(cdb_column* c, char* buf, size_t cap) {
     if (!c || !buf || cap == 0) return CDB_E_INVALID;
-    std::lock_guard<std::mutex> g(c->ws.mu);
-    std::string s;
-    for (auto& kv : c->ws.prof.recs) {
-        char line[256];
-        std::snprintf(line, sizeof(line), "%s %.6f %llu %llu\n", kv.first.c_str(), kv.second.ms, (unsigned long long)kv.second.launches,
-                      (unsigned long long)kv.second.bytes);
-        s += line;
-    }
-    std::strncpy(buf, s.c_str(), cap - 1);
-    buf[cap - 1] = 0;
+    (void)profile_dump(c->ws, buf, cap);
     return CDB_OK;
 }
 

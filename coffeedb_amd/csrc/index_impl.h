@@ -187,7 +187,7 @@ struct Index {
     int device = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;  // serialises device work of one index (queries from several host threads)
-    // coalescing of concurrent single-keyword queries (capi.hip: cdb_query)
+    // coalescing of concurrent single-keyword queries (capi_query.hip: cdb_query)
     std::mutex qmu;
     std::condition_variable qcv;
     std::vector<void*> qpending;
@@ -445,6 +445,13 @@ struct Index {
     std::string err;
 };
 
+// every entry point that touches the device: the handle's device current (a column's or a row set's handle is its `ws`), and the
+// block cache told which stream this thread issues work on (common.h: blocks released meanwhile are tagged with it)
+struct DeviceScope {
+    StreamScope ss;
+    explicit DeviceScope(Index& ix) : ss(ix.stream) { CDB_HIP(hipSetDevice(ix.device)); }
+};
+
 // capi.hip — ids / doc_start on the host (fetched from the device after a resident build)
 void ensure_host_tables(Index& ix);
 void ensure_host_staging(Index& ix);
@@ -664,7 +671,7 @@ template <typename F> inline auto sa_dispatch(const Index& ix, F&& f) {
 
 }  // namespace cdb
 
-// the object behind the C ABI's opaque handle (capi.hip, shards.hip)
+// the object behind the C ABI's opaque handle (capi.hip, capi_query.hip, shards.hip)
 struct cdb_index {
     cdb::Index ix;
 };
@@ -729,7 +736,6 @@ void rowset_page_device(cdb_rowset* rs, uint64_t first, uint64_t last, DevicePag
 cdb_rowset* rowset_new(int device);
 void rowset_delete(cdb_rowset* rs);
 void rowset_adopt_equal_counts(cdb_rowset* rs, hipStream_t s, int64_t count);
-void rowset_download_rows(hipStream_t s, const int64_t* d_ids, const int64_t* d_counts, uint64_t n, int64_t** ids, int64_t** counts, size_t* nrows);
 // render.hip — cdb_render_rows over ids that already lie in device memory on the handle's GPU (complete when the call is made; the
 // caller keeps them unchanged during it).  Takes the handle's lock and throws.
 void render_index_device_rows(cdb_index* h, const int64_t* d_ids, uint64_t nrows, const char* blob, const uint64_t* offsets, uint64_t nkw,
@@ -751,16 +757,12 @@ void column_publish(cdb_column* c, ColumnArrays& a);
 void column_build(cdb_column* c, const char* who = "cdb_column_build");
 // cdb_column_remove's host path: download, filter on the host, column_build over the rest (built and staged rows alike)
 void column_remove_host(cdb_column* c, const int64_t* ids, uint64_t nids, uint64_t* removed, uint64_t* missing);
-struct ColumnScope {  // the column's stream and device for the calling thread
-    StreamScope ss;
-    explicit ColumnScope(cdb_column* c) : ss(c->ws.stream) { CDB_HIP(hipSetDevice(c->ws.device)); }
-};
 // column_maintain.hip — the device path of a removal (no staged rows) in two halves, as a string index has them (remove_prepare /
 // column_commit above).  Prepare: mark, two stable compactions, one gather of the positions, all into fresh blocks beside the
 // serving arrays; removed / missing are complete when it returns, `changed` says whether there is anything to commit; it throws
 // and leaves the column untouched.  Commit: column_publish plus the stats of a cdb_column_remove; it cannot fail.  A removal that
 // is dropped uncommitted hands its blocks back (release: on the column's device and stream); the column never knew of it.
-// The caller holds the column's lock and, for prepare and commit, a ColumnScope.
+// The caller holds the column's lock and, for prepare and commit, a DeviceScope on c->ws.
 struct ColumnRemoval {
     ColumnArrays a;
     uint64_t removed = 0, missing = 0;
@@ -803,6 +805,10 @@ template <typename F>
 int guarded_ix(Index& ix, F&& f) {
     return guarded_call(ix.err_mu, ix.err, std::forward<F>(f));
 }
+inline void set_error(Index& ix, const std::string& msg) {
+    std::lock_guard<std::mutex> g(ix.err_mu);
+    ix.err = msg;
+}
 // What a *_last_error accessor returns: the text copied under its lock into the accessor's own per-thread string, so that
 // another thread's failing call cannot pull it away under the reader.
 inline const char* last_error_copy(std::mutex& err_mu, const std::string& err, std::string& copy) {
@@ -810,16 +816,25 @@ inline const char* last_error_copy(std::mutex& err_mu, const std::string& err, s
     copy = err;
     return copy.c_str();
 }
-// columns.hip — the body cdb_query_and_columns and cdb_filter (rowset.hip) share: filter_lead names the handle that runs the merge
-// and carries the error (nullptr: CDB_E_INVALID); filter_rows_on_lead validates, locks, resolves and merges the keys and calls
-// `consume` under those locks with the rows in ix.q_ids / q_counts on ix.stream
+// columns.hip — the body cdb_query_and (capi_query.hip: no column keys), cdb_query_and_columns and cdb_filter (rowset.hip) share:
+// filter_lead names the handle that runs the merge and carries the error (nullptr: CDB_E_INVALID); filter_rows_on_lead validates,
+// locks, resolves and merges the keys and calls `consume` under those locks with the rows in ix.q_ids / q_counts on ix.stream.
+// The errors speak in the entry point's name.
+struct FilterNames {
+    const char* who;
+    const char* one_gpu;  // the refusal of keys on several GPUs, whole
+};
+constexpr FilterNames QUERY_AND_NAMES{"cdb_query_and", "cdb_query_and: all string keys must live on one GPU"};
+constexpr FilterNames QUERY_AND_COLUMNS_NAMES{"cdb_query_and_columns", "cdb_query_and_columns: all keys must live on one GPU"};
 Index* filter_lead(const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols);
-void filter_rows_on_lead(Index& ix, const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols, bool ranked,
-                         int64_t corr_lo, int64_t corr_hi, uint64_t limit, const std::function<void(hipStream_t, DeviceCsr)>& consume);
+void filter_rows_on_lead(Index& ix, const FilterNames& names, const cdb_key_query* keys, int nkeys, const cdb_column_key* cols, int ncols,
+                         bool ranked, int64_t corr_lo, int64_t corr_hi, uint64_t limit,
+                         const std::function<void(hipStream_t, DeviceCsr)>& consume);
 // cluster.hip — cdb_cluster / cdb_column_cluster over ids that already lie in device memory on the field's GPU (complete when the
 // call is made; the caller keeps them unchanged during it).  They take the field's lock and throw.
 void cluster_index_device_rows(cdb_index* h, const int64_t* d_ids, uint64_t nrows, bool with_values, cdb_clusters* out);
 void cluster_column_device_rows(cdb_column* c, const int64_t* d_ids, uint64_t nrows, cdb_clusters* out);
+// capi_query.hip — cdb_query_and on `lead`'s device and stream (shards.hip: every key of a sharded AND arrives as a row list)
 int query_and_with_lead(cdb_index* lead, const cdb_key_query* keys, int nkeys, int ranked, int64_t corr_lo, int64_t corr_hi,
                         uint64_t limit, int64_t** ids, int64_t** counts, size_t* nrows);
 }

@@ -19,7 +19,7 @@
 #include <cstring>
 
 #include "../../include/coffeedb_gpu.h"
-#include "index_impl.h"
+#include "host_io.h"
 #include "scan.h"
 
 using namespace cdb;
@@ -274,45 +274,12 @@ __global__ __launch_bounds__(256) void rnd_finish_kernel(const uint64_t* __restr
     }
 }
 
-struct IndexScope {
-    StreamScope ss;
-    explicit IndexScope(Index& ix) : ss(ix.stream) { CDB_HIP(hipSetDevice(ix.device)); }
-};
-
 // the result arrays: host blocks of the result cache, filled from the device
-struct Rendered {
-    cdb_rendered r{};
-    hipStream_t stream;  // (copies into the arrays may still be in flight when an error unwinds)
-    explicit Rendered(hipStream_t s) : stream(s) {}
-    ~Rendered() {
-        if (r.found || r.text_ptr || r.text_blob || r.span_ptr || r.begin || r.end) (void)hipStreamSynchronize(stream);
-        cdb_rendered_free(&r);
-    }
-    template <typename T> static T* fetch(hipStream_t s, const void* d, uint64_t count) {
-        T* h = (T*)host_alloc(count * sizeof(T));
-        if (count) {
-            const hipError_t e = hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, s);
-            if (e != hipSuccess) {
-                host_free(h);
-                CDB_HIP(e);
-            }
-        }
-        return h;
-    }
-    void hand_over(cdb_rendered* out) {
-        *out = r;
-        r = cdb_rendered{};
-    }
-};
+using Rendered = ResultOwner<cdb_rendered, cdb_rendered_free>;
 
-struct Keywords {  // validated on the host: kw j = blob[off[j] .. off[j + 1])
-    const char* blob;
-    const uint64_t* off;
-    uint64_t n;
-};
-
-// the rows as the caller's host ids, or (d_rows != nullptr) as ids that already lie on the handle's device: only the upload differs
-void render_rows(Index& ix, const int64_t* ids, const int64_t* d_rows, uint64_t nrows, const Keywords& kws, const char* left, uint64_t L,
+// the rows as the caller's host ids, or (d_rows != nullptr) as ids that already lie on the handle's device: only the upload differs;
+// the keywords are checked (none is empty)
+void render_rows(Index& ix, const int64_t* ids, const int64_t* d_rows, uint64_t nrows, const KeywordList& kws, const char* left, uint64_t L,
                  const char* right, uint64_t R, int what, Rendered& res) {
     hipStream_t s = ix.stream;
     const double t0 = wall_ms();
@@ -478,16 +445,16 @@ void render_rows(Index& ix, const int64_t* ids, const int64_t* d_rows, uint64_t 
 
     res.r.missing = missing;
     res.r.nspans = nspans;
-    res.r.found = Rendered::fetch<uint8_t>(s, d_found.p, nrows);
+    res.r.found = res.fetch<uint8_t>(d_found.p, nrows);
     if (want_text) {
         res.r.text_bytes = P + nspans * (L + R);
-        res.r.text_ptr = Rendered::fetch<uint64_t>(s, d_tptr.p, nrows + 1);
-        res.r.text_blob = Rendered::fetch<char>(s, d_blob.p, res.r.text_bytes);
+        res.r.text_ptr = res.fetch<uint64_t>(d_tptr.p, nrows + 1);
+        res.r.text_blob = res.fetch<char>(d_blob.p, res.r.text_bytes);
     }
     if (want_spans) {
-        res.r.span_ptr = Rendered::fetch<uint64_t>(s, d_sptr.p, nrows + 1);
-        res.r.begin = Rendered::fetch<uint64_t>(s, d_begin.p, nspans);
-        res.r.end = Rendered::fetch<uint64_t>(s, d_end.p, nspans);
+        res.r.span_ptr = res.fetch<uint64_t>(d_sptr.p, nrows + 1);
+        res.r.begin = res.fetch<uint64_t>(d_begin.p, nspans);
+        res.r.end = res.fetch<uint64_t>(d_end.p, nspans);
     }
     CDB_HIP(hipStreamSynchronize(s));  // (the device blocks go back to the pool behind this scope)
     ix.prof.resolve();
@@ -501,9 +468,9 @@ void render_rows(Index& ix, const int64_t* ids, const int64_t* d_rows, uint64_t 
 void cdb::render_index_device_rows(cdb_index* h, const int64_t* d_ids, uint64_t nrows, const char* blob, const uint64_t* offsets, uint64_t nkw,
                                    const char* left, uint64_t left_len, const char* right, uint64_t right_len, int what, cdb_rendered* out) {
     std::lock_guard<std::mutex> g(h->ix.mu);
-    IndexScope scope(h->ix);
+    DeviceScope scope(h->ix);
     Rendered res(h->ix.stream);
-    render_rows(h->ix, nullptr, d_ids, nrows, Keywords{blob, offsets, nkw}, left, left_len, right, right_len, what, res);
+    render_rows(h->ix, nullptr, d_ids, nrows, KeywordList{blob, offsets, nkw}, left, left_len, right, right_len, what, res);
     res.hand_over(out);
 }
 
@@ -514,13 +481,11 @@ int cdb_render_rows(cdb_index* h, const int64_t* ids, uint64_t nrows, const char
     if (!h || !out || (nrows && !ids) || (nkw && !offsets) || (left_len && !left) || (right_len && !right)) return CDB_E_INVALID;
     *out = cdb_rendered{};
     return guarded_ix(h->ix, [&] {
-        for (uint64_t j = 0; j < nkw; ++j)
-            if (offsets[j + 1] <= offsets[j]) throw Error("Empty keywords are not allowed");  // index.cpp:239-241
-        if (nkw && !blob) throw Error("cdb_render_rows: keywords without bytes");
+        check_keywords(KeywordList{blob, offsets, nkw}, "cdb_render_rows", KW_NONE_EMPTY | KW_BYTES);
         std::lock_guard<std::mutex> g(h->ix.mu);
-        IndexScope scope(h->ix);
+        DeviceScope scope(h->ix);
         Rendered res(h->ix.stream);
-        render_rows(h->ix, ids, nullptr, nrows, Keywords{blob, offsets, nkw}, left, left_len, right, right_len, what, res);
+        render_rows(h->ix, ids, nullptr, nrows, KeywordList{blob, offsets, nkw}, left, left_len, right, right_len, what, res);
         res.hand_over(out);
     });
 }

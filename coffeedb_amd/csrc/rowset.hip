@@ -12,11 +12,11 @@
 // scan.h's U2 over ballot-ranked tiles; stable_tiles.h ranks one flag and synchronises for its total, this take needs two counts
 // and no total); those K pairs are sorted and rows [first, K) go out.  K == m, or option debug_page_path = 2: every row is keyed
 // and sorted (the sort path).  The page is made in two halves — rowset_page_device leaves ids and counts in device buffers,
-// rowset_download_rows fetches them — so that cdb_rowset_select (select.hip) can read the page's fields from the device ids.
+// download_rows (host_io.h) fetches them — so that cdb_rowset_select (select.hip) can read the page's fields from the device ids.
 #include <cstring>
 
 #include "../../include/coffeedb_gpu.h"
-#include "index_impl.h"
+#include "host_io.h"
 #include "scan.h"
 
 using namespace cdb;
@@ -217,11 +217,6 @@ __global__ __launch_bounds__(256) void pg_out_kernel(const uint64_t* __restrict_
     counts[r] = page_count(key[first + r]);
 }
 
-struct SetScope {
-    StreamScope ss;
-    explicit SetScope(cdb_rowset* rs) : ss(rs->ws.stream) { CDB_HIP(hipSetDevice(rs->ws.device)); }
-};
-
 }  // namespace
 
 cdb_rowset* cdb::rowset_new(int device) {
@@ -278,27 +273,6 @@ void cdb::rowset_adopt_equal_counts(cdb_rowset* rs, hipStream_t s, int64_t count
     CDB_HIP(hipMemcpyAsync(rs->state.p, init, sizeof(init), hipMemcpyHostToDevice, s));
     CDB_HIP(hipStreamSynchronize(s));  // (init is read by the copy)
     rs->key_diff = 0;
-}
-
-void cdb::rowset_download_rows(hipStream_t s, const int64_t* d_ids, const int64_t* d_counts, uint64_t n, int64_t** ids, int64_t** counts, size_t* nrows) {
-    int64_t* hi = (int64_t*)host_alloc(n * 8);
-    int64_t* hc = nullptr;
-    try {
-        hc = (int64_t*)host_alloc(n * 8);
-        if (n) {
-            CDB_HIP(hipMemcpyAsync(hi, d_ids, n * 8, hipMemcpyDeviceToHost, s));
-            CDB_HIP(hipMemcpyAsync(hc, d_counts, n * 8, hipMemcpyDeviceToHost, s));
-        }
-        CDB_HIP(hipStreamSynchronize(s));
-    } catch (...) {
-        (void)hipStreamSynchronize(s);
-        host_free(hi);
-        host_free(hc);
-        throw;
-    }
-    *ids = hi;
-    *counts = hc;
-    *nrows = (size_t)n;
 }
 
 namespace {
@@ -387,7 +361,7 @@ void rowset_page(cdb_rowset* rs, uint64_t first, uint64_t last, int64_t** ids, i
     const double t0 = wall_ms();
     DevicePage pg;
     rowset_page_device(rs, first, last, pg);
-    rowset_download_rows(rs->ws.stream, pg.ids.as<int64_t>(), pg.counts.as<int64_t>(), pg.n, ids, counts, nrows);
+    download_rows(rs->ws.stream, pg.ids.as<int64_t>(), pg.counts.as<int64_t>(), pg.n, ids, counts, nrows);
     if (pg.n) rs->ws.prof.resolve();
     rs->page_ms = wall_ms() - t0;
 }
@@ -407,7 +381,7 @@ int cdb_filter(const cdb_key_query* keys, int nkeys, const cdb_column_key* cols,
         cdb_rowset* rs = nullptr;
         try {
             // (the lead's locks are held inside; the row set's own arrays are filled on the lead's stream, which is idle on return)
-            filter_rows_on_lead(ix, keys, nkeys, cols, ncols, false, 0, 0, 0, [&](hipStream_t s, DeviceCsr r) {
+            filter_rows_on_lead(ix, QUERY_AND_COLUMNS_NAMES, keys, nkeys, cols, ncols, false, 0, 0, 0, [&](hipStream_t s, DeviceCsr r) {
                 rs = rowset_new(ix.device);
                 const int64_t* q_ids = ix.q_ids.as<int64_t>();
                 const int64_t* q_counts = ix.q_counts.as<int64_t>();
@@ -456,8 +430,8 @@ int cdb_rowset_rows(cdb_rowset* rs, int64_t** ids, int64_t** counts, size_t* nro
     *nrows = 0;
     return guarded_ix(rs->ws, [&] {
         std::lock_guard<std::mutex> g(rs->ws.mu);
-        SetScope scope(rs);
-        rowset_download_rows(rs->ws.stream, rs->ids.as<int64_t>(), rs->counts.as<int64_t>(), rs->m, ids, counts, nrows);
+        DeviceScope scope(rs->ws);
+        download_rows(rs->ws.stream, rs->ids.as<int64_t>(), rs->counts.as<int64_t>(), rs->m, ids, counts, nrows);
     });
 }
 
@@ -468,7 +442,7 @@ int cdb_rowset_page(cdb_rowset* rs, uint64_t first, uint64_t last, int64_t** ids
     *nrows = 0;
     return guarded_ix(rs->ws, [&] {
         std::lock_guard<std::mutex> g(rs->ws.mu);
-        SetScope scope(rs);
+        DeviceScope scope(rs->ws);
         rowset_page(rs, first, last, ids, counts, nrows);
     });
 }
@@ -528,7 +502,7 @@ int cdb_debug_rowset_from_rows(int device, const int64_t* ids, const int64_t* co
     return guarded_call(err_mu, err, [&] {
         cdb_rowset* rs = rowset_new(device);
         try {
-            SetScope scope(rs);
+            DeviceScope scope(rs->ws);
             hipStream_t s = rs->ws.stream;
             rs->m = n;
             rs->ids.alloc(n * 8);
@@ -562,17 +536,7 @@ int cdb_debug_rowset_set_option(cdb_rowset* rs, const char* name, int64_t value)
 
 int cdb_debug_rowset_profile_dump(cdb_rowset* rs, char* buf, size_t cap) {
     if (!rs || !buf || cap == 0) return CDB_E_INVALID;
-    std::lock_guard<std::mutex> g(rs->ws.mu);
-    std::string s;
-    for (auto& kv : rs->ws.prof.recs) {
-        char line[256];
-        std::snprintf(line, sizeof(line), "%s %.6f %llu %llu\n", kv.first.c_str(), kv.second.ms, (unsigned long long)kv.second.launches,
-                      (unsigned long long)kv.second.bytes);
-        s += line;
-    }
-    std::strncpy(buf, s.c_str(), cap - 1);
-    buf[cap - 1] = 0;
-    return s.size() < cap ? CDB_OK : CDB_E_INVALID;  // (a table cut short is an error, not a shorter table)
+    return profile_dump(rs->ws, buf, cap) ? CDB_OK : CDB_E_INVALID;  // (a table cut short is an error, not a shorter table)
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "../../include/coffeedb_gpu.h"
-#include "index_impl.h"
+#include "host_io.h"
 #include "scan.h"
 #include "stable_tiles.h"
 
@@ -62,8 +62,7 @@ struct IdList {
 // the ascending ids a field holds (empty: never built, or built over nothing); the field's lock is held, its stream idle on return
 IdList index_id_list(Index& ix) {
     if (!ix.width || !ix.ndocs) return IdList{nullptr, 0};
-    CDB_HIP(hipSetDevice(ix.device));
-    StreamScope ss(ix.stream);
+    DeviceScope scope(ix);
     id_table_prepare(ix);  // (synchronises where it makes the table)
     return IdList{ix.idt.ids_ascend ? ix.d_ids.as<int64_t>() : ix.idt.id_sorted.as<int64_t>(), ix.ndocs};
 }
@@ -76,11 +75,6 @@ struct FieldLocks {
         mus.erase(std::unique(mus.begin(), mus.end()), mus.end());
         for (std::mutex* m : mus) locks.emplace_back(*m);
     }
-};
-
-struct SetScope {
-    StreamScope ss;
-    explicit SetScope(cdb_rowset* rs) : ss(rs->ws.stream) { CDB_HIP(hipSetDevice(rs->ws.device)); }
 };
 
 // the device half of cdb_rowset_all on the set's stream; synchronises
@@ -143,7 +137,7 @@ void rowset_all(cdb_rowset* rs, cdb_index* const* indexes, int nindexes, cdb_col
         N += l.n;
         nonempty += l.n ? 1 : 0;
     }
-    SetScope scope(rs);
+    DeviceScope scope(rs->ws);
     Index& ws = rs->ws;
     hipStream_t s = ws.stream;
     Profiler& prof = ws.prof;
@@ -193,7 +187,7 @@ void rowset_remove(cdb_rowset* rs, cdb_remove_field* fields, int nfields, uint64
             if (f.index) {
                 work[k].index_change = remove_prepare(f.index->ix, ids, m, &f.removed, &f.missing);
             } else {
-                ColumnScope cs(f.column);
+                DeviceScope cs(f.column->ws);
                 work[k].column_change.t0 = wall_ms();
                 column_remove_prepare(f.column, ids, m, work[k].column_change);
                 f.removed = work[k].column_change.removed;
@@ -225,7 +219,7 @@ void rowset_remove(cdb_rowset* rs, cdb_remove_field* fields, int nfields, uint64
                 column_commit(f.index->ix, *work[k].index_change);
                 work[k].index_change.reset();
             } else if (work[k].column_change.changed) {
-                ColumnScope cs(f.column);
+                DeviceScope cs(f.column->ws);
                 f.committed = 1;
                 column_remove_commit(f.column, work[k].column_change);
             }

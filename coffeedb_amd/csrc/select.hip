@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/coffeedb_gpu.h"
-#include "index_impl.h"
+#include "host_io.h"
 
 using namespace cdb;
 
@@ -94,25 +94,8 @@ uint8_t* select_values(hipStream_t s, Profiler& prof, const int64_t* d_ids, cons
 
 constexpr unsigned SEL_MAX_COLUMNS = 65535;  // gridDim.y
 
-struct SetScope {
-    StreamScope ss;
-    explicit SetScope(cdb_rowset* rs) : ss(rs->ws.stream) { CDB_HIP(hipSetDevice(rs->ws.device)); }
-};
-
-// the result while it is made: copies into its arrays may still be in flight when an error unwinds
-struct Selected {
-    cdb_selected r{};
-    hipStream_t stream;
-    explicit Selected(hipStream_t s) : stream(s) {}
-    ~Selected() {
-        if (r.ids || r.fields) (void)hipStreamSynchronize(stream);
-        cdb_selected_free(&r);
-    }
-    void hand_over(cdb_selected* out) {
-        *out = r;
-        r = cdb_selected{};
-    }
-};
+// the result while it is made (every piece of it arrives behind a synchronise of its own: download_rows, select_values, the renders)
+using Selected = ResultOwner<cdb_selected, cdb_selected_free>;
 
 bool field_is_valid(const cdb_select_field& f) {
     if ((f.index != nullptr) + (f.shards != nullptr) + (f.column != nullptr) != 1) return false;
@@ -129,7 +112,7 @@ void rowset_select(cdb_rowset* rs, uint64_t first, uint64_t last, const cdb_sele
     DevicePage pg;
     rowset_page_device(rs, first, last, pg);
     size_t n = 0;
-    rowset_download_rows(s, pg.ids.as<int64_t>(), pg.counts.as<int64_t>(), pg.n, &res.r.ids, &res.r.counts, &n);
+    download_rows(s, pg.ids.as<int64_t>(), pg.counts.as<int64_t>(), pg.n, &res.r.ids, &res.r.counts, &n);
     rs->page_ms = wall_ms() - t0;
     res.r.nrows = n;
     res.r.nfields = nfields;
@@ -192,7 +175,7 @@ int cdb_column_values(cdb_column* c, const int64_t* ids, uint64_t nrows, uint64_
     if (missing) *missing = 0;
     return guarded_ix(c->ws, [&] {
         std::lock_guard<std::mutex> g(c->ws.mu);
-        ColumnScope scope(c);
+        DeviceScope scope(c->ws);
         if (nrows == 0) return;
         hipStream_t s = c->ws.stream;
         DevBuf d_ids;
@@ -220,9 +203,7 @@ int cdb_rowset_select(cdb_rowset* rs, uint64_t first, uint64_t last, const cdb_s
         size_t ncols = 0;
         for (int k = 0; k < nfields; ++k) {
             const cdb_select_field& q = fields[k];
-            for (uint64_t j = 0; j < q.nkw; ++j)
-                if (q.kw_offsets[j + 1] <= q.kw_offsets[j]) throw Error("Empty keywords are not allowed");  // index.cpp:239-241
-            if (q.nkw && !q.kw_blob) throw Error("cdb_rowset_select: keywords without bytes");
+            check_keywords(KeywordList{q.kw_blob, q.kw_offsets, q.nkw}, "cdb_rowset_select", KW_NONE_EMPTY | KW_BYTES);
             ncols += q.column != nullptr;
         }
         if (ncols > SEL_MAX_COLUMNS) throw Error("cdb_rowset_select: more than 65535 column fields");
@@ -232,7 +213,7 @@ int cdb_rowset_select(cdb_rowset* rs, uint64_t first, uint64_t last, const cdb_s
             if ((q.index && q.index->ix.device != rs->ws.device) || (q.column && q.column->ws.device != rs->ws.device))
                 throw Error("cdb_rowset_select: a field lives on another GPU");
         }
-        SetScope scope(rs);
+        DeviceScope scope(rs->ws);
         Selected res(rs->ws.stream);
         rowset_select(rs, first, last, fields, nfields, left, left_len, right, right_len, res);
         res.hand_over(out);

@@ -19,7 +19,7 @@
 
 #include "../../include/coffeedb_gpu.h"
 #include "cluster_merge.h"
-#include "index_impl.h"
+#include "host_io.h"
 #include "shard_merge.h"
 #include "shard_plan.h"
 
@@ -513,8 +513,7 @@ int cdb_shards_query(cdb_shards* h, const char* keyword, size_t len, int64_t** i
                 for (int i = 0; i < G; ++i) {
                     Index& ix = shard[i]->ix;
                     locks.emplace_back(ix.mu);
-                    CDB_HIP(hipSetDevice(ix.device));
-                    StreamScope ss(ix.stream);
+                    DeviceScope scope(ix);
                     part[i].state = query_single_launch(ix, keyword, len);
                     in_flight[i] = part[i].state == SingleLaunch::Launched;
                 }
@@ -522,8 +521,7 @@ int cdb_shards_query(cdb_shards* h, const char* keyword, size_t len, int64_t** i
                     Index& ix = shard[i]->ix;
                     if (part[i].state == SingleLaunch::Absent) query_single_empty(ix, &part[i].ids, &part[i].counts, &part[i].n);
                     else if (part[i].state == SingleLaunch::Launched) {
-                        CDB_HIP(hipSetDevice(ix.device));
-                        StreamScope ss(ix.stream);
+                        DeviceScope scope(ix);
                         in_flight[i] = 0;  // (collect waits for the answer or throws after the stream was synchronised)
                         if (!query_single_collect(ix, &part[i].ids, &part[i].counts, &part[i].n)) part[i].state = SingleLaunch::NotApplicable;
                     }
@@ -624,10 +622,7 @@ int cdb_shards_query_and(const cdb_shards_key_query* keys, int nkeys, int ranked
             const cdb_shards_key_query& q = keys[k];
             std::memset(&flat[k], 0, sizeof(cdb_key_query));
             if (q.shards) {
-                if (q.nkw == 0) throw Error("The constraint list cannot be empty");  // interface.cpp:75-77
-                if (!q.offsets) throw Error("cdb_shards_query_and: keyword offsets missing");
-                for (uint64_t j = 0; j < q.nkw; ++j)
-                    if (q.offsets[j + 1] <= q.offsets[j]) throw Error("Empty keywords are not allowed");
+                check_keywords(KeywordList{q.blob, q.offsets, q.nkw}, "cdb_shards_query_and", KW_LIST_NOT_EMPTY | KW_OFFSETS | KW_NONE_EMPTY);
                 std::vector<std::pair<int64_t, int64_t>> rows;
                 shards_or_rows(q.shards, q.blob, q.offsets, q.nkw, false, 0, 0, 0, rows);
                 hi[k].reserve(rows.size());
@@ -814,9 +809,7 @@ void shards_batch_host(cdb_shards* h, int G, const char* blob, const uint64_t* o
 // every shard ends up holding the merged CSR, shard 0 hands it to the host)
 void shards_batch_device(cdb_shards* h, int G, const char* blob, const uint64_t* offsets, uint64_t npat, cdb_result* out) {
     const std::vector<cdb_index*>& shard = h->gen.shard;
-    const uint64_t base = npat ? offsets[0] : 0, nbytes = npat ? offsets[npat] - base : 0;
-    std::vector<uint64_t> rel(npat + 1);
-    for (uint64_t j = 0; j <= npat; ++j) rel[j] = npat ? offsets[j] - base : 0;
+    const Rebased kw = rebase(KeywordList{blob, offsets, npat});  // (once: every shard uploads the same list)
     std::vector<cdb_device_result> local(G), merged(G);
     // every shard stays locked from its query to the end of the merge (the merge reads the shard's result
     // buffers, which a concurrent query on that shard would overwrite); ascending shard order
@@ -824,14 +817,9 @@ void shards_batch_device(cdb_shards* h, int G, const char* blob, const uint64_t*
     for (int i = 0; i < G; ++i) locks.emplace_back(shard[i]->ix.mu);
     parallel_shards(G, [&](int i) {
         Index& ix = shard[i]->ix;
-        CDB_HIP(hipSetDevice(ix.device));
-        StreamScope ss(ix.stream);
-        hipStream_t s = ix.stream;
-        ix.q_pat.ensure(nbytes + 16);
-        ix.q_offs.ensure((npat + 1) * 8);
-        if (nbytes) CDB_HIP(hipMemcpyAsync(ix.q_pat.p, blob + base, nbytes, hipMemcpyHostToDevice, s));
-        CDB_HIP(hipMemcpyAsync(ix.q_offs.p, rel.data(), (npat + 1) * 8, hipMemcpyHostToDevice, s));
-        const DeviceCsr r = query_batch_on_device(ix, ix.q_pat.as<uint8_t>(), ix.q_offs.as<uint64_t>(), npat);
+        DeviceScope scope(ix);
+        const DeviceKeywords d = upload_keywords(ix, kw);
+        const DeviceCsr r = query_batch_on_device(ix, d.pat, d.offs, npat);
         local[i] = cdb_device_result{npat, r.nrows, r.nhits, ix.q_rowptr.as<uint64_t>(), ix.q_ids.as<int64_t>(), ix.q_counts.as<int64_t>()};
     });
     uint64_t hits = 0;
@@ -840,20 +828,16 @@ void shards_batch_device(cdb_shards* h, int G, const char* blob, const uint64_t*
     parallel_shards(G, [&](int i) { merge_core(*h->gen.ranks[i], local[i], merged[i]); });
     Index& ix0 = shard[0]->ix;
     CDB_HIP(hipSetDevice(ix0.device));
-    hipStream_t s = ix0.stream;
     const cdb_device_result& m = merged[0];
-    out->npat = npat;
-    out->nrows = m.nrows;
-    out->nhits = hits;
-    out->row_ptr = (uint64_t*)host_alloc((npat + 1) * 8);
-    out->ids = (int64_t*)host_alloc(m.nrows * 8);
-    out->counts = (int64_t*)host_alloc(m.nrows * 8);
-    CDB_HIP(hipMemcpyAsync(out->row_ptr, m.d_row_ptr, (npat + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (m.nrows) {
-        CDB_HIP(hipMemcpyAsync(out->ids, m.d_ids, m.nrows * 8, hipMemcpyDeviceToHost, s));
-        CDB_HIP(hipMemcpyAsync(out->counts, m.d_counts, m.nrows * 8, hipMemcpyDeviceToHost, s));
-    }
-    CDB_HIP(hipStreamSynchronize(s));
+    ResultOwner<cdb_result, cdb_result_free> res(ix0.stream);
+    res.r.npat = npat;
+    res.r.nrows = m.nrows;
+    res.r.nhits = hits;
+    res.r.row_ptr = res.fetch<uint64_t>(m.d_row_ptr, npat + 1);
+    res.r.ids = res.fetch<int64_t>(m.d_ids, m.nrows);
+    res.r.counts = res.fetch<int64_t>(m.d_counts, m.nrows);
+    CDB_HIP(hipStreamSynchronize(ix0.stream));
+    res.hand_over(out);
 }
 
 int shards_batch_impl(cdb_shards* h, const char* blob, const uint64_t* offsets, uint64_t npat, cdb_result* out, cdb_hits* hits) {
@@ -861,8 +845,7 @@ int shards_batch_impl(cdb_shards* h, const char* blob, const uint64_t* offsets, 
     std::memset(out, 0, sizeof(*out));
     if (hits) std::memset(hits, 0, sizeof(*hits));
     const int rc = guarded_on(h, [&] {
-        for (uint64_t j = 0; j < npat; ++j)
-            if (offsets[j + 1] <= offsets[j]) throw Error("Empty keywords are not allowed");  // index.cpp:239-241
+        check_keywords(KeywordList{blob, offsets, npat}, "cdb_shards_query_batch", KW_NONE_EMPTY);
         std::shared_lock<StateLock> st(h->state);
         const int G = std::max(h->gen.used, 1);
         if (G == 1) {
