@@ -339,7 +339,7 @@ struct Index {
     int self_check_fallbacks = 0;
     bool debug_fail_self_check = false;  // test hook: the first spot check of a build reports a failure
     // ---- proof after publish (self_check = 3).  The reference's array is sorted by construction (std::sort leaves, index.cpp:86-95);
-    // here the order rests on an observed LDS lane order (radix_sort.h:12-15) and a sample proves nothing about one stray pair.  So
+    // here the order rests on an observed LDS lane order (radix_pass.h: hardware mapping, RsCfg::ATOMRANK) and a sample proves nothing about one stray pair.  So
     // the build publishes as before and a helper thread then compares EVERY adjacent pair against the text on a low-priority stream
     // of its own, slice by slice, beside the queries (it reads arrays that nothing changes until proof_stop).  Damage found: the
     // thread takes ix.mu (queries wait: a wrong array is not served while it is being replaced), switches the device to the ballot

@@ -1,7 +1,7 @@
 """Verify after publish (option self_check = 3, the default): the order proof behind every build.
 
 The reference's suffix array is sorted by construction (std::sort leaves, index.cpp:86-95).  This library's radix passes rest on
-an observed LDS lane order (radix_sort.h:12-15), and the sample behind a build proves nothing about one stray pair — so after
+an observed LDS lane order (radix_pass.h: hardware mapping, RsCfg::ATOMRANK), and the sample behind a build proves nothing about one stray pair — so after
 cdb_build* / cdb_load return, a helper thread compares EVERY adjacent pair of the published array against the text, beside the
 queries; damage makes the handle rebuild itself under its lock.  Checked here with the oracle as the referee."""
 import threading

@@ -1,6 +1,6 @@
 // gen_bench.hip — the C1 initial sort (radix_sort_msd: generated pass on the top digit + 4 segmented passes) outside the
 // library, on 2^lg bytes of printable ASCII in 1024-byte documents: the generated pass can be timed and ablated in seconds
-// (-DRS_GEN_ABL=bits, see radix_sort.h) without building the library.
+// (-DRS_GEN_ABL=bits, see radix_pass.h) without building the library.
 // build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../coffeedb_amd/csrc gen_bench.hip -o gen_bench [-DRS_GEN_ABL=n]
 // run:   ./gen_bench [log2 n = 30] [rounds = 3] [pair form = 1]
 #include "radix_sort.h"
@@ -278,7 +278,7 @@ int main(int argc, char** argv) {
         std::printf("generated pass alone, counted tile bases (no look-back), %d threads x 16: %.3f ms   check: wrong bucket %llu, wrong key %llu, out of text order %llu\n",
                     GEN_NT, bms, out[0], out[1], out[2]);
     }
-    if (RS_GEN_ABL != 0 || GEN_NT != 1024) return 0;  // (GEN_NT=512 needs BLK in radix_sort.h relaxed to NT == 512: an experiment)
+    if (RS_GEN_ABL != 0 || GEN_NT != 1024) return 0;  // (GEN_NT=512 needs RsTraits::BLK in radix_pass.h relaxed to NT == 512: an experiment)
     for (int r = 0; r <= rounds; ++r) {
         prof.reset();
         SortStats st;
