@@ -41,6 +41,7 @@ EXPORTS = [
     "cdb_debug_rowset_profile_dump",
     "cdb_column_values", "cdb_rowset_select", "cdb_selected_free",
     "cdb_rowset_remove", "cdb_rowset_all",
+    "cdb_insert_objects", "cdb_insert_get_stat",
     "cdb_debug_scan", "cdb_debug_scan_partials", "cdb_debug_stable_ranks",
     "cdb_debug_sweep_records", "cdb_debug_vl_tables",
     "cdb_debug_carried_inplace", "cdb_debug_segsort",
@@ -112,6 +113,12 @@ class CdbSelected(C.Structure):
 class CdbRemoveField(C.Structure):
     _fields_ = [("index", C.c_void_p), ("column", C.c_void_p), ("removed", C.c_uint64), ("missing", C.c_uint64),
                 ("status", C.c_int32), ("committed", C.c_int32)]
+
+
+class CdbInsertField(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("column", C.c_void_p), ("rows", C.c_void_p), ("nrows", C.c_uint64), ("blob", C.c_void_p),
+                ("doc_start", C.c_void_p), ("values", C.c_void_p), ("appended", C.c_uint64), ("status", C.c_int32),
+                ("committed", C.c_int32)]
 
 
 SELECT_STRING = 3   # cdb_selected_field.kind of a string field (the reference's tag)
@@ -305,6 +312,8 @@ def load_library():
     lib.cdb_column_values.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
     lib.cdb_rowset_remove.argtypes = [vp, C.POINTER(CdbRemoveField), C.c_int, C.POINTER(u64)]
     lib.cdb_rowset_all.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.POINTER(vp)]
+    lib.cdb_insert_objects.argtypes = [vp, u64, C.POINTER(CdbInsertField), C.c_int, C.POINTER(u64)]
+    lib.cdb_insert_get_stat.argtypes = [vp, vp, cp, C.POINTER(C.c_double)]
     lib.cdb_rowset_select.argtypes = [vp, u64, u64, C.POINTER(CdbSelectField), C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(CdbSelected)]
     lib.cdb_selected_free.argtypes = [C.POINTER(CdbSelected)]
     lib.cdb_selected_free.restype = None
@@ -1009,7 +1018,7 @@ class GpuColumn:
 
     def set_option(self, name, value):
         """Test / measurement hook (cdb_debug_column_set_option): "profile", "debug_query_path", "debug_cluster_path",
-        "debug_maintain_path", "debug_fail_prepare"."""
+        "debug_maintain_path", "debug_fail_prepare", "debug_fail_append_prepare"."""
         self._check(self._lib.cdb_debug_column_set_option(self._h, name.encode(), int(value)))
 
     def profile(self):
@@ -1406,6 +1415,81 @@ def rowset_all(fields):
         err = lib.cdb_last_error if idx else lib.cdb_column_last_error
         raise RuntimeError(err(lead._h).decode(errors="replace"))
     return GpuRowSet(h)
+
+
+class InsertObjectsError(RuntimeError):
+    """insert_objects failed: `.code` is the library's return code, `.fields` the per-field results."""
+    code, fields = 0, ()
+
+
+def insert_objects(ids, fields):
+    """cdb_insert_objects: the objects `ids` join every field of `fields`, all or none.  A field is a tuple (handle, rows, payload):
+    handle a GpuStringIndex or a GpuColumn; rows the strictly ascending indices into `ids` of the objects that hold the field, or
+    None for every object; payload (blob, doc_start) for a string field — as GpuStringIndex.append takes them — and the values for a
+    column.  Returns (inserted, per-field dicts "appended", "status", "committed" in the caller's order).  A failure raises
+    InsertObjectsError, a RuntimeError with the first field's error text that carries the return code as `.code` and the per-field
+    dicts as `.fields`."""
+    lib = load_library()
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    packed = (CdbInsertField * max(len(fields), 1))()
+    keep = []   # the arrays the packed pointers refer to
+    for k, (f, rows, payload) in enumerate(fields):
+        q = packed[k]
+        if rows is None:
+            q.nrows = len(ids)
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.uint64)
+            q.nrows = len(rows)
+            if not len(rows):
+                rows = np.zeros(1, dtype=np.uint64)   # (no row: the C ABI still wants a pointer, NULL means every object)
+            keep.append(rows)
+            q.rows = _ptr(rows)
+        n = int(q.nrows)
+        if isinstance(f, GpuColumn):
+            q.column = f._h
+            vals = f._values(payload if payload is not None else [])
+            if len(vals) != n:
+                raise ValueError(f"insert_objects: field {k}: {len(vals)} values for {n} rows")
+            keep.append(vals)
+            q.values = _ptr(vals) if n else None
+        elif isinstance(f, GpuStringIndex):
+            q.index = f._h
+            blob, doc_start = payload if payload is not None else (np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.uint64))
+            blob = np.ascontiguousarray(blob, dtype=np.uint8)
+            doc_start = np.ascontiguousarray(doc_start, dtype=np.uint64)
+            if len(doc_start) != n + 1:
+                raise ValueError(f"insert_objects: field {k}: doc_start holds {len(doc_start)} entries for {n} rows")
+            if int(doc_start[-1]) > len(blob):   # (the C ABI takes plain pointers: a short blob would be read past its end)
+                raise ValueError(f"insert_objects: field {k}: blob holds {len(blob)} bytes, doc_start[-1] = {int(doc_start[-1])}")
+            if not len(blob):
+                blob = np.zeros(1, dtype=np.uint8)   # (empty documents only: the C ABI still wants a pointer)
+            keep += [blob, doc_start]
+            q.blob, q.doc_start = _ptr(blob), _ptr(doc_start)
+        else:
+            raise TypeError(f"insert_objects: field {k}: {type(f).__name__} is neither a GpuStringIndex nor a GpuColumn")
+    inserted = C.c_uint64(0)
+    rc_ = lib.cdb_insert_objects(_ptr(ids) if len(ids) else None, len(ids), packed, len(fields), C.byref(inserted))
+    out = [{"appended": int(q.appended), "status": int(q.status), "committed": int(q.committed)} for q in packed[:len(fields)]]
+    if rc_ != 0:
+        lead = fields[0][0] if fields else None
+        if lead is None:
+            raise RuntimeError(f"cdb_insert_objects failed (code {rc_}): no field given")
+        err = lib.cdb_last_error if isinstance(lead, GpuStringIndex) else lib.cdb_column_last_error
+        e = InsertObjectsError(err(lead._h).decode(errors="replace"))
+        e.code, e.fields = rc_, out
+        raise e
+    return int(inserted.value), out
+
+
+def insert_stat(lead, name):
+    """cdb_insert_get_stat on the handle that led insert_objects calls (their first field): "inserts", "insert_fields",
+    "insert_objects", "insert_ms"."""
+    lib = load_library()
+    v = C.c_double(0)
+    col = isinstance(lead, GpuColumn)
+    if lib.cdb_insert_get_stat(None if col else lead._h, lead._h if col else None, name.encode(), C.byref(v)) != 0:
+        raise KeyError(name)
+    return v.value
 
 
 def filter_rows(keys, corr=None):

@@ -1146,7 +1146,8 @@ ColumnChangePtr append_prepare(Index& ix, const int64_t* ids, const char* blob, 
     c->docs = ndocs;
     c->bytes = m;
     if (!built_docs) {  // never built, or built over nothing: a build of the given documents
-        build_view_prepare(ix, ids, blob, doc_start, ndocs, c->col);
+        build_view_prepare(ix, ids, blob, doc_start, ndocs, c->col);  // (synchronises)
+        if (ix.debug_fail_append_prepare) throw DeviceError("debug: append prepare failure requested (test hook)");
         return c;
     }
     const uint64_t n = ix.size, D = ix.ndocs;
@@ -1180,6 +1181,7 @@ ColumnChangePtr append_prepare(Index& ix, const int64_t* ids, const char* blob, 
         const bool valid = n > 0 && ix.sa_sorted && (!ix.reference_compat || !p.high_bytes);
         c->kept_array = valid && ix.debug_append_path != 2;
         if (c->kept_array) append_merge(ix, p, (int)L.bits, L.mask, L.width, layout_packable(ix, L));
+        if (ix.debug_fail_append_prepare) throw DeviceError("debug: append prepare failure requested (test hook)");
         adopt_blocks(ix, col, p);
     });
     return c;
@@ -1314,6 +1316,7 @@ int cdb_set_option(cdb_index* h, const char* name, int64_t value) {
     else if (!std::strcmp(name, "force_big_path")) ix.force_big_path = value != 0;
     else if (!std::strcmp(name, "debug_fail_build")) ix.debug_fail_build = value != 0;
     else if (!std::strcmp(name, "debug_fail_prepare")) ix.debug_fail_prepare = value != 0;
+    else if (!std::strcmp(name, "debug_fail_append_prepare")) ix.debug_fail_append_prepare = value != 0;
     else if (!std::strcmp(name, "debug_append_path")) ix.debug_append_path = value == 1 || value == 2 ? (int)value : 0;  // cdb_append: 0 automatic, 1 merge where valid, 2 rebuild
     else if (!std::strcmp(name, "debug_no_segcap")) ix.debug_no_segcap = value != 0;  // test hook: "a bucket does not fit the record memory"
     else if (!std::strcmp(name, "debug_starve_group")) ix.debug_starve_group = (int)value;  // 1 = reported after the sorts, 2 = error flag up before the initial sort

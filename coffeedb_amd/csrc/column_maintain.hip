@@ -15,6 +15,7 @@
 // Everything is written into fresh blocks while the old arrays stand and published at the end as column_build publishes.  A removal
 // does so in two halves (index_impl.h: column_remove_prepare / column_remove_commit): cdb_column_remove runs them back to back,
 // cdb_rowset_remove (rowset_maintain.hip) prepares every field of a call, from the row set's device ids, before it commits any.
+// An append has the same halves (column_append_prepare / column_append_commit) for cdb_insert_objects (insert.hip).
 #include <algorithm>
 #include <cstring>
 
@@ -194,8 +195,8 @@ __global__ __launch_bounds__(256) void col_ap_id_concat_kernel(const int64_t* __
     }
 }
 
-// the merge of cdb_column_append: n = c->n > 0 old rows, m > 0 new ones (ids, raw values on the host)
-void column_append_device(cdb_column* c, const int64_t* ids, const std::vector<uint64_t>& raw, uint64_t m) {
+// the merge of cdb_column_append: n = c->n > 0 old rows, m > 0 new ones (ids, raw values on the host), left in r.a
+void column_append_merge(cdb_column* c, const int64_t* ids, const std::vector<uint64_t>& raw, uint64_t m, ColumnAppendChange& r) {
     Index& ws = c->ws;
     hipStream_t s = ws.stream;
     Profiler& prof = ws.prof;
@@ -287,15 +288,66 @@ void column_append_device(cdb_column* c, const int64_t* ids, const std::vector<u
         prof.end(t, "col_ap_id", N * 29 + ntiles * 8, s);
     }
     CDB_HIP(hipGetLastError());
+    if (ws.debug_fail_append_prepare) {  // (the new blocks go back with the stream drained; the serving arrays were only read)
+        (void)hipStreamSynchronize(s);
+        throw DeviceError("debug: append prepare failure requested (test hook)");
+    }
     CDB_HIP(hipStreamSynchronize(s));
     prof.resolve();
     a.n = N;
     a.n_false = c->n_false + b.n_false;
-    column_publish(c, a);
-    if (concat) ++c->append_id_concat;
+    r.a = std::move(a);
+    r.concat = concat;
+}
+
+// the build of cdb_column_append: the old rows in their key order (none: a column without rows), then the batch, sorted as
+// column_build sorts built and staged rows — without staging the batch on the handle
+void column_append_build(cdb_column* c, const int64_t* ids, const std::vector<uint64_t>& raw, uint64_t m, ColumnAppendChange& r) {
+    hipStream_t s = c->ws.stream;
+    r.build_t0 = wall_ms();
+    const uint64_t n_old = c->n, n = n_old + m;
+    DevBuf idk0, key0;
+    idk0.alloc(n * 8);
+    key0.alloc(n * 8);
+    if (n_old) {
+        CDB_HIP(hipMemcpyAsync(idk0.p, c->ids_v.p, n_old * 8, hipMemcpyDeviceToDevice, s));
+        CDB_HIP(hipMemcpyAsync(key0.p, c->keys_v.p, n_old * 8, hipMemcpyDeviceToDevice, s));
+    }
+    CDB_HIP(hipMemcpyAsync(idk0.as<uint64_t>() + n_old, ids, m * 8, hipMemcpyHostToDevice, s));
+    CDB_HIP(hipMemcpyAsync(key0.as<uint64_t>() + n_old, raw.data(), m * 8, hipMemcpyHostToDevice, s));
+    column_sort_rows(c, idk0, key0, n, n_old, "cdb_column_append", r.a);  // (synchronises)
+    if (c->ws.debug_fail_append_prepare) {
+        r.a = ColumnArrays{};
+        throw DeviceError("debug: append prepare failure requested (test hook)");
+    }
 }
 
 }  // namespace
+
+void cdb::column_append_prepare(cdb_column* c, const int64_t* ids, const std::vector<uint64_t>& raw, uint64_t m, ColumnAppendChange& r) {
+    r.rows = m;
+    r.concat = false;
+    try {
+        if (r.merge) column_append_merge(c, ids, raw, m, r);
+        else column_append_build(c, ids, raw, m, r);
+    } catch (...) {  // (uploads from ids / raw may still be queued: the caller's arrays are read until the stream is idle)
+        (void)hipStreamSynchronize(c->ws.stream);
+        throw;
+    }
+    r.changed = true;
+}
+
+void cdb::column_append_commit(cdb_column* c, ColumnAppendChange& r) {
+    if (!r.merge) c->id_sort_skipped = r.a.id_sort_skipped;
+    column_publish(c, r.a);
+    r.changed = false;
+    if (r.merge && r.concat) ++c->append_id_concat;
+    if (!r.merge) c->build_ms = wall_ms() - r.build_t0;
+    ++c->appends;
+    ++(r.merge ? c->append_merges : c->append_rebuilds);
+    c->append_rows = r.rows;
+    c->append_ms = wall_ms() - r.t0;
+}
 
 void cdb::column_remove_prepare(cdb_column* c, RowIds ids, uint64_t nids, ColumnRemoval& r) {
     Index& ws = c->ws;
@@ -393,26 +445,13 @@ int cdb_column_append(cdb_column* c, const int64_t* ids, const void* values, uin
         if (!n) return;
         if (!c->staged_ids.empty()) throw Error("append: rows were added since the last build");
         if (c->n + n > COLUMN_MAX_ROWS) throw Error("cdb_column_append: a column holds at most 2^32 - 1 rows");
-        const double t0 = wall_ms();
-        // a column without rows takes the build of the batch; so does debug_maintain_path = 2 (stage + column_build)
-        const bool merge = c->n > 0 && c->debug_maintain_path != 2;
-        if (merge) {
-            column_append_device(c, ids, raw, n);
-        } else {
-            c->staged_ids.assign(ids, ids + n);
-            c->staged_raw = raw;
-            try {
-                column_build(c, "cdb_column_append");
-            } catch (...) {
-                c->staged_ids.clear();
-                c->staged_raw.clear();
-                throw;
-            }
-        }
-        ++c->appends;
-        ++(merge ? c->append_merges : c->append_rebuilds);
-        c->append_rows = n;
-        c->append_ms = wall_ms() - t0;
+        // a column without rows takes the build of the batch; so does debug_maintain_path = 2 (the build over old rows and batch).
+        // The two halves back to back (cdb_insert_objects prepares every field before it commits any)
+        ColumnAppendChange r;
+        r.t0 = wall_ms();
+        r.merge = c->n > 0 && c->debug_maintain_path != 2;
+        column_append_prepare(c, ids, raw, n, r);
+        column_append_commit(c, r);
         if (appended) *appended = n;
     });
 }

@@ -979,6 +979,10 @@ int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value) 
         c->ws.debug_fail_prepare = value != 0;
         return CDB_OK;
     }
+    if (!std::strcmp(name, "debug_fail_append_prepare")) {
+        c->ws.debug_fail_append_prepare = value != 0;
+        return CDB_OK;
+    }
     return CDB_E_INVALID;
 }
 

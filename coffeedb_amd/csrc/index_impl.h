@@ -1,5 +1,6 @@
 // index_impl.h — state of one GPU string index (the object behind the opaque cdb_index handle).
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -375,6 +376,7 @@ struct Index {
     int debug_starve_group = 0;     // test hook: a build in XCD-aware tile order reports a look-back timeout once
     bool debug_fail_build = false;  // test hook: the build throws after its sorts (exercises the failure paths)
     bool debug_fail_prepare = false;  // test hook: the prepare half of a removal throws behind its device work (index and column alike)
+    bool debug_fail_append_prepare = false;  // test hook: ... of an append (append_prepare, column_append_prepare)
     bool force_big_path = false;  // test hook: use the >= 2^32 code path (u64 ranks, bucket-wise sort) at any size
     bool fuse_keygen = true;  // first radix pass computes keys from the text (no key/entry materialisation)
     int digit_bits = 0;
@@ -436,6 +438,12 @@ struct Index {
         int with_keys = 0;
     } ap;
     int debug_append_path = 0;  // test hook: 0 = automatic, 1 = merge where it is valid, 2 = always rebuild
+    // ---- cdb_insert_objects (insert.hip), kept on the handle that leads a call (its first field): calls that reached the commit, and
+    // the fields, objects and wall time of the last one
+    struct InsertStats {
+        uint64_t calls = 0, fields = 0, objects = 0;
+        double last_ms = 0;
+    } ins;
 
     double host_upload_ms = 0, host_free_ms = 0;  // cdb_build: staged column to the device / staging copy released
     Profiler prof;
@@ -475,6 +483,28 @@ __device__ __forceinline__ uint64_t lower_bound_id(const int64_t* __restrict__ i
     }
     return a;
 }
+
+// the ascending ids a field holds, as the calls that span fields read them (cdb_rowset_all, cdb_insert_objects)
+struct IdList {
+    const int64_t* ids;
+    uint64_t n;
+};
+// ... of a string index (empty: never built, or built over nothing); the field's lock is held, its stream idle on return
+inline IdList index_id_list(Index& ix) {
+    if (!ix.width || !ix.ndocs) return IdList{nullptr, 0};
+    DeviceScope scope(ix);
+    id_table_prepare(ix);  // (synchronises where it makes the table)
+    return IdList{ix.idt.ids_ascend ? ix.d_ids.as<int64_t>() : ix.idt.id_sorted.as<int64_t>(), ix.ndocs};
+}
+// the fields' locks, taken together in address order (columns.hip: filter_rows_on_lead's rule)
+struct FieldLocks {
+    std::vector<std::unique_lock<std::mutex>> locks;
+    explicit FieldLocks(std::vector<std::mutex*> mus) {
+        std::sort(mus.begin(), mus.end());
+        mus.erase(std::unique(mus.begin(), mus.end()), mus.end());
+        for (std::mutex* m : mus) locks.emplace_back(*m);
+    }
+};
 
 inline KeptKeys keys_of(const Index& ix) {
     return KeptKeys{ix.d_keys.as<uint64_t>(), ix.d_keys32.as<uint32_t>(), ix.d_keylow.as<uint8_t>(), ix.key_low_bits,
@@ -777,6 +807,29 @@ struct ColumnRemoval {
 };
 void column_remove_prepare(cdb_column* c, RowIds ids, uint64_t nids, ColumnRemoval& r);
 void column_remove_commit(cdb_column* c, ColumnRemoval& r);
+// column_maintain.hip — cdb_column_append in the same two halves (cdb_insert_objects, insert.hip, prepares every field of a call before
+// it commits any).  The caller has checked the call (no staged rows, the row limit, raw = column_raw_values) and sets t0 and `merge`:
+// true = the two-way merge of a built column with rows (c->n > 0); false = the build over the old rows and the batch, which for a
+// column without rows is column_sort_rows of the batch alone.  Prepare leaves the new arrays in fresh blocks beside the serving ones
+// and throws what cdb_column_append reports (the duplicate-id refusal among it), the column untouched.  Commit: column_publish plus
+// the stats of a cdb_column_append; it cannot fail.  release: as ColumnRemoval's.  Lock and DeviceScope as for the removal.
+struct ColumnAppendChange {
+    ColumnArrays a;
+    uint64_t rows = 0;
+    bool merge = false;    // in: which path
+    bool concat = false;   // merge: the id order was a concatenation
+    bool changed = false;  // prepared and not yet committed
+    double t0 = 0;         // wall_ms() when the call began (append_ms); the build path's own start is build_t0
+    double build_t0 = 0;
+    void release(cdb_column* c) {
+        (void)hipSetDevice(c->ws.device);
+        StreamScope ss(c->ws.stream);
+        a = ColumnArrays{};
+        changed = false;
+    }
+};
+void column_append_prepare(cdb_column* c, const int64_t* ids, const std::vector<uint64_t>& raw, uint64_t m, ColumnAppendChange& r);
+void column_append_commit(cdb_column* c, ColumnAppendChange& r);
 // the value (bit pattern) behind a column's order-preserving key (columns.hip: order_key; kind: 0 bool, 1 int64, 2 double)
 __host__ __device__ __forceinline__ uint64_t column_key_raw(int kind, uint64_t key) {
     constexpr uint64_t S = 1ull << 63;

@@ -54,29 +54,6 @@ __global__ __launch_bounds__(256) void all_unique_kernel(const uint64_t* __restr
     }
 }
 
-struct IdList {
-    const int64_t* ids;
-    uint64_t n;
-};
-
-// the ascending ids a field holds (empty: never built, or built over nothing); the field's lock is held, its stream idle on return
-IdList index_id_list(Index& ix) {
-    if (!ix.width || !ix.ndocs) return IdList{nullptr, 0};
-    DeviceScope scope(ix);
-    id_table_prepare(ix);  // (synchronises where it makes the table)
-    return IdList{ix.idt.ids_ascend ? ix.d_ids.as<int64_t>() : ix.idt.id_sorted.as<int64_t>(), ix.ndocs};
-}
-
-// the fields' locks, taken together in address order (columns.hip: filter_rows_on_lead's rule)
-struct FieldLocks {
-    std::vector<std::unique_lock<std::mutex>> locks;
-    explicit FieldLocks(std::vector<std::mutex*> mus) {
-        std::sort(mus.begin(), mus.end());
-        mus.erase(std::unique(mus.begin(), mus.end()), mus.end());
-        for (std::mutex* m : mus) locks.emplace_back(*m);
-    }
-};
-
 // the device half of cdb_rowset_all on the set's stream; synchronises
 void rowset_all_device(cdb_rowset* rs, const std::vector<IdList>& lists, int nonempty, uint64_t N) {
     Index& ws = rs->ws;

@@ -229,7 +229,8 @@ int cdb_column_get_stat(const cdb_column* c, const char* name, double* value);
  * union paths and the crossover measurement of tools/bench_columns.py); "debug_maintain_path" (0 = automatic,
  * 1 = the device path of cdb_column_append / cdb_column_remove wherever it is valid, 2 = stage + build / host filter + build:
  * DESIGN.md §7.8); "debug_fail_prepare" (0/1: the prepare half of a device removal throws a device error behind its queued work, the
- * column stays as it was — like cdb_set_option's "debug_fail_build" and "debug_fail_prepare" for a string index: cdb_rowset_remove). */
+ * column stays as it was — like cdb_set_option's "debug_fail_build" and "debug_fail_prepare" for a string index: cdb_rowset_remove); "debug_fail_append_prepare" (0/1: the same for the
+ * prepare half of an append: cdb_insert_objects). */
 int cdb_debug_column_set_option(cdb_column* c, const char* name, int64_t value);
 int cdb_debug_column_profile_dump(cdb_column* c, char* buf, size_t cap);
 
@@ -590,6 +591,76 @@ int cdb_rowset_all(cdb_index* const* indexes, int nindexes, cdb_column* const* c
  * timed as ap_*.
  * A sharded string column appends with cdb_shards_append. */
 int cdb_append(cdb_index* h, const int64_t* ids, const char* blob, const uint64_t* doc_start, uint64_t ndocs, uint64_t* appended);
+
+/* ---- objects join every field at once (insert.hip) --------------------------------------------------------------
+ * cdb_insert_objects — replaces "insert ... build" (interface.cpp:157-180, :286-288; database.cpp:283-379, then :170-282) for all
+ * fields of the objects at once, the counterpart of cdb_rowset_remove.  The objects join every field given, ALL OR NONE: every field
+ * prepares its new column beside the serving one, and only when every field stands does any commit.  Before, an object with five
+ * fields took five calls of cdb_append / cdb_column_append, and a failure in field 3 of 5 left fields 1 and 2 with the objects and
+ * the others without them for good.
+ *   Arguments.  ids[nobjects]: one id per object (the reference has one timestamp per insert).  Field k receives the pairs
+ * (ids[rows[j]], value j), j < nrows: `rows` are strictly ascending indices into ids[], or NULL = every object (nrows == nobjects).
+ * A string field's documents are blob / doc_start[nrows + 1] as for cdb_append, a column's values are `values` as for
+ * cdb_column_append (by kind).  nrows = 0 is valid: the field takes part in the id check and the locks only.  Exactly one of index /
+ * column is set in every entry; nfields >= 1; no handle twice; every field on one GPU.
+ *   Results.  *inserted (may be NULL) = nobjects.  Per field, appended = the rows that joined it.  nobjects = 0 is valid, changes
+ * nothing and counts no call in any field.  After a successful call every field cannot be told from one that received the same rows
+ * through its own cdb_append / cdb_column_append, the counting stats included ("appends", "append_merges" / "append_rebuilds",
+ * "append_docs" / "append_rows", ...): a field that was never built, or holds nothing, is built over its rows of the batch.  The TIME
+ * stats differ: a field's "append_ms" (and a column's "build_ms" on the build path) runs from its own prepare to its own commit, and
+ * every commit comes behind every prepare, so it includes the prepares of the fields behind it in the call.
+ *   Order of the call.  A cdb_reserve still running is waited for; every field's lock together in address order (cdb_filter's rule);
+ * validation; the id check on the device; every field with rows PREPARES, one after another in the caller's order; every field
+ * commits; unlock.  Queries on the fields wait, as during cdb_append.
+ *   Refused as a whole with CDB_E_INVALID before any device work: nfields < 1 or > 65535, fields NULL, a field entry with none or both pointers
+ * set, the same handle twice, ids NULL with nobjects > 0, a field with nrows > 0 that lacks its payload pointers (blob and doc_start,
+ * or values), rows NULL with nrows != nobjects (these like a NULL argument: the code alone, before any handle is read); fields on
+ * different GPUs ("cdb_insert_objects: all fields must live on one GPU"), an index or a column with pending additions ("append:
+ * documents / rows were added since the last build"), rows not strictly ascending or >= nobjects, an object that no field lists
+ * ("cdb_insert_objects: object <i> holds no field": the reference's "Empty objects are not allowed", database.cpp:284-286), NaN in a
+ * double field and the column row limit (cdb_column_append's messages).  The column option debug_maintain_path is not consulted:
+ * this call has only the device path.
+ *   The id check (CDB_E_INVALID, nothing changed).  No id may stand twice in ids[] ("cdb_insert_objects: object id N twice in the
+ * batch", N the smallest such id), and no id of the batch may be held by any field given, whether the object lists that field or not
+ * ("cdb_insert_objects: object id N is already held by field <k>": N the smallest such id as a signed number, k the first field in
+ * the caller's order that holds it).  ONE STATED DIVERGENCE: the reference overwrites raw/<id>, so inserting an id again replaces
+ * the object at the next build; here a replace is cdb_rowset_remove followed by this call.  Only built rows count, as for every query.
+ *   A failure in a prepare.  The call returns that field's code (the first in the caller's order; the prepares behind it do not run),
+ * the error text says "field <i>: <message>", that field's status carries the code, every committed and every appended is 0, every
+ * prepared column is dropped and every field answers exactly as before.
+ *   One step can still fail behind the commit point: on the reference-order path (reference_compat = 1 and bytes >= 0x80, see
+ * cdb_append "Paths"), and for a string field that held nothing, the array is built over the new text AFTER the field's commit.  The
+ * single-handle rule then applies per field.  What a caller finds after such a failure: the call returns the failing field's error;
+ * that field is "never built" (it answers {} and holds no document: the documents it served are gone from the column), its status
+ * carries the code and its committed is 1; every other field has committed its change.  The database is consistent and answers every
+ * query, but that field is neither the old nor the new one: rebuild it from the source.
+ *   Memory.  At the peak every field's new column stands beside its old one AT THE SAME TIME (the per-field calls hold one pair at a
+ * time).  In front of that the id check holds 24 bytes per object on the first field's GPU (the ids, their keys and the sort's second
+ * buffer), 8 bytes per 4096 objects of tile counts and bases, and the radix sort's work space that the first field's handle keeps across
+ * calls; the check's blocks are released before the first prepare.  A caller short of memory gets CDB_E_DEVICE and an unchanged database.
+ *   Errors are reported where cdb_rowset_all reports them: on the FIRST field's handle (cdb_last_error / cdb_column_last_error).
+ *   Sharded string columns stay out: use cdb_shards_append for them as before.
+ *   Stats live on that first field's handle too and are read with cdb_insert_get_stat(index, column, ...), exactly one of the two
+ * set: "inserts" (calls that reached the commit), and of the last one "insert_fields", "insert_objects", "insert_ms".  With the first
+ * field's option profile on, its profile holds the id check's kernels as ins_* lines.
+ *   Test hook, NOT part of the stable ABI (beside debug_fail_prepare): option "debug_fail_append_prepare" of cdb_set_option and
+ * cdb_debug_column_set_option makes the prepare half of an append to that field throw a device error after its device work has been
+ * queued and its blocks allocated, so that the release path runs. */
+typedef struct cdb_insert_field {
+    cdb_index*      index;      /* a string field, or NULL            — exactly one of the two          */
+    cdb_column*     column;     /* a numeric / bool field, or NULL                                       */
+    const uint64_t* rows;       /* which objects of the batch hold this field: strictly ascending indices
+                                   into ids[], nrows of them; NULL = every object (nrows == nobjects)   */
+    uint64_t        nrows;      /* 0 is valid: the field takes part in the id check and the locks only   */
+    const char*     blob;       /* string field: the documents, as for cdb_append ...                    */
+    const uint64_t* doc_start;  /* ... doc_start[nrows + 1]                                              */
+    const void*     values;     /* column field: nrows values, as for cdb_column_append (by kind)        */
+    uint64_t        appended;   /* out: rows that joined this field                                      */
+    int32_t         status;     /* out: CDB_OK, or the code of the failure that arose in this field      */
+    int32_t         committed;  /* out: 1 = the field's old column no longer serves                      */
+} cdb_insert_field;
+int cdb_insert_objects(const int64_t* ids, uint64_t nobjects, cdb_insert_field* fields, int nfields, uint64_t* inserted);
+int cdb_insert_get_stat(const cdb_index* index, const cdb_column* column, const char* name, double* value);
 
 /* Batched query with patterns and results left in device memory (multi-GPU merge over RCCL, HBM-
  * resident timing).  d_blob/d_offsets are device pointers.  On return the library-owned device arrays
