@@ -2,7 +2,7 @@
 // (radix_sort.h: radix_sort_segmented over five passes, radix_sort_top_first), in a translation unit of its own like the other
 // debug_*.hip.  Nothing here is called by a production path; the hook runs what run_segmented (sa_build.hip) runs for ONE bucket
 // group behind the sweep, with the same functions: rs_seg_tilemap_kernel, then either rs_seg_hist_kernel + radix_sort_segmented<u16>
-// or radix_sort_top_first<u16> with the SegFinalArgs the build fills in.  Host arrays in, host arrays out, a stream of its own,
+// or radix_sort_top_first<u16> with the SegFinalArgs the build fills in (as SegFinalCellArgs: rs_top_first_fin).  Host arrays in, host arrays out, a stream of its own,
 // poisoned guards around every device array a pass writes.
 #include <cstdio>
 #include <cstring>
@@ -126,7 +126,7 @@ int cdb_debug_segsort(int device, int form, int packed, uint64_t n, uint32_t nb,
         d_tile_seg.alloc((size_t)tiles * sizeof(uint32_t));
         d_hist.alloc((size_t)nb * 8 * 256 * sizeof(uint64_t));
         d_starts.alloc((size_t)nb * 8 * 256 * sizeof(uint64_t));
-        edges.alloc((size_t)cell_tiles_max * 256 * sizeof(SegEdge));
+        edges.alloc((size_t)cell_tiles_max * 256 * (form == CDB_DEBUG_SEGSORT_TOP_FIRST ? sizeof(SegCellEdge) : sizeof(SegEdge)));
         hipLaunchKernelGGL(rs_seg_tilemap_kernel, dim3((unsigned)ceil_div(tiles, 256u)), dim3(256), 0, s, (const SegInfo*)d_segs.as<SegInfo>(), nb, tiles,
                            d_tile_seg.as<uint32_t>());
         // the last pass's arguments as run_segmented fills them in (variable-length keys: kbase 2, no magic; blow = 8)
@@ -155,11 +155,11 @@ int cdb_debug_segsort(int device, int form, int packed, uint64_t n, uint32_t nb,
         uint32_t ncell = 0;
         if (form == CDB_DEBUG_SEGSORT_TOP_FIRST) {
             tfw.alloc(nb * 256u, cell_tiles_max);
-            rs_top_first_fin(fin, ehb);
+            const SegFinalCellArgs cfin = rs_top_first_fin(fin, ehb);
             ncell = radix_sort_top_first<uint16_t>(s, ws, prof, k[0].ptr<uint32_t>(), k[1].ptr<uint32_t>(), v[0].ptr<uint32_t>(), v[1].ptr<uint32_t>(),
                                                    w[0].ptr<uint16_t>(), w[1].ptr<uint16_t>(), n, (const SegInfo*)d_segs.as<SegInfo>(), segs.data(),
                                                    (const uint32_t*)d_tile_seg.as<uint32_t>(), nb, tiles, d_hist.as<unsigned long long>(),
-                                                   d_starts.as<unsigned long long>(), tfw, fin, nullptr);
+                                                   d_starts.as<unsigned long long>(), tfw, cfin, nullptr);
         } else {
             CDB_HIP(hipMemsetAsync(d_hist.p, 0, (size_t)nb * 8 * 256 * sizeof(uint64_t), s));
             hipLaunchKernelGGL((rs_seg_hist_kernel<uint16_t>), dim3((unsigned)ceil_div(tiles, (uint32_t)RS_MSD_HIST_TILES)), dim3(1024), 0, s,

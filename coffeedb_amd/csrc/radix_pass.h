@@ -14,7 +14,7 @@
 //     tile ids come from an atomic ticket so a tile only ever waits on tiles that already started, and
 //     every spin is bounded (a stuck look-back raises an error flag instead of hanging the GPU).
 //
-// In this file: RsCfg and the named configurations; rs_load / rs_store; TextGen*, Seg*Args, SegEdge; rs_pack_key,
+// In this file: RsCfg and the named configurations; rs_load / rs_store; TextGen*, Seg*Args, SegEdge (SegCellEdge: seg_cell_edge.h); rs_pack_key,
 // rs_doc_upper; the status-word accessors; RsTraits (every compile-time switch of an instantiation, derived once); the rules the
 // kernel body uses more than once as functions (rs_group_flag, rs_load_striped) and the kernel.  radix_sort.h includes it and holds the host half: histograms, workspace, variant
 // table, rs_launch_pass, the drivers and the segmented, MSD and tile-base parts.
@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "seg_cell_edge.h"
 
 namespace cdb {
 
@@ -244,6 +245,22 @@ struct SegFinalArgs : SegArgs {
     int carry_shift = 0;
 };
 
+// ... as a type of its own for the last pass over the CELLS of a top-digit-first sort (radix_sort_top_first): byte-wide aux words
+// that hold nothing of the key (entry bits 32.. from bit 0, carried bits above them), 32-bit keys of variable-length code (a key
+// ends inside the document <=> its bit 0 is clear), no bucket written rotated.  What SegFinalArgs reads from runtime fields per
+// element is fixed here: head and tail come from the neighbouring keys alone, the aux byte is read from the LDS once and serves
+// the flag byte and the entry, and a (tile, digit) run leaves a 16-byte edge record (seg_cell_edge.h).
+struct SegFinalCellArgs : SegArgs {
+    uint64_t* eout = nullptr;   // entries / packed entries / flags of the group: as in SegFinalArgs
+    uint32_t* elo = nullptr;
+    uint8_t* ehi = nullptr;
+    uint8_t* flags = nullptr;
+    SegCellEdge* edges = nullptr;  // [tiles][256]
+    uint32_t hi_mask = 0xFFu;      // entry bits 32.. = aux & hi_mask
+    uint32_t carry_mask = 0;       // flag byte = f | ((aux >> carry_shift) & carry_mask) << 2
+    int carry_shift = 0;
+};
+
 // The last pass of an ordinary (single-segment) sort of split records can do the same and still write its records (the
 // kept search keys): the suffix-array build below 2^32 then needs no flag kernel (5-6 B read + 1 B written per suffix).
 // tile_sums (optional): per scan tile of `sums_tile` flags {unresolved entries, unresolved group heads} as pairs of u64 —
@@ -318,7 +335,8 @@ struct RsTraits {
     static constexpr bool FINAL = std::is_same<Seg, SegFinalArgs>::value;
     static constexpr bool KEEPM = std::is_same<Seg, SegFinalKeepMsdArgs>::value;  // ... of an MSD-first sort (no auxiliary input)
     static constexpr bool KEEP = std::is_same<Seg, SegFinalKeepArgs>::value || KEEPM;  // flags + edge records beside the ordinary record write-out
-    static constexpr bool FLAGS = FINAL || KEEP;
+    static constexpr bool CELL = std::is_same<Seg, SegFinalCellArgs>::value;  // last pass over the cells of a top-digit-first sort
+    static constexpr bool FLAGS = FINAL || KEEP || CELL;
     static constexpr bool SHRINK = std::is_same<Seg, SegShrinkArgs>::value;  // the aux word leaves without its low byte, as a byte (seg.wout8)
     static constexpr bool HAS_V = !std::is_same<V, NoVal>::value;
     static constexpr bool HAS_W = !std::is_same<W, NoVal>::value;
@@ -363,6 +381,8 @@ struct RsTraits {
 
     static_assert(!SHRINK || (std::is_same<W, uint16_t>::value && Cfg::REUSE && !std::is_same<V, NoVal>::value), "shrinking pass: u16 aux words, shared staging");
     static_assert(!SEG || (!GEN && !Cfg::DMA), "segmented passes: materialised records");
+    static_assert(!CELL || (std::is_same<K, uint32_t>::value && std::is_same<V, uint32_t>::value && std::is_same<W, uint8_t>::value && (IPT % 4) == 0),
+                  "last pass over cells: (u32, u32, u8) records");
     static_assert(!FLAGS || Cfg::REUSE || KEEPM, "flag-writing passes: shared staging (the MSD-first last pass also runs with keys and values staged at once)");
     static_assert(!HAS_W || KEEPM || (Cfg::REUSE && HAS_V && !Cfg::DMA), "the auxiliary byte needs the shared-staging configuration");
     static_assert(!(GM_PAIR || GM_REC) || (BLK && HAS_W), "pair / records generators: 16 Ki tiles with an auxiliary word");
@@ -490,7 +510,7 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::MINW) void rs_onesweep_kernel(
     WS aux[T::HAS_W ? T::IPT : 1] = {};
     uint32_t gdig[T::GM_REC ? T::IPT / 4 : 1] = {};  // records generators: the elements' sort digits, four per register
     auto digit_of = [&](K k, WS a) -> uint32_t {
-        if constexpr (T::HAS_W) {
+        if constexpr (T::HAS_W && !T::CELL) {  // (a cell's aux byte holds no digit)
             if (aux_shift >= 0) return ((uint32_t)a >> aux_shift) & dmask;
         }
         return (uint32_t)(k >> shift) & dmask;
@@ -987,7 +1007,12 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::MINW) void rs_onesweep_kernel(
         s_gbase[d] = (Cfg::ABL & 2) ? base : (prebased ? pre : dstart + excl) - (uint64_t)tstart;
     }
     __syncthreads();
-    if constexpr (T::FLAGS) {
+    if constexpr (T::CELL) {
+        if (tid < 256) {  // edge record of this tile's run of digit d, 16 bytes: the keys are the 32 bits in LDS
+            const uint32_t a = tstart, b = tstart + (uint32_t)real - 1u;
+            seg.edges[tile * 256 + d] = seg_cell_edge_pack(real ? s_keys[a] : 0u, real ? s_keys[b] : 0u, dstart + excl, (uint32_t)real);
+        }
+    } else if constexpr (T::FLAGS) {
         if (tid < 256) {  // edge record of this tile's run of digit d (the sorted keys sit in LDS until the next barrier)
             SegEdge e;
             e.first = e.last = 0;
@@ -1033,6 +1058,48 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::MINW) void rs_onesweep_kernel(
                 }
                 if (!T::GEN || kout) rs_store<T::NTM>(kout + dst, k);  // generated pass: kout may be null (entries only)
                 if constexpr (T::HAS_V) rs_store<T::NTM>(vout + dst, (V)s_vals[i]);
+            }
+        }
+    } else if constexpr (T::CELL) {
+        // last pass over cells: flags from the neighbouring keys; digit and aux byte of every element stay packed in registers,
+        // four to a word, across the barrier — the entry phase reads neither s_keys nor s_aux again
+        uint32_t dig4[T::IPT / 4] = {}, aux4[T::IPT / 4] = {};
+#pragma unroll
+        for (int j = 0; j < T::IPT; ++j) {
+            const uint32_t i = j * T::NT + tid;
+            if (i < valid) {
+                const uint32_t k = s_keys[i];
+                const uint32_t dd = (k >> shift) & dmask;
+                const uint32_t a = (uint32_t)s_aux[i];
+                dig4[j >> 2] |= dd << (8 * (j & 3));
+                aux4[j >> 2] |= a << (8 * (j & 3));
+                bool head = true, tail = true;
+                if (!(RS_SEG_ABL & 4)) {
+                    if (i > 0) head = s_keys[i - 1] != k;
+                    if (i + 1 < valid) tail = s_keys[i + 1] != k;
+                }
+                uint32_t f = head ? 1u : 0u;
+                if (!(head && tail) && (k & 1u)) f |= 2u;  // (bit 0 clear: the key ends inside the document)
+                f |= ((a >> seg.carry_shift) & seg.carry_mask) << 2;
+                if (!(RS_SEG_ABL & 1)) seg.flags[s_gbase[dd] + i] = (uint8_t)f;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < T::IPT; ++j) s_vals[rank[j]] = val[j];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < T::IPT; ++j) {
+            const uint32_t i = j * T::NT + tid;
+            if (i < valid && !(RS_SEG_ABL & 2)) {
+                const unsigned long long slot = s_gbase[(dig4[j >> 2] >> (8 * (j & 3))) & 0xFFu] + i;
+                const uint32_t hi32 = (aux4[j >> 2] >> (8 * (j & 3))) & seg.hi_mask;  // (hi_mask <= 0xFF: the byte's neighbours drop out)
+                if (seg.elo) {  // (uniform) 5 bytes per entry instead of 8
+                    seg.elo[slot] = (uint32_t)s_vals[i];
+                    seg.ehi[slot] = (uint8_t)hi32;
+                } else {
+                    seg.eout[slot] = ((uint64_t)hi32 << 32) | (uint64_t)s_vals[i];
+                }
             }
         }
     } else {

@@ -127,34 +127,45 @@ static __global__ __launch_bounds__(256) void rs_tiledoc_kernel(const uint64_t* 
 // digit d) the run in front of it in the output is the nearest earlier tile of the same segment that holds digit d
 // — its last element sits right in front of this run's first.  Equal keys there: the first element is no group head,
 // and both elements belong to an unresolved group unless the key ends inside the document.
-static __global__ __launch_bounds__(256) void rs_seg_edge_fix_kernel(const SegEdge* __restrict__ edges, const uint32_t* __restrict__ tile_seg,
-                                                                     const SegInfo* __restrict__ segs, uint32_t tiles,
-                                                                     uint8_t* __restrict__ flags, uint32_t kbase, unsigned long long kmagic,
-                                                                     unsigned long long* __restrict__ tile_sums = nullptr,
-                                                                     uint32_t sums_tile = 1, const uint32_t* __restrict__ err = nullptr) {
+// (the body is shared by the two record types: the accessors below are all it knows of a record.  CELL records — seg_cell_edge.h —
+//  belong to unrotated cells)
+__device__ __forceinline__ unsigned long long rs_edge_pos(const SegEdge& e) { return e.pos; }
+__device__ __forceinline__ uint32_t rs_edge_cnt(const SegEdge& e) { return e.cnt; }
+__device__ __forceinline__ unsigned long long rs_edge_first(const SegEdge& e) { return e.first; }
+__device__ __forceinline__ unsigned long long rs_edge_last(const SegEdge& e) { return e.last; }
+__device__ __forceinline__ unsigned long long rs_edge_pos(const SegCellEdge& e) { return seg_cell_edge_pos(e.pos_cnt); }
+__device__ __forceinline__ uint32_t rs_edge_cnt(const SegCellEdge& e) { return seg_cell_edge_cnt(e.pos_cnt); }
+__device__ __forceinline__ unsigned long long rs_edge_first(const SegCellEdge& e) { return e.first; }
+__device__ __forceinline__ unsigned long long rs_edge_last(const SegCellEdge& e) { return e.last; }
+template <typename E>
+__device__ __forceinline__ void rs_seg_edge_fix_body(const E* __restrict__ edges, const uint32_t* __restrict__ tile_seg,
+                                                     const SegInfo* __restrict__ segs, uint32_t tiles, uint8_t* __restrict__ flags, uint32_t kbase,
+                                                     unsigned long long kmagic, unsigned long long* __restrict__ tile_sums, uint32_t sums_tile,
+                                                     const uint32_t* __restrict__ err) {
+    constexpr bool CELL = std::is_same<E, SegCellEdge>::value;
     const uint32_t t = blockIdx.x, d = threadIdx.x;
     if (t >= tiles) return;
     if (err && *err) return;  // (a failed pass left edge records unwritten: their stale slots must not be touched)
-    const SegEdge e = edges[(size_t)t * 256 + d];
-    if (!e.cnt) return;
+    const E e = edges[(size_t)t * 256 + d];
+    if (!rs_edge_cnt(e)) return;
+    const unsigned long long epos = rs_edge_pos(e), efirst = rs_edge_first(e);
     const SegInfo si = segs[tile_seg ? tile_seg[t] : 0u];
     const uint32_t t0 = si.tile_begin;
     if (t == t0) return;
     // largest t' in [t0, t) whose run starts in front of this one (runs of tiles without the digit share its start)
     uint32_t lo = t0, hi = t;  // invariant: answer (if any) in [lo, hi)
-    if (edges[(size_t)(t - 1) * 256 + d].pos < e.pos) {
+    if (rs_edge_pos(edges[(size_t)(t - 1) * 256 + d]) < epos) {
         lo = t - 1;
     } else {
-        if (edges[(size_t)t0 * 256 + d].pos >= e.pos) return;  // first run of this digit in the segment
+        if (rs_edge_pos(edges[(size_t)t0 * 256 + d]) >= epos) return;  // first run of this digit in the segment
         hi = t - 1;
         while (hi - lo > 1) {  // pos[lo] < e.pos <= pos[hi]
             const uint32_t mid = lo + (hi - lo) / 2;
-            if (edges[(size_t)mid * 256 + d].pos < e.pos) lo = mid; else hi = mid;
+            if (rs_edge_pos(edges[(size_t)mid * 256 + d]) < epos) lo = mid; else hi = mid;
         }
     }
-    const SegEdge pe = edges[(size_t)lo * 256 + d];
-    if (pe.last != e.first) return;
-    const bool exhausted = kmagic ? (e.first - __umul64hi(e.first, kmagic) * kbase) == 0 : (e.first & (uint64_t)(kbase - 1u)) == 0;
+    if (rs_edge_last(edges[(size_t)lo * 256 + d]) != efirst) return;
+    const bool exhausted = kmagic ? (efirst - __umul64hi(efirst, kmagic) * kbase) == 0 : (efirst & (uint64_t)(kbase - 1u)) == 0;
     // one atomic per change; the old value each one returns says exactly what that change did to the tile sums
     auto change = [&](unsigned long long slot, uint32_t clear, uint32_t set) {
         // (the word that holds the byte: `flags` points at the group's first flag, which need not be 4-byte aligned;
@@ -178,12 +189,26 @@ static __global__ __launch_bounds__(256) void rs_seg_edge_fix_kernel(const SegEd
             if (db) atomicAdd(ts + 1, (unsigned long long)db);
         }
     };
-    const unsigned long long sb = rs_seg_rotated(si, e.pos), sa_ = rs_seg_rotated(si, e.pos - 1);
+    const unsigned long long sb = CELL ? epos : rs_seg_rotated(si, epos), sa_ = CELL ? epos - 1 : rs_seg_rotated(si, epos - 1);
     change(sb, 1u, 0u);                    // first of this run: not a head
     if (!exhausted) {
         change(sb, 0u, 2u);                // ... and part of an unresolved group, like
         change(sa_, 0u, 2u);               // the last of the run in front: not a tail
     }
+}
+static __global__ __launch_bounds__(256) void rs_seg_edge_fix_kernel(const SegEdge* __restrict__ edges, const uint32_t* __restrict__ tile_seg,
+                                                                     const SegInfo* __restrict__ segs, uint32_t tiles,
+                                                                     uint8_t* __restrict__ flags, uint32_t kbase, unsigned long long kmagic,
+                                                                     unsigned long long* __restrict__ tile_sums = nullptr,
+                                                                     uint32_t sums_tile = 1, const uint32_t* __restrict__ err = nullptr) {
+    rs_seg_edge_fix_body(edges, tile_seg, segs, tiles, flags, kbase, kmagic, tile_sums, sums_tile, err);
+}
+// ... over the 16-byte records of a last pass over cells: variable-length keys (a key ends inside the document <=> bit 0 clear),
+// no rotation, no tile sums
+static __global__ __launch_bounds__(256) void rs_seg_edge_fix_cell_kernel(const SegCellEdge* __restrict__ edges, const uint32_t* __restrict__ tile_seg,
+                                                                          const SegInfo* __restrict__ segs, uint32_t tiles,
+                                                                          uint8_t* __restrict__ flags, const uint32_t* __restrict__ err) {
+    rs_seg_edge_fix_body(edges, tile_seg, segs, tiles, flags, 2u, 0ull, (unsigned long long*)nullptr, 1u, err);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -708,15 +733,23 @@ static __global__ __launch_bounds__(256) void rs_seg_digit_start_kernel(const un
 // buffers 0; `lead` low digits sit in the auxiliary word (sorted first), key_bits bits in k32.  The last pass writes
 // entries and group flags through `fin` (eout / flags / edges filled in by the caller) instead of records.
 // d_hist: digit counts [nseg][8][256], lowest digit first; d_starts: scratch of the same shape.
-template <typename W>
+// Fin = SegFinalCellArgs: the last pass over the cells of a top-digit-first sort (byte-wide aux words without key bits, 32-bit
+// keys, no rotation), with 16-byte edge records and their edge fix.
+template <typename W, typename Fin = SegFinalArgs>
 void radix_sort_segmented(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uint32_t* k0, uint32_t* k1, uint32_t* v0, uint32_t* v1,
                           W* w0, W* w1, uint64_t m, const SegInfo* d_segs, const uint32_t* d_tile_seg, uint32_t nseg, uint32_t tiles,
-                          const unsigned long long* d_hist, unsigned long long* d_starts, int key_bits, int lead, SegFinalArgs fin,
+                          const unsigned long long* d_hist, unsigned long long* d_starts, int key_bits, int lead, Fin fin,
                           SortStats* stats) {
+    constexpr bool CELL = std::is_same<Fin, SegFinalCellArgs>::value;
     if (!rs_atomic_rank_ok(s)) throw InternalError("radix_sort_segmented: needs the one-atomic ranking (internal)");
     const int kpass = (int)ceil_div((uint64_t)key_bits, 8);
     const int npass = kpass + lead;
     if (npass < 1 || npass > 8 || kpass < 1) throw InternalError("radix_sort_segmented: unsupported pass count (internal)");
+    if constexpr (CELL) {
+        static_assert(std::is_same<W, uint8_t>::value, "last pass over cells: byte-wide aux words");
+        if (lead != 0 || key_bits != 32 || fin.hi_mask > 0xFFu) throw InternalError("radix_sort_segmented: cell form (internal)");
+        seg_cell_edge_check_limits(m, RS_SEG_TILE);  // (the output slots of a group are [0, m))
+    }
     const int last_bits = key_bits - 8 * (kpass - 1);
     const uint32_t last_mask = (1u << last_bits) - 1u;
     ws.prepare((uint64_t)tiles * RS_SEG_TILE, RS_SEG_TILE, s);
@@ -752,9 +785,15 @@ void radix_sort_segmented(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uin
         if (stats) stats->passes_run++;
     }
     int t = prof.begin(s);
-    hipLaunchKernelGGL(rs_seg_edge_fix_kernel, dim3(tiles), dim3(256), 0, s, (const SegEdge*)fin.edges, d_tile_seg, d_segs, tiles,
-                       fin.flags, fin.kbase, fin.kmagic, (unsigned long long*)nullptr, 1u, (const uint32_t*)ws.err_ptr());
-    prof.end(t, "rs_seg_edge_fix", (uint64_t)tiles * 256 * sizeof(SegEdge), s);
+    if constexpr (CELL) {
+        hipLaunchKernelGGL(rs_seg_edge_fix_cell_kernel, dim3(tiles), dim3(256), 0, s, (const SegCellEdge*)fin.edges, d_tile_seg, d_segs, tiles,
+                           fin.flags, (const uint32_t*)ws.err_ptr());
+        prof.end(t, "rs_seg_edge_fix", (uint64_t)tiles * 256 * sizeof(SegCellEdge), s);
+    } else {
+        hipLaunchKernelGGL(rs_seg_edge_fix_kernel, dim3(tiles), dim3(256), 0, s, (const SegEdge*)fin.edges, d_tile_seg, d_segs, tiles,
+                           fin.flags, fin.kbase, fin.kmagic, (unsigned long long*)nullptr, 1u, (const uint32_t*)ws.err_ptr());
+        prof.end(t, "rs_seg_edge_fix", (uint64_t)tiles * 256 * sizeof(SegEdge), s);
+    }
     CDB_HIP(hipGetLastError());
 }
 
@@ -933,21 +972,30 @@ inline void rs_check_cells(const std::vector<SegInfo>& cells, uint32_t tiles, co
     }
     if (c != cells.size() || t != (uint64_t)tiles) throw InternalError("radix_sort_top_first: cell tiles (internal)");
 }
-// the last pass's view of the byte-wide aux word behind the top pass: entry bits 32.. | carried bits, nothing of the key
-inline void rs_top_first_fin(SegFinalArgs& fin, int ehb) {
-    fin.hi_shift = 0;
-    fin.low_bits = 0;
-    fin.hi_mask = (1u << ehb) - 1u;
-    fin.carry_shift = ehb;
+// the last pass over cells from the arguments the five-pass form would take: the byte-wide aux word behind the top pass holds
+// entry bits 32.. (ehb of them) | carried bits and nothing of the key, which is why the pass has a type of its own
+// (SegFinalCellArgs).  The edge records of `fin` are reused as 16-byte ones.
+inline SegFinalCellArgs rs_top_first_fin(const SegFinalArgs& fin, int ehb) {
+    if (fin.kbase != 2 || fin.kmagic != 0 || ehb < 0 || ehb > 8) throw InternalError("radix_sort_top_first: variable-length keys, at most 8 entry bits in the aux byte (internal)");
+    SegFinalCellArgs c;
+    c.eout = fin.eout;
+    c.elo = fin.elo;
+    c.ehi = fin.ehi;
+    c.flags = fin.flags;
+    c.edges = reinterpret_cast<SegCellEdge*>(fin.edges);
+    c.hi_mask = (1u << ehb) - 1u;
+    c.carry_mask = fin.carry_mask;
+    c.carry_shift = ehb;
+    return c;
 }
 // Records of m elements in buffers 0 (w0: u16 = top key byte | everything else << 8), the buckets as for radix_sort_segmented
 // (h_segs: their host copy, no rotations); d_hist / d_starts: scratch [nseg][8][256].  The passes leave buffers 0 and 1 as the
-// five-pass form does (the last pass reads buffers 0); fin as for radix_sort_segmented over (u32, u32, u8) records.
+// five-pass form does (the last pass reads buffers 0); fin: the last pass over the cells (rs_top_first_fin).
 template <typename W>  // (uint16_t; a template so that only the build instantiates its kernels)
 uint32_t radix_sort_top_first(hipStream_t s, RadixWorkspace& ws, Profiler& prof, uint32_t* k0, uint32_t* k1, uint32_t* v0, uint32_t* v1,
                                      W* w0, W* w1, uint64_t m, const SegInfo* d_segs, const SegInfo* h_segs, const uint32_t* d_tile_seg,
                                      uint32_t nseg, uint32_t tiles, unsigned long long* d_hist, unsigned long long* d_starts, TopFirstWork& tw,
-                                     SegFinalArgs fin, SortStats* stats) {
+                                     SegFinalCellArgs fin, SortStats* stats) {
     static_assert(std::is_same<W, uint16_t>::value, "top digit first: (u32, u32, u16) records");
     if (!rs_atomic_rank_ok(s)) throw InternalError("radix_sort_top_first: needs the one-atomic ranking (internal)");
     for (uint32_t b = 0; b < nseg; ++b)
@@ -991,7 +1039,7 @@ uint32_t radix_sort_top_first(hipStream_t s, RadixWorkspace& ws, Profiler& prof,
                        (const uint8_t*)b1, 0, 4, (const uint32_t*)tw.tile_seg.as<uint32_t>(), (const SegInfo*)tw.cells.as<SegInfo>(), ctiles,
                        tw.hist.as<unsigned long long>());
     prof.end(t, "rs_seg_hist_cells", m * sizeof(uint32_t), s);
-    radix_sort_segmented<uint8_t>(s, ws, prof, k1, k0, v1, v0, b1, b0, m, (const SegInfo*)tw.cells.as<SegInfo>(), (const uint32_t*)tw.tile_seg.as<uint32_t>(), ncell,
+    radix_sort_segmented<uint8_t, SegFinalCellArgs>(s, ws, prof, k1, k0, v1, v0, b1, b0, m, (const SegInfo*)tw.cells.as<SegInfo>(), (const uint32_t*)tw.tile_seg.as<uint32_t>(), ncell,
                                   ctiles, (const unsigned long long*)tw.hist.as<unsigned long long>(), tw.starts.as<unsigned long long>(), 32, 0, fin, stats);
     return ncell;
 }

@@ -1897,7 +1897,7 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
             }
             wb[q].alloc(max_elems * (top_first && q == 1 ? 1 : sizeof(W)));  // (top digit first: buffer 1 only ever holds byte-wide aux words)
         }
-        edges.alloc((size_t)cell_tiles_max * 256 * sizeof(SegEdge));
+        edges.alloc((size_t)cell_tiles_max * 256 * (top_first ? sizeof(SegCellEdge) : sizeof(SegEdge)));  // (the last pass over cells: 16-byte records)
         if (top_first) tfw.alloc(max_gb * 256u, cell_tiles_max);
         d_starts.alloc((size_t)max_gb * 8 * 256 * sizeof(uint64_t));
         d_bh2.alloc((size_t)max_gb * 8 * 256 * sizeof(uint64_t));
@@ -2011,11 +2011,11 @@ void run_segmented(Index& ix, const Alphabet& al, const KeyPlan& kp, const Bucke
             }
             if constexpr (std::is_same<W, uint16_t>::value) {
                 if (top_first) {  // (the aux word behind the top pass: entry bits 32.. | carried bits, nothing of the key)
-                    rs_top_first_fin(fin, ehb);
+                    const SegFinalCellArgs cfin = rs_top_first_fin(fin, ehb);
                     st.top_first_cells += radix_sort_top_first(s, ix.rws, ix.prof, kbp[0], kbp[1], ebp[0], ebp[1], wb[0].as<W>(), wb[1].as<W>(),
                                                                g.elems, (const SegInfo*)(d_segs.as<SegInfo>() + g.b0), h_segs.data() + g.b0,
                                                                (const uint32_t*)tile_seg.as<uint32_t>(), gb, g.tiles, d_bh2.as<unsigned long long>(),
-                                                               d_starts.as<unsigned long long>(), tfw, fin, &ss);
+                                                               d_starts.as<unsigned long long>(), tfw, cfin, &ss);
                     st.bucket_groups++;
                     continue;
                 }
